@@ -33,8 +33,17 @@ Per time step: a looser linear solve is cheaper per iteratio
 the same run goes on to --stat-calls calls in all; over the whole converged time steps inside them `per_time_step` reports the Newton
 iterations per time step, the device ms per converged time step (chopped attempts included) and the ms per simulated day.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 (N > 1: one rank per GPU under torch.distributed.run; launched without WORLD_SIZE the script starts that launcher itself as a child process)
+
+A plain run does what the headline needs and nothing more: deck set-up, W warm-up and K timed Newton iterations, the line.  Its `roofline`,
+`cpu_baseline`, `per_time_step`, `variants` and `decks` are null / empty.  --full adds everything else described above: the calls after the
+timed ones up to --stat-calls, the per-kernel pass, the same-run variants, the other BASELINE decks, the SpMV roofline and the CPU baseline.
+
+--dump-outputs DIR: after the K timed iterations, the state the last one left (pressure, saturations, rs, rv, hydrocarbon state; with wells
+the well state: bhp, surface rates, perforation pressures and rates) as DIR/<name>.npy in float64 / float32, at most 64 MB in all (a larger
+deck writes the same seeded sample of its cells, with their indices in cell_index.npy).  The decks are seeded: the same arguments give the
+same inputs, so two builds can be compared output for output.
 """
 import argparse
 import ctypes as C
@@ -144,10 +153,13 @@ def parse_args(argv):
     ap.add_argument("--stage2-relax", type=float, default=None,
                     help="opmgpu_params.cpr_stage2_relax (library extension: damping of the stage-2 ILU0 alone; 1.0 = the reference's form).  Default: 1.0 -- except on the "
                          "DECOMPOSED SPE10-like deck, 0.9: with the undamped second stage the 4-rank run chops 9 of 12 steps (profiles/r04_z_dist_spe10_relax.log)")
-    ap.add_argument("--stat-calls", type=int, default=60, help="calls (the K timed ones included) the per-time-step statistics are taken over")
-    ap.add_argument("--only-main", action="store_true", help="skip the same-run variants, the other decks, the roofline micro-runs and the per-kernel pass (profiling)")
-    ap.add_argument("--no-other-decks", action="store_true", help="skip the SPE9-like / SPE10-like / Norne-like legs")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: per-time-step statistics, per-kernel pass, same-run variants, other decks, roofline, CPU baseline (off: the headline alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the state the last timed iteration left as DIR/<name>.npy (at most 64 MB in all)")
+    ap.add_argument("--stat-calls", type=int, default=60, help="--full: calls (the K timed ones included) the per-time-step statistics are taken over")
+    ap.add_argument("--only-main", action="store_true", help="--full: skip the same-run variants, the other decks, the roofline micro-runs and the per-kernel pass (profiling)")
+    ap.add_argument("--no-other-decks", action="store_true", help="--full: skip the SPE9-like / SPE10-like / Norne-like legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline")
     ap.add_argument("--force-dist", action="store_true", help="take the domain-decomposition code path (torch.distributed + RCCL communicator) even with one rank")
     ap.add_argument("--cpu-threads", type=int, default=1)
     ap.add_argument("--detail", default=os.path.join(ROOT, "bench_detail.json"), help="where the full record goes (the stdout line stays < 4 KB)")
@@ -157,6 +169,34 @@ def parse_args(argv):
 
 
 MAX_LINE_BYTES = 4096          # the driver keeps 8 KB of stdout; a longer line reaches it without its head
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs: all files of one run together
+DUMP_SAMPLE_SEED = 12345
+
+
+def write_outputs(out_dir, per_cell, other, limit=DUMP_LIMIT_BYTES, suffix=""):
+    """--dump-outputs: every array as <out_dir>/<name><suffix>.npy, in float64 (float32 for integer arrays of 4 bytes or less).  per_cell:
+    arrays whose first axis runs over the cells.  When all files would pass `limit` bytes, the per-cell arrays are cut to the same fixed,
+    seeded sample of cells, whose indices go to cell_index<suffix>.npy.  Returns the names written."""
+    import numpy as np
+
+    def cast(a):
+        a = np.asarray(a)
+        return a if a.dtype in (np.float32, np.float64) else a.astype(np.float32 if a.dtype.itemsize <= 4 else np.float64)
+
+    per_cell = {k: cast(v) for k, v in per_cell.items()}
+    other = {k: cast(v) for k, v in other.items()}
+    room = limit - sum(a.nbytes for a in other.values()) - 256 * (len(per_cell) + len(other) + 1)        # 256: bound on a .npy header
+    nc = len(next(iter(per_cell.values())))
+    if sum(a.nbytes for a in per_cell.values()) > room:
+        per_row = sum(a.nbytes // nc for a in per_cell.values()) + 8
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(nc, max(0, room) // per_row, replace=False))
+        per_cell = {k: v[idx] for k, v in per_cell.items()}
+        per_cell["cell_index"] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = dict(per_cell, **other)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + suffix + ".npy"), np.ascontiguousarray(v))
+    return sorted(arrays)
 
 
 def per_time_step_stats(log, ms, solved, lin):
@@ -375,11 +415,22 @@ def main(argv=None):
         state["it"] = it
         return lin, steps_done, failed
 
-    def timed_run(core, wells, st0, dt, single, nc, kernel_table=False, stat_calls=None):
+    def dump_outputs(model):
+        """--dump-outputs: what a caller of the Newton iteration receives -- the resident state and, with wells, the well state"""
+        core = getattr(model, "m", model)           # a DeviceWellModel wraps the reservoir model
+        s = core.getState()
+        per_cell = {"pressure": s.p, "saturation": s.sat, "rs": s.rs, "rv": s.rv, "hydrocarbon_state": s.hc}
+        other = {}
+        if isinstance(model, W.DeviceWellModel):
+            ws = model.pull_well_state()
+            other = {"well_bhp": ws.bhp, "well_rates": ws.qs, "perf_pressure": ws.perf_press, "perf_rates": ws.perf_rates}
+        write_outputs(args.dump_outputs, per_cell, other, limit=DUMP_LIMIT_BYTES // world, suffix="_rank%d" % rank if world > 1 else "")
+
+    def timed_run(core, wells, st0, dt, single, nc, kernel_table=False, stat_calls=None, dump=False):
         """deck set-up (spin-up time steps) -> W warm-up Newton iterations -> barrier -> exactly K timed Newton iterations -> barrier ->
-        (statistics only) further calls up to stat_calls"""
+        (dump=True) --dump-outputs -> (--full, statistics only) further calls up to stat_calls"""
         model = core if wells is None else W.DeviceWellModel(core, wells, W.WellState(wells, st0.p))
-        stat_calls = max(args.steps, args.stat_calls if stat_calls is None else stat_calls)
+        stat_calls = max(args.steps, args.stat_calls if stat_calls is None else stat_calls) if args.full else args.steps
         # set-up: the run starts the way the reference's time stepper starts one, with a first step of at most 1 d
         # (timestep.initial_timestep_in_days = 1, AdaptiveTimeStepping_impl.hpp:110) that grows by at most 3 per step towards dt; the measurement begins
         # once `spin_up` steps have passed AND the step length has reached dt
@@ -406,6 +457,8 @@ def main(argv=None):
             lin_total += l; steps_done += d; failed += f
         barrier()
         elapsed = time.perf_counter() - t0
+        if dump:
+            dump_outputs(model)
         out = {"lin": lin_total, "steps_done": steps_done, "steps_not_converged": failed, "chopped": state["chopped"], "chopped_timed": state["chopped"] - chopped_before,
                "dt_end": state["dt"], "calls_f32": state.get("calls_f32", 0) - f32_before, "nc": nc}
         solving_ms = solving_mean = None
@@ -422,7 +475,7 @@ def main(argv=None):
             kk = min(K, n)
             out["calls"] = {"ms": [round(float(x), 4) for x in ms], "solved": [int(x) for x in sol], "linear_iterations": [int(x) for x in lit],
                             "event": [e for e, _ in state["log"][:n]], "timed": kk}
-            if n == len(state["log"]):
+            if args.full and n == len(state["log"]):
                 out["per_time_step"] = per_time_step_stats(state["log"], ms, sol, lit)
             if sol[:kk].any():
                 s = sol[:kk]
@@ -481,8 +534,8 @@ def main(argv=None):
         return s
 
     # ---- timed region: exactly K Newton iterations of the headline workload ----
-    extras = rank == 0 and not use_dist and not args.only_main
-    res = timed_run(model, main_wells, st, dt_main, single_main, nc_global, kernel_table=extras)
+    extras = args.full and rank == 0 and not use_dist and not args.only_main
+    res = timed_run(model, main_wells, st, dt_main, single_main, nc_global, kernel_table=extras, dump=args.dump_outputs is not None)
     main_sum = summary(res, dt_main, single_main)
 
     # same-run variants: the reference's default solver, the CPR plug-in's documented defaults, the other arithmetic / Krylov method, the
@@ -564,15 +617,16 @@ def main(argv=None):
     out = detail = None
     if rank == 0:
         nb = grid.nc
-        rowptr, col, _ = model.jacobian()
-        nnzb = int(col.size)
+        nnzb_c = C.c_int32(0)
+        model._chk(model.lib.opmgpu_get_jacobian_nnzb(model.ctx, C.byref(nnzb_c)))          # (the count alone: no copy of the matrix)
+        nnzb = int(nnzb_c.value)
         roof = {}
-        if not args.only_main:
+        if args.full and not args.only_main:
             # ---- roofline of the dominant kernel: the 3x3-block SpMV (k_spmv<S,0>), HIP events on the launch stream.  `achieved` is
             # measured with the matrix rotating over 4 copies (HBM-resident operands, like any deck larger than the 256 MiB Infinity
             # Cache); the back-to-back replay of ONE copy (partly cache-resident at 100^3 in float) is reported beside it.
             for name, sp in (("f32", True), ("f64", False)):
-                _, _, val = model.jacobian()
+                rowptr, col, val = model.jacobian()
                 s = GpuNewtonIteration(prm, device=local_rank)
                 s.load(rowptr, col, val, sp)
                 ms_cold = s.time_kernel(capi.K_SPMV_COLD, reps=40)
@@ -621,7 +675,7 @@ def main(argv=None):
             kernel_table["sum_ms_per_newton"] = float(tot.sum() / max(1, n_calls))
 
         cpu = cpu_all = None
-        if not args.no_cpu_baseline and not use_dist:
+        if args.full and not args.no_cpu_baseline and not use_dist:
             cpu_single = reference_single("ilu0", dt_main)          # the port runs the reference's DEFAULT solver in the reference's arithmetic for it
             cpu = cpu_baseline(grid, tab, st, main_wells, prm, dt_main, cpu_single, threads=args.cpu_threads)
             # the same port with its OpenMP loops (assembly, SpMV, vector updates, and since round 4 the ILU0 factorisation and sweeps by

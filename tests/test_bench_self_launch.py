@@ -71,3 +71,41 @@ def test_per_time_step_statistics_count_whole_steps_only():
 
 def test_bench_line_budget_constant():
     assert _load_bench().MAX_LINE_BYTES == 4096
+
+
+def test_plain_run_is_lean_by_default():
+    """A plain `bench.py --gpus 1 --steps K --warmup W` times the headline alone; everything else is behind --full."""
+    a = _load_bench().parse_args(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert a.steps == 7 and a.warmup == 2 and a.full is False and a.dump_outputs is None
+    a = _load_bench().parse_args(["--full", "--dump-outputs", "some_dir"])
+    assert a.full is True and a.dump_outputs == "some_dir"
+
+
+def test_dump_outputs_types_budget_and_seeded_sample(tmp_path):
+    """bench.write_outputs (--dump-outputs): float32 / float64 files; under the budget everything is written whole, over it the per-cell
+    arrays are cut to the same seeded sample of cells (indices in cell_index.npy) and the files stay within the budget."""
+    import numpy as np
+    bench = _load_bench()
+    nc = 5000
+    rng = np.random.default_rng(1)
+    per_cell = {"pressure": rng.random(nc), "saturation": rng.random((nc, 3)), "hydrocarbon_state": rng.integers(0, 3, nc).astype(np.int8)}
+    other = {"well_bhp": rng.random(5)}
+    names = bench.write_outputs(str(tmp_path / "whole"), per_cell, other)
+    assert names == sorted(["pressure", "saturation", "hydrocarbon_state", "well_bhp"])
+    p = np.load(tmp_path / "whole" / "pressure.npy")
+    assert p.dtype == np.float64 and np.array_equal(p, per_cell["pressure"])
+    hc = np.load(tmp_path / "whole" / "hydrocarbon_state.npy")
+    assert hc.dtype == np.float32 and np.array_equal(hc, per_cell["hydrocarbon_state"])
+    limit = 64 * 1024
+    for run in ("a", "b"):
+        names = bench.write_outputs(str(tmp_path / run), per_cell, other, limit=limit, suffix="_rank1")
+        assert "cell_index" in names
+        files = list((tmp_path / run).iterdir())
+        assert len(files) == 5 and all(f.name.endswith("_rank1.npy") for f in files)
+        assert sum(f.stat().st_size for f in files) <= limit
+    idx = np.load(tmp_path / "a" / "cell_index_rank1.npy")
+    assert idx.dtype == np.float64 and 0 < idx.size < nc and np.all(np.diff(idx) > 0)
+    assert np.array_equal(idx, np.load(tmp_path / "b" / "cell_index_rank1.npy"))
+    s = np.load(tmp_path / "a" / "saturation_rank1.npy")
+    assert np.array_equal(s, per_cell["saturation"][idx.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / "a" / "well_bhp_rank1.npy"), other["well_bhp"])

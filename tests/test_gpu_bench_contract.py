@@ -1,7 +1,7 @@
 """GPU: `python bench.py` on a small deck prints ONE JSON line of < 4 KB that carries the driver's contract (metric / value / unit / n_gpus /
-steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload) plus the `roofline`, `cpu_baseline`
-and `per_time_step` objects and the compact variant map; the full records live in the detail file; the distributed code path with one
-rank prints the same contract."""
+steps / warmup / ms_per_step / higher_is_better / scaling / vs_baseline / dtype / data / config.workload); with --full also the `roofline`,
+`cpu_baseline` and `per_time_step` objects and the compact variant map; the full records live in the detail file; a plain run times the K
+calls and nothing else, and --dump-outputs writes the state they left; the distributed code path with one rank prints the same contract."""
 import json
 import os
 import subprocess
@@ -13,9 +13,8 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _run(*args, detail="bench_detail_test.json"):
-    dpath = os.path.join(ROOT, "gpurun_out", detail)
-    os.makedirs(os.path.dirname(dpath), exist_ok=True)
+def _run(tmp_path, *args):
+    dpath = str(tmp_path / "bench_detail_test.json")
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--nx", "24", "--ny", "24", "--nz", "12", "--steps", "4", "--warmup", "1", "--rate", "10",
                           "--stat-calls", "24", "--detail", dpath, *args], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert out.returncode == 0, out.stderr[-3000:]
@@ -27,8 +26,8 @@ def _run(*args, detail="bench_detail_test.json"):
         return json.loads(lines[0]), json.load(f)
 
 
-def test_bench_line_contract(gpu_lib):
-    d, full = _run()
+def test_bench_line_contract(gpu_lib, tmp_path):
+    d, full = _run(tmp_path, "--full")
     assert d["metric"].startswith("Mcell-updates/sec") and d["unit"] == "Mcell-updates/s"
     assert d["n_gpus"] == 1 and d["steps"] == 4 and d["warmup"] == 1 and d["higher_is_better"] is True and d["scaling"] == "weak"
     assert d["vs_baseline"] is None and d["data"] == "synthetic" and d["dtype"] == "f64"
@@ -73,21 +72,21 @@ def test_bench_line_contract(gpu_lib):
     assert d["decks"] == {}             # the other BASELINE decks ride on the full-size run only
 
 
-def test_bench_distributed_path_with_one_rank(gpu_lib):
-    d, _ = _run("--force-dist", "--only-main", "--no-cpu-baseline", detail="bench_detail_test_dist.json")
+def test_bench_distributed_path_with_one_rank(gpu_lib, tmp_path):
+    d, _ = _run(tmp_path, "--force-dist", "--only-main", "--no-cpu-baseline")
     assert d["n_gpus"] == 1 and d["value"] > 0 and d["config"]["parallelism"] == "1 GPU"
     assert d["config"]["linear_solver"].endswith("gmres(40)") and d["config"]["workload"].endswith("_fivespot")
     assert d["value"] == pytest.approx(d["config"]["cells"] / (d["ms_per_solving_iteration_median"] * 1e-3) / 1e6, rel=2e-3)
 
 
-def test_bench_norne_like_deck_decomposed_over_the_test_transport(gpu_lib):
+def test_bench_norne_like_deck_decomposed_over_the_test_transport(gpu_lib, tmp_path):
     """BASELINE configs[4] decomposed: `bench.py --deck nornelike --gpus 2` launched like the driver launches it (torch.distributed.run, one rank
     per process; here both ranks on cuda:0, coupled by the shared-memory TEST transport and gloo): the ACTNUM deck is cut into slabs of whole
     j-rows balanced by active cells, every vertical well stays on one rank, the run prints the contract line and chops no time step."""
-    dpath = os.path.join(ROOT, "gpurun_out", "bench_detail_test_norne2.json")
+    dpath = str(tmp_path / "bench_detail_test_norne2.json")
     env = dict(os.environ, OPMGPU_COMM_TRANSPORT="shm")
     out = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", "29977",
-                          os.path.join(ROOT, "bench.py"), "--gpus", "2", "--deck", "nornelike", "--steps", "30", "--warmup", "2", "--stat-calls", "30", "--no-cpu-baseline",
+                          os.path.join(ROOT, "bench.py"), "--gpus", "2", "--deck", "nornelike", "--steps", "30", "--warmup", "2", "--stat-calls", "30", "--full", "--no-cpu-baseline",
                           "--detail", dpath], capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     lines = [l for l in out.stdout.splitlines() if l.strip().startswith("{")]
@@ -97,3 +96,26 @@ def test_bench_norne_like_deck_decomposed_over_the_test_transport(gpu_lib):
     assert 0.4 * d["config"]["cells"] < d["config"]["cells_per_gpu"] < 0.6 * d["config"]["cells"]
     assert d["per_time_step"]["chopped_attempts"] == 0 and d["per_time_step"]["time_steps"] >= 5, d["per_time_step"]
     assert d["config"]["linear_its_per_solve"] < 20, d["config"]
+
+
+def test_bench_plain_run_times_the_headline_alone_and_dumps_its_outputs(gpu_lib, tmp_path):
+    """Without --full: the K timed calls and no call after them, none of the extra measurements; --dump-outputs writes the state and the
+    well state the last timed call left, float64 / float32, within 64 MB."""
+    import numpy as np
+    out = tmp_path / "outputs"
+    d, full = _run(tmp_path, "--dump-outputs", str(out))
+    assert d["steps"] == 4 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["dtype"] == "f64" and d["higher_is_better"] is True
+    assert d["value"] == pytest.approx(d["config"]["cells"] / (d["ms_per_solving_iteration_median"] * 1e-3) / 1e6, rel=2e-3)
+    calls = full["main"]["calls"]
+    assert calls["timed"] == 4 and len(calls["ms"]) == 4           # --stat-calls 24 is a --full option: no call after the timed ones
+    assert d["roofline"] is None and d["cpu_baseline"] is None and d["per_time_step"] is None and d["variants"] == {} and d["decks"] == {}
+    assert full["kernel_table"] is None
+    nc = d["config"]["cells"]
+    files = {f.name: f for f in out.iterdir()}
+    assert sum(f.stat().st_size for f in files.values()) <= 64 << 20
+    p, s = np.load(out / "pressure.npy"), np.load(out / "saturation.npy")
+    assert p.dtype == np.float64 and p.shape == (nc,) and s.shape == (nc, 3) and np.all(p > 0)
+    assert np.all(np.isfinite(s)) and np.all(s.sum(axis=1) <= 1 + 1e-9) and "cell_index.npy" not in files
+    for name in ("rs", "rv", "hydrocarbon_state", "well_bhp", "well_rates", "perf_pressure", "perf_rates"):
+        assert np.load(out / (name + ".npy")).dtype in (np.float32, np.float64), name
+    assert np.load(out / "well_bhp.npy").shape == (5,)

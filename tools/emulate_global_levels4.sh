@@ -1,6 +1,6 @@
 #!/bin/bash
 # the weak-scaling deck of 4 ranks on one GPU (4 M cells), preconditioner cut into 4 slabs: coarsest level global or not
-run1() { echo "== $*"; env $1 $2 $3 $4 timeout -k 10 700 python bench.py --only-main --no-cpu-baseline --steps 12 --warmup 2 --detail gpurun_out/weak_detail.json ${@:5} 2>/dev/null \
+run1() { echo "== $*"; env $1 $2 $3 $4 timeout -k 10 700 python bench.py --full --only-main --no-cpu-baseline --steps 12 --warmup 2 --detail ${TMPDIR:-/tmp}/weak_detail.json ${@:5} 2>/dev/null \
       | python -c "import json,sys; d=json.loads(sys.stdin.read()); print(d['value'], d['config']['linear_its_per_solve'], d['per_time_step'])"; }
 run1 A=0 B=0 C=0 D=0 --stack 4 --krylov gmres
 run1 OPMGPU_EMULATE_RANKS=4 OPMGPU_EMULATE_WHAT=3 OPMGPU_EMULATE_GLOBAL_LEVELS=0 D=0 --stack 4 --krylov gmres

@@ -6,7 +6,7 @@ TAG=${1:-rehearsal}
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
 export OPMGPU_COMM_TRANSPORT=shm
-COMMON="--steps 8 --warmup 2 --no-cpu-baseline"
+COMMON="--full --steps 8 --warmup 2 --no-cpu-baseline"
 run() { name=$1; shift; echo "== $name: $*"; timeout -k 10 400 "$@" > $OUT/$name.json 2> $OUT/$name.err; echo "   exit $?"; tail -c 400 $OUT/$name.json; echo; }
 run weak2 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29541 bench.py --gpus 2 --nx 40 --ny 40 --nz 40 $COMMON
 run strong2 python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29542 bench.py --gpus 2 --nx 40 --ny 40 --nz 40 --scaling strong $COMMON

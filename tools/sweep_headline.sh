@@ -2,7 +2,7 @@
 # A/B of the pressure-stage knobs on the HEADLINE configuration (bench deck with its 5-spot, CPR in double + GMRES(40)): one bench.py --only-main
 # run per setting, one line each (Mcell-updates/s, median ms, linear iterations).    gpurun -- 'bash tools/sweep_headline.sh > gpurun_out/sweep.log'
 run() {
-  env "$@" python bench.py --only-main --no-cpu-baseline 2>/dev/null | python -c "
+  env "$@" python bench.py --full --only-main --no-cpu-baseline 2>/dev/null | python -c "
 import sys, json
 d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1])
 print('%-70s value %6.1f  ms %.3f  its %.2f  chopped %s' % ('$*', d['value'], d['ms_per_solving_iteration_median'], d['config'].get('linear_iterations_per_solving_iteration') or 0, d['config'].get('time_steps_chopped')), flush=True)
@@ -11,7 +11,7 @@ print('%-70s value %6.1f  ms %.3f  its %.2f  chopped %s' % ('$*', d['value'], d[
 if [ "$1" = "adapt" ]; then       # the two-setting policy for the correction factor (OPMGPU_AMG_ADAPT), on against off
   rund() {
     tag="$1"; shift
-    python bench.py --only-main --no-cpu-baseline "$@" 2>/dev/null | python -c "
+    python bench.py --full --only-main --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import sys, json
 d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1])
 c=d['config']
@@ -35,7 +35,7 @@ fi
 if [ "$1" = "decks" ]; then       # the correction factor across decks and solver variants
   rund() {
     tag="$1"; shift
-    python bench.py --only-main --no-cpu-baseline "$@" 2>/dev/null | python -c "
+    python bench.py --full --only-main --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import sys, json
 d=json.loads([l for l in sys.stdin.read().splitlines() if l.startswith('{')][-1])
 c=d['config']
