@@ -231,6 +231,23 @@ int opmgpu_point_ilu_apply(opmgpu_ctx* ctx, const double* d3, double* v3, double
  * section 5: 1.9, or on matrices of the model's own assembly the per-time-step choice between 1.9 and 2.3 -- and, after a failed solve, which is
  * repeated with 1.0, from the ladder 1.0 / 1.45 / 1.9 / 2.3; external matrices of the B1 path keep 1.9).  OPMGPU_EINVAL before the first CPR solve. */
 int opmgpu_cpr_correction_factors(opmgpu_ctx* ctx, double* into_level0, double* below);
+/* diagnostics of the pressure hierarchy of the last CPR solve, in the precision it ran in (the float work set under single precision or
+ * preconditioner_single).  They change nothing the next solve sees; OPMGPU_EINVAL before the first CPR solve.  tests/test_gpu_cpr_stages.py
+ * checks every level and application against a float64 restatement (tests/amg_reference.py).
+ *   opmgpu_cpr_levels: *nlevels in = room in n / nnz (may be 0), out = number of levels; n[l] = rows of level l (level 0 counts its well
+ *     border rows), nnz[l] = its stored entries; *nw = wells of the border (0: no border).
+ *   opmgpu_cpr_level_get: level l as CSR with values widened to double.  Level 0 in caller numbering -- cells in caller order, then one
+ *     row per well --, coarse levels in their own.  agg[n] = coarse row of every row (not for the last level); dense_inv = the coarsest
+ *     level's explicit inverse, row-major n x n, when it has one (n <= 96).  Any output pointer may be NULL.
+ *   opmgpu_cpr_vcycle_apply: x = one V-cycle from a zero start on the level-0 vector b (n[0] entries, numbered like level 0).
+ *   opmgpu_cpr_apply: v3 = the whole two-stage preconditioner as a solve applies it (d3 / v3 block-interleaved like opmgpu_ilu0_apply).
+ *   opmgpu_cpr_elliptic_ilu_apply: x = cpr_relax (L U)^-1 b with the point ILU0 of A_p that preconditions the inner elliptic solve
+ *     (cpr_use_amg = 0, cpr_max_ell_iter > 0); border rows by their own diagonal.  b / x numbered like level 0. */
+int opmgpu_cpr_levels(opmgpu_ctx* ctx, int32_t* nlevels, int32_t* n, int64_t* nnz, int32_t* nw);
+int opmgpu_cpr_level_get(opmgpu_ctx* ctx, int level, int32_t* rowptr, int32_t* col, double* val, int32_t* agg, double* dense_inv);
+int opmgpu_cpr_vcycle_apply(opmgpu_ctx* ctx, const double* b, double* x);
+int opmgpu_cpr_apply(opmgpu_ctx* ctx, const double* d3, double* v3);
+int opmgpu_cpr_elliptic_ilu_apply(opmgpu_ctx* ctx, const double* b, double* x);
 
 /* ------------------------------------------------------------------------------------------
  * B2 boundary: BlackoilModel hooks (BlackoilModelBase_impl.hpp:239-326: assemble ->

@@ -207,6 +207,15 @@ struct Border {
     const int32_t *connpos = nullptr, *perf_row = nullptr, *perf_of_row = nullptr, *perf_well = nullptr;
     const S *bcol = nullptr, *crow = nullptr, *dw = nullptr;
 };
+template <class S>
+Border<S> border_of(const AmgLevel<S>& F, int gcells)
+{
+    Border<S> B;
+    if (F.nw == 0) return B;
+    B.nw = F.nw; B.n = F.n; B.gcells = gcells; B.connpos = F.b_connpos; B.perf_row = F.b_perf_row; B.perf_of_row = F.b_perf_of_row; B.perf_well = F.b_perf_well;
+    B.bcol = F.val.p + F.nentries; B.crow = B.bcol + F.nperf; B.dw = B.crow + F.nperf;
+    return B;
+}
 // cell row: the column entry towards its well's unknown
 template <class S, class XF>
 __device__ __forceinline__ S border_cell(const Border<S>& B, int row, XF xfun)
@@ -422,16 +431,27 @@ __global__ __launch_bounds__(kBlock) void k_amg_prolong(int n, const int32_t* __
 // 2 x 72 KiB of the 160 KiB per CU); one workgroup of 1024 threads, no pivoting (the pressure operators are diagonally
 // dominant M-matrix-like).  Thread (i0, j) owns column j of rows i0, i0 + rows_per_pass, ...: no integer division in the loop.
 constexpr int kDenseMax = 96;
+// A bordered level 0 that is also the coarsest (a handful of cells and wells) is inverted whole: n = cells + wells, the SELL part
+// fills rows [0, B.n), the border entries the well rows and columns (each at its own position: no two threads add to one element).
 template <class S, int kRows>
 __global__ __launch_bounds__(1024) void k_dense_invert(int n, int log2_np, const int32_t* __restrict__ slice_ptr, const int32_t* __restrict__ col,
-                                                       const S* __restrict__ val, double* __restrict__ inv)
+                                                       const S* __restrict__ val, double* __restrict__ inv, Border<S> B = Border<S>())
 {
     extern __shared__ double a[];    // 2 x [n][n]
     for (int t = threadIdx.x; t < n * n; t += blockDim.x) a[t] = 0.0;
     __syncthreads();
-    for (int row = threadIdx.x; row < n; row += blockDim.x) {
+    const int ncell = B.nw ? B.n : n;
+    for (int row = threadIdx.x; row < ncell; row += blockDim.x) {
         const int base = slice_ptr[row >> 6], width = slice_ptr[(row >> 6) + 1] - base, lane = row & 63;
         for (int k = 0; k < width; ++k) { const long e = long(base + k) * 64 + lane; a[row * n + col[e]] += double(val[e]); }   // padding entries carry 0
+    }
+    if (B.nw) {
+        for (int j = threadIdx.x; j < B.connpos[B.nw]; j += blockDim.x) {
+            const int r = B.perf_row[j], w = B.n + B.perf_well[j];
+            a[r * n + w] = double(B.bcol[j]);
+            a[w * n + r] = double(B.crow[j]);
+        }
+        for (int k = threadIdx.x; k < B.nw; k += blockDim.x) a[(B.n + k) * n + B.n + k] = double(B.dw[k]);
     }
     __syncthreads();
     const int np = 1 << log2_np, j = threadIdx.x & (np - 1), i0 = threadIdx.x >> log2_np, istep = blockDim.x >> log2_np;
@@ -512,7 +532,11 @@ void AmgHierarchy<S>::setup(const Plan& P, const int32_t* d_slice_ptr, const int
     const int nwb = (border && border->nw > 0 && border->nw <= kDenseMax / 2) ? border->nw : 0;
     const int npb = nwb ? border->nperf : 0;
     std::vector<int32_t> perf_of(P.nb, -1);
-    for (int j = 0; j < npb; ++j) perf_of[border->perf_row[j]] = j;
+    for (int j = 0; j < npb; ++j) {
+        // one perforation per cell: the row kernels see ONE border column per cell (perf_of_row), the dense coarsest inverse scatters each
+        if (perf_of[border->perf_row[j]] >= 0) throw HipError(OPMGPU_EINVAL, "CPR well border: a cell is perforated by two wells");
+        perf_of[border->perf_row[j]] = j;
+    }
     HostCsr A;
     A.n = P.nb + nwb; A.rowptr.assign(A.n + 1, 0);
     for (int r = 0; r < P.nb; ++r) A.rowptr[r + 1] = A.rowptr[r] + P.rowlen[r] + (perf_of[r] >= 0 ? 1 : 0);
@@ -602,11 +626,13 @@ void AmgHierarchy<S>::setup(const Plan& P, const int32_t* d_slice_ptr, const int
         Lc->own_slice_ptr.upload(sp, stream); Lc->own_col.upload(scol, stream);
         Lc->slice_ptr = Lc->own_slice_ptr.p; Lc->col = Lc->own_col.p;
         Lc->diag_entry.upload(dent, stream);
+        Lc->h_rowlen.resize(C.n);
+        for (int r = 0; r < C.n; ++r) Lc->h_rowlen[r] = C.rowptr[r + 1] - C.rowptr[r];
         levels.push_back(std::move(L));
         L = std::move(Lc);
         A = std::move(C);
     }
-    n_coarsest = levels.back()->n;
+    n_coarsest = levels.back()->ntot();      // a bordered level 0 that is also the coarsest: its well rows are part of the coarse solve
     if (n_coarsest <= kDenseMax)        // > 64 KiB of dynamic LDS must be requested explicitly
         OPMGPU_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(&k_dense_invert<S, 12>), hipFuncAttributeMaxDynamicSharedMemorySize, 2 * kDenseMax * kDenseMax * int(sizeof(double))));
     if (std::getenv("OPMGPU_VERBOSE")) { std::fprintf(stderr, "[opmgpu] AMG levels:"); for (int n : level_sizes) std::fprintf(stderr, " %d", n); std::fprintf(stderr, "\n"); }
@@ -652,9 +678,10 @@ void AmgHierarchy<S>::galerkin(bool coarse_levels, const std::function<void()>& 
             OPMGPU_HIP(hipStreamWaitEvent(inv_stream, ev_inv[0], 0));
             q = inv_stream;
         }
-        int lg = 0; while ((1 << lg) < B.n) ++lg;
-        if (B.n <= 64) hipLaunchKernelGGL((k_dense_invert<S, 4>), dim3(1), dim3(1024), size_t(2) * B.n * B.n * sizeof(double), q, B.n, lg, B.slice_ptr, B.col, B.val.p, dense_inv.p);
-        else hipLaunchKernelGGL((k_dense_invert<S, 12>), dim3(1), dim3(1024), size_t(2) * B.n * B.n * sizeof(double), q, B.n, lg, B.slice_ptr, B.col, B.val.p, dense_inv.p);
+        const int nc = n_coarsest;          // == B.ntot()
+        int lg = 0; while ((1 << lg) < nc) ++lg;
+        if (nc <= 64) hipLaunchKernelGGL((k_dense_invert<S, 4>), dim3(1), dim3(1024), size_t(2) * nc * nc * sizeof(double), q, nc, lg, B.slice_ptr, B.col, B.val.p, dense_inv.p, border_of(B, 0));
+        else hipLaunchKernelGGL((k_dense_invert<S, 12>), dim3(1), dim3(1024), size_t(2) * nc * nc * sizeof(double), q, nc, lg, B.slice_ptr, B.col, B.val.p, dense_inv.p, border_of(B, 0));
         OPMGPU_HIP(hipGetLastError());
         if (inv_overlap) { OPMGPU_HIP(hipEventRecord(ev_inv[1], inv_stream)); inv_pending = true; }
     }
@@ -750,12 +777,15 @@ void AmgHierarchy<S>::vcycle(const SolveCtl* ctl, bool level0_presmoothed)
     AmgLevel<S>& B = *levels.back();
     if (n_coarsest <= kDenseMax) {
         join_inverse();
-        hipLaunchKernelGGL((k_dense_apply<S>), dim3((B.n + 3) / 4), dim3(kBlock), 0, stream, B.n, dense_inv.p, B.b.p, B.x.p, ctl);
-    } else {        // coarsening stalled above the dense limit: a few Jacobi sweeps stand in for the coarse solve
-        hipLaunchKernelGGL((k_amg_smooth0<S>), dim3(grid_for(B.n)), dim3(kBlock), 0, stream, B.n, om, B.dinv.p, B.b.p, B.x.p, ctl);
+        hipLaunchKernelGGL((k_dense_apply<S>), dim3((n_coarsest + 3) / 4), dim3(kBlock), 0, stream, n_coarsest, dense_inv.p, B.b.p, B.x.p, ctl);
+    } else {        // coarsening stalled above the dense limit: a few Jacobi sweeps stand in for the coarse solve (on the border too when it is level 0)
+        const int gb = grid_for(B.n);
+        hipLaunchKernelGGL((k_amg_smooth0<S>), dim3(grid_for(B.ntot())), dim3(kBlock), 0, stream, B.ntot(), om, B.dinv.p, B.b.p, B.x.p, ctl);
         for (int s = 0; s < coarse_sweeps; ++s) {
-            hipLaunchKernelGGL((k_amg_residual<S, 1>), dim3(grid_for(B.n)), dim3(kBlock), 0, stream, B.n, B.slice_ptr, B.col, B.val.p, B.b.p, B.x.p, om, B.dinv.p, B.x2.p, ctl);
-            hipLaunchKernelGGL((k_amg_residual<S, 1>), dim3(grid_for(B.n)), dim3(kBlock), 0, stream, B.n, B.slice_ptr, B.col, B.val.p, B.b.p, B.x2.p, om, B.dinv.p, B.x.p, ctl);
+            hipLaunchKernelGGL((k_amg_residual<S, 1>), dim3(gb + B.nw), dim3(kBlock), 0, stream, B.n, B.slice_ptr, B.col, B.val.p, B.b.p, B.x.p, om, B.dinv.p, B.x2.p, ctl,
+                               (const int32_t*)nullptr, (const S*)nullptr, S(0), border_of(B, gb));
+            hipLaunchKernelGGL((k_amg_residual<S, 1>), dim3(gb + B.nw), dim3(kBlock), 0, stream, B.n, B.slice_ptr, B.col, B.val.p, B.b.p, B.x2.p, om, B.dinv.p, B.x.p, ctl,
+                               (const int32_t*)nullptr, (const S*)nullptr, S(0), border_of(B, gb));
         }
     }
     mark("coarsest");

@@ -40,6 +40,7 @@ struct AmgLevel {
     DevArray<int32_t> contrib_ptr, contrib_idx; // fine entries summed into every coarse entry (Galerkin), entries sorted by trip count
     DevArray<int32_t> contrib_diag;             // per (sorted) coarse entry: its row if it is the diagonal one, else -1
     int n_coarse = 0, nentries_coarse = 0, galerkin_lpe = 1;
+    std::vector<int32_t> h_rowlen;              // coarse levels: real slots of every row (host copy, diagnostics; level 0: the plan's rowlen)
     // Level 0 only -- BORDERED operator [A_p Bc; Cr Dw]: one extra unknown per well (its bhp) that couples the well's perforated cells
     // like the reference's explicit Schur complement does, without filling the borrowed block-plan structure with a clique per well.
     // Vectors of a bordered level have n + nw entries (well k at index n + k); the border values live behind the SELL values:
@@ -90,7 +91,7 @@ public:
     double graph_key[6] = { 0, 0, 0, 0, 0, 0 };
     bool graph_pre = false, use_graph = false;
     std::vector<std::unique_ptr<AmgLevel<S>>> levels;
-    DevArray<double> dense_inv;      // coarsest: explicit inverse (double), n_c x n_c
+    DevArray<double> dense_inv;      // coarsest: explicit inverse (double), n_c x n_c (border rows included when level 0 is the coarsest)
     // the inversion runs on inv_stream behind the work that follows galerkin(); the first user of dense_inv joins it
     hipStream_t inv_stream = nullptr;
     hipEvent_t ev_inv[2] = { nullptr, nullptr };

@@ -301,6 +301,191 @@ int opmgpu_cpr_correction_factors(opmgpu_ctx* c, double* into_level0, double* be
     return OPMGPU_OK;
 }
 
+} // extern "C"
+
+// ---------------------------------------------------------------- diagnostics of the CPR pressure hierarchy (tests/test_gpu_cpr_stages.py)
+// They read the hierarchy of the last CPR solve in the precision it ran in and leave the solver's state as they found it: the x / x2 roles
+// of every level and level 0's right-hand side are restored, the correction factors and `tuned` are not touched.
+template <class S> static AmgHierarchy<S>* cpr_hierarchy(LinSolver& ls)
+{
+    SolverWork<S>& w = ls.work<S>();
+    return (w.amg && w.amg->ready()) ? w.amg.get() : nullptr;
+}
+static bool cpr_float(opmgpu_ctx* c) { return c->cur_single == 1 || c->ls->mixed; }
+
+template <class S> static int cpr_levels_t(LinSolver& ls, int32_t* nlevels, int32_t* n, int64_t* nnz, int32_t* nw)
+{
+    AmgHierarchy<S>* H = cpr_hierarchy<S>(ls);
+    if (!H) return OPMGPU_EINVAL;
+    const int nl = int(H->levels.size());
+    const int cap = *nlevels;
+    *nlevels = nl;
+    if (nw) *nw = H->levels[0]->nw;
+    for (int l = 0; l < nl && l < cap; ++l) {
+        const AmgLevel<S>& F = *H->levels[l];
+        int64_t cnt = 2 * int64_t(F.nperf) + F.nw;
+        if (l == 0) for (int r = 0; r < F.n; ++r) cnt += ls.plan.rowlen[r];
+        else for (int r = 0; r < F.n; ++r) cnt += F.h_rowlen[r];
+        if (n) n[l] = F.ntot();
+        if (nnz) nnz[l] = cnt;
+    }
+    return OPMGPU_OK;
+}
+
+template <class S> static int cpr_level_get_t(LinSolver& ls, int level, int32_t* rowptr, int32_t* col, double* val, int32_t* agg, double* dense_inv)
+{
+    AmgHierarchy<S>* H = cpr_hierarchy<S>(ls);
+    if (!H || level < 0 || level >= int(H->levels.size())) return OPMGPU_EINVAL;
+    const hipStream_t st = ls.stream;
+    H->join_inverse();
+    const AmgLevel<S>& F = *H->levels[level];
+    const int n = F.n, nw = F.nw, nt = F.ntot(), nperf = F.nperf;
+    std::vector<int32_t> sp(F.nslices + 1), sc(F.nentries), connpos(nw + 1, 0), perf_row(nperf);
+    std::vector<S> sv(F.nentries + 2 * size_t(nperf) + nw);
+    OPMGPU_HIP(hipMemcpyAsync(sp.data(), F.slice_ptr, sp.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    OPMGPU_HIP(hipMemcpyAsync(sc.data(), F.col, sc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    F.val.download(sv.data(), sv.size(), st);
+    if (nw) {
+        OPMGPU_HIP(hipMemcpyAsync(connpos.data(), F.b_connpos, connpos.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+        OPMGPU_HIP(hipMemcpyAsync(perf_row.data(), F.b_perf_row, perf_row.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    }
+    const bool last = level + 1 == int(H->levels.size());
+    std::vector<int32_t> ag;
+    if (!last) { ag.resize(nt); F.agg.download(ag.data(), nt, st); }
+    std::vector<double> inv;
+    if (last && H->n_coarsest <= 96) { inv.resize(size_t(nt) * nt); H->dense_inv.download(inv.data(), inv.size(), st); }
+    OPMGPU_HIP(hipStreamSynchronize(st));
+    // numbering of the output: level 0 in caller order (cells), then the wells; coarse levels their own
+    std::vector<int32_t> internal(nt), outer(nt);
+    for (int i = 0; i < nt; ++i) internal[i] = outer[i] = i;
+    if (level == 0) for (int i = 0; i < n; ++i) { internal[i] = ls.plan.pos[i]; outer[ls.plan.pos[i]] = i; }
+    std::vector<int32_t> perf_of(n, -1), well_of(nperf, 0);
+    for (int k = 0; k < nw; ++k) for (int j = connpos[k]; j < connpos[k + 1]; ++j) { perf_of[perf_row[j]] = j; well_of[j] = k; }
+    const S* bcol = sv.data() + F.nentries; const S* crow = bcol + nperf; const S* dw = crow + nperf;
+    int64_t q = 0;
+    if (rowptr) rowptr[0] = 0;
+    auto put = [&](int c, double v) { if (col) col[q] = outer[c]; if (val) val[q] = v; ++q; };
+    for (int o = 0; o < nt; ++o) {
+        const int r = internal[o];
+        if (r < n) {
+            const int len = level == 0 ? int(ls.plan.rowlen[r]) : F.h_rowlen[r];
+            for (int k = 0; k < len; ++k) { const long e = long(sp[r >> 6] + k) * 64 + (r & 63); put(sc[e], double(sv[e])); }
+            if (nw && perf_of[r] >= 0) put(n + well_of[perf_of[r]], double(bcol[perf_of[r]]));
+        } else {
+            const int k = r - n;
+            for (int j = connpos[k]; j < connpos[k + 1]; ++j) put(perf_row[j], double(crow[j]));
+            put(r, double(dw[k]));
+        }
+        if (rowptr) rowptr[o + 1] = int32_t(q);
+    }
+    if (agg && !last) for (int o = 0; o < nt; ++o) agg[o] = ag[internal[o]];
+    if (dense_inv && !inv.empty())          // the device keeps it transposed (k_dense_apply): inv[j * n + i] = Ainv(i, j)
+        for (int i = 0; i < nt; ++i) for (int j = 0; j < nt; ++j) dense_inv[size_t(outer[i]) * nt + outer[j]] = inv[size_t(j) * nt + i];
+    return OPMGPU_OK;
+}
+
+// the x / x2 buffers of every level (a cycle swaps them; the solver's captured cycle relies on their roles)
+template <class S> static std::vector<std::pair<S*, S*>> cpr_roles(AmgHierarchy<S>& H)
+{
+    std::vector<std::pair<S*, S*>> r;
+    for (auto& L : H.levels) r.emplace_back(L->x.p, L->x2.p);
+    return r;
+}
+template <class S> static void cpr_restore_roles(AmgHierarchy<S>& H, const std::vector<std::pair<S*, S*>>& r)
+{
+    for (size_t l = 0; l < r.size(); ++l) { H.levels[l]->x.p = r[l].first; H.levels[l]->x2.p = r[l].second; }
+}
+
+template <class S> static int cpr_vcycle_apply_t(LinSolver& ls, const double* b, double* x)
+{
+    AmgHierarchy<S>* H = cpr_hierarchy<S>(ls);
+    if (!H) return OPMGPU_EINVAL;
+    AmgLevel<S>& L0 = *H->levels[0];
+    const int n = L0.n, nt = L0.ntot();
+    const hipStream_t st = ls.stream;
+    std::vector<S> hb(nt), hx(nt);
+    for (int i = 0; i < n; ++i) hb[ls.plan.pos[i]] = S(b[i]);
+    for (int k = n; k < nt; ++k) hb[k] = S(b[k]);
+    DevArray<S> keep; keep.alloc(nt);
+    OPMGPU_HIP(hipMemcpyAsync(keep.p, L0.b.p, nt * sizeof(S), hipMemcpyDeviceToDevice, st));
+    const auto roles = cpr_roles(*H);
+    L0.b.upload(hb.data(), nt, st);
+    H->vcycle_graph(nullptr, false);
+    OPMGPU_HIP(hipMemcpyAsync(hx.data(), L0.x.p, nt * sizeof(S), hipMemcpyDeviceToHost, st));
+    cpr_restore_roles(*H, roles);
+    OPMGPU_HIP(hipMemcpyAsync(L0.b.p, keep.p, nt * sizeof(S), hipMemcpyDeviceToDevice, st));
+    OPMGPU_HIP(hipStreamSynchronize(st));
+    for (int i = 0; i < n; ++i) x[i] = double(hx[ls.plan.pos[i]]);
+    for (int k = n; k < nt; ++k) x[k] = double(hx[k]);
+    return OPMGPU_OK;
+}
+
+template <class S> static int cpr_apply_t(LinSolver& ls, const double* d3, double* v3, double relax)
+{
+    AmgHierarchy<S>* H = cpr_hierarchy<S>(ls);
+    if (!H) return OPMGPU_EINVAL;
+    SolverWork<S>& w = ls.work<S>();
+    const auto roles = cpr_roles(*H);
+    ls.vec_from_host<S>(d3, VEC_BLOCK_INTERLEAVED, w.p.p);
+    ls.cpr_apply<S>(w.p.p, w.y.p, relax, nullptr);
+    ls.vec_to_host<S>(w.y.p, VEC_BLOCK_INTERLEAVED, v3);
+    cpr_restore_roles(*H, roles);
+    return OPMGPU_OK;
+}
+
+template <class S> static int cpr_elliptic_ilu_apply_t(LinSolver& ls, const double* b, double* x)
+{
+    AmgHierarchy<S>* H = cpr_hierarchy<S>(ls);
+    SolverWork<S>& w = ls.work<S>();
+    if (!H || !w.plu.p || !ls.ell.inner || ls.ell.use_amg) return OPMGPU_EINVAL;
+    const AmgLevel<S>& L0 = *H->levels[0];
+    const int n = L0.n, nt = L0.ntot();
+    const hipStream_t st = ls.stream;
+    std::vector<S> hb(nt), hx(nt);
+    for (int i = 0; i < n; ++i) hb[ls.plan.pos[i]] = S(b[i]);
+    for (int k = n; k < nt; ++k) hb[k] = S(b[k]);
+    DevArray<S> db, dx; db.alloc(nt); dx.alloc(nt);
+    db.upload(hb.data(), nt, st);
+    dx.zero(st);
+    ls.elliptic_ilu_apply<S>(db.p, dx.p);
+    dx.download(hx.data(), nt, st);
+    OPMGPU_HIP(hipStreamSynchronize(st));
+    for (int i = 0; i < n; ++i) x[i] = double(hx[ls.plan.pos[i]]);
+    for (int k = n; k < nt; ++k) x[k] = double(hx[k]);
+    return OPMGPU_OK;
+}
+
+extern "C" {
+
+int opmgpu_cpr_elliptic_ilu_apply(opmgpu_ctx* c, const double* b, double* x)
+{
+    if (!c || !c->ls || !b || !x) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { return cpr_float(c) ? cpr_elliptic_ilu_apply_t<float>(*c->ls, b, x) : cpr_elliptic_ilu_apply_t<double>(*c->ls, b, x); });
+}
+int opmgpu_cpr_levels(opmgpu_ctx* c, int32_t* nlevels, int32_t* n, int64_t* nnz, int32_t* nw)
+{
+    if (!c || !c->ls || !nlevels) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { return cpr_float(c) ? cpr_levels_t<float>(*c->ls, nlevels, n, nnz, nw) : cpr_levels_t<double>(*c->ls, nlevels, n, nnz, nw); });
+}
+int opmgpu_cpr_level_get(opmgpu_ctx* c, int level, int32_t* rowptr, int32_t* col, double* val, int32_t* agg, double* dense_inv)
+{
+    if (!c || !c->ls) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { return cpr_float(c) ? cpr_level_get_t<float>(*c->ls, level, rowptr, col, val, agg, dense_inv)
+                                                  : cpr_level_get_t<double>(*c->ls, level, rowptr, col, val, agg, dense_inv); });
+}
+int opmgpu_cpr_vcycle_apply(opmgpu_ctx* c, const double* b, double* x)
+{
+    if (!c || !c->ls || !b || !x) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { return cpr_float(c) ? cpr_vcycle_apply_t<float>(*c->ls, b, x) : cpr_vcycle_apply_t<double>(*c->ls, b, x); });
+}
+int opmgpu_cpr_apply(opmgpu_ctx* c, const double* d3, double* v3)
+{
+    if (!c || !c->ls || !d3 || !v3) return OPMGPU_EINVAL;
+    if (!c->factored) return fail(c, OPMGPU_EINVAL, "no factored CPR solve yet");
+    const double relax = c->prm.cpr_relax * c->prm.cpr_stage2_relax;          // what solve_loaded hands the solvers under CPR
+    return guarded(c, [&]() { return cpr_float(c) ? cpr_apply_t<float>(*c->ls, d3, v3, relax) : cpr_apply_t<double>(*c->ls, d3, v3, relax); });
+}
+
 int opmgpu_get_matbalscale(opmgpu_ctx* c, double* scale3)
 {
     if (!c || !c->model || !scale3) return OPMGPU_EINVAL;

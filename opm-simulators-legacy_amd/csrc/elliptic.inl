@@ -171,6 +171,31 @@ template <class S> void LinSolver::elliptic_factor()
     }
 }
 
+// out = relax (LU)^-1 d with the point ILU0 of A_p (elliptic_factor); a border row of the level is preconditioned by its own diagonal
+template <class S> void LinSolver::elliptic_ilu_apply(const S* d, S* out)
+{
+    SolverWork<S>& w = work<S>();
+    AmgLevel<S>& L0 = *w.amg->levels[0];
+    const int n = L0.n, nw = L0.nw;
+    const S wrel = S(ell.relax);
+    const int L = plan.nlevels, n0 = plan.level_ptr[1];
+    if (L == 1) {
+        hipLaunchKernelGGL((k_pilu_lower<S>), dim3(grid_for(n0)), dim3(kBlock), 0, stream, 0, n0, 0, 1, wrel, dp.slice_ptr.p, dp.col.p, dp.nlower.p, (const S*)w.plu.p, d, out);
+    } else {
+        for (int l = 1; l < L; ++l) {
+            const int lo = plan.level_ptr[l], hi = plan.level_ptr[l + 1];
+            if (hi > lo) hipLaunchKernelGGL((k_pilu_lower<S>), dim3(grid_for(hi - lo)), dim3(kBlock), 0, stream, lo, hi, n0, int(l == L - 1), wrel, dp.slice_ptr.p, dp.col.p,
+                                            dp.nlower.p, (const S*)w.plu.p, d, out);
+        }
+        for (int l = L - 2; l >= 0; --l) {
+            const int lo = plan.level_ptr[l], hi = plan.level_ptr[l + 1];
+            if (hi > lo) hipLaunchKernelGGL((k_pilu_upper<S>), dim3(grid_for(hi - lo)), dim3(kBlock), 0, stream, lo, hi, n0, wrel, dp.slice_ptr.p, dp.col.p, dp.nlower.p,
+                                            dp.rowlen.p, (const S*)w.plu.p, d, out);
+        }
+    }
+    if (nw) hipLaunchKernelGGL((k_ell_border_diag<S>), dim3(grid_for(nw)), dim3(kBlock), 0, stream, n, nw, wrel, (const S*)L0.dinv.p, d, out);
+}
+
 // levels[0].x = approximate solution of A_p x = levels[0].b from x = 0 (see the head of this file)
 template <class S> void LinSolver::elliptic_solve()
 {
@@ -190,7 +215,6 @@ template <class S> void LinSolver::elliptic_solve()
     double* const parts = ell_parts.p; double* const red = parts + size_t(2) * kMaxPart;
     EllBorder B = { nw, gcells, L0.b_connpos, L0.b_perf_row, L0.b_perf_of_row, L0.b_perf_well };
     const S* const bcol = L0.val.p + L0.nentries; const S* const crow = bcol + L0.nperf; const S* const dw = crow + L0.nperf;
-    const S wrel = S(ell.relax);
     auto spmv = [&](const S* in, S* out) {
         hipLaunchKernelGGL((k_ell_spmv<S>), dim3(gcells + nw), dim3(kBlock), 0, stream, n, L0.slice_ptr, L0.col, (const S*)L0.val.p, in, out, B, bcol, crow, dw);
     };
@@ -202,22 +226,7 @@ template <class S> void LinSolver::elliptic_solve()
             OPMGPU_HIP(hipMemcpyAsync(out, H.levels[0]->x.p, size_t(N) * sizeof(S), hipMemcpyDeviceToDevice, stream));
             return;
         }
-        const int L = plan.nlevels, n0 = plan.level_ptr[1];
-        if (L == 1) {
-            hipLaunchKernelGGL((k_pilu_lower<S>), dim3(grid_for(n0)), dim3(kBlock), 0, stream, 0, n0, 0, 1, wrel, dp.slice_ptr.p, dp.col.p, dp.nlower.p, (const S*)w.plu.p, d, out);
-        } else {
-            for (int l = 1; l < L; ++l) {
-                const int lo = plan.level_ptr[l], hi = plan.level_ptr[l + 1];
-                if (hi > lo) hipLaunchKernelGGL((k_pilu_lower<S>), dim3(grid_for(hi - lo)), dim3(kBlock), 0, stream, lo, hi, n0, int(l == L - 1), wrel, dp.slice_ptr.p, dp.col.p,
-                                                dp.nlower.p, (const S*)w.plu.p, d, out);
-            }
-            for (int l = L - 2; l >= 0; --l) {
-                const int lo = plan.level_ptr[l], hi = plan.level_ptr[l + 1];
-                if (hi > lo) hipLaunchKernelGGL((k_pilu_upper<S>), dim3(grid_for(hi - lo)), dim3(kBlock), 0, stream, lo, hi, n0, wrel, dp.slice_ptr.p, dp.col.p, dp.nlower.p,
-                                                dp.rowlen.p, (const S*)w.plu.p, d, out);
-            }
-        }
-        if (nw) hipLaunchKernelGGL((k_ell_border_diag<S>), dim3(grid_for(nw)), dim3(kBlock), 0, stream, n, nw, wrel, (const S*)L0.dinv.p, d, out);
+        elliptic_ilu_apply<S>(d, out);
     };
     // the two sums a step needs, on the host
     auto fetch2 = [&](double& s0, double& s1) {

@@ -3208,6 +3208,7 @@ double LinSolver::time_kernel(int kernel, int reps, int single_precision)
     template void LinSolver::spmv<S>(const S*, S*);                                      \
     template void LinSolver::spmv_at<S>(const S*, S*, const S*, const int32_t*);        \
     template void LinSolver::cpr_prepare<S>();                                           \
+    template void LinSolver::elliptic_ilu_apply<S>(const S*, S*);                         \
     template void LinSolver::cpr_reference_transform<S>();                               \
     template void LinSolver::cpr_reweigh_rows<S>(const int32_t*, int);                   \
     template const S* LinSolver::pre_matrix<S>();                                        \

@@ -159,6 +159,7 @@ public:
     DevArray<double> ell_parts;
     template <class S> void elliptic_factor();
     template <class S> void elliptic_solve();
+    template <class S> void elliptic_ilu_apply(const S* d, S* out);   // out = relax (LU)^-1 d: the point ILU0 of A_p (border rows: their diagonal)
     template <class S> void cpr_apply(const S* d, S* v, double relax, const SolveCtl* ctl, const double* cr_given = nullptr);
     // opmgpu_params.cpr_reference_transform: the reference's CPR formulation (NewtonIterationUtilities.cpp:253-287 formEllipticSystem,
     // NewtonIterationBlackoilCPR.cpp:117-131): the WHOLE system is row-transformed by the per-cell matrix L -- first row = the sum of the

@@ -160,6 +160,11 @@ SIGNATURES = {
     "opmgpu_get_matbalscale": (C.c_int, [C.c_void_p, _dp]),
     "opmgpu_cpr_elliptic_stats": (C.c_int, [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "opmgpu_cpr_correction_factors": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "opmgpu_cpr_levels": (C.c_int, [C.c_void_p, _ip, _ip, C.POINTER(C.c_int64), _ip]),
+    "opmgpu_cpr_level_get": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, _dp, _ip, _dp]),
+    "opmgpu_cpr_vcycle_apply": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "opmgpu_cpr_apply": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "opmgpu_cpr_elliptic_ilu_apply": (C.c_int, [C.c_void_p, _dp, _dp]),
     "opmgpu_point_ilu_apply": (C.c_int, [C.c_void_p, _dp, _dp, C.c_double]),
     "opmgpu_comm_set_coarse_blocks": (C.c_int, [C.c_void_p, C.c_int, _ip]),
     "opmgpu_nonlinear_iteration": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int, C.POINTER(NewtonCtl), C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, _dp]),

@@ -46,7 +46,53 @@ def _raise(lib, ctx, st):
     raise RuntimeError("opmgpu status %d: %s" % (st, msg))
 
 
-class GpuNewtonIteration:
+class _CprDiagnostics:
+    """The pressure hierarchy of the last CPR solve (opmgpu_cpr_levels / _level_get / _vcycle_apply / _apply); needs self.lib, self.ctx
+    and an error check self._status(st)."""
+
+    def cpr_levels(self):
+        """(level sizes, stored entries per level, wells of the level-0 border)"""
+        nl, nw = C.c_int32(0), C.c_int32(0)
+        self._status(self.lib.opmgpu_cpr_levels(self.ctx, C.byref(nl), None, None, C.byref(nw)))
+        n, nnz = np.zeros(nl.value, np.int32), np.zeros(nl.value, np.int64)
+        self._status(self.lib.opmgpu_cpr_levels(self.ctx, C.byref(nl), capi.iptr(n), nnz.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(nw)))
+        return n, nnz, nw.value
+
+    def cpr_level(self, level):
+        """level `level` as (rowptr, col, val, agg or None, dense inverse or None); level 0 in caller numbering, wells last"""
+        n, nnz, _ = self.cpr_levels()
+        last = level == len(n) - 1
+        rowptr, col, val = np.zeros(n[level] + 1, np.int32), np.zeros(nnz[level], np.int32), np.zeros(nnz[level])
+        agg = None if last else np.zeros(n[level], np.int32)
+        inv = np.zeros((n[level], n[level])) if last and n[level] <= 96 else None
+        self._status(self.lib.opmgpu_cpr_level_get(self.ctx, level, capi.iptr(rowptr), capi.iptr(col), capi.dptr(val), capi.iptr(agg), capi.dptr(inv)))
+        return rowptr, col, val, agg, inv
+
+    def cpr_vcycle_apply(self, b):
+        b = capi.f64(b)
+        x = np.zeros_like(b)
+        self._status(self.lib.opmgpu_cpr_vcycle_apply(self.ctx, capi.dptr(b), capi.dptr(x)))
+        return x
+
+    def cpr_apply(self, d3):
+        d3 = capi.f64(d3)
+        v = np.zeros_like(d3)
+        self._status(self.lib.opmgpu_cpr_apply(self.ctx, capi.dptr(d3), capi.dptr(v)))
+        return v
+
+    def cpr_elliptic_ilu_apply(self, b):
+        b = capi.f64(b)
+        x = np.zeros_like(b)
+        self._status(self.lib.opmgpu_cpr_elliptic_ilu_apply(self.ctx, capi.dptr(b), capi.dptr(x)))
+        return x
+
+    def cpr_correction_factors(self):
+        a, b = C.c_double(0), C.c_double(0)
+        self._status(self.lib.opmgpu_cpr_correction_factors(self.ctx, C.byref(a), C.byref(b)))
+        return a.value, b.value
+
+
+class GpuNewtonIteration(_CprDiagnostics):
     """B1: computeNewtonIncrement on a BCRS<3x3> system handed over as BSR."""
 
     def __init__(self, params=None, device=0):
@@ -72,6 +118,9 @@ class GpuNewtonIteration:
 
     def iterations(self):
         return self._iterations
+
+    def _status(self, st):
+        _raise(self.lib, self.ctx, st)
 
     def parallelInformation(self):
         return None         # empty boost::any <=> serial
@@ -122,7 +171,7 @@ class GpuNewtonIteration:
         return ms.value
 
 
-class GpuBlackoilModel:
+class GpuBlackoilModel(_CprDiagnostics):
     """B2: the BlackoilModel hooks, state resident on the device."""
 
     def __init__(self, grid, tables, params=None, device=0, wells=None):
@@ -152,6 +201,9 @@ class GpuBlackoilModel:
             self.close()
         except Exception:
             pass
+
+    def _status(self, st):
+        self._chk(st)
 
     def _chk(self, st):
         _raise(self.lib, self.ctx, st)
