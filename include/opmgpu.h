@@ -246,6 +246,18 @@ int opmgpu_cpr_correction_factors(opmgpu_ctx* ctx, double* into_level0, double* 
 int opmgpu_cpr_levels(opmgpu_ctx* ctx, int32_t* nlevels, int32_t* n, int64_t* nnz, int32_t* nw);
 int opmgpu_cpr_level_get(opmgpu_ctx* ctx, int level, int32_t* rowptr, int32_t* col, double* val, int32_t* agg, double* dense_inv);
 int opmgpu_cpr_vcycle_apply(opmgpu_ctx* ctx, const double* b, double* x);
+/* The distributed pressure hierarchy (opmgpu_comm_set_pressure_hierarchy mode 1) in global numbering.
+ *   opmgpu_cpr_dist_levels: number of levels, and how many of them are distributed (0: a rank-local or single-domain hierarchy); the
+ *   levels behind those are replicated on every rank.
+ *   opmgpu_cpr_dist_level_get: counts[0] = rows returned, counts[1] = their entries (every other pointer may be NULL to ask for these).
+ *   A distributed level returns this rank's owned rows: level 0 in caller-local numbering (owned cells in order, columns may be ghost
+ *   cells, the wells at n_local + k), coarser ones with global row and column ids.  A replicated level returns the whole matrix.
+ *   agg_gid = global id of the aggregate of every row (-1 on the coarsest level).
+ * On a decomposed context with the distributed hierarchy opmgpu_cpr_vcycle_apply is collective and b / x hold the rank's owned cells,
+ * then its wells. */
+int opmgpu_cpr_dist_levels(opmgpu_ctx* ctx, int32_t* nlevels, int32_t* ndist);
+int opmgpu_cpr_dist_level_get(opmgpu_ctx* ctx, int level, int64_t* counts, int64_t* row_gid, int32_t* rowptr, int64_t* col_gid, double* val,
+                              int64_t* agg_gid);
 int opmgpu_cpr_apply(opmgpu_ctx* ctx, const double* d3, double* v3);
 int opmgpu_cpr_elliptic_ilu_apply(opmgpu_ctx* ctx, const double* b, double* x);
 
@@ -572,6 +584,16 @@ typedef struct opmgpu_transport {
  * wells: block_of_owned_cell[c] in [0, m) for the owned cells in local numbering.  Same m on every rank; m = 0 restores the default.
  * Call after opmgpu_comm_init*, before the first CPR solve (the map is agreed collectively there). */
 int opmgpu_comm_set_coarse_blocks(opmgpu_ctx* ctx, int m, const int32_t* block_of_owned_cell);
+/* Pressure hierarchy of the decomposed CPR stage: 0 = rank-local levels below a level 0 that sees the neighbours, plus one coarse unknown
+ * per rank (Nicolaides); 1 = a distributed hierarchy whose levels span all ranks -- aggregates inside a rank, Galerkin products with the
+ * couplings to the neighbours' aggregates, an exchange before every operation that reads them, and the levels of at most 384 global
+ * rows replicated on every rank (one all-reduce per cycle into them).  Default: OPMGPU_CPR_GLOBAL_AMG (1 = mode 1, else 0), read at
+ * opmgpu_comm_init*.  Call after opmgpu_comm_init*, before the first CPR solve; no effect on one rank.  OPMGPU_EINVAL for another
+ * mode, and for mode 1 with level-0 Gauss-Seidel (OPMGPU_AMG_GS; with OPMGPU_CPR_GLOBAL_AMG=1 the default then stays 0, with a message on
+ * stderr).  In mode 1 building the hierarchy is collective (all-reduces and neighbour exchanges), like the solve: every call that drops
+ * it -- opmgpu_set_device_wells, a change of the sparsity pattern, a change of the mode -- must be made on all ranks alike, so that all
+ * rebuild it at the same CPR solve. */
+int opmgpu_comm_set_pressure_hierarchy(opmgpu_ctx* ctx, int mode);
 int opmgpu_comm_init_transport(opmgpu_ctx* ctx, int rank, int nranks, const opmgpu_transport* transport, int32_t n_owned,
                                int n_neigh, const int32_t* neigh_rank, const int32_t* send_ptr,
                                const int32_t* send_cells, const int32_t* recv_ptr, const int32_t* recv_cells);

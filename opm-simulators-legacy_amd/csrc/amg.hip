@@ -27,18 +27,21 @@ struct HostCsr {
 // greedy strength-based aggregation (Vanek-style, as in dune-istl's aggregation AMG): a node whose strong
 // neighbours are all free seeds an aggregate with them; leftovers join their strongest aggregated neighbour.
 // npin: the last npin rows (well unknowns of the bordered pressure system) stay singletons on every level
-int aggregate(const HostCsr& A, double theta, std::vector<int32_t>& agg, int npin = 0)
+// mark (optional, [A.n]): 1 = a row outside the aggregation (a ghost row of a distributed level: agg -1, never a strong neighbour),
+// 2 = a singleton numbered after the other aggregates (a well row inside a replicated level); columns >= A.n - npin are never strong
+int aggregate(const HostCsr& A, double theta, std::vector<int32_t>& agg, int npin = 0, const std::vector<int8_t>* mark = nullptr)
 {
     const int n = A.n - npin;
     agg.assign(A.n, -1);
+    auto out = [&](int j) { return mark && (*mark)[j] != 0; };
     std::vector<double> maxoff(A.n, 0.0);
     for (int i = 0; i < n; ++i)
         for (int s = A.rowptr[i]; s < A.rowptr[i + 1]; ++s)
-            if (A.col[s] != i && A.col[s] < n) maxoff[i] = std::max(maxoff[i], std::fabs(A.val[s]));
-    auto strong = [&](int i, int s) { return A.col[s] != i && A.col[s] < n && std::fabs(A.val[s]) >= theta * maxoff[i] && maxoff[i] > 0.0; };
+            if (A.col[s] != i && A.col[s] < n && !out(A.col[s])) maxoff[i] = std::max(maxoff[i], std::fabs(A.val[s]));
+    auto strong = [&](int i, int s) { return A.col[s] != i && A.col[s] < n && !out(A.col[s]) && std::fabs(A.val[s]) >= theta * maxoff[i] && maxoff[i] > 0.0; };
     int na = 0;
     for (int i = 0; i < n; ++i) {
-        if (agg[i] >= 0) continue;
+        if (agg[i] >= 0 || out(i)) continue;
         bool free_nb = true;
         for (int s = A.rowptr[i]; s < A.rowptr[i + 1] && free_nb; ++s) if (strong(i, s) && agg[A.col[s]] >= 0) free_nb = false;
         if (!free_nb) continue;
@@ -47,14 +50,45 @@ int aggregate(const HostCsr& A, double theta, std::vector<int32_t>& agg, int npi
         ++na;
     }
     for (int i = 0; i < n; ++i) {
-        if (agg[i] >= 0) continue;
+        if (agg[i] >= 0 || out(i)) continue;
         double best = -1.0; int bj = -1;
         for (int s = A.rowptr[i]; s < A.rowptr[i + 1]; ++s)
             if (strong(i, s) && agg[A.col[s]] >= 0 && std::fabs(A.val[s]) > best) { best = std::fabs(A.val[s]); bj = A.col[s]; }
         agg[i] = bj >= 0 ? agg[bj] : na++;
     }
+    if (mark) for (int i = 0; i < n; ++i) if ((*mark)[i] == 2) agg[i] = na++;
     for (int i = n; i < A.n; ++i) agg[i] = na++;
     return na;
+}
+
+// Galerkin product of a distributed level: the coarse rows are this rank's aggregates, each sums only this rank's rows (row_agg[i] in
+// [0, na) for an owned row, -1 otherwise); a fine column j goes to coarse column col_agg[j] (a ghost's: the owner's aggregate, numbered
+// by the caller); the diagonal comes first with column diag0 + I.  coarse_of_fine is -1 for the entries of rows that are not owned.
+void coarsen_dist(const HostCsr& A, const std::vector<int32_t>& row_agg, const std::vector<int32_t>& col_agg, int na, int diag0, int ncols,
+                  HostCsr& C, std::vector<int32_t>& coarse_of_fine, std::vector<int32_t>& agg_ptr, std::vector<int32_t>& agg_rows)
+{
+    agg_ptr.assign(na + 1, 0);
+    for (int i = 0; i < A.n; ++i) if (row_agg[i] >= 0) agg_ptr[row_agg[i] + 1]++;
+    for (int I = 0; I < na; ++I) agg_ptr[I + 1] += agg_ptr[I];
+    agg_rows.resize(agg_ptr[na]);
+    { std::vector<int32_t> fill(agg_ptr.begin(), agg_ptr.end() - 1); for (int i = 0; i < A.n; ++i) if (row_agg[i] >= 0) agg_rows[fill[row_agg[i]]++] = i; }
+    C.n = na; C.rowptr.assign(na + 1, 0); C.col.clear(); C.val.clear();
+    coarse_of_fine.assign(A.col.size(), -1);
+    std::vector<int32_t> marker(ncols, -1);
+    for (int I = 0; I < na; ++I) {
+        const int start = int(C.col.size());
+        marker[diag0 + I] = start; C.col.push_back(diag0 + I); C.val.push_back(0.0);
+        for (int q = agg_ptr[I]; q < agg_ptr[I + 1]; ++q) {
+            const int i = agg_rows[q];
+            for (int s = A.rowptr[i]; s < A.rowptr[i + 1]; ++s) {
+                const int J = col_agg[A.col[s]];
+                if (marker[J] < start) { marker[J] = int(C.col.size()); C.col.push_back(J); C.val.push_back(0.0); }
+                C.val[marker[J]] += A.val[s];
+                coarse_of_fine[s] = marker[J];
+            }
+        }
+        C.rowptr[I + 1] = int(C.col.size());
+    }
 }
 
 // Galerkin product with piecewise-constant prolongation: Ac(I,J) = sum_{i in I, j in J} A(i,j).
@@ -426,6 +460,65 @@ __global__ __launch_bounds__(kBlock) void k_amg_prolong(int n, const int32_t* __
     if (i >= n) return;
     x[i] += pdamp * xc[agg[i]];
 }
+// ---- distributed levels (amg.hpp): ghost refresh, and the hand-over to the replicated tail.  One thread per entry, fixed order.
+template <class T>
+__global__ __launch_bounds__(kBlock) void k_xchg_pack(int n, const int32_t* __restrict__ idx, const T* __restrict__ x, T* __restrict__ buf,
+                                                      const SolveCtl* __restrict__ ctl)
+{
+    if (ctl && ctl->done) return;
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < n) buf[i] = x[idx[i]];
+}
+// b != nullptr (level 0): the ghost rows are identity rows, their right-hand side follows the iterate
+template <class T>
+__global__ __launch_bounds__(kBlock) void k_xchg_unpack(int n, const int32_t* __restrict__ idx, const T* __restrict__ buf, T* __restrict__ x, T* __restrict__ b,
+                                                        const SolveCtl* __restrict__ ctl)
+{
+    if (ctl && ctl->done) return;
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const T v = buf[i];
+    x[idx[i]] = v;
+    if (b) b[idx[i]] = v;
+}
+// restriction into the tail: entry I of the global-length vector is this rank's aggregate I - off when it owns it, else 0 (all-reduced next)
+template <class S>
+__global__ __launch_bounds__(kBlock) void k_tail_restrict(int nc, int off, int nown, const int32_t* __restrict__ aptr, const int32_t* __restrict__ arows,
+                                                          const S* __restrict__ r, double* __restrict__ out, const SolveCtl* __restrict__ ctl)
+{
+    if (ctl && ctl->done) return;
+    const int I = blockIdx.x * kBlock + threadIdx.x;
+    if (I >= nc) return;
+    S s = 0;
+    if (I >= off && I < off + nown)
+        for (int q = aptr[I - off]; q < aptr[I - off + 1]; ++q) s += r[arows[q]];
+    out[I] = double(s);
+}
+template <class S>
+__global__ __launch_bounds__(kBlock) void k_tail_take(int n, const double* __restrict__ in, S* __restrict__ out, const SolveCtl* __restrict__ ctl)
+{
+    if (ctl && ctl->done) return;
+    const int i = blockIdx.x * kBlock + threadIdx.x;
+    if (i < n) out[i] = S(in[i]);
+}
+// Galerkin sums of this rank's entries of the first tail level, at their csr positions of the gathered level (the buffer is zero elsewhere)
+template <class S>
+__global__ __launch_bounds__(kBlock) void k_tail_galerkin(int nce, const int32_t* __restrict__ cptr, const int32_t* __restrict__ cidx,
+                                                          const int32_t* __restrict__ pos, const S* __restrict__ fine, double* __restrict__ out)
+{
+    const int e = blockIdx.x * kBlock + threadIdx.x;
+    if (e >= nce) return;
+    double s = 0.0;
+    for (int q = cptr[e]; q < cptr[e + 1]; ++q) s += double(fine[cidx[q]]);
+    out[pos[e]] = s;
+}
+template <class S>
+__global__ __launch_bounds__(kBlock) void k_tail_store(int nnz, const double* __restrict__ in, const int32_t* __restrict__ dev, S* __restrict__ val)
+{
+    const int k = blockIdx.x * kBlock + threadIdx.x;
+    if (k < nnz) val[dev[k]] = S(in[k]);
+}
+
 // coarsest level: the sparse operator is scattered into LDS and inverted by Gauss-Jordan between two LDS copies (ping-pong: every
 // element of step p is a function of the previous copy only, so ONE barrier per pivot instead of three; n <= kDenseMax = 96:
 // 2 x 72 KiB of the 160 KiB per CU); one workgroup of 1024 threads, no pivoting (the pressure operators are diagonally
@@ -511,6 +604,204 @@ static int galerkin_lanes(int nce)
     return (v == 1 || v == 8 || v == 16) ? v : 64;
 }
 template <class S>
+void AmgHierarchy<S>::allreduce_chunked(double* d, int64_t n)
+{
+    for (int64_t k = 0; k < n; k += kReduceChunk) dcomm->allreduce_sum(d + k, int(std::min<int64_t>(kReduceChunk, n - k)), stream);
+}
+
+// the ghost entries of x (and, on level 0, of b) from their owners: pack, one exchange with the level's neighbours, unpack
+template <class S>
+template <class T>
+void AmgHierarchy<S>::xchg(AmgLevel<S>& F, T* x, T* b, const SolveCtl* ctl)
+{
+    const int ns = int(F.xchg_send.n), nr = int(F.xchg_recv.n);
+    T* sb = reinterpret_cast<T*>(F.xchg_sbuf.p); T* rb = reinterpret_cast<T*>(F.xchg_rbuf.p);
+    if (ns) hipLaunchKernelGGL((k_xchg_pack<T>), dim3(grid_for(ns)), dim3(kBlock), 0, stream, ns, F.xchg_send.p, (const T*)x, sb, ctl);
+    const std::vector<int64_t>* by = F.xchg_bytes[sizeof(T) == 8 ? 1 : 0];
+    dcomm->exchange_bytes(F.xchg_neigh, reinterpret_cast<const char*>(sb), by[0], by[1], reinterpret_cast<char*>(rb), by[2], by[3], stream);
+    if (nr) hipLaunchKernelGGL((k_xchg_unpack<T>), dim3(grid_for(nr)), dim3(kBlock), 0, stream, nr, F.xchg_recv.p, (const T*)rb, x, b, ctl);
+}
+
+// Distributed levels of a decomposed hierarchy (amg.hpp), once per sparsity pattern.  Level l's owned rows are aggregated by the
+// single-domain rule (ghost rows excluded, wells pinned); the global numbering of level l + 1 is a rank offset (one all-reduce of the
+// per-rank counts) plus the local index; one exchange of the aggregate ids over level l's lists tells every rank the coarse ids of its
+// ghosts.  Level l + 1's ghosts from neighbour q are the distinct aggregates of the ghosts q sent, in q's order; what this rank sends q
+// is the distinct aggregates of the rows it sent q -- the same set, so no request round is needed.  When the next level's global size is at
+// most tail_rows (or the coarsening stalls), that level is gathered onto every rank: row lengths, columns and first values through
+// zero-padded all-reduces; A, L, npin and pinmark are left describing it for the single-domain loop of setup().
+template <class S>
+static void setup_dist(AmgHierarchy<S>& H, const Plan& P, HostCsr& A, std::unique_ptr<AmgLevel<S>>& L, int& npin, std::vector<int8_t>& pinmark, int max_levels)
+{
+    CommBase& cm = *H.dcomm;
+    const hipStream_t st = H.stream;
+    const int rank = cm.my_rank(), nranks = cm.num_ranks();
+    DevArray<double> red;
+    auto allsum = [&](std::vector<double>& v) {
+        if (v.empty()) return;
+        red.upload(v, st);
+        H.allreduce_chunked(red.p, int64_t(v.size()));
+        red.download(v.data(), v.size(), st);
+        OPMGPU_HIP(hipStreamSynchronize(st));
+    };
+    auto offsets = [&](int64_t mine, int64_t& off, int64_t& total) {
+        std::vector<double> c(nranks, 0.0); c[rank] = double(mine); allsum(c);
+        off = total = 0;
+        for (int q = 0; q < nranks; ++q) { if (q < rank) off += int64_t(c[q]); total += int64_t(c[q]); }
+    };
+    std::vector<int32_t> lneigh, lsp, lsi, lrp, lri;          // the current level's lists in its local numbering
+    cm.level0_lists(P, lneigh, lsp, lsi, lrp, lri);
+    std::vector<int8_t> own(P.nbp, 0);
+    OPMGPU_HIP(hipMemcpyAsync(own.data(), cm.owner_mask(), size_t(P.nbp), hipMemcpyDeviceToHost, st));
+    OPMGPU_HIP(hipStreamSynchronize(st));
+    std::vector<int8_t> mark0(A.n, 0);
+    int nown0 = L->nw;
+    for (int r = 0; r < P.nb; ++r) { mark0[r] = own[r] ? 0 : 1; nown0 += own[r] ? 1 : 0; }
+    L->h_owned.assign(own.begin(), own.begin() + P.nb);
+    offsets(nown0, L->goff, L->nglobal);
+    for (int level = 0;; ++level) {
+        AmgLevel<S>& F = *L;
+        F.dist = true;
+        {
+            std::vector<int32_t> si, ri;
+            for (size_t t = 0; t + 1 < lsp.size(); ++t) {
+                const int ns = lsp[t + 1] - lsp[t], nr = lrp[t + 1] - lrp[t];
+                if (!ns && !nr) continue;
+                F.xchg_neigh.push_back(lneigh[t]);
+                F.xchg_soff.push_back(int64_t(si.size())); F.xchg_scnt.push_back(ns); F.xchg_roff.push_back(int64_t(ri.size())); F.xchg_rcnt.push_back(nr);
+                si.insert(si.end(), lsi.begin() + lsp[t], lsi.begin() + lsp[t + 1]);
+                ri.insert(ri.end(), lri.begin() + lrp[t], lri.begin() + lrp[t + 1]);
+            }
+            for (int w = 0; w < 2; ++w) {
+                const int64_t es = w ? 8 : 4;
+                const std::vector<int64_t>* src[4] = { &F.xchg_soff, &F.xchg_scnt, &F.xchg_roff, &F.xchg_rcnt };
+                for (int k = 0; k < 4; ++k) { F.xchg_bytes[w][k] = *src[k]; for (int64_t& v : F.xchg_bytes[w][k]) v *= es; }
+            }
+            F.xchg_send.upload(si, st); F.xchg_recv.upload(ri, st);
+            F.xchg_sbuf.alloc(std::max<size_t>(si.size(), 1)); F.xchg_rbuf.alloc(std::max<size_t>(ri.size(), 1));
+        }
+        const int nvec = F.next();
+        F.val.alloc(F.nentries + 2 * size_t(F.nperf) + F.nw); F.dinv.alloc(nvec); F.x.alloc(nvec); F.b.alloc(nvec); F.r.alloc(nvec); F.x2.alloc(nvec);
+        F.x.zero(st); F.b.zero(st); F.r.zero(st); F.x2.zero(st); F.dinv.zero(st);
+        if (level > 0) F.val.zero(st);
+        H.level_sizes.push_back(F.ntot());
+        std::vector<int32_t> agg;
+        const int na = aggregate(A, 0.25, agg, npin, level == 0 ? &mark0 : nullptr);
+        int64_t coff = 0, nc = 0;
+        offsets(na, coff, nc);
+        const bool tail = nc <= H.tail_rows || nc * 10 > F.nglobal * 8 || int(H.levels.size()) + 2 >= max_levels;
+        // global coarse id of every entry: own rows from agg, ghosts from their owners
+        std::vector<double> gv(nvec, -1.0);
+        for (int i = 0; i < A.n; ++i) if (agg[i] >= 0) gv[i] = double(coff + agg[i]);
+        {
+            DevArray<double> d; d.upload(gv, st);
+            H.template xchg<double>(F, d.p, (double*)nullptr, (const SolveCtl*)nullptr);
+            d.download(gv.data(), gv.size(), st);
+            OPMGPU_HIP(hipStreamSynchronize(st));
+        }
+        std::vector<int32_t> row_agg(A.n, -1), col_agg(nvec, 0), nsp(1, 0), nsi, nrp(1, 0), nri;
+        std::vector<int64_t> gid_next(na);
+        for (int I = 0; I < na; ++I) gid_next[I] = coff + I;
+        for (int i = 0; i < A.n; ++i) if (agg[i] >= 0) { row_agg[i] = agg[i]; col_agg[i] = tail ? int32_t(coff + agg[i]) : agg[i]; }
+        int ng = 0;
+        for (size_t t = 0; t + 1 < lsp.size(); ++t) {
+            std::vector<int64_t> rg;
+            for (int k = lrp[t]; k < lrp[t + 1]; ++k) rg.push_back(std::llround(gv[lri[k]]));
+            std::vector<int64_t> ru(rg); std::sort(ru.begin(), ru.end()); ru.erase(std::unique(ru.begin(), ru.end()), ru.end());
+            for (int k = lrp[t]; k < lrp[t + 1]; ++k) {
+                const int64_t G = rg[k - lrp[t]];
+                col_agg[lri[k]] = tail ? int32_t(G) : int32_t(na + ng + (std::lower_bound(ru.begin(), ru.end(), G) - ru.begin()));
+            }
+            for (size_t u = 0; u < ru.size(); ++u) { gid_next.push_back(ru[u]); nri.push_back(na + ng + int(u)); }
+            ng += int(ru.size());
+            nrp.push_back(int32_t(nri.size()));
+            std::vector<int32_t> sg;
+            for (int k = lsp[t]; k < lsp[t + 1]; ++k) sg.push_back(agg[lsi[k]]);
+            std::sort(sg.begin(), sg.end()); sg.erase(std::unique(sg.begin(), sg.end()), sg.end());
+            nsi.insert(nsi.end(), sg.begin(), sg.end());
+            nsp.push_back(int32_t(nsi.size()));
+        }
+        HostCsr C; std::vector<int32_t> cof, aptr, arows;
+        coarsen_dist(A, row_agg, col_agg, na, tail ? int(coff) : 0, tail ? int(nc) : na + ng, C, cof, aptr, arows);
+        F.agg.upload(col_agg, st); F.agg_ptr.upload(aptr, st); F.agg_rows.upload(arows, st);
+        F.n_coarse = na;
+        const int nce = int(C.col.size());
+        std::vector<int32_t> cptr(nce + 1, 0), cidx;
+        for (size_t q = 0; q < cof.size(); ++q) if (cof[q] >= 0) cptr[cof[q] + 1]++;
+        for (int e = 0; e < nce; ++e) cptr[e + 1] += cptr[e];
+        cidx.resize(cptr[nce]);
+        { std::vector<int32_t> fill(cptr.begin(), cptr.end() - 1); for (size_t q = 0; q < cof.size(); ++q) if (cof[q] >= 0) cidx[fill[cof[q]]++] = A.dev[q]; }
+        std::unique_ptr<AmgLevel<S>> Lc(new AmgLevel<S>());
+        if (!tail) {
+            std::vector<int32_t> sp, scol, dent; int nent = 0;
+            to_sell(C, sp, scol, dent, nent);
+            std::vector<int32_t> cptr2(nent + 1, 0), cidx2(cidx.size()), cdiag2(nent, -1);
+            for (int e = 0; e < nce; ++e) cptr2[C.dev[e] + 1] = cptr[e + 1] - cptr[e];
+            for (int d = 0; d < nent; ++d) cptr2[d + 1] += cptr2[d];
+            for (int r = 0; r < C.n; ++r)
+                for (int e = C.rowptr[r]; e < C.rowptr[r + 1]; ++e) {
+                    std::copy(cidx.begin() + cptr[e], cidx.begin() + cptr[e + 1], cidx2.begin() + cptr2[C.dev[e]]);
+                    if (C.col[e] == r) cdiag2[C.dev[e]] = r;
+                }
+            F.contrib_ptr.upload(cptr2, st); F.contrib_idx.upload(cidx2, st); F.contrib_diag.upload(cdiag2, st);
+            F.nentries_coarse = nent; F.galerkin_lpe = galerkin_lanes(nce);
+            Lc->n = na; Lc->nslices = (na + 63) / 64; Lc->nentries = nent;
+            Lc->own_slice_ptr.upload(sp, st); Lc->own_col.upload(scol, st);
+            Lc->slice_ptr = Lc->own_slice_ptr.p; Lc->col = Lc->own_col.p;
+            Lc->diag_entry.upload(dent, st);
+            Lc->h_rowlen.resize(C.n);
+            for (int r = 0; r < C.n; ++r) Lc->h_rowlen[r] = C.rowptr[r + 1] - C.rowptr[r];
+            Lc->nghost = ng; Lc->goff = coff; Lc->nglobal = nc; Lc->h_gid = gid_next;
+            H.levels.push_back(std::move(L));
+            L = std::move(Lc);
+            A = std::move(C);
+            lsp.swap(nsp); lsi.swap(nsi); lrp.swap(nrp); lri.swap(nri);
+            continue;
+        }
+        // the first tail level, gathered: row lengths and well marks, then columns and the first matrix's values
+        std::vector<double> rl(nc, 0.0), pm(nc, 0.0);
+        for (int I = 0; I < na; ++I) { rl[coff + I] = C.rowptr[I + 1] - C.rowptr[I]; if (I >= na - npin) pm[coff + I] = 1.0; }
+        allsum(rl); allsum(pm);
+        HostCsr T;
+        T.n = int(nc); T.rowptr.assign(nc + 1, 0);
+        for (int64_t I = 0; I < nc; ++I) T.rowptr[I + 1] = T.rowptr[I] + int32_t(std::llround(rl[I]));
+        const int64_t nnz = T.rowptr[nc];
+        std::vector<double> cc(nnz, 0.0), vv(nnz, 0.0);
+        std::vector<int32_t> pos(nce);
+        for (int I = 0; I < na; ++I)
+            for (int e = C.rowptr[I]; e < C.rowptr[I + 1]; ++e) {
+                pos[e] = T.rowptr[coff + I] + (e - C.rowptr[I]);
+                cc[pos[e]] = C.col[e]; vv[pos[e]] = C.val[e];
+            }
+        allsum(cc); allsum(vv);
+        T.col.resize(nnz); T.val = vv;
+        for (int64_t k = 0; k < nnz; ++k) T.col[k] = int32_t(std::llround(cc[k]));
+        std::vector<int32_t> sp, scol, dent; int nent = 0;
+        to_sell(T, sp, scol, dent, nent);
+        F.contrib_ptr.upload(cptr, st); F.contrib_idx.upload(cidx, st);
+        F.nentries_coarse = nce;
+        H.tail_pos.upload(pos, st); H.tail_dev.upload(T.dev, st);
+        H.tail_nnz = nnz; H.tail_off = coff; H.tail_own = na;
+        H.tail_buf.alloc(size_t(std::max<int64_t>(std::max<int64_t>(nnz, nc), 1)));
+        Lc->n = int(nc); Lc->nslices = (Lc->n + 63) / 64; Lc->nentries = nent;
+        Lc->own_slice_ptr.upload(sp, st); Lc->own_col.upload(scol, st);
+        Lc->slice_ptr = Lc->own_slice_ptr.p; Lc->col = Lc->own_col.p;
+        Lc->diag_entry.upload(dent, st);
+        Lc->h_rowlen.resize(T.n);
+        for (int r = 0; r < T.n; ++r) Lc->h_rowlen[r] = T.rowptr[r + 1] - T.rowptr[r];
+        Lc->goff = 0; Lc->nglobal = nc;
+        H.levels.push_back(std::move(L));
+        H.ndist = int(H.levels.size());
+        L = std::move(Lc);
+        A = std::move(T);
+        npin = 0;
+        pinmark.assign(nc, 0);
+        for (int64_t I = 0; I < nc; ++I) if (pm[I] > 0.5) pinmark[I] = 2;
+        OPMGPU_HIP(hipStreamSynchronize(st));
+        return;
+    }
+}
+
+template <class S>
 void AmgHierarchy<S>::setup(const Plan& P, const int32_t* d_slice_ptr, const int32_t* d_col, const std::vector<double>& ap_host, const AmgBorderSpec* border)
 {
     if (inv_stream) { OPMGPU_HIP(hipStreamSynchronize(inv_stream)); inv_pending = false; }       // dense_inv is re-allocated below
@@ -572,6 +863,11 @@ void AmgHierarchy<S>::setup(const Plan& P, const int32_t* d_slice_ptr, const int
     int kMaxLevels = 12;
     if (const char* e = std::getenv("OPMGPU_AMG_MAXLEVELS")) kMaxLevels = std::max(2, std::atoi(e));
     if (const char* e = std::getenv("OPMGPU_AMG_COARSE_SWEEPS")) coarse_sweeps = std::max(0, std::atoi(e));
+    ndist = 0;
+    tail_rows = kTailRows;
+    if (const char* e = std::getenv("OPMGPU_AMG_TAIL_ROWS")) tail_rows = std::max(1, std::atoi(e));
+    std::vector<int8_t> pinmark;            // replicated tail: the wells' rows stay singletons (aggregate(): mark 2)
+    if (dcomm) setup_dist(*this, P, A, L, npin, pinmark, kMaxLevels);
     while (true) {
         const int n = A.n;              // unknowns of this level (a bordered level 0: cells + wells)
         L->val.alloc(L->nentries + 2 * size_t(L->nperf) + L->nw); L->dinv.alloc(n); L->x.alloc(n); L->b.alloc(n); L->r.alloc(n); L->x2.alloc(n);
@@ -581,7 +877,7 @@ void AmgHierarchy<S>::setup(const Plan& P, const int32_t* d_slice_ptr, const int
         std::vector<int32_t> agg;
         int na = 0;
         const bool stop = n <= kMaxDense || int(levels.size()) + 1 >= kMaxLevels;
-        if (!stop) na = aggregate(A, 0.25, agg, npin);
+        if (!stop) na = aggregate(A, 0.25, agg, npin, pinmark.empty() ? nullptr : &pinmark);
         // aggressive coarsening (OPMGPU_AMG_AGGR=l: from level l on, aggregate twice and compose): the levels below ~100 k rows are
         // launch-latency bound (~5 us per dependent kernel), so fewer of them shortens the cycle; costs convergence per cycle
         static const int aggr_from = std::getenv("OPMGPU_AMG_AGGR") ? std::atoi(std::getenv("OPMGPU_AMG_AGGR")) : -1;
@@ -597,6 +893,11 @@ void AmgHierarchy<S>::setup(const Plan& P, const int32_t* d_slice_ptr, const int
         }
         HostCsr C; std::vector<int32_t> cof, aptr, arows;
         coarsen(A, agg, na, C, cof, aptr, arows);
+        if (!pinmark.empty()) {
+            std::vector<int8_t> cm(na, 0);
+            for (int i = 0; i < n; ++i) if (pinmark[i] == 2) cm[agg[i]] = 2;
+            pinmark.swap(cm);
+        }
         std::vector<int32_t> sp, scol, dent; int nent = 0;
         to_sell(C, sp, scol, dent, nent);
         // contribution lists per coarse csr entry, in fine DEVICE entry ids
@@ -653,6 +954,18 @@ void AmgHierarchy<S>::galerkin(bool coarse_levels, const std::function<void()>& 
     for (size_t l = 0; l + 1 < levels.size(); ++l) {
         AmgLevel<S>& F = *levels[l]; AmgLevel<S>& C = *levels[l + 1];
         const int nce = F.nentries_coarse;
+        if (int(l) + 1 == ndist) {
+            // into the replicated tail: this rank's entries at their csr positions, zero elsewhere, summed over the ranks (each entry has
+            // exactly one contributor: the same bits on every rank), then placed in the tail's SELL layout with its inverse diagonal
+            const int nnz = int(tail_nnz);
+            OPMGPU_HIP(hipMemsetAsync(tail_buf.p, 0, size_t(nnz) * sizeof(double), stream));
+            if (nce) hipLaunchKernelGGL((k_tail_galerkin<S>), dim3(grid_for(nce)), dim3(kBlock), 0, stream, nce, F.contrib_ptr.p, F.contrib_idx.p, tail_pos.p, (const S*)F.val.p, tail_buf.p);
+            allreduce_chunked(tail_buf.p, nnz);
+            hipLaunchKernelGGL((k_tail_store<S>), dim3(grid_for(nnz)), dim3(kBlock), 0, stream, nnz, (const double*)tail_buf.p, tail_dev.p, C.val.p);
+            hipLaunchKernelGGL((k_amg_dinv<S>), dim3(grid_for(C.n)), dim3(kBlock), 0, stream, C.n, C.diag_entry.p, (const S*)C.val.p, C.dinv.p);
+            if (l == 0 && after_level0) after_level0();
+            continue;
+        }
 #define OPMGPU_GALERKIN(LPE) hipLaunchKernelGGL((k_amg_galerkin<S, LPE>), dim3(grid8_for(long(nce) * LPE)), dim3(kBlock), 0, stream, xcd_mode(), nce, \
                                F.contrib_ptr.p, F.contrib_idx.p, F.contrib_diag.p, F.val.p, C.val.p, C.dinv.p)
         switch (F.galerkin_lpe) {
@@ -729,6 +1042,30 @@ void AmgHierarchy<S>::vcycle(const SolveCtl* ctl, bool level0_presmoothed)
     for (int l = 0; l < nl - 1; ++l) {
         AmgLevel<S>& F = *levels[l]; AmgLevel<S>& C = *levels[l + 1];
         const int g = grid_for(F.n);
+        if (l < ndist) {
+            // distributed level: unfused launches, the ghost entries of the iterate from their owners before every operation that reads them
+            if (!presmoothed) hipLaunchKernelGGL((k_amg_smooth0<S>), dim3(grid_for(F.ntot())), dim3(kBlock), 0, stream, F.ntot(), om, F.dinv.p, F.b.p, F.x.p, ctl);
+            xchg<S>(F, F.x.p, l == 0 ? F.b.p : (S*)nullptr, ctl);
+            residual_level(F, ctl);
+            for (int sw = 1; sw < npre; ++sw) {
+                sweep(F, ctl);
+                xchg<S>(F, F.x.p, l == 0 ? F.b.p : (S*)nullptr, ctl);
+                residual_level(F, ctl);
+            }
+            if (l + 1 == ndist) {           // into the replicated tail: one all-reduce of the zero-padded aggregate sums
+                const int nc = C.n;
+                hipLaunchKernelGGL((k_tail_restrict<S>), dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, int(tail_off), int(tail_own), F.agg_ptr.p, F.agg_rows.p,
+                                   (const S*)F.r.p, tail_buf.p, ctl);
+                allreduce_chunked(tail_buf.p, nc);
+                hipLaunchKernelGGL((k_tail_take<S>), dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, (const double*)tail_buf.p, C.b.p, ctl);
+            } else {
+                hipLaunchKernelGGL((k_amg_restrict<S>), dim3(grid_for(C.n)), dim3(kBlock), 0, stream, C.n, F.agg_ptr.p, F.agg_rows.p, F.r.p, C.b.p, om,
+                                   (const S*)nullptr, (S*)nullptr, ctl);
+            }
+            presmoothed = false;
+            mark("down L" + std::to_string(l));
+            continue;
+        }
         if (l == 0 && level0_halo) {
             // decomposed run: x0 = omega D^-1 b, ghost entries from their owners, then the residual on the global level-0 matrix
             if (!presmoothed) hipLaunchKernelGGL((k_amg_smooth0<S>), dim3(grid_for(F.ntot())), dim3(kBlock), 0, stream, F.ntot(), om, F.dinv.p, F.b.p, F.x.p, ctl);
@@ -795,6 +1132,12 @@ void AmgHierarchy<S>::vcycle(const SolveCtl* ctl, bool level0_presmoothed)
         int done_sweeps = 0;
         const int npost = l == 0 ? this->npost0 : this->npost;
         const double pdamp = l == 0 ? this->pdamp0 : this->pdamp;          // (shadows the member: the correction INTO level l)
+        if (l < ndist) {
+            hipLaunchKernelGGL((k_amg_prolong<S>), dim3(grid_for(F.ntot())), dim3(kBlock), 0, stream, F.ntot(), F.agg.p, C.x.p, F.x.p, S(pdamp), ctl);
+            for (int sw = 0; sw < npost; ++sw) { xchg<S>(F, F.x.p, l == 0 ? F.b.p : (S*)nullptr, ctl); sweep(F, ctl); }
+            mark("up L" + std::to_string(l));
+            continue;
+        }
         if (l == 0 && level0_halo) {
             // decomposed run: prolongation, then every post-smoothing sweep on an iterate whose ghost entries are the owners'
             hipLaunchKernelGGL((k_amg_prolong<S>), dim3(grid_for(F.ntot())), dim3(kBlock), 0, stream, F.ntot(), F.agg.p, C.x.p, F.x.p, S(pdamp), ctl);
@@ -847,7 +1190,7 @@ template <class S>
 void AmgHierarchy<S>::vcycle_graph(const SolveCtl* ctl, bool level0_presmoothed)
 {
     const bool even = (npost % 2 == 0) && (npost0 % 2 == 0) && npre == 1;
-    if (!use_graph || !even || level0_halo) { vcycle(ctl, level0_presmoothed); return; }          // (the exchange is not capturable)
+    if (!use_graph || !even || level0_halo || ndist > 0) { vcycle(ctl, level0_presmoothed); return; }          // (the exchange is not capturable)
     join_inverse();          // an event of another stream cannot be waited for inside a capture
     // the captured launches carry the smoother / correction constants as baked-in kernel arguments: they are part of the cache key
     const double key[6] = { pdamp0, pdamp, omega0(), double(npost), double(npost0), double(npre) };
@@ -945,6 +1288,30 @@ void AmgHierarchy<S>::restore_rhs()
     OPMGPU_HIP(hipMemcpyAsync(F.b.p, tune_b.p, size_t(F.ntot()) * sizeof(S), hipMemcpyDeviceToDevice, stream));
 }
 
+// r = b - A x on one level (unfused: the distributed levels)
+template <class S>
+void AmgHierarchy<S>::residual_level(AmgLevel<S>& F, const SolveCtl* ctl)
+{
+    const S om = S(omega);
+    const int g = grid_for(F.n);
+    Border<S> B;
+    if (F.nw) {
+        B.nw = F.nw; B.n = F.n; B.connpos = F.b_connpos; B.perf_row = F.b_perf_row; B.perf_of_row = F.b_perf_of_row; B.perf_well = F.b_perf_well;
+        B.bcol = F.val.p + F.nentries; B.crow = B.bcol + F.nperf; B.dw = B.crow + F.nperf;
+    }
+    if (sub_rows(F)) {
+        hipLaunchKernelGGL((k_amg_row_sub<S, 0, kSubLanes>), dim3(sub_grid(F.n)), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, (const S*)F.x.p, om, F.dinv.p, F.r.p, (S*)nullptr, ctl);
+    } else if (F.n > 20000) {
+        B.gcells = g;
+        hipLaunchKernelGGL((k_amg_residual<S, 0>), dim3(g + F.nw), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, F.x.p, om, F.dinv.p, F.r.p, ctl,
+                           (const int32_t*)nullptr, (const S*)nullptr, S(0), B);
+    } else {
+        B.gcells = (F.n + 3) / 4;
+        hipLaunchKernelGGL((k_amg_row_wave<S, 0>), dim3((F.n + 3) / 4 + F.nw), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, (const S*)F.x.p, om, F.dinv.p, F.r.p, (S*)nullptr, ctl,
+                           (const int32_t*)nullptr, (const S*)nullptr, S(0), B);
+    }
+}
+
 // one damped-Jacobi sweep x <- x + omega D^-1 (b - A x) (ping-pong between x and x2)
 template <class S>
 void AmgHierarchy<S>::sweep(AmgLevel<S>& F, const SolveCtl* ctl)
@@ -971,5 +1338,7 @@ void AmgHierarchy<S>::sweep(AmgLevel<S>& F, const SolveCtl* ctl)
 
 template class AmgHierarchy<float>;
 template class AmgHierarchy<double>;
+template void AmgHierarchy<float>::xchg<float>(AmgLevel<float>&, float*, float*, const SolveCtl*);
+template void AmgHierarchy<double>::xchg<double>(AmgLevel<double>&, double*, double*, const SolveCtl*);
 
 } // namespace opmgpu

@@ -24,6 +24,7 @@
 namespace opmgpu {
 
 struct SolveCtl;
+struct CommBase;
 
 template <class S>
 struct AmgLevel {
@@ -52,6 +53,21 @@ struct AmgLevel {
     const int32_t* b_perf_of_row = nullptr;     // [>= n] perforation of a row or -1
     const int32_t* b_perf_well = nullptr;       // [nperf]
     int ntot() const { return n + nw; }
+    // Distributed level of a decomposed hierarchy (AmgHierarchy::setup with a communicator).  Level 0: the rows are the
+    // plan's, ghost rows included (identity rows); levels >= 1: n = owned rows (wells last), followed in every vector by `nghost` ghost
+    // entries (the neighbours' coarse unknowns this rank's rows couple to).  The ghost entries of the iterate are refreshed from their
+    // owners by xchg_*: pack xchg_send, exchange with xchg_neigh, unpack into xchg_recv (level 0: x and b of the ghost rows).
+    bool dist = false;
+    int nghost = 0;
+    int64_t goff = 0, nglobal = 0;              // global numbering of the owned rows: goff + local index (levels >= 1; wells included)
+    std::vector<int64_t> h_gid;                 // levels >= 1: global id of every local entry, ghosts included (diagnostics)
+    std::vector<int8_t> h_owned;                // level 0: owned plan rows (host copy)
+    std::vector<int32_t> xchg_neigh;
+    std::vector<int64_t> xchg_soff, xchg_scnt, xchg_roff, xchg_rcnt;      // in elements, per neighbour
+    std::vector<int64_t> xchg_bytes[2][4];      // the same in bytes for 4- [0] and 8-byte [1] entries: send offset, count, receive offset, count
+    DevArray<int32_t> xchg_send, xchg_recv;
+    DevArray<double> xchg_sbuf, xchg_rbuf;
+    int next() const { return n + nw + nghost; }    // entries of a vector of this level
 };
 
 // host description of the border handed to AmgHierarchy::setup
@@ -134,6 +150,22 @@ public:
     bool gs_level0() const { return use_gs && gs_n0 > 0 && npre == 1; }
     double omega0() const { return gs_level0() ? 1.0 : omega; }      // weight of the caller's fused first sweep on level 0
     void sweep(AmgLevel<S>& F, const SolveCtl* ctl);
+    // Distributed hierarchy (opmgpu_comm_set_pressure_hierarchy mode 1): set dcomm before setup().  Levels [0, ndist) are distributed
+    // (aggregates inside a rank, Galerkin products keep the couplings to the neighbours' aggregates); level ndist, the first whose global
+    // size is at most kTailRows, and all coarser ones are replicated on every rank (the tail).  ndist = 0: the rank-local hierarchy.
+    static constexpr int kTailRows = 384;
+    int tail_rows = kTailRows;               // OPMGPU_AMG_TAIL_ROWS (A/B and tests: a smaller value keeps more levels distributed)
+    CommBase* dcomm = nullptr;
+    int ndist = 0;
+    int64_t tail_off = 0, tail_own = 0;      // this rank's rows of the first tail level
+    int64_t tail_nnz = 0;                    // csr entries of the first tail level
+    DevArray<int32_t> tail_pos;              // per own Galerkin entry of the last distributed level: its csr position in the first tail level
+    DevArray<int32_t> tail_dev;              // [tail_nnz] SELL slot of every csr entry of the first tail level
+    DevArray<double> tail_buf;               // zero-padded partial sums: Galerkin values / restricted right-hand side of the tail
+    void allreduce_chunked(double* d, int64_t n);      // all-reduces of at most kReduceChunk doubles (32 KiB messages)
+    static constexpr int kReduceChunk = 4096;
+    template <class T> void xchg(AmgLevel<S>& F, T* x, T* b, const SolveCtl* ctl);
+    void residual_level(AmgLevel<S>& F, const SolveCtl* ctl);
 };
 
 } // namespace opmgpu

@@ -364,7 +364,7 @@ template <class S> static int cpr_level_get_t(LinSolver& ls, int level, int32_t*
     const S* bcol = sv.data() + F.nentries; const S* crow = bcol + nperf; const S* dw = crow + nperf;
     int64_t q = 0;
     if (rowptr) rowptr[0] = 0;
-    auto put = [&](int c, double v) { if (col) col[q] = outer[c]; if (val) val[q] = v; ++q; };
+    auto put = [&](int c, double v) { if (col) col[q] = c < nt ? outer[c] : c; if (val) val[q] = v; ++q; };
     for (int o = 0; o < nt; ++o) {
         const int r = internal[o];
         if (r < n) {
@@ -404,8 +404,10 @@ template <class S> static int cpr_vcycle_apply_t(LinSolver& ls, const double* b,
     const int n = L0.n, nt = L0.ntot();
     const hipStream_t st = ls.stream;
     std::vector<S> hb(nt), hx(nt);
-    for (int i = 0; i < n; ++i) hb[ls.plan.pos[i]] = S(b[i]);
-    for (int k = n; k < nt; ++k) hb[k] = S(b[k]);
+    // a distributed hierarchy (collective call): the rank's owned cells, then its wells; the ghost rows follow their owners inside the cycle
+    const int nown = H->ndist > 0 ? int(std::count(L0.h_owned.begin(), L0.h_owned.end(), int8_t(1))) : n;
+    for (int i = 0; i < nown; ++i) hb[ls.plan.pos[i]] = S(b[i]);
+    for (int k = n; k < nt; ++k) hb[k] = S(b[nown + k - n]);
     DevArray<S> keep; keep.alloc(nt);
     OPMGPU_HIP(hipMemcpyAsync(keep.p, L0.b.p, nt * sizeof(S), hipMemcpyDeviceToDevice, st));
     const auto roles = cpr_roles(*H);
@@ -415,8 +417,55 @@ template <class S> static int cpr_vcycle_apply_t(LinSolver& ls, const double* b,
     cpr_restore_roles(*H, roles);
     OPMGPU_HIP(hipMemcpyAsync(L0.b.p, keep.p, nt * sizeof(S), hipMemcpyDeviceToDevice, st));
     OPMGPU_HIP(hipStreamSynchronize(st));
-    for (int i = 0; i < n; ++i) x[i] = double(hx[ls.plan.pos[i]]);
-    for (int k = n; k < nt; ++k) x[k] = double(hx[k]);
+    for (int i = 0; i < nown; ++i) x[i] = double(hx[ls.plan.pos[i]]);
+    for (int k = n; k < nt; ++k) x[nown + k - n] = double(hx[k]);
+    return OPMGPU_OK;
+}
+
+// A distributed hierarchy in global numbering (tests/test_gpu_dist_hierarchy.py).  Rows of a distributed level: this rank's owned ones (level 0:
+// owned cells in caller order, ids in caller-local numbering with the wells at n_local + k, as opmgpu_cpr_level_get); coarse levels: global
+// ids.  agg_gid: the global id of every row's aggregate (-1 on the coarsest level).  A tail level comes back whole.
+template <class S> static int cpr_dist_level_get_t(LinSolver& ls, int level, int64_t* counts, int64_t* row_gid, int32_t* rowptr, int64_t* col_gid,
+                                                   double* val, int64_t* agg_gid)
+{
+    AmgHierarchy<S>* H = cpr_hierarchy<S>(ls);
+    if (!H || level < 0 || level >= int(H->levels.size())) return OPMGPU_EINVAL;
+    int32_t nl = int32_t(H->levels.size());
+    std::vector<int32_t> n(nl); std::vector<int64_t> nnz(nl);
+    int st = cpr_levels_t<S>(ls, &nl, n.data(), nnz.data(), nullptr);
+    if (st != OPMGPU_OK) return st;
+    const int nt = n[level];
+    std::vector<int32_t> rp(nt + 1), cl(nnz[level]), ag(nt, -1);
+    std::vector<double> vl(nnz[level]);
+    st = cpr_level_get_t<S>(ls, level, rp.data(), cl.data(), vl.data(), ag.data(), nullptr);
+    if (st != OPMGPU_OK) return st;
+    const AmgLevel<S>& F = *H->levels[level];
+    const bool last = level + 1 == nl;
+    auto agg_g = [&](int o) -> int64_t {
+        if (last) return -1;
+        const AmgLevel<S>& C = *H->levels[level + 1];
+        return C.dist ? C.h_gid[ag[o]] : int64_t(ag[o]);
+    };
+    std::vector<int> rows;
+    int64_t cnt = 0;
+    const int nown0 = level == 0 && F.dist ? int(std::count(F.h_owned.begin(), F.h_owned.end(), int8_t(1))) : 0;
+    for (int o = 0; o < nt; ++o) {
+        if (level == 0 && F.dist && o >= nown0 && o < F.n) continue;          // a ghost cell
+        rows.push_back(o); cnt += rp[o + 1] - rp[o];
+    }
+    if (counts) { counts[0] = int64_t(rows.size()); counts[1] = cnt; }
+    int64_t q = 0;
+    if (rowptr) rowptr[0] = 0;
+    for (size_t k = 0; k < rows.size(); ++k) {
+        const int o = rows[k];
+        if (row_gid) row_gid[k] = (F.dist && level > 0) ? F.h_gid[o] : int64_t(o);
+        if (agg_gid) agg_gid[k] = agg_g(o);
+        for (int e = rp[o]; e < rp[o + 1]; ++e, ++q) {
+            if (col_gid) col_gid[q] = (F.dist && level > 0) ? F.h_gid[cl[e]] : int64_t(cl[e]);
+            if (val) val[q] = vl[e];
+        }
+        if (rowptr) rowptr[k + 1] = int32_t(q);
+    }
     return OPMGPU_OK;
 }
 
@@ -472,6 +521,20 @@ int opmgpu_cpr_level_get(opmgpu_ctx* c, int level, int32_t* rowptr, int32_t* col
     if (!c || !c->ls) return OPMGPU_EINVAL;
     return guarded(c, [&]() { return cpr_float(c) ? cpr_level_get_t<float>(*c->ls, level, rowptr, col, val, agg, dense_inv)
                                                   : cpr_level_get_t<double>(*c->ls, level, rowptr, col, val, agg, dense_inv); });
+}
+int opmgpu_cpr_dist_levels(opmgpu_ctx* c, int32_t* nlevels, int32_t* ndist)
+{
+    if (!c || !c->ls || !nlevels || !ndist) return OPMGPU_EINVAL;
+    return guarded(c, [&]() {
+        auto get = [&](auto* H) { if (!H) return int(OPMGPU_EINVAL); *nlevels = int32_t(H->levels.size()); *ndist = H->ndist; return int(OPMGPU_OK); };
+        return cpr_float(c) ? get(cpr_hierarchy<float>(*c->ls)) : get(cpr_hierarchy<double>(*c->ls));
+    });
+}
+int opmgpu_cpr_dist_level_get(opmgpu_ctx* c, int level, int64_t* counts, int64_t* row_gid, int32_t* rowptr, int64_t* col_gid, double* val, int64_t* agg_gid)
+{
+    if (!c || !c->ls) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { return cpr_float(c) ? cpr_dist_level_get_t<float>(*c->ls, level, counts, row_gid, rowptr, col_gid, val, agg_gid)
+                                                  : cpr_dist_level_get_t<double>(*c->ls, level, counts, row_gid, rowptr, col_gid, val, agg_gid); });
 }
 int opmgpu_cpr_vcycle_apply(opmgpu_ctx* c, const double* b, double* x)
 {
@@ -1045,6 +1108,12 @@ static int comm_init_common(opmgpu_ctx* c, int rank, int nranks, const uint8_t* 
                                 n_neigh ? recv_ptr : zero2, recv_cells);
         if (st != OPMGPU_OK) return fail(c, st, transport ? "invalid transport / neighbour lists" : "RCCL communicator initialisation failed");
         cm->rebuild(c->model->plan(), c->stream);
+        c->ls->cpr_hier_mode = (std::getenv("OPMGPU_CPR_GLOBAL_AMG") && std::atoi(std::getenv("OPMGPU_CPR_GLOBAL_AMG")) == 1) ? 1 : 0;
+        if (c->ls->cpr_hier_mode == 1 && std::getenv("OPMGPU_AMG_GS") && std::atoi(std::getenv("OPMGPU_AMG_GS")) != 0) {
+            // the distributed cycle smooths by damped Jacobi only (opmgpu_comm_set_pressure_hierarchy refuses the pair): keep mode 0
+            std::fprintf(stderr, "[opmgpu] OPMGPU_CPR_GLOBAL_AMG=1 ignored: OPMGPU_AMG_GS is set (level-0 Gauss-Seidel); the pressure hierarchy stays rank-local\n");
+            c->ls->cpr_hier_mode = 0;
+        }
         c->comm = std::move(cm);
         c->model->attach_comm(c->comm.get(), n_owned);
         c->matrix_loaded = false;
@@ -1072,6 +1141,17 @@ int opmgpu_comm_set_coarse_blocks(opmgpu_ctx* c, int m, const int32_t* block_of_
     const int st = c->comm->set_coarse_blocks(m, block_of_owned_cell);
     if (st != OPMGPU_OK) return fail(c, st, "opmgpu_comm_set_coarse_blocks: 0 <= block < m <= 8 for every owned cell");
     c->ls->cs_for = nullptr;           // the subdomain map is rebuilt (collectively) at the next CPR solve
+    return OPMGPU_OK;
+}
+
+int opmgpu_comm_set_pressure_hierarchy(opmgpu_ctx* c, int mode)
+{
+    if (!c || !c->comm || !c->ls) return OPMGPU_EINVAL;
+    if (mode != 0 && mode != 1) return fail(c, OPMGPU_EINVAL, "opmgpu_comm_set_pressure_hierarchy: mode 0 (rank-local) or 1 (distributed)");
+    const char* gs = std::getenv("OPMGPU_AMG_GS");
+    if (mode == 1 && gs && std::atoi(gs) != 0) return fail(c, OPMGPU_EINVAL, "opmgpu_comm_set_pressure_hierarchy: the distributed hierarchy smooths by damped Jacobi (OPMGPU_AMG_GS is set)");
+    if (c->ls->cpr_hier_mode != mode) c->ls->drop_hierarchies();           // rebuilt (collectively) at the next CPR solve
+    c->ls->cpr_hier_mode = mode;
     return OPMGPU_OK;
 }
 

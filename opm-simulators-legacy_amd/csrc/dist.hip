@@ -271,6 +271,21 @@ void RcclComm::coarse_blocks_of_rows(const Plan& P, int m, hipStream_t s, std::v
     for (int c = n_owned; c < n_local; ++c) sub[P.pos[c]] = int32_t(h[P.pos[c]] + 0.5);
 }
 
+void RcclComm::level0_lists(const Plan& P, std::vector<int32_t>& neigh, std::vector<int32_t>& sptr, std::vector<int32_t>& srows,
+                            std::vector<int32_t>& rptr, std::vector<int32_t>& rrows) const
+{
+    neigh = neigh_rank; sptr = send_ptr; rptr = recv_ptr;
+    srows.resize(send_cells.size()); rrows.resize(recv_cells.size());
+    for (size_t i = 0; i < send_cells.size(); ++i) srows[i] = P.pos[send_cells[i]];
+    for (size_t i = 0; i < recv_cells.size(); ++i) rrows[i] = P.pos[recv_cells[i]];
+}
+
+void RcclComm::exchange_bytes(const std::vector<int32_t>& neigh, const char* sb, const std::vector<int64_t>& soff, const std::vector<int64_t>& sbytes,
+                              char* rb, const std::vector<int64_t>& roff, const std::vector<int64_t>& rbytes, hipStream_t s)
+{
+    transport->exchange(neigh, sb, soff, sbytes, rb, roff, rbytes, s);
+}
+
 int RcclComm::set_coarse_blocks(int m, const int32_t* blk)
 {
     if (m < 0 || m > 8 || (m > 0 && !blk)) return OPMGPU_EINVAL;

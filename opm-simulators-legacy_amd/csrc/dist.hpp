@@ -31,6 +31,10 @@ public:
     void coarse_blocks_of_rows(const Plan& P, int m, hipStream_t s, std::vector<int32_t>& sub, std::vector<int8_t>& blk) override;
 
     int user_coarse_blocks() const override { return user_m; }
+    void level0_lists(const Plan& P, std::vector<int32_t>& neigh, std::vector<int32_t>& sptr, std::vector<int32_t>& srows,
+                      std::vector<int32_t>& rptr, std::vector<int32_t>& rrows) const override;
+    void exchange_bytes(const std::vector<int32_t>& neigh, const char* sb, const std::vector<int64_t>& soff, const std::vector<int64_t>& sbytes,
+                        char* rb, const std::vector<int64_t>& roff, const std::vector<int64_t>& rbytes, hipStream_t s) override;
     int set_coarse_blocks(int m, const int32_t* block_of_owned_cell);      // 0 <= block < m per owned cell (local caller numbering); m <= 8
     std::vector<int32_t> user_blk;
     int user_m = 0;

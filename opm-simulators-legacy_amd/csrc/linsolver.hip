@@ -1911,6 +1911,7 @@ template <class S> void LinSolver::cpr_prepare()
     coarse_nsub = coarse_mode != 0 && (nsub >= 2 || single_ok) ? nsub : 0;
     if (coarse_nsub > 64) coarse_nsub = 0;        // table sizes of the kernels
     if (ell.inner) coarse_nsub = 0;               // the inner Krylov method of the elliptic part works on A_p itself (rank-local when decomposed)
+    if (dist_hierarchy()) coarse_nsub = 0;        // the distributed hierarchy reaches the whole domain itself
     // Scaling of the coarse-grid corrections: 1.9 in general; the correction into level 0 by 2.2 when ONE subdomain carries the coarse
     // space (one GPU, no wells) -- the global constant is then removed exactly for the whole domain and the hierarchy is global:
     // measured +4 % (100^3), +9 % (200^3), +7 % (300^3) throughput, 0 % on the sigma = 2 deck (2.2 on every level: better at 100^3 /
@@ -2005,6 +2006,7 @@ template <class S> void LinSolver::cpr_prepare()
             bs.bcol.assign(hb.begin(), hb.begin() + bs.nperf); bs.crow.assign(hb.begin() + bs.nperf, hb.begin() + 2 * bs.nperf); bs.dw.assign(hb.begin() + 2 * bs.nperf, hb.end());
             bs.d_connpos = lowrank.connpos; bs.d_perf_row = lowrank.perf_row; bs.d_perf_of_row = lowrank.perf_of_row; bs.d_perf_well = lowrank.perf_well;
         }
+        w.amg->dcomm = dist_hierarchy() ? comm : nullptr;
         w.amg->setup(plan, dp.slice_ptr.p, dp.col.p, hd, bs.nw > 0 ? &bs : nullptr);
     }
     hipLaunchKernelGGL((k_extract_pressure<S>), dim3(grid_for(plan.nbp)), dim3(kBlock), 0, stream, plan.nb, plan.nbp, dp.slice_ptr.p, (const S*)w.cprw.p, ((emulate_what & 2) ? pre_matrix<S>() : matrix<S>()),
@@ -2200,7 +2202,7 @@ template <class S> void LinSolver::cpr_apply(const S* d, S* v, double relax, con
     }
     kt.end(KT_CPR_OTHER, kt_a);
     kt_a = kt.begin();
-    if (comm && cpr_l0_halo && !ell.inner) {
+    if (comm && cpr_l0_halo && !ell.inner && w.amg->ndist == 0) {
         S* const hx = w.hx.p; CommBase* const cm = comm; const int nbl = plan.nb; hipStream_t st = stream;
         w.amg->level0_halo = [=](S* x, S* b) {
             OPMGPU_HIP(hipMemcpyAsync(hx, x, size_t(nbl) * sizeof(S), hipMemcpyDeviceToDevice, st));

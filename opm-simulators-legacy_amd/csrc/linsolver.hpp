@@ -59,6 +59,12 @@ struct CommBase {
     // caller-supplied coarse blocks of the owned cells (opmgpu_comm_set_coarse_blocks): > 0 = their number per rank; such blocks keep every
     // well inside ONE block (the caller's contract), so they are used in runs with wells too
     virtual int user_coarse_blocks() const { return 0; }
+    // distributed pressure hierarchy (amg.hip): level 0's neighbours and send / receive lists in internal rows, and a byte exchange with
+    // per-call lists (per neighbour q: sbytes[q] from sb + soff[q], rbytes[q] into rb + roff[q]), enqueued on s
+    virtual void level0_lists(const Plan& P, std::vector<int32_t>& neigh, std::vector<int32_t>& sptr, std::vector<int32_t>& srows,
+                              std::vector<int32_t>& rptr, std::vector<int32_t>& rrows) const = 0;
+    virtual void exchange_bytes(const std::vector<int32_t>& neigh, const char* sb, const std::vector<int64_t>& soff, const std::vector<int64_t>& sbytes,
+                                char* rb, const std::vector<int64_t>& roff, const std::vector<int64_t>& rbytes, hipStream_t s) = 0;
     int n_owned_global = 0;
 };
 
@@ -362,6 +368,11 @@ public:
     // iterations when only the AMG's matrix is cut, 9 with level 0 uncut: profiles/r04_ag_emulate_l0_global.log); on smooth decks the
     // counts are the single-domain ones without it.  opmgpu_params has no field for it: OPMGPU_CPR_L0_HALO=1 / 0, default 1 (on).
     bool cpr_l0_halo = true, cpr_l0_halo_down = true;
+    // Decomposed CPR, opmgpu_comm_set_pressure_hierarchy (default OPMGPU_CPR_GLOBAL_AMG, read at comm init): 0 = the rank-local cycle above with
+    // the Nicolaides coarse space, 1 = the distributed hierarchy of amg.hpp (every level global; no coarse space, level 0's exchanges are
+    // the hierarchy's own).  No effect on one rank.
+    int cpr_hier_mode = 0;
+    bool dist_hierarchy() const { return comm && comm->num_ranks() > 1 && cpr_hier_mode == 1 && !ell.inner; }
     DevArray<double> cs_state;     // [2 ns]: restricted residual of p, of r
     hipStream_t halo_stream = nullptr;
     hipEvent_t ev_halo[2] = { nullptr, nullptr };

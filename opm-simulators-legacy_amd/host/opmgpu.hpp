@@ -122,6 +122,8 @@ public:
     }
     /// VFPPROD / VFPINJ tables for THP controls (VFPProperties), before setDeviceWells
     void setVfpTables(int n, const opmgpu_vfp_table* tables) { throw_on_status(ctx_, opmgpu_set_vfp_tables(ctx_, n, tables)); }
+    /// decomposed runs (after opmgpu_comm_init*, before the first CPR solve): 0 = rank-local pressure hierarchy, 1 = distributed (opmgpu.h)
+    void setPressureHierarchy(int mode) { throw_on_status(ctx_, opmgpu_comm_set_pressure_hierarchy(ctx_, mode)); }
     /// once per report step, where SimulatorBase::run calls props.updateSatOilMax / updateSatHyst (SimulatorBase_impl.hpp:190-192)
     void updateSatOilMax() { throw_on_status(ctx_, opmgpu_update_sat_oil_max(ctx_)); }
     void updateSatHyst() { throw_on_status(ctx_, opmgpu_update_hysteresis(ctx_)); }

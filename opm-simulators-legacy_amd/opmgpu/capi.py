@@ -167,6 +167,10 @@ SIGNATURES = {
     "opmgpu_cpr_elliptic_ilu_apply": (C.c_int, [C.c_void_p, _dp, _dp]),
     "opmgpu_point_ilu_apply": (C.c_int, [C.c_void_p, _dp, _dp, C.c_double]),
     "opmgpu_comm_set_coarse_blocks": (C.c_int, [C.c_void_p, C.c_int, _ip]),
+    "opmgpu_comm_set_pressure_hierarchy": (C.c_int, [C.c_void_p, C.c_int]),
+    "opmgpu_cpr_dist_levels": (C.c_int, [C.c_void_p, _ip, _ip]),
+    "opmgpu_cpr_dist_level_get": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _ip, C.POINTER(C.c_int64), _dp,
+                                            C.POINTER(C.c_int64)]),
     "opmgpu_nonlinear_iteration": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int, C.POINTER(NewtonCtl), C.POINTER(C.c_int), C.POINTER(C.c_int), _dp, _dp]),
     "opmgpu_update_hysteresis": (C.c_int, [C.c_void_p]),
     "opmgpu_set_hysteresis": (C.c_int, [C.c_void_p, _dp, _dp]),

@@ -68,6 +68,23 @@ class _CprDiagnostics:
         self._status(self.lib.opmgpu_cpr_level_get(self.ctx, level, capi.iptr(rowptr), capi.iptr(col), capi.dptr(val), capi.iptr(agg), capi.dptr(inv)))
         return rowptr, col, val, agg, inv
 
+    def cpr_dist_levels(self):
+        """(levels, distributed levels) of a decomposed hierarchy; (n, 0) for a rank-local or single-domain one"""
+        nl, nd = C.c_int32(0), C.c_int32(0)
+        self._status(self.lib.opmgpu_cpr_dist_levels(self.ctx, C.byref(nl), C.byref(nd)))
+        return nl.value, nd.value
+
+    def cpr_dist_level(self, level):
+        """level `level` of a distributed hierarchy in global numbering: (row ids, rowptr, column ids, values, aggregate ids); this rank's
+        owned rows of a distributed level (level 0: caller-local ids, wells at n_local + k), the whole matrix of a replicated one"""
+        p64 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int64))      # noqa: E731
+        cnt = np.zeros(2, np.int64)
+        self._status(self.lib.opmgpu_cpr_dist_level_get(self.ctx, level, p64(cnt), None, None, None, None, None))
+        nr, nz = int(cnt[0]), int(cnt[1])
+        rows, rowptr, cols, val, agg = np.zeros(nr, np.int64), np.zeros(nr + 1, np.int32), np.zeros(nz, np.int64), np.zeros(nz), np.zeros(nr, np.int64)
+        self._status(self.lib.opmgpu_cpr_dist_level_get(self.ctx, level, p64(cnt), p64(rows), capi.iptr(rowptr), p64(cols), capi.dptr(val), p64(agg)))
+        return rows, rowptr, cols, val, agg
+
     def cpr_vcycle_apply(self, b):
         b = capi.f64(b)
         x = np.zeros_like(b)

@@ -117,8 +117,9 @@ def shm_test_transport_wanted():
     return os.environ.get("OPMGPU_COMM_TRANSPORT") == "shm"
 
 
-def attach_comm(model, dom, rank, world, unique_id):
-    """opmgpu_comm_init (RCCL) -- or opmgpu_comm_init_transport with the shared-memory test transport -- for a model created on dom.grid."""
+def attach_comm(model, dom, rank, world, unique_id, pressure_hierarchy=None):
+    """opmgpu_comm_init (RCCL) -- or opmgpu_comm_init_transport with the shared-memory test transport -- for a model created on dom.grid.
+    pressure_hierarchy: 0 / 1 = opmgpu_comm_set_pressure_hierarchy (None: the library's default, OPMGPU_CPR_GLOBAL_AMG)."""
     lib = capi.load()
     lists = (dom.n_owned, int(dom.neigh_rank.size), capi.iptr(dom.neigh_rank), capi.iptr(dom.send_ptr), capi.iptr(dom.send_cells),
              capi.iptr(dom.recv_ptr), capi.iptr(dom.recv_cells))
@@ -138,6 +139,16 @@ def attach_comm(model, dom, rank, world, unique_id):
         st = lib.opmgpu_comm_init(model.ctx, rank, world, idb, *lists)
     if st != capi.OK:
         raise RuntimeError("opmgpu_comm_init failed with status %d: %s" % (st, lib.opmgpu_last_error(model.ctx)))
+    if pressure_hierarchy is not None:
+        set_pressure_hierarchy(model, pressure_hierarchy)
+
+
+def set_pressure_hierarchy(model, mode):
+    """opmgpu_comm_set_pressure_hierarchy: 0 = rank-local CPR pressure levels + one coarse unknown per rank, 1 = a hierarchy spanning all ranks."""
+    lib = capi.load()
+    st = lib.opmgpu_comm_set_pressure_hierarchy(model.ctx, int(mode))
+    if st != capi.OK:
+        raise RuntimeError("opmgpu_comm_set_pressure_hierarchy(%r) failed with status %d: %s" % (mode, st, lib.opmgpu_last_error(model.ctx)))
 
 
 def make_unique_id():
