@@ -47,6 +47,8 @@ struct AmgLevel {
     // Vectors of a bordered level have n + nw entries (well k at index n + k); the border values live behind the SELL values:
     // val[nentries + j] = column entry of perforation j (row perf_row[j], column n + well), val[nentries + nperf + j] = row entry
     // (row n + well, column perf_row[j]), val[nentries + 2 nperf + k] = diagonal of well k.
+    // The wells' rows stay singletons on every level down to the coarsest, whose dense inverse holds kDenseMax = 96 rows: setup() builds the
+    // border for at most kDenseMax / 2 = 48 wells and none beyond (the wells then act through their cells' diagonal terms only).
     int nw = 0, nperf = 0;
     const int32_t* b_connpos = nullptr;         // [nw+1]  (device, owned by the well model)
     const int32_t* b_perf_row = nullptr;        // [nperf]

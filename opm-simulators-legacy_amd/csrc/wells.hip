@@ -212,34 +212,43 @@ __global__ void k_well_avg_press(int nw, WellArgs A, const int32_t* __restrict__
 // well: the lanes stage a tile of perforation data in LDS with parallel loads, lane 0 then walks the tile in the reference's order (the
 // running sums are sequential by definition; a thread fetching every perforation's operands itself spends 1.6 us per perforation waiting
 // for them: 164 us for a 100-perforation well, 8x this version).
+// qout[nperf][3]: q_out of every perforation, filled bottom to top EXACTLY as the reference does.  The segment below the lowest flowing
+// perforation must carry a flow of exactly 0.0 (its mixture is then the well's comp_frac, WellDensitySegmented.cpp:103-109): a total taken
+// at the top and reduced on the way down leaves rounding residue there, and with it the mixture of that residue.
+// A well's part of qout is written and read back by that well's workgroup alone: the barrier between the two passes orders it.
 constexpr int kCdpTile = 128;
-__global__ __launch_bounds__(64) void k_well_cdp(int nw, WellArgs A, double gravity, const int32_t* __restrict__ gate)
+__global__ __launch_bounds__(64) void k_well_cdp(int nw, WellArgs A, double gravity, const int32_t* __restrict__ gate, double* __restrict__ qout)
 {
     __shared__ double s_rate[3 * kCdpTile], s_pvt[5 * kCdpTile], s_sd[3 * kCdpTile], s_z[kCdpTile], s_dens[kCdpTile], s_cdp[kCdpTile];
     if (gate && !*gate) return;
     const int w = blockIdx.x, lane = threadIdx.x;
     if (w >= nw) return;
     const int lo = A.connpos[w], hi = A.connpos[w + 1];
-    // q_out[perf] = flow out of the segment above perforation perf = sum_{k >= perf} (-rate_k) (the reference fills it bottom to
-    // top, WellDensitySegmented.cpp:83-95); here: total at the top first, then q_out[perf + 1] = q_out[perf] + rate[perf] going down.
-    double q[3] = { 0.0, 0.0, 0.0 };
-    for (int t1 = hi; t1 > lo; t1 -= kCdpTile) {
-        const int t0 = t1 - kCdpTile > lo ? t1 - kCdpTile : lo, nt = t1 - t0;
-        for (int i = lane; i < 3 * nt; i += 64) s_rate[i] = A.perf_rates[3 * long(t0) + i];
-        __syncthreads();
-        if (lane == 0) for (int i = nt - 1; i >= 0; --i) for (int a = 0; a < 3; ++a) q[a] -= s_rate[3 * i + a];
-        __syncthreads();
+    // q_out[perf] = flow out of the segment above perforation perf = sum_{k >= perf} (-rate_k), from the bottom up
+    // (WellDensitySegmented.cpp:83-95): q_out[perf] = q_out[perf + 1] - rate[perf], 0.0 below the last one
+    {
+        double q[3] = { 0.0, 0.0, 0.0 };
+        for (int t1 = hi; t1 > lo; t1 -= kCdpTile) {
+            const int t0 = t1 - kCdpTile > lo ? t1 - kCdpTile : lo, nt = t1 - t0;
+            for (int i = lane; i < 3 * nt; i += 64) s_rate[i] = A.perf_rates[3 * long(t0) + i];
+            __syncthreads();
+            if (lane == 0) for (int i = nt - 1; i >= 0; --i) for (int a = 0; a < 3; ++a) { q[a] -= s_rate[3 * i + a]; s_sd[3 * i + a] = q[a]; }
+            __syncthreads();
+            for (int i = lane; i < 3 * nt; i += 64) qout[3 * long(t0) + i] = s_sd[i];
+            __syncthreads();
+        }
     }
     double run = 0.0, z_above = A.depth_ref[w];
     for (int t0 = lo; t0 < hi; t0 += kCdpTile) {
         const int nt = hi - t0 < kCdpTile ? hi - t0 : kCdpTile;
-        for (int i = lane; i < 3 * nt; i += 64) { s_rate[i] = A.perf_rates[3 * long(t0) + i]; s_sd[i] = A.surf_dens_perf[3 * long(t0) + i]; }
+        for (int i = lane; i < 3 * nt; i += 64) { s_rate[i] = qout[3 * long(t0) + i]; s_sd[i] = A.surf_dens_perf[3 * long(t0) + i]; }
         for (int i = lane; i < 5 * nt; i += 64) s_pvt[i] = A.perf_pvt[5 * long(t0) + i];
         for (int i = lane; i < nt; i += 64) s_z[i] = A.z_perf[t0 + i];
         __syncthreads();
         if (lane == 0) {
             for (int i = 0; i < nt; ++i) {
                 const double* pv = s_pvt + 5 * i;
+                const double* q = s_rate + 3 * i;
                 const double tot = q[0] + q[1] + q[2];
                 double mix[3], x[3];
                 for (int a = 0; a < 3; ++a) { mix[a] = tot != 0.0 ? fabs(q[a] / tot) : A.comp_frac[3 * w + a]; x[a] = mix[a]; }
@@ -256,7 +265,6 @@ __global__ __launch_bounds__(64) void k_well_cdp(int nw, WellArgs A, double grav
                 run += (s_z[i] - z_above) * dens * gravity;
                 z_above = s_z[i];
                 s_cdp[i] = run;
-                for (int a = 0; a < 3; ++a) q[a] += s_rate[3 * i + a];
             }
         }
         __syncthreads();
@@ -836,7 +844,7 @@ struct BlackoilDevice::WellsDev {
     bool vfp_active = false;            // isVFPActive (BlackoilModelBase_impl.hpp:982-1008): some well has a THP control
     DevArray<int32_t> connpos, perf_row, perf_well, perf_of_row, type, allow_cf, ctrl_type, ctrl_ptr, ctrl_vfp, thp_ctrl, current, isnap, isaved;
     DevArray<double> WI, comp_frac, ctrl_target, ctrl_distr, ctrl_alq, depth_ref, z_perf, surf_dens_perf;
-    DevArray<double> wstate, thp, cdp, perf_dens, perf_pvt, avgp, perf_rates, perf_press, P, Q, Fsave, wellE, Dinv, t, wdy, wdy_old;
+    DevArray<double> wstate, thp, cdp, perf_dens, perf_pvt, avgp, qout, perf_rates, perf_press, P, Q, Fsave, wellE, Dinv, t, wdy, wdy_old;
     DevArray<double> bsums, bscratch, snap, presolve_sync, ctrl_row;
     DevArray<double> saved;         // snapshot for AdaptiveTimeStepping: wstate | thp | cdp | perf_rates | perf_press | perf_dens
     DevArray<int32_t> flags;
@@ -949,7 +957,7 @@ int BlackoilDevice::set_device_wells(const opmgpu_wells* s)
     upd(W.ctrl_distr, s->ctrl_distr, 3 * size_t(nct)); upd(W.ctrl_alq, s->ctrl_alq, nct); upd(W.depth_ref, s->depth_ref, nw);
     W.current.alloc(nw); W.current.zero(stream); W.isnap.alloc(nw + 1); W.isaved.alloc(nw);
     W.thp.alloc(nw); W.thp.zero(stream);
-    W.perf_dens.alloc(np); W.perf_dens.zero(stream); W.perf_pvt.alloc(5 * size_t(np)); W.avgp.alloc(np);
+    W.perf_dens.alloc(np); W.perf_dens.zero(stream); W.perf_pvt.alloc(5 * size_t(np)); W.avgp.alloc(np); W.qout.alloc(3 * size_t(np));
     W.ctrl_row.alloc(4 * size_t(nw)); W.ctrl_row.zero(stream);
     W.wdy.alloc(4 * size_t(nw)); W.wdy.zero(stream); W.wdy_old.alloc(4 * size_t(nw)); W.wdy_old.zero(stream);
     W.bsums.alloc(16); W.bscratch.alloc(13 * size_t(kMaxRedBlocks)); W.snap.alloc(5 * size_t(nw) + 4 * size_t(np));
@@ -1027,7 +1035,7 @@ void BlackoilDevice::wells_connection_pressures(const int32_t* gate)
     const int g = (W.nw + 63) / 64;
     hipLaunchKernelGGL(k_well_avg_press, dim3(g), dim3(64), 0, stream, W.nw, A, gate, W.avgp.p);
     perf_pvt_device(W.avgp.p, W.perf_pvt.p, gate);
-    hipLaunchKernelGGL(k_well_cdp, dim3(W.nw), dim3(64), 0, stream, W.nw, A, gravity, gate);
+    hipLaunchKernelGGL(k_well_cdp, dim3(W.nw), dim3(64), 0, stream, W.nw, A, gravity, gate, W.qout.p);
 }
 
 // called by assemble() after the reservoir kernels; the well part of BlackoilModelBase::assemble in the reference's order (:757-840)

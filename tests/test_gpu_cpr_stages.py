@@ -64,11 +64,12 @@ def _rel(a, b):
     return np.linalg.norm((a - b) / m) / np.linalg.norm(b / m)
 
 
-def check_hierarchy(obj, rowptr, col, val9, single, case, knobs=(), npost0=2, gs_first=None, cpr=None, npre=1, pilu=None):
-    """all checks of the module docstring on the hierarchy `obj` (GpuNewtonIteration or GpuBlackoilModel) holds after its solve"""
+def check_hierarchy(obj, rowptr, col, val9, single, case, knobs=(), npost0=2, gs_first=None, cpr=None, npre=1, pilu=None, seen=SEEN):
+    """all checks of the module docstring on the hierarchy `obj` (GpuNewtonIteration or GpuBlackoilModel) holds after its solve.
+    seen: where the case is recorded for test_coverage_of_the_cases (callers from other modules pass a dict of their own)"""
     nb = rowptr.size - 1
     n, nnz, nw = obj.cpr_levels()
-    SEEN[case] = (list(n), nw, tuple(knobs), list(nnz))
+    seen[case] = (list(n), nw, tuple(knobs), list(nnz))
     nl = len(n)
     levels = [obj.cpr_level(l) for l in range(nl)]
     A = [ar.csr(*levels[l][:3], n[l]) for l in range(nl)]

@@ -186,104 +186,8 @@ def test_norne_like_unstructured(gpu_lib, oracle):
 # ------------------------------------------------------------------------------------------------------------------------
 # full-size oracle parity
 # ------------------------------------------------------------------------------------------------------------------------
-def _perforated_diag_mask(rowptr, col, cells):
-    """blocks (c, c) of the perforated cells: the only Jacobian entries the device well model changes in the matrix itself"""
-    nb = rowptr.size - 1
-    rows = np.repeat(np.arange(nb, dtype=np.int64), np.diff(rowptr))
-    perf = np.zeros(nb, bool); perf[np.asarray(cells, int)] = True
-    return (rows == col) & perf[rows]
-
-
-def _lockstep_parity(gpu_lib, oracle, grid, tab, st, dt, wl, niter=2, cpr=1, reduction=1e-10, maxiter=2000, tol_p=1e-6, tol_s=1e-6,
-                     single=False, gmres=0, verify=0, oracle_reduction=None, tol_jac=1e-11, tol_op=1e-9, stage2_relax=1.0):
-    """Newton iterations 0..niter-1 of one time step, GPU (device wells, CPR or ILU0) and oracle (+ host well model with
-    the explicit Schur complement) side by side.  Every assembly is compared at rounding level; after every update the two states are
-    compared at the linear tolerance and the oracle then CONTINUES FROM THE GPU's state, so the next assembly is again a rounding-level
-    comparison (a free-running comparison is test_*_newton_count below).
-
-    single / gmres / verify select the configurations bench.py TIMES: restarted GMRES(40) (newton_use_gmres) under CPR in double -- the
-    headline --, and the float variant (the Jacobian written as float, the float CPR solve, GMRES with the true-residual check).  The
-    oracle side stays the f64 reference solve (ILU0 + BiCGStab) at `oracle_reduction`, the residual (always f64) stays a rounding-level
-    comparison, a float Jacobian / operator are compared at float rounding level (tol_jac / tol_op)."""
-    from opmgpu import wells as W
-    from util import OracleBackend, rel_err
-    oracle.set_threads(16)
-    prm_g = capi.default_params(linear_solver_reduction=reduction, linear_solver_maxiter=maxiter, cpr_use_amg=1, cpr_max_ell_iter=0, use_cpr=cpr, newton_use_gmres=gmres, gmres_verify_residual=verify,
-                                cpr_stage2_relax=stage2_relax)
-    prm_o = capi.default_params(linear_solver_reduction=oracle_reduction or reduction, linear_solver_maxiter=4 * maxiter)
-    nc = grid.nc
-    gm = GpuBlackoilModel(grid, tab, prm_g)
-    rowptr0, col0 = oracle.pattern(grid)
-    scale = np.asarray(prm_g.matbalscale[:])
-    if wl is not None:
-        md = W.DeviceWellModel(gm, wl, W.WellState(wl, st.p))
-        ob = OracleBackend(oracle, grid, tab, prm_o, wells=wl.arrays())
-        mo = W.WellCoupledModel(ob, W.StandardWellsHost(wl, grid.z, tab.surface_density[0]), W.WellState(wl, st.p))
-        diag_perf = _perforated_diag_mask(rowptr0, col0, wl.cells)
-    else:
-        md, ob = gm, OracleBackend(oracle, grid, tab, prm_o)
-        mo = ob
-    md.prepareStep(dt, st); mo.prepareStep(dt, st)
-    rng = np.random.default_rng(5)
-    for it in range(niter):
-        # ---- assembly ----
-        gm.setSolvePrecision(single)
-        gm.assemble(it == 0)
-        mo.assemble(it == 0)            # with wells: control switching, reservoir, [connection pressures + well pre-solve], well terms
-        val_res = None
-        if wl is not None:
-            # reservoir-only oracle Jacobian on the stencil pattern: everything but the perforated cells' diagonal blocks must match it
-            _, val_res, _, _ = oracle.assemble(grid, tab, dt, ob.st, rowptr0, col0, scale=tuple(scale), accum0=ob.acc0)
-            if it == 0:
-                md.pull_well_state()
-                assert md.presolve_converged and md.presolve_iterations == mo.wh.well_iterations
-        gr, gc, gv = gm.jacobian()
-        assert np.array_equal(gr, rowptr0) and np.array_equal(gc, col0)
-        assert rel_err(gm.residual(), ob.r) < 1e-11, (it, rel_err(gm.residual(), ob.r))
-        if wl is None:
-            assert rel_err(gv, ob.val) < tol_jac, it
-        else:
-            keep = ~diag_perf
-            assert rel_err(gv[keep], val_res[keep]) < tol_jac, (it, rel_err(gv[keep], val_res[keep]))
-            # the coupled operator (matrix + factored rank-7 Schur complement per well) against the oracle's explicit clique matrix
-            for _ in range(2):
-                x3 = rng.standard_normal(3 * nc) * np.tile([1e5, 1e-2, 1e-2], nc)
-                yo = oracle.spmv(ob.rowptr, ob.col, ob.val, x3)
-                yg = gm.spmv(x3)
-                assert rel_err(yg, yo) < tol_op, (it, rel_err(yg, yo))
-        del gv, val_res
-        # ---- convergence scalars ----
-        cg = gm.getConvergence(); co = ob.getConvergence()
-        assert np.allclose(gm.CNV, ob.CNV, rtol=1e-9) and np.allclose(gm.MB, ob.MB, rtol=1e-7, atol=1e-18) and np.allclose(gm.B_avg, ob.B_avg, rtol=1e-12)
-        if wl is not None:
-            cg = md.wellConvergence() and cg; co = mo.wh.converged(ob.B_avg) and co
-            assert np.allclose(md.well_flux_residual, mo.wh.well_flux_residual, rtol=1e-7, atol=1e-14)
-            assert md.well_ctrl_residual == pytest.approx(mo.wh.well_ctrl_residual, rel=1e-7, abs=1e-14)
-        assert cg == co
-        # ---- solve + update ----
-        gm.solveJacobianSystem(single_precision=single)
-        assert gm.linear_reduction <= reduction, (it, gm.linear_reduction)        # with gmres_verify_residual: the TRUE residual's reduction
-        gm.updateState()
-        ob.solveJacobianSystem(single_precision=False)
-        if wl is not None:
-            mo.wh.recover_and_update(ob.perfDx(wl.nperf), mo.ws)
-        ob.updateState()
-        a, b = gm.getState(), ob.getState()
-        assert np.array_equal(a.hc, b.hc), it
-        assert np.abs(a.p - b.p).max() <= tol_p * np.abs(b.p).max(), (it, np.abs(a.p - b.p).max() / np.abs(b.p).max())
-        assert np.abs(a.sat - b.sat).max() <= tol_s, (it, np.abs(a.sat - b.sat).max())
-        # rs / rv at a fixed 1e-5 (float: rs / rv of the undersaturated cells are unknowns of the float solve themselves).  Round 3 had widened
-        # this to 10 * tol_p after the SPE10-like leg measured 0.9e-5 .. 1.9e-5 from run to run: the checker's 16-thread dot products were not
-        # bit-reproducible (an OpenMP reduction clause).  They are summed in fixed blocks now (oracle.cpp dot_t), so the old gate is back.
-        tol_r = 1e-5 if not single else 2.5 * tol_s
-        assert np.abs(a.rs - b.rs).max() <= tol_r * max(np.abs(b.rs).max(), 1.0) and np.abs(a.rv - b.rv).max() <= tol_r * max(np.abs(b.rv).max(), 1e-3)
-        ob.st = a.copy()                                 # lockstep: the oracle continues from the device state
-        if wl is not None:
-            ws = md.pull_well_state()
-            assert np.allclose(ws.bhp, mo.ws.bhp, rtol=max(1e-6, tol_p)), (it, ws.bhp, mo.ws.bhp)
-            assert np.allclose(ws.qs, mo.ws.qs, rtol=max(1e-5, 10 * tol_p), atol=max(1e-8, tol_p) * np.abs(mo.ws.qs).max()), it
-            mo.ws.assign(ws)
-    gm.close()
+# the walker of the lockstep comparisons lives in tests/util.py: test_gpu_well_sizes.py walks its decks with it too
+from util import lockstep_parity as _lockstep_parity, perforated_diag_mask as _perforated_diag_mask  # noqa: E402,F401
 
 
 def _run_time_step(model, dt, st, single, ns, max_iter=15):
