@@ -806,15 +806,15 @@ void AmgHierarchy<S>::setup(const Plan& P, const int32_t* d_slice_ptr, const int
 {
     if (inv_stream) { OPMGPU_HIP(hipStreamSynchronize(inv_stream)); inv_pending = false; }       // dense_inv is re-allocated below
     levels.clear(); level_sizes.clear();
-    if (const char* e = std::getenv("OPMGPU_AMG_INV_OVERLAP")) inv_overlap = std::atoi(e) != 0;
+    inv_overlap = env_flag("OPMGPU_AMG_INV_OVERLAP", inv_overlap);
     if (const char* e = std::getenv("OPMGPU_AMG_OMEGA")) omega = std::atof(e);
     if (const char* e = std::getenv("OPMGPU_AMG_PDAMP")) { pdamp = std::atof(e); pdamp0 = pdamp; pdamp_user = true; }
     if (const char* e = std::getenv("OPMGPU_AMG_PDAMP0")) { pdamp0 = std::atof(e); pdamp_user = true; }
-    if (const char* e = std::getenv("OPMGPU_AMG_NPRE")) npre = std::atoi(e);
-    if (const char* e = std::getenv("OPMGPU_AMG_NPOST")) npost = std::atoi(e);
-    if (const char* e = std::getenv("OPMGPU_AMG_FUSE")) fuse = std::atoi(e) != 0;
-    if (const char* e = std::getenv("OPMGPU_AMG_GRAPH")) use_graph = std::atoi(e) != 0;
-    if (const char* e = std::getenv("OPMGPU_AMG_GS")) use_gs = std::atoi(e) != 0;
+    npre = env_int("OPMGPU_AMG_NPRE", npre);
+    npost = env_int("OPMGPU_AMG_NPOST", npost);
+    fuse = env_flag("OPMGPU_AMG_FUSE", fuse);
+    use_graph = env_flag("OPMGPU_AMG_GRAPH", use_graph);
+    use_gs = env_flag("OPMGPU_AMG_GS", use_gs);
     gs_n0 = (P.nlevels == 2) ? P.level_ptr[1] : 0;        // two colours: rows [0, n0) and [n0, nb)
     if (graph_exec) { (void)hipGraphExecDestroy(graph_exec); graph_exec = nullptr; }
     npost0 = npost;
@@ -861,11 +861,11 @@ void AmgHierarchy<S>::setup(const Plan& P, const int32_t* d_slice_ptr, const int
     int npin = nwb;
     const int kMaxDense = kDenseMax;
     int kMaxLevels = 12;
-    if (const char* e = std::getenv("OPMGPU_AMG_MAXLEVELS")) kMaxLevels = std::max(2, std::atoi(e));
-    if (const char* e = std::getenv("OPMGPU_AMG_COARSE_SWEEPS")) coarse_sweeps = std::max(0, std::atoi(e));
+    kMaxLevels = std::max(2, env_int("OPMGPU_AMG_MAXLEVELS", kMaxLevels));
+    coarse_sweeps = std::max(0, env_int("OPMGPU_AMG_COARSE_SWEEPS", coarse_sweeps));
     ndist = 0;
     tail_rows = kTailRows;
-    if (const char* e = std::getenv("OPMGPU_AMG_TAIL_ROWS")) tail_rows = std::max(1, std::atoi(e));
+    tail_rows = std::max(1, env_int("OPMGPU_AMG_TAIL_ROWS", tail_rows));
     std::vector<int8_t> pinmark;            // replicated tail: the wells' rows stay singletons (aggregate(): mark 2)
     if (dcomm) setup_dist(*this, P, A, L, npin, pinmark, kMaxLevels);
     while (true) {
@@ -878,15 +878,6 @@ void AmgHierarchy<S>::setup(const Plan& P, const int32_t* d_slice_ptr, const int
         int na = 0;
         const bool stop = n <= kMaxDense || int(levels.size()) + 1 >= kMaxLevels;
         if (!stop) na = aggregate(A, 0.25, agg, npin, pinmark.empty() ? nullptr : &pinmark);
-        // aggressive coarsening (OPMGPU_AMG_AGGR=l: from level l on, aggregate twice and compose): the levels below ~100 k rows are
-        // launch-latency bound (~5 us per dependent kernel), so fewer of them shortens the cycle; costs convergence per cycle
-        static const int aggr_from = std::getenv("OPMGPU_AMG_AGGR") ? std::atoi(std::getenv("OPMGPU_AMG_AGGR")) : -1;
-        if (!stop && aggr_from >= 0 && int(levels.size()) >= aggr_from && na > kMaxDense && na * 10 <= n * 8) {
-            HostCsr C1; std::vector<int32_t> cof1, aptr1, arows1, agg2;
-            coarsen(A, agg, na, C1, cof1, aptr1, arows1);
-            const int na2 = aggregate(C1, 0.25, agg2, npin);
-            if (na2 >= 1 && na2 * 10 <= na * 8) { for (int i = 0; i < n; ++i) agg[i] = agg2[agg[i]]; na = na2; }
-        }
         if (stop || na * 10 > n * 8 || na < 1) {           // coarsest level (or coarsening stalled)
             levels.push_back(std::move(L));
             break;
@@ -1208,84 +1199,6 @@ void AmgHierarchy<S>::vcycle_graph(const SolveCtl* ctl, bool level0_presmoothed)
         graph_ctl = ctl; graph_pre = level0_presmoothed;
     }
     OPMGPU_HIP(hipGraphLaunch(graph_exec, stream));
-}
-
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_amg_norm2_parts(int n, const S* __restrict__ r, double* __restrict__ parts)
-{
-    __shared__ double sm[4];
-    double acc[1] = { 0.0 };
-    for (long i = blockIdx.x * long(kBlock) + threadIdx.x; i < n; i += long(gridDim.x) * kBlock) acc[0] += double(r[i]) * double(r[i]);
-    block_sum<1>(acc, sm);
-    if (threadIdx.x == 0) parts[blockIdx.x] = acc[0];
-}
-__global__ __launch_bounds__(kBlock) void k_amg_sum_parts(int np, const double* __restrict__ parts, double* __restrict__ out)
-{
-    __shared__ double sm[4];
-    double acc[1] = { 0.0 };
-    for (int i = threadIdx.x; i < np; i += kBlock) acc[0] += parts[i];
-    block_sum<1>(acc, sm);
-    if (threadIdx.x == 0) out[0] = acc[0];
-}
-template <class S>
-void AmgHierarchy<S>::residual0(const SolveCtl* ctl)
-{
-    AmgLevel<S>& F = *levels[0];
-    const int g = grid_for(F.n);
-    Border<S> B;
-    if (F.nw) {
-        B.nw = F.nw; B.n = F.n; B.gcells = g; B.connpos = F.b_connpos; B.perf_row = F.b_perf_row; B.perf_of_row = F.b_perf_of_row; B.perf_well = F.b_perf_well;
-        B.bcol = F.val.p + F.nentries; B.crow = B.bcol + F.nperf; B.dw = B.crow + F.nperf;
-    }
-    hipLaunchKernelGGL((k_amg_residual<S, 0>), dim3(g + F.nw), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, F.x.p, S(omega), F.dinv.p, F.r.p, ctl,
-                       (const int32_t*)nullptr, (const S*)nullptr, S(0), B);
-}
-template <class S>
-void AmgHierarchy<S>::residual_norm2(double* d_out)
-{
-    AmgLevel<S>& F = *levels[0];
-    const int g = grid_for(F.n);
-    Border<S> B;
-    if (F.nw) {
-        B.nw = F.nw; B.n = F.n; B.gcells = g; B.connpos = F.b_connpos; B.perf_row = F.b_perf_row; B.perf_of_row = F.b_perf_of_row; B.perf_well = F.b_perf_well;
-        B.bcol = F.val.p + F.nentries; B.crow = B.bcol + F.nperf; B.dw = B.crow + F.nperf;
-    }
-    hipLaunchKernelGGL((k_amg_residual<S, 0>), dim3(g + F.nw), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, F.x.p, S(omega), F.dinv.p, F.r.p, (const SolveCtl*)nullptr,
-                       (const int32_t*)nullptr, (const S*)nullptr, S(0), B);
-    const int np = 512;
-    if (tune_parts.n < size_t(np)) tune_parts.alloc(np);
-    hipLaunchKernelGGL((k_amg_norm2_parts<S>), dim3(np), dim3(kBlock), 0, stream, F.ntot(), (const S*)F.r.p, tune_parts.p);
-    hipLaunchKernelGGL(k_amg_sum_parts, dim3(1), dim3(kBlock), 0, stream, np, (const double*)tune_parts.p, d_out);
-}
-
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_amg_hash_fill(int n, S* __restrict__ x)
-{
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= n) return;
-    uint32_t h = uint32_t(i) * 2654435761u; h ^= h >> 15; h *= 2246822519u; h ^= h >> 13; h *= 3266489917u; h ^= h >> 16;
-    x[i] = S(double(h) / 2147483648.0 - 1.0);
-}
-template <class S>
-void AmgHierarchy<S>::smooth_test_rhs(int sweeps)
-{
-    AmgLevel<S>& F = *levels[0];
-    const size_t nt = size_t(F.ntot());
-    if (tune_b.n < nt) tune_b.alloc(nt);
-    OPMGPU_HIP(hipMemcpyAsync(tune_b.p, F.b.p, nt * sizeof(S), hipMemcpyDeviceToDevice, stream));
-    OPMGPU_HIP(hipMemsetAsync(F.b.p, 0, nt * sizeof(S), stream));
-    hipLaunchKernelGGL((k_amg_hash_fill<S>), dim3(grid_for(F.n)), dim3(kBlock), 0, stream, F.n, F.x.p);
-    if (F.nw) OPMGPU_HIP(hipMemsetAsync(F.x.p + F.n, 0, F.nw * sizeof(S), stream));
-    for (int k = 0; k < 2 * ((sweeps + 1) / 2); ++k) sweep(F, nullptr);       // an even count: x / x2 keep their roles
-    if (tune_parts.n < 512) tune_parts.alloc(512);
-    residual_norm2(tune_parts.p);                                             // r = 0 - A s
-    OPMGPU_HIP(hipMemcpyAsync(F.b.p, F.r.p, nt * sizeof(S), hipMemcpyDeviceToDevice, stream));
-}
-template <class S>
-void AmgHierarchy<S>::restore_rhs()
-{
-    AmgLevel<S>& F = *levels[0];
-    OPMGPU_HIP(hipMemcpyAsync(F.b.p, tune_b.p, size_t(F.ntot()) * sizeof(S), hipMemcpyDeviceToDevice, stream));
 }
 
 // r = b - A x on one level (unfused: the distributed levels)

@@ -125,23 +125,15 @@ public:
     double pdamp = 1.9;           // coarse-grid correction scaling (dune-istl's prolongation damping factor); see LinSolver::cpr_prepare for 2.2
     double pdamp0 = 1.9;          // ... of the correction into level 0 (OPMGPU_AMG_PDAMP0)
     bool pdamp_user = false;      // OPMGPU_AMG_PDAMP given: no automatic choice
-    bool tuned = false;           // the correction factors were chosen for this hierarchy (LinSolver::cpr_tune)
-    // ||b - A x||^2 over level 0 (border rows included) into d_out[0]; two launches, fixed summation order
-    void residual_norm2(double* d_out);
-    // levels[0].r = b - A x on level 0 (border rows included); one launch
-    void residual0(const SolveCtl* ctl);
+    // Set by the first application of this hierarchy (LinSolver::cpr_apply).  Until then cpr_prepare assigns its fixed factors (1.9, or 2.2 into
+    // level 0) whenever the correction policy does not choose; afterwards such matrices keep what pdamp0 / pdamp hold.
+    bool factors_kept = false;
     // Decomposed runs (set by LinSolver per application, empty otherwise): called with level 0's iterate before every level-0 operation
     // that reads neighbours' entries of it -- the residual of the down leg and each post-smoothing sweep.  The callback refreshes the ghost
     // entries from their owners (one halo exchange) so that level 0 of the cycle works on the GLOBAL pressure matrix; the coarse levels
     // stay rank-local.  With the hook set the cycle takes the unfused level-0 launches (smooth / residual / prolong / sweeps).
     std::function<void(S* x, S* b)> level0_halo;
     bool level0_halo_down = true;          // false: only the post-smoothing sweeps see the neighbours (A/B: OPMGPU_CPR_L0_HALO=2)
-    DevArray<double> tune_parts;
-    // levels[0].b := A s for an algebraically smooth s (pseudo-random start, `sweeps` Jacobi sweeps on A s = 0): the kind of error the
-    // coarse-grid correction of a cycle meets.  The caller's right-hand side is parked in tune_b until restore_rhs().
-    void smooth_test_rhs(int sweeps);
-    void restore_rhs();
-    DevArray<S> tune_b;
     int npre = 1, npost = 2;      // smoothing sweeps before / after the coarse-grid correction
     int npost0 = 2;               // post-smoothing sweeps on level 0 (cheap per sweep there; coarse levels are launch-latency bound)
     bool npost0_user = false;     // OPMGPU_AMG_NPOST0 given: the solvers do not choose (BiCGStab 2, GMRES 1)

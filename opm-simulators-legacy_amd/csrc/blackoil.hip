@@ -1552,13 +1552,13 @@ template <class MS> void BlackoilDevice::assemble_kernels(double dt, bool initia
     KtScope kts(ls.kt, KT_FLUX);
     // compiled for 3 waves per SIMD (168 VGPRs, 14 spilled; default) or for 2 (173 VGPRs, none; OPMGPU_ASM_WAVES=2).  Measured at 100^3
     // (profiles/r03_asm_waves_ab.log): 0.232 against 0.240 ms with a double Jacobian, 0.181 against 0.206 ms with a float one
-    static const int waves = std::getenv("OPMGPU_ASM_WAVES") ? std::atoi(std::getenv("OPMGPU_ASM_WAVES")) : 3;
+    static const int waves = env_int("OPMGPU_ASM_WAVES", 3);
     const bool lds = tab_lds_words() > 0;
     // all ten neighbour values in one batch (default; measured 0.202 against 0.211 ms with a double Jacobian, profiles/r03_asm_batch_ab.log) or
     // the upwind-dependent five only when needed (OPMGPU_ASM_BATCH=0)
-    static const bool batch = !(std::getenv("OPMGPU_ASM_BATCH") && std::atoi(std::getenv("OPMGPU_ASM_BATCH")) == 0);
+    static const bool batch = env_flag("OPMGPU_ASM_BATCH", true);
     // mixed precision: the float copy of a DOUBLE Jacobian is written in the same pass (A/B: OPMGPU_MIXED_DUALWRITE=0 converts before the solve)
-    static const bool dual = !(std::getenv("OPMGPU_MIXED_DUALWRITE") && std::atoi(std::getenv("OPMGPU_MIXED_DUALWRITE")) == 0);
+    static const bool dual = env_flag("OPMGPU_MIXED_DUALWRITE", true);
     float* a32 = nullptr;
     if (dual && sizeof(MS) == 8 && prm.preconditioner_single && !props_only && ls.emulate_ranks <= 1 && !(prm.use_cpr && prm.cpr_reference_transform)) { a32 = ls.matrix_f(); dual_written = true; }
     auto kern = !lds ? k_assemble_rows<MS, 2, false, false, false>

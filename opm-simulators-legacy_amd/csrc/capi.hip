@@ -152,7 +152,7 @@ template <class S> int solve_loaded(opmgpu_ctx* c, bool matrix_changed, SolveRes
     }
     // next to the pressure stage's set-up (cpr_prepare, inside the solver); not in the emulated-decomposition diagnostics, whose cut copy of
     // the matrix is built lazily by whichever of the two asks first
-    static const bool after_rows = !(std::getenv("OPMGPU_FACTOR_AFTER_ROWS") && std::atoi(std::getenv("OPMGPU_FACTOR_AFTER_ROWS")) == 0);      // measured +0.5 %
+    static const bool after_rows = env_flag("OPMGPU_FACTOR_AFTER_ROWS", true);      // measured +0.5 %
     const bool early = ls.factor_early == (mixed ? 4 : int(sizeof(S))) && matrix_changed && !prm.cpr_reference_transform;      // the model started it behind the assembly (LinSolver::factor_early)
     ls.factor_early = 0;
     if (ls.point_stage2) { /* the point ILU0 above is the second stage: no block factorisation */ }
@@ -305,7 +305,7 @@ int opmgpu_cpr_correction_factors(opmgpu_ctx* c, double* into_level0, double* be
 
 // ---------------------------------------------------------------- diagnostics of the CPR pressure hierarchy (tests/test_gpu_cpr_stages.py)
 // They read the hierarchy of the last CPR solve in the precision it ran in and leave the solver's state as they found it: the x / x2 roles
-// of every level and level 0's right-hand side are restored, the correction factors and `tuned` are not touched.
+// of every level and level 0's right-hand side are restored, the correction factors and `factors_kept` are not touched.
 template <class S> static AmgHierarchy<S>* cpr_hierarchy(LinSolver& ls)
 {
     SolverWork<S>& w = ls.work<S>();
@@ -1108,8 +1108,8 @@ static int comm_init_common(opmgpu_ctx* c, int rank, int nranks, const uint8_t* 
                                 n_neigh ? recv_ptr : zero2, recv_cells);
         if (st != OPMGPU_OK) return fail(c, st, transport ? "invalid transport / neighbour lists" : "RCCL communicator initialisation failed");
         cm->rebuild(c->model->plan(), c->stream);
-        c->ls->cpr_hier_mode = (std::getenv("OPMGPU_CPR_GLOBAL_AMG") && std::atoi(std::getenv("OPMGPU_CPR_GLOBAL_AMG")) == 1) ? 1 : 0;
-        if (c->ls->cpr_hier_mode == 1 && std::getenv("OPMGPU_AMG_GS") && std::atoi(std::getenv("OPMGPU_AMG_GS")) != 0) {
+        c->ls->cpr_hier_mode = env_int("OPMGPU_CPR_GLOBAL_AMG", 0) == 1 ? 1 : 0;
+        if (c->ls->cpr_hier_mode == 1 && env_flag("OPMGPU_AMG_GS", false)) {
             // the distributed cycle smooths by damped Jacobi only (opmgpu_comm_set_pressure_hierarchy refuses the pair): keep mode 0
             std::fprintf(stderr, "[opmgpu] OPMGPU_CPR_GLOBAL_AMG=1 ignored: OPMGPU_AMG_GS is set (level-0 Gauss-Seidel); the pressure hierarchy stays rank-local\n");
             c->ls->cpr_hier_mode = 0;

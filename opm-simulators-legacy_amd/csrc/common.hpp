@@ -98,6 +98,10 @@ struct StreamSwapGuard {
     StreamSwapGuard& operator=(const StreamSwapGuard&) = delete;
 };
 
+// environment knobs (OPMGPU_*): the default when the variable is not set
+inline int env_int(const char* name, int dflt) { const char* e = std::getenv(name); return e ? std::atoi(e) : dflt; }
+inline bool env_flag(const char* name, bool dflt) { return env_int(name, dflt) != 0; }
+
 constexpr int kBlock = 256;          // 4 wavefronts = 4 SELL slices per workgroup
 constexpr int kMaxRedBlocks = 2048;  // grid cap of the reduction kernels (256 CUs x 8)
 

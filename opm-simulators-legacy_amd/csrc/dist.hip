@@ -149,7 +149,7 @@ struct RcclTransport : RcclComm::Transport {
         // of two).  Mixing a collective with sends / receives in one group is NCCL API since 2.8, but it has run here with ONE rank only (no
         // multi-GPU node in this pool), so the DEFAULT issues the two operations back to back on the stream, the pattern every RCCL has
         // run for years: the first multi-rank run of this library should not depend on the less-trodden path
-        static const bool fused = std::getenv("OPMGPU_RCCL_FUSED") && std::atoi(std::getenv("OPMGPU_RCCL_FUSED")) != 0;
+        static const bool fused = env_flag("OPMGPU_RCCL_FUSED", false);
         if (!fused) { allreduce(d, n, false, s); exchange(neigh, sb, soff, sbytes, rb, roff, rbytes, s); return; }
         rccl_check(g_rccl.GroupStart(), "ncclGroupStart");
         int rc = g_rccl.AllReduce(d, d, size_t(n), ncclFloat64, ncclSum, comm, s);

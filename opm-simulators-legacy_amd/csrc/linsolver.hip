@@ -24,7 +24,7 @@ namespace opmgpu {
 
 int xcd_mode()
 {
-    static const int m = [] { const char* e = std::getenv("OPMGPU_XCD"); return e ? std::atoi(e) : 1; }();
+    static const int m = env_int("OPMGPU_XCD", 1);
     return m;
 }
 
@@ -382,249 +382,6 @@ __global__ __launch_bounds__(kBlock) void k_ilu_factor(int lo, int hi, const int
   }
 }
 
-// copy the status fields to the host-mapped block (one thread; only when the solve stops / at the final check)
-__device__ __forceinline__ void publish(const SolveCtl* ctl, SolveCtl* hst)
-{
-    hst->norm0_2 = ctl->norm0_2; hst->norm2 = ctl->norm2; hst->flag = ctl->flag; hst->iters = ctl->iters; hst->decided = ctl->decided;
-    __threadfence_system();
-    hst->done = ctl->done;
-}
-
-// ---- BiCGStab (Dune::BiCGSTABSolver::apply) ------------------------------------------------
-// iteration j = 1, 2, ...:
-//   k_update_p (j)  : [test ||r||^2 of iteration j-1]  rho_new = <rt,r>; beta; p = r + beta (p - omega v)
-//   ILU, k_spmv<1>  : y = M^-1 p ; v = A y ; partials h = <rt,v>
-//   k_update_xr1(j) : alpha = rho_new / h ; x += alpha y ; r -= alpha v ; partials ||r||^2
-//   ILU, k_spmv<2>  : y = M^-1 r ; t = A y ; partials <t,r>, <t,t>
-//   k_update_xr2(j) : [test ||r||^2 of the first half step]  omega ; x += omega y ; r -= omega t ; partials ||r||^2, <rt,r>
-// Every workgroup derives the scalars from the partial arrays itself; workgroup 0 records them.
-// Restricted residuals of the subdomain coarse space carried along the BiCGStab recurrences (LinSolver::cs_recur): C(x)[q] = sum over
-// the rows of coarse unknown q of (CPR weights . x) is linear in x, so with the GLOBAL C(v), C(t) of the two products of an iteration
-//   C(r) -= alpha C(v) ; C(r) -= omega C(t) ; C(p) = C(r) + beta (C(p) - omega C(v))
-// hold exactly what restricting r and p would give.  Workgroup 0 of the vector kernels advances them (ns <= 64 <= kBlock).
-struct CsRec { double* Cp; double* Cr; const double* Cv; const double* Ct; const double* C0; int ns; };
-
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_update_p(long n, int j, double eps, SolveCtl* __restrict__ ctl, SolveCtl* __restrict__ hst, const double* __restrict__ p_n2,
-                                                     const double* __restrict__ p_rho, int np, const S* __restrict__ r,
-                                                     const S* __restrict__ v, S* __restrict__ p, CsRec cs)
-{
-    __shared__ double sm[12];
-    if (ctl->done) return;
-    const double* const arr[2] = { p_n2, p_rho };
-    double s[2];
-    reduce_partials<2>(arr, np, s, sm);
-    const double norm2 = s[0], rho_new = s[1];
-    const bool first = (j == 1);
-    if (first) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) { ctl->norm0_2 = norm2; ctl->norm2 = norm2; ctl->rho[1] = rho_new; }
-        if (!(norm2 == norm2)) { if (blockIdx.x == 0 && threadIdx.x == 0) { ctl->flag = 2; ctl->decided = j; ctl->done = 1; publish(ctl, hst); } return; }
-        if (norm2 < 1e-60) { if (blockIdx.x == 0 && threadIdx.x == 0) { ctl->iters = 0; ctl->decided = j; ctl->done = 1; publish(ctl, hst); } return; }
-        if (blockIdx.x == 0 && int(threadIdx.x) < cs.ns) { const double c = cs.C0[threadIdx.x]; cs.Cr[threadIdx.x] = c; cs.Cp[threadIdx.x] = c; }
-        for (long i = blockIdx.x * long(kBlock) + threadIdx.x; i < n; i += long(gridDim.x) * kBlock) p[i] = r[i];
-        return;
-    }
-    // convergence test after the second half of iteration j-1:  norm < reduction * norm0  ||  norm < 1e-30
-    if (norm2 < ctl->thresh2 || norm2 < 1e-60) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) { ctl->norm2 = norm2; ctl->iters = j - 1; ctl->decided = j; ctl->done = 1; publish(ctl, hst); }
-        return;
-    }
-    const double rho_old = ctl->rho[(j - 1) & 1], omega = ctl->omega, alpha = ctl->alpha;
-    if (fabs(rho_old) <= eps || fabs(omega) <= eps || !(rho_old == rho_old) || !(omega == omega) || !(norm2 == norm2)) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) { ctl->norm2 = norm2; ctl->flag = 2; ctl->iters = j - 1; ctl->decided = j; ctl->done = 1; publish(ctl, hst); }
-        return;
-    }
-    if (blockIdx.x == 0 && threadIdx.x == 0) { ctl->rho[j & 1] = rho_new; ctl->norm2 = norm2; }
-    const double beta_d = (rho_new / rho_old) * (alpha / omega);
-    const S beta = S(beta_d), om = S(omega);
-    if (blockIdx.x == 0 && int(threadIdx.x) < cs.ns) cs.Cp[threadIdx.x] = cs.Cr[threadIdx.x] + beta_d * (cs.Cp[threadIdx.x] - omega * cs.Cv[threadIdx.x]);
-    constexpr int L = 16 / sizeof(S);              // 16-byte lanes (n is a multiple of 192)
-    struct alignas(16) Pack { S v[L]; };
-    const long nv = n / L;
-    for (long q = blockIdx.x * long(kBlock) + threadIdx.x; q < nv; q += long(gridDim.x) * kBlock) {
-        Pack pp = reinterpret_cast<Pack*>(p)[q];
-        const Pack vv = reinterpret_cast<const Pack*>(v)[q], rr = reinterpret_cast<const Pack*>(r)[q];
-#pragma unroll
-        for (int u = 0; u < L; ++u) pp.v[u] = (pp.v[u] - om * vv.v[u]) * beta + rr.v[u];
-        reinterpret_cast<Pack*>(p)[q] = pp;
-    }
-    for (long i = nv * L + blockIdx.x * long(kBlock) + threadIdx.x; i < n; i += long(gridDim.x) * kBlock) p[i] = (p[i] - om * v[i]) * beta + r[i];
-}
-
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_update_xr1(long n, int j, double eps, SolveCtl* __restrict__ ctl, SolveCtl* __restrict__ hst, const double* __restrict__ p_h, int np,
-                                                       const S* __restrict__ y, const S* __restrict__ q, S* __restrict__ x, S* __restrict__ r,
-                                                       double* __restrict__ p_n1, CsRec cs)
-{
-    __shared__ double sm[12];
-    if (ctl->done) return;
-    const double* const arr[1] = { p_h };
-    double s[1];
-    reduce_partials<1>(arr, np, s, sm);
-    const double h = s[0];
-    if (fabs(h) < eps || !(h == h)) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) { ctl->flag = 1; ctl->iters = j; ctl->decided = j; ctl->done = 1; publish(ctl, hst); }
-        return;
-    }
-    const double alpha = ctl->rho[j & 1] / h;
-    if (blockIdx.x == 0 && threadIdx.x == 0) ctl->alpha = alpha;
-    if (blockIdx.x == 0 && int(threadIdx.x) < cs.ns) cs.Cr[threadIdx.x] -= alpha * cs.Cv[threadIdx.x];
-    const S a = S(alpha);
-    double acc[1] = { 0.0 };
-    constexpr int L = 16 / sizeof(S);
-    struct alignas(16) Pack { S v[L]; };
-    const long nv = n / L;
-    for (long k = blockIdx.x * long(kBlock) + threadIdx.x; k < nv; k += long(gridDim.x) * kBlock) {
-        Pack xx = reinterpret_cast<Pack*>(x)[k], rr = reinterpret_cast<Pack*>(r)[k];
-        const Pack yy = reinterpret_cast<const Pack*>(y)[k], qq = reinterpret_cast<const Pack*>(q)[k];
-#pragma unroll
-        for (int u = 0; u < L; ++u) { xx.v[u] += a * yy.v[u]; rr.v[u] = rr.v[u] - a * qq.v[u]; acc[0] += double(rr.v[u]) * double(rr.v[u]); }
-        reinterpret_cast<Pack*>(x)[k] = xx; reinterpret_cast<Pack*>(r)[k] = rr;
-    }
-    for (long i = nv * L + blockIdx.x * long(kBlock) + threadIdx.x; i < n; i += long(gridDim.x) * kBlock) {
-        x[i] += a * y[i];
-        const S rn = r[i] - a * q[i];
-        r[i] = rn;
-        acc[0] += double(rn) * double(rn);
-    }
-    block_sum<1>(acc, sm);
-    if (threadIdx.x == 0) p_n1[blockIdx.x] = acc[0];
-}
-
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_update_xr2(long n, int j, SolveCtl* __restrict__ ctl, SolveCtl* __restrict__ hst, const double* __restrict__ p_n1,
-                                                       const double* __restrict__ p_tr, const double* __restrict__ p_tt, int np_v, int np_s,
-                                                       const S* __restrict__ y, const S* __restrict__ q, const S* __restrict__ rt,
-                                                       S* __restrict__ x, S* __restrict__ r, double* __restrict__ p_n2, double* __restrict__ p_rho, CsRec cs)
-{
-    __shared__ double sm[12];
-    if (ctl->done) return;
-    double s1[1], s2[2];
-    { const double* const arr[1] = { p_n1 }; reduce_partials<1>(arr, np_v, s1, sm); }
-    if (s1[0] < ctl->thresh2) {          // converged after the first half step of iteration j: x is final
-        if (blockIdx.x == 0 && threadIdx.x == 0) { ctl->norm2 = s1[0]; ctl->iters = j; ctl->decided = j; ctl->done = 1; publish(ctl, hst); }
-        return;
-    }
-    { const double* const arr[2] = { p_tr, p_tt }; reduce_partials<2>(arr, np_s, s2, sm); }
-    const double omega = s2[0] / s2[1];
-    if (blockIdx.x == 0 && threadIdx.x == 0) ctl->omega = omega;
-    if (blockIdx.x == 0 && int(threadIdx.x) < cs.ns) cs.Cr[threadIdx.x] -= omega * cs.Ct[threadIdx.x];
-    const S a = S(omega);
-    double acc[2] = { 0.0, 0.0 };
-    constexpr int L = 16 / sizeof(S);
-    struct alignas(16) Pack { S v[L]; };
-    const long nv = n / L;
-    for (long k = blockIdx.x * long(kBlock) + threadIdx.x; k < nv; k += long(gridDim.x) * kBlock) {
-        Pack xx = reinterpret_cast<Pack*>(x)[k], rr = reinterpret_cast<Pack*>(r)[k];
-        const Pack yy = reinterpret_cast<const Pack*>(y)[k], qq = reinterpret_cast<const Pack*>(q)[k], tt = reinterpret_cast<const Pack*>(rt)[k];
-#pragma unroll
-        for (int u = 0; u < L; ++u) {
-            xx.v[u] += a * yy.v[u]; rr.v[u] = rr.v[u] - a * qq.v[u];
-            acc[0] += double(rr.v[u]) * double(rr.v[u]); acc[1] += double(tt.v[u]) * double(rr.v[u]);
-        }
-        reinterpret_cast<Pack*>(x)[k] = xx; reinterpret_cast<Pack*>(r)[k] = rr;
-    }
-    for (long i = nv * L + blockIdx.x * long(kBlock) + threadIdx.x; i < n; i += long(gridDim.x) * kBlock) {
-        x[i] += a * y[i];
-        const S rn = r[i] - a * q[i];
-        r[i] = rn;
-        acc[0] += double(rn) * double(rn);
-        acc[1] += double(rt[i]) * double(rn);
-    }
-    block_sum<2>(acc, sm);
-    if (threadIdx.x == 0) { p_n2[blockIdx.x] = acc[0]; p_rho[blockIdx.x] = acc[1]; }
-}
-
-// convergence test after the last enqueued iteration (what k_update_p(j+1) would have done)
-// tick (optional): a host-mapped word the host spins on instead of synchronising the stream -- written last, after a system fence
-__global__ __launch_bounds__(kBlock) void k_final_check(int j, SolveCtl* __restrict__ ctl, SolveCtl* __restrict__ hst, const double* __restrict__ p_n2, int np,
-                                                        int* __restrict__ tick_ptr = nullptr, int tick = 0)
-{
-    __shared__ double sm[12];
-    if (ctl->done) { if (threadIdx.x == 0) { publish(ctl, hst); if (tick_ptr) { __threadfence_system(); *(volatile int*)tick_ptr = tick; } } return; }
-    const double* const arr[1] = { p_n2 };
-    double s[1];
-    reduce_partials<1>(arr, np, s, sm);
-    if (threadIdx.x == 0) {
-        ctl->norm2 = s[0];
-        ctl->iters = j;
-        if (s[0] < ctl->thresh2 || s[0] < 1e-60) ctl->done = 1;
-        publish(ctl, hst);
-        if (tick_ptr) { __threadfence_system(); *(volatile int*)tick_ptr = tick; }
-    }
-}
-__global__ void k_ctl_init(SolveCtl* ctl, SolveCtl* hst, double red)
-{
-    hst->done = 0; hst->flag = 0; hst->iters = 0; hst->decided = 0; hst->norm2 = 0.0; hst->norm0_2 = 0.0;
-    ctl->rho[0] = 1.0; ctl->rho[1] = 1.0; ctl->alpha = 1.0; ctl->omega = 1.0;
-    ctl->norm0_2 = 0.0; ctl->norm2 = 0.0; ctl->thresh2 = 0.0; ctl->done = 0; ctl->flag = 0; ctl->iters = 0; ctl->decided = 0;
-    (void)red;
-}
-// thresh2 = (reduction * ||r0||)^2 needs ||r0||^2: one workgroup, right after the initial dot
-__global__ __launch_bounds__(kBlock) void k_ctl_thresh(SolveCtl* __restrict__ ctl, double red, const double* __restrict__ p_n2, int np)
-{
-    __shared__ double sm[12];
-    const double* const arr[1] = { p_n2 };
-    double s[1];
-    reduce_partials<1>(arr, np, s, sm);
-    if (threadIdx.x == 0) { ctl->norm0_2 = s[0]; ctl->norm2 = s[0]; ctl->thresh2 = red * red * s[0]; }
-}
-// multi-GPU bridge: collapse partial arrays to their sums (fixed order) so they can be all-reduced
-template <int NV>
-__global__ __launch_bounds__(kBlock) void k_sum_partials(const double* __restrict__ a0, const double* __restrict__ a1, int np, double* __restrict__ out)
-{
-    __shared__ double sm[12];
-    const double* const arr[2] = { a0, a1 ? a1 : a0 };
-    double s[2];
-    reduce_partials<2>(arr, np, s, sm);
-    if (threadIdx.x == 0) { out[0] = s[0]; if (NV == 2) out[1] = s[1]; }
-}
-
-// this rank's block sums of (CPR weights . d): parts[u * gridDim.x + workgroup] for its coarse unknowns u < m (blk: block of a row,
-// -1 = not owned; without blocks the owner mask decides and m = 1)
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_cs_wdot(int nb, int nbp, const S* __restrict__ d, const S* __restrict__ w, const int8_t* __restrict__ owned,
-                                                    const int8_t* __restrict__ blk, int m, double* __restrict__ parts, const SolveCtl* __restrict__ ctl)
-{
-    __shared__ double sm[32];
-    if (ctl && ctl->done) return;
-    double acc[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    for (long i = blockIdx.x * long(kBlock) + threadIdx.x; i < nb; i += long(gridDim.x) * kBlock) {
-        const int b = blk ? int(blk[i]) : ((!owned || owned[i]) ? 0 : -1);
-        if (b < 0) continue;
-        const S bs = w[i] * d[i] + w[nbp + i] * d[nbp + i] + w[2 * long(nbp) + i] * d[2 * long(nbp) + i];      // as k_cpr_sum_eqs forms it
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc[u] += (u == b) ? double(bs) : 0.0;
-    }
-    block_sum<8>(acc, sm);
-    if (threadIdx.x == 0) for (int u = 0; u < m; ++u) parts[long(u) * gridDim.x + blockIdx.x] = acc[u];
-}
-// bridge with the coarse-space sums: out[0..NV) as k_sum_partials, out[NV + q] = this rank's sum for coarse unknown q (its own slots
-// mine*m .. mine*m + m - 1), zero for the others' -- the all-reduce that follows then delivers every rank's
-template <int NV>
-__global__ __launch_bounds__(kBlock) void k_bridge_cs(const double* __restrict__ a0, const double* __restrict__ a1, int np, const double* __restrict__ cparts, int ncp,
-                                                      int ns, int m, int mine, double* __restrict__ out)
-{
-    __shared__ double sm[12];
-    __shared__ double tot[8];
-    const double* const arr[2] = { a0, a1 ? a1 : a0 };
-    double s[2];
-    reduce_partials<2>(arr, np, s, sm);
-    if (threadIdx.x == 0) { out[0] = s[0]; if (NV == 2) out[1] = s[1]; }
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int b = 0; b < m; ++b) {
-        double v = 0.0;
-        for (int i = threadIdx.x; i < ncp; i += kBlock) v += cparts[long(b) * ncp + i];
-        const double sw = wave_sum(v);
-        __syncthreads();
-        if (lane == 0) sm[wv] = sw;
-        __syncthreads();
-        if (threadIdx.x == 0) tot[b] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-    }
-    __syncthreads();
-    if (int(threadIdx.x) < ns) { const int b = int(threadIdx.x) - mine * m; out[NV + threadIdx.x] = (b >= 0 && b < m) ? tot[b] : 0.0; }
-}
-
 template <class S>
 __global__ __launch_bounds__(kBlock) void k_dot(long n, const S* __restrict__ a, const S* __restrict__ b, double* __restrict__ partials)
 {
@@ -666,221 +423,6 @@ __global__ __launch_bounds__(kBlock) void k_convert(long n, const A* __restrict_
 __global__ __launch_bounds__(kBlock) void k_copy16(long n16, const double2* __restrict__ a, double2* __restrict__ b)
 {
     for (long i = blockIdx.x * long(kBlock) + threadIdx.x; i < n16; i += long(gridDim.x) * kBlock) b[i] = a[i];
-}
-
-// ---- CPR (NewtonIterationBlackoilCPR.cpp:79-185) ----
-// formEllipticSystem (NewtonIterationUtilities.cpp:197-287): the pressure equation of a cell is the sum of those (matbal-scaled)
-// phase equations whose pressure derivative is strong on the diagonal -- |J_ii| / (column sum of |J_ji|, j != i) > 0.01 --
-// with the reference's fix-up for a weak oil equation (:233-252): if no equation is strong the oil equation alone is used.
-// Equations here are ordered water, oil, gas (the reference swaps oil first: "a concession to MRST").  Weights are 0 / 1.
-template <class S>
-__device__ inline void cpr_row_weights(int lane, int base, int len, int nl, const int32_t* __restrict__ tpos, const S* __restrict__ A, int mode, S w[3])
-{
-    if (mode == 1) {
-        // quasi-IMPES: w = first row of A_ii^-1, i.e. the combination of the cell's equations that eliminates its own saturation /
-        // composition unknowns from the diagonal block (w . A_ii = [1 0 0]); not what the reference does (experiment knob)
-        const long e = long(base + nl) * 64 + lane;
-        const S* b = A + (e >> 6) * 576 + (e & 63);
-        double m[9];
-        for (int q = 0; q < 9; ++q) m[q] = double(b[q * 64]);
-        const double c0 = m[4] * m[8] - m[5] * m[7], c1 = m[5] * m[6] - m[3] * m[8], c2 = m[3] * m[7] - m[4] * m[6];
-        const double det = m[0] * c0 + m[1] * c1 + m[2] * c2;
-        const double id = (det != 0.0 && det == det) ? 1.0 / det : 0.0;
-        double w0 = c0 * id, w1 = (m[2] * m[7] - m[1] * m[8]) * id, w2 = (m[1] * m[5] - m[2] * m[4]) * id;
-        if (id == 0.0) { w0 = 1.0; w1 = 1.0; w2 = 1.0; }
-        w[0] = S(w0); w[1] = S(w1); w[2] = S(w2);
-        return;
-    }
-    double sod[3] = { 0.0, 0.0, 0.0 }, dj[3] = { 0.0, 0.0, 0.0 };
-    for (int k = 0; k < len; ++k) {
-        const long e = long(base + k) * 64 + lane;
-        if (k == nl) {
-            const S* b = A + (e >> 6) * 576 + (e & 63);
-            dj[0] = fabs(double(b[0])); dj[1] = fabs(double(b[192])); dj[2] = fabs(double(b[384]));
-        } else {
-            const int t = tpos[e];
-            if (t < 0) continue;
-            const S* b = A + long(t >> 6) * 576 + (t & 63);
-            sod[0] += fabs(double(b[0])); sod[1] += fabs(double(b[192])); sod[2] += fabs(double(b[384]));
-        }
-    }
-    const bool sw = dj[0] / sod[0] > 0.01, sg = dj[2] / sod[2] > 0.01;       // NaN (0/0) compares false like the reference's Eigen cast
-    bool so = dj[1] / sod[1] > 0.01;
-    if (!so && !sw && !sg) so = true;
-    w[0] = sw ? S(1) : S(0); w[1] = so ? S(1) : S(0); w[2] = sg ? S(1) : S(0);
-}
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_cpr_weights(int nb, int nbp, const int32_t* __restrict__ slice_ptr, const int16_t* __restrict__ rowlen,
-                                                        const int16_t* __restrict__ nlower, const int32_t* __restrict__ tpos, const S* __restrict__ A,
-                                                        S* __restrict__ w, int mode)
-{
-    const int row = blockIdx.x * kBlock + threadIdx.x;
-    if (row >= nb) return;
-    S ww[3];
-    cpr_row_weights<S>(row & 63, slice_ptr[row >> 6], rowlen[row], nlower[row], tpos, A, mode, ww);
-    w[row] = ww[0]; w[nbp + row] = ww[1]; w[2 * long(nbp) + row] = ww[2];
-}
-// the same for a list of rows: the assembly kernel wrote the weights of every row from the reservoir equations, the device well model then
-// changed the diagonal blocks of its perforated cells -- their weights are redone from the final matrix (off-diagonal blocks, and with
-// them every other row's column sums, are untouched by the wells)
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_cpr_weights_rows(int nrows, const int32_t* __restrict__ rows, int nbp, const int32_t* __restrict__ slice_ptr,
-                                                             const int16_t* __restrict__ rowlen, const int16_t* __restrict__ nlower, const int32_t* __restrict__ tpos,
-                                                             const S* __restrict__ A, S* __restrict__ w, int mode)
-{
-    // one wavefront per row, one lane per entry (rows are <= 64 wide here or fall back to the serial walk): the serial form is a chain of
-    // ~14 dependent round trips (transposed position -> block), 17 us for 500 rows in one workgroup
-    const int q = blockIdx.x * 4 + (threadIdx.x >> 6), l = threadIdx.x & 63;
-    if (q >= nrows) return;
-    const int row = rows[q];
-    const int lane = row & 63, base = slice_ptr[row >> 6], len = rowlen[row], nl = nlower[row];
-    if (mode == 1 || len > 64) {
-        if (l == 0) { S ww[3]; cpr_row_weights<S>(lane, base, len, nl, tpos, A, mode, ww); w[row] = ww[0]; w[nbp + row] = ww[1]; w[2 * long(nbp) + row] = ww[2]; }
-        return;
-    }
-    double sod[3] = { 0.0, 0.0, 0.0 }, dj[3] = { 0.0, 0.0, 0.0 };
-    if (l < len) {
-        const long e = long(base + l) * 64 + lane;
-        if (l == nl) {
-            const S* b = A + (e >> 6) * 576 + (e & 63);
-            dj[0] = fabs(double(b[0])); dj[1] = fabs(double(b[192])); dj[2] = fabs(double(b[384]));
-        } else {
-            const int t = tpos[e];
-            if (t >= 0) {
-                const S* b = A + long(t >> 6) * 576 + (t & 63);
-                sod[0] = fabs(double(b[0])); sod[1] = fabs(double(b[192])); sod[2] = fabs(double(b[384]));
-            }
-        }
-    }
-#pragma unroll
-    for (int a = 0; a < 3; ++a) { sod[a] = wave_sum(sod[a]); dj[a] = wave_sum(dj[a]); }       // fixed lane order: deterministic
-    if (l == 0) {
-        const bool sw = dj[0] / sod[0] > 0.01, sg = dj[2] / sod[2] > 0.01;       // as cpr_row_weights
-        bool so = dj[1] / sod[1] > 0.01;
-        if (!so && !sw && !sg) so = true;
-        w[row] = sw ? S(1) : S(0); w[nbp + row] = so ? S(1) : S(0); w[2 * long(nbp) + row] = sg ? S(1) : S(0);
-    }
-}
-// A_p(i,j) = sum over the selected equations of A_ij[eq][pressure]; one thread per row (padding slots included: value 0)
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_extract_pressure(int nb, int nbp, const int32_t* __restrict__ slice_ptr, const S* __restrict__ w,
-                                                             const S* __restrict__ A, S* __restrict__ Ap)
-{
-    const int row = blockIdx.x * kBlock + threadIdx.x;
-    if (row >= nbp) return;
-    const int base = slice_ptr[row >> 6], width = slice_ptr[(row >> 6) + 1] - base, lane = row & 63;
-    const bool real = row < nb;
-    const S w0 = real ? w[row] : S(0), w1 = real ? w[nbp + row] : S(0), w2 = real ? w[2 * long(nbp) + row] : S(0);
-    for (int k = 0; k < width; ++k) {
-        const long e = long(base + k) * 64 + lane;
-        const S* b = A + (e >> 6) * 576 + (e & 63);
-        Ap[e] = w0 * b[0] + w1 * b[192] + w2 * b[384];
-    }
-}
-// r_p = the same combination of the three (scaled) phase residuals.  CSM (coarse space of the pressure stage): 0 = none -- the first
-// pre-smoothing sweep of the V-cycle from a zero guess is fused here (one launch less); 1 / 2 = the restriction of r_p onto the one
-// unknown / the blocks of this rank is fused instead (per-workgroup partials, k_cs_place / k_cs_place_cr reduce them in a fixed order;
-// the coarse-space correction then writes the first sweep from the corrected residual)
-template <class S, int CSM>
-__global__ __launch_bounds__(kBlock) void k_cpr_sum_eqs(int nb, int nbp, const S* __restrict__ d, const S* __restrict__ w, S* __restrict__ bp, S omega,
-                                                        const S* __restrict__ dinv, S* __restrict__ x0, const SolveCtl* __restrict__ ctl,
-                                                        const int8_t* __restrict__ owned, const int8_t* __restrict__ blk, double* __restrict__ parts,
-                                                        S* __restrict__ xw = nullptr, int nw = 0)
-{
-    __shared__ double sm[32];
-    if (ctl && ctl->done) return;
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < nw) xw[i] = S(0);              // bordered level 0: the wells' unknowns start from zero (a memset is two more launches)
-    S b = S(0);
-    if (i < nb) {
-        b = w[i] * d[i] + w[nbp + i] * d[nbp + i] + w[2 * long(nbp) + i] * d[2 * long(nbp) + i];
-        bp[i] = b;
-        if (CSM == 0) x0[i] = omega * dinv[i] * b;
-    }
-    if (CSM == 1) {
-        double acc[1] = { (i < nb && (!owned || owned[i])) ? double(b) : 0.0 };
-        block_sum<1>(acc, sm);
-        if (threadIdx.x == 0) parts[blockIdx.x] = acc[0];
-    }
-    if (CSM == 2) {
-        const int bl = i < nb ? int(blk[i]) : -1;
-        double acc[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc[u] = (u == bl) ? double(b) : 0.0;
-        block_sum<8>(acc, sm);
-        if (threadIdx.x == 0) for (int u = 0; u < 8; ++u) parts[long(u) * gridDim.x + blockIdx.x] = acc[u];
-    }
-}
-// Border of the level-0 pressure system (amg.hpp): one unknown per well, its bhp.  With q_a = sum_j cq_s[a][j] (flux equations) the
-// well's control equation g(q, bhp) = 0 is the extra ROW: sum_j (sum_a g_a dcq_s[a][j]/dp_j) dp_j + (g_bhp + sum_a g_a sum_j dcq_s[a][j]/dbhp)
-// dbhp; the extra COLUMN is what the cells' (matbal-scaled, CPR-weighted) equations see of bhp: -sum_a w_a(row) scale_a dcq_s[a][j]/dbhp.
-// Eliminating the unknown again gives the pressure part of the explicit Schur complement the reference forms (minus the wellbore-mixture
-// terms) -- without its clique fill.  One workgroup per well; out = [bcol (nperf) | crow (nperf) | dw (nw)].
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_cpr_border(LowRankOp lr, int nbp, const S* __restrict__ w, S* __restrict__ out, double colscale = 1.0)
-{
-    __shared__ double sm[4];
-    const int k = blockIdx.x;
-    const double* g = lr.ctrl_row + 4 * k;
-    double acc[1] = { 0.0 };
-    for (int j = lr.connpos[k] + threadIdx.x; j < lr.connpos[k + 1]; j += kBlock) {
-        const double* Fs = lr.Fsave + 21 * long(j);
-        const int row = lr.perf_row[j];
-        double bc = 0.0, cr = 0.0;
-        for (int a = 0; a < 3; ++a) {
-            bc -= double(w[long(a) * nbp + row]) * lr.scale[a] * Fs[18 + a];
-            cr += g[a] * Fs[3 * a];
-            acc[0] += g[a] * Fs[18 + a];
-        }
-        out[j] = S(colscale * bc); out[lr.nperf + j] = S(cr);
-    }
-    block_sum<1>(acc, sm);
-    if (threadIdx.x == 0) {
-        double d = g[3] + acc[0];
-        if (d == 0.0 || !(d == d)) d = 1.0;          // a decoupled (dead) well: identity row
-        out[2 * lr.nperf + k] = S(d);
-    }
-}
-// z = d - A [x_p; 0; 0]   (only the pressure column of every block is read: 1/3 of the matrix)
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_cpr_presidual(int xm, int nb, int nbp, const int32_t* __restrict__ slice_ptr, const int32_t* __restrict__ col,
-                                                          const S* __restrict__ val, const S* __restrict__ d, const S* __restrict__ xp,
-                                                          S* __restrict__ z, const int8_t* __restrict__ mask, const SolveCtl* __restrict__ ctl,
-                                                          int phase = 0, const int8_t* __restrict__ interior = nullptr)
-{
-    if (ctl && ctl->done) return;
-    const int nchunks = (nb + kBlock - 1) / kBlock;
-    const int ch = xcd_first(nchunks, xm);
-    if (ch >= xcd_end(nchunks, xm)) return;
-    const int row = ch * kBlock + threadIdx.x;
-    if (row >= nb) return;
-    if (phase && (phase == 1) != (interior[row] != 0)) return;          // halo exchange of x_p in flight: see k_spmv
-    const int base = slice_ptr[row >> 6], width = slice_ptr[(row >> 6) + 1] - base, lane = row & 63;
-    const S* __restrict__ v = val + vidx(base, lane);
-    const int32_t* __restrict__ c = col + long(base) * 64 + lane;
-    if (mask && !mask[row]) { z[row] = 0; z[nbp + row] = 0; z[2 * long(nbp) + row] = 0; return; }     // ghost rows stay zero (block-Jacobi second stage)
-    S z0 = d[row], z1 = d[nbp + row], z2 = d[2 * long(nbp) + row];
-    for (int k = 0; k < width; ++k) {
-        const S x0 = xp[c[k * 64]];
-        const S* __restrict__ b = v + k * 576;
-        z0 -= b[0] * x0; z1 -= b[192] * x0; z2 -= b[384] * x0;
-    }
-    z[row] = z0; z[nbp + row] = z1; z[2 * long(nbp) + row] = z2;
-}
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_amg_restore_x0(int n, S omega, const S* __restrict__ dinv, const S* __restrict__ b, S* __restrict__ x)
-{
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < n) x[i] = omega * dinv[i] * b[i];
-}
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_cpr_add_p(int nb, const S* __restrict__ xp, S* __restrict__ v, const SolveCtl* __restrict__ ctl, S c)
-{
-    // c = cpr_relax: the reference's CPRPreconditioner scales the pressure part by it when it is not 1 (the ILU0 part carries it already)
-    if (ctl && ctl->done) return;
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i >= nb) return;
-    v[i] += c * xp[i];
 }
 
 // ---- layout conversion kernels ----
@@ -958,33 +500,31 @@ LinSolver::LinSolver(hipStream_t s) : stream(s)
     OPMGPU_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h_tick_dev), h_tick, 0));
     OPMGPU_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_pub), kPubWords * sizeof(uint32_t), hipHostMallocMapped));
     OPMGPU_HIP(hipHostGetDevicePointer(reinterpret_cast<void**>(&h_pub_dev), h_pub, 0));
-    if (const char* e = std::getenv("OPMGPU_POLL")) poll_status = std::atoi(e) != 0;
+    poll_status = env_flag("OPMGPU_POLL", poll_status);
     ctl.alloc(1); ctl.zero(stream);
     OPMGPU_HIP(hipHostMalloc(reinterpret_cast<void**>(&h_flags), 4 * sizeof(int32_t)));
     OPMGPU_HIP(hipEventCreateWithFlags(&ev[0], hipEventDisableTiming));
     OPMGPU_HIP(hipEventCreateWithFlags(&ev[1], hipEventDisableTiming));
-    if (const char* e = std::getenv("OPMGPU_CLOSED")) closed_form_level0 = std::atoi(e) != 0;
-    if (const char* e = std::getenv("OPMGPU_WELL_WOODBURY")) well_woodbury = std::atoi(e) != 0;
-    if (const char* e = std::getenv("OPMGPU_CPR_SPECULATE")) cpr_speculate = std::atoi(e) != 0;
-    if (const char* e = std::getenv("OPMGPU_CPR_WEIGHTS")) cpr_weight_mode = std::atoi(e);
-    if (const char* e = std::getenv("OPMGPU_AMG_LAG")) amg_lag = std::atoi(e);
-    if (const char* e = std::getenv("OPMGPU_AMG_LAG_COARSE")) coarse_lag = std::max(0, std::atoi(e));
-    if (const char* e = std::getenv("OPMGPU_COARSE_BLOCKS")) cs_blocks_req = std::max(1, std::atoi(e));
-    if (const char* e = std::getenv("OPMGPU_CPR_HALO_XP")) cpr_halo_xp = std::atoi(e) != 0;
-    if (const char* e = std::getenv("OPMGPU_HALO_OVERLAP")) halo_overlap = std::atoi(e) != 0;
-    if (const char* e = std::getenv("OPMGPU_FACTOR_OVERLAP")) factor_overlap = std::atoi(e) != 0;
+    closed_form_level0 = env_flag("OPMGPU_CLOSED", closed_form_level0);
+    well_woodbury = env_flag("OPMGPU_WELL_WOODBURY", well_woodbury);
+    cpr_speculate = env_flag("OPMGPU_CPR_SPECULATE", cpr_speculate);
+    cpr_weight_mode = env_int("OPMGPU_CPR_WEIGHTS", cpr_weight_mode);
+    amg_lag = env_int("OPMGPU_AMG_LAG", amg_lag);
+    coarse_lag = std::max(0, env_int("OPMGPU_AMG_LAG_COARSE", coarse_lag));
+    cs_blocks_req = std::max(1, env_int("OPMGPU_COARSE_BLOCKS", cs_blocks_req));
+    cpr_halo_xp = env_flag("OPMGPU_CPR_HALO_XP", cpr_halo_xp);
+    halo_overlap = env_flag("OPMGPU_HALO_OVERLAP", halo_overlap);
+    factor_overlap = env_flag("OPMGPU_FACTOR_OVERLAP", factor_overlap);
     if (const char* e = std::getenv("OPMGPU_FACTOR_EARLY")) { factor_early_on = std::atoi(e) != 0; if (factor_early_on) factor_early_mode = std::atoi(e) == 2 ? 2 : 1; }
-    if (const char* e = std::getenv("OPMGPU_FACTOR_GRID")) factor_grid_cap = std::atoi(e);
-    if (const char* e = std::getenv("OPMGPU_CS_RECUR")) cs_recur = std::atoi(e) != 0;
-    if (const char* e = std::getenv("OPMGPU_CS_FUSED")) cs_fused_env = std::atoi(e) != 0;
+    factor_grid_cap = env_int("OPMGPU_FACTOR_GRID", factor_grid_cap);
+    cs_recur = env_flag("OPMGPU_CS_RECUR", cs_recur);
     if (const char* e = std::getenv("OPMGPU_CPR_L0_HALO")) { cpr_l0_halo = std::atoi(e) != 0; cpr_l0_halo_down = std::atoi(e) != 2; }
-    if (const char* e = std::getenv("OPMGPU_AMG_AUTOTUNE")) amg_autotune = std::atoi(e) != 0;
-    if (const char* e = std::getenv("OPMGPU_AMG_ADAPT")) corr_policy.on = std::atoi(e) != 0;
+    corr_policy.on = env_flag("OPMGPU_AMG_ADAPT", corr_policy.on);
     if (const char* e = std::getenv("OPMGPU_AMG_ADAPT_ARM")) corr_policy.arm[CorrectionPolicy::kBase + 1] = std::atof(e);
     if (const char* e = std::getenv("OPMGPU_AMG_ADAPT_MARGIN")) corr_policy.margin = std::atof(e);
-    if (const char* e = std::getenv("OPMGPU_EMULATE_RANKS")) emulate_ranks = std::atoi(e);
-    if (const char* e = std::getenv("OPMGPU_EMULATE_WHAT")) emulate_what = std::atoi(e);
-    if (const char* e = std::getenv("OPMGPU_COARSE")) coarse_mode = std::atoi(e);
+    emulate_ranks = env_int("OPMGPU_EMULATE_RANKS", emulate_ranks);
+    emulate_what = env_int("OPMGPU_EMULATE_WHAT", emulate_what);
+    coarse_mode = env_int("OPMGPU_COARSE", coarse_mode);
 }
 LinSolver::~LinSolver()
 {
@@ -1225,7 +765,7 @@ template <class S> void LinSolver::factor_async()
     if (!factor_stream) {
         // lowest priority: the factorisation is needed only by the first ILU0 sweep (behind the hierarchy set-up AND the first V-cycle),
         // the Galerkin chain next to it is the critical path -- the dispatcher should give that one the free slots first
-        static const bool low = !(std::getenv("OPMGPU_FACTOR_PRIORITY") && std::atoi(std::getenv("OPMGPU_FACTOR_PRIORITY")) == 0);
+        static const bool low = env_flag("OPMGPU_FACTOR_PRIORITY", true);
         int least = 0, greatest = 0;
         OPMGPU_HIP(hipDeviceGetStreamPriorityRange(&least, &greatest));
         OPMGPU_HIP(hipStreamCreateWithPriority(&factor_stream, hipStreamNonBlocking, low ? least : greatest));
@@ -1292,999 +832,29 @@ template <class S> void LinSolver::lowrank_reduce(const S* x, const SolveCtl* ct
     if (lowrank.nw > 0) hipLaunchKernelGGL((k_lowrank_reduce<S>), dim3(lowrank.nw), dim3(kBlock), 0, stream, lowrank, plan.nbp, x, ctl);
 }
 
-static void halo_dispatch(CommBase* c, float* v, hipStream_t s) { c->halo_exchange_f(v, s); }
-static void halo_dispatch(CommBase* c, double* v, hipStream_t s) { c->halo_exchange_d(v, s); }
-
-// ---- global coarse space of the CPR pressure stage (multi-GPU / emulated ranks): one unknown per subdomain ----
-// The AMG is subdomain-local, so nothing in it couples the subdomains: pressure error that is smooth across several of them is
-// only reduced at the cuts and the iteration count grows with the number of ranks (measured with OPMGPU_EMULATE_RANKS: 4.3 -> 8.0
-// iterations at 8 slabs).  Classical remedy (Nicolaides coarse space): before the local V-cycle the residual is corrected by the
-// Galerkin problem on the span of the subdomains' indicator vectors, A_c = P^T A_p P (n_sub x n_sub, inverted on every rank),
-//   e = A_c^-1 P^T r ;  r' = r - A_p P e ;  x_p = P e + Vcycle(r') .
-// P e is constant per subdomain, so its ghost entries are known without a halo exchange; the only communication is the sum of the
-// n_sub restricted residuals (one small all-reduce per application) and of the rows of A_c (once per matrix).
-__global__ __launch_bounds__(kBlock) void k_cs_sub_emulated(int nb, int nbp, int nranks, const int32_t* __restrict__ nat, int32_t* __restrict__ sub)
+// the communicator's halo operations by vector type
+static void halo(CommBase* c, float* v, hipStream_t s) { c->halo_exchange_f(v, s); }
+static void halo(CommBase* c, double* v, hipStream_t s) { c->halo_exchange_d(v, s); }
+static void allreduce_halo(CommBase* c, double* d, int n, float* v, hipStream_t s) { c->allreduce_sum_halo_f(d, n, v, s); }
+static void allreduce_halo(CommBase* c, double* d, int n, double* v, hipStream_t s) { c->allreduce_sum_halo_d(d, n, v, s); }
+// The halo exchange of v on the halo stream next to launch(1), the rows that read no ghost entry; launch(2), the rows next to a cut,
+// follows the exchange (LinSolver::halo_overlap)
+template <class S, class F> static void halo_overlapped(LinSolver& ls, S* v, F launch)
 {
-    const int row = blockIdx.x * kBlock + threadIdx.x;
-    if (row >= nbp) return;
-    sub[row] = row < nb ? int32_t(long(nat[row]) * nranks / nb) : 0;
-}
-// partial sums per workgroup: out[block][k] for k < ns2 (fixed order inside the block: thread 0 adds the per-thread tables of its
-// block serially -- small tables, rows of one block belong to one or two subdomains).  Deterministic.
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_cs_matrix(int nb, int nbp, int ns, const int32_t* __restrict__ slice_ptr, const int32_t* __restrict__ col,
-                                                      const int16_t* __restrict__ rowlen, const int32_t* __restrict__ sub, const int8_t* __restrict__ owned,
-                                                      const S* __restrict__ w, const S* __restrict__ A, double* __restrict__ cA)
-{
-    const int row = blockIdx.x * kBlock + threadIdx.x;
-    if (row >= nb || (owned && !owned[row])) return;
-    const int base = slice_ptr[row >> 6], lane = row & 63, a = sub[row];
-    const double w0 = double(w[row]), w1 = double(w[nbp + row]), w2 = double(w[2 * long(nbp) + row]);
-    int bcur = -1; double acc = 0.0;
-    for (int k = 0, len = rowlen[row]; k < len; ++k) {
-        const long e = long(base + k) * 64 + lane;
-        const S* bl = A + (e >> 6) * 576 + (e & 63);
-        const double v = w0 * double(bl[0]) + w1 * double(bl[192]) + w2 * double(bl[384]);
-        const int b = sub[col[e]];
-        if (b != bcur) { if (bcur >= 0) atomicAdd(&cA[a * ns + bcur], acc); bcur = b; acc = 0.0; }
-        acc += v;
-    }
-    if (bcur >= 0) atomicAdd(&cA[a * ns + bcur], acc);
-}
-__global__ void k_cs_invert(int ns, const double* __restrict__ cA, double* __restrict__ inv)
-{
-    // Gauss-Jordan with partial pivoting, one thread (ns <= 64)
-    extern __shared__ double m[];          // [ns][2 ns]
-    const int n2 = 2 * ns;
-    for (int i = 0; i < ns; ++i) for (int j = 0; j < n2; ++j) m[i * n2 + j] = j < ns ? cA[i * ns + j] : (j - ns == i ? 1.0 : 0.0);
-    for (int p = 0; p < ns; ++p) {
-        int piv = p;
-        for (int i = p + 1; i < ns; ++i) if (fabs(m[i * n2 + p]) > fabs(m[piv * n2 + p])) piv = i;
-        if (m[piv * n2 + p] == 0.0) { for (int i = 0; i < ns * ns; ++i) inv[i] = 0.0; return; }     // singular: no correction
-        if (piv != p) for (int j = 0; j < n2; ++j) { const double t = m[p * n2 + j]; m[p * n2 + j] = m[piv * n2 + j]; m[piv * n2 + j] = t; }
-        const double d = 1.0 / m[p * n2 + p];
-        for (int j = 0; j < n2; ++j) m[p * n2 + j] *= d;
-        for (int i = 0; i < ns; ++i) if (i != p) { const double f = m[i * n2 + p]; for (int j = 0; j < n2; ++j) m[i * n2 + j] -= f * m[p * n2 + j]; }
-    }
-    for (int i = 0; i < ns; ++i) for (int j = 0; j < ns; ++j) inv[i * ns + j] = m[i * n2 + ns + j];
-}
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_cs_restrict(int nb, const int32_t* __restrict__ sub, const int8_t* __restrict__ owned, const S* __restrict__ r,
-                                                        double* __restrict__ cr, const SolveCtl* __restrict__ ctl)
-{
-    if (ctl && ctl->done) return;
-    const int row = blockIdx.x * kBlock + threadIdx.x;
-    const bool act = row < nb && (!owned || owned[row]);
-    const int a = act ? sub[row] : -1;
-    const double v = act ? double(r[row]) : 0.0;
-    // wave-uniform subdomain (the usual case): one atomic per wave, fixed lane order inside it
-    const int a0 = __shfl(a, 0, 64);
-    if (__all(a == a0)) { const double s_ = wave_sum(v); if ((threadIdx.x & 63) == 0 && a0 >= 0) atomicAdd(&cr[a0], s_); }
-    else if (act) atomicAdd(&cr[a], v);
-}
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_cs_correct(int nb, int nbp, int ns, const int32_t* __restrict__ slice_ptr, const int32_t* __restrict__ col,
-                                                       const int16_t* __restrict__ rowlen, const int32_t* __restrict__ sub, const S* __restrict__ w,
-                                                       const S* __restrict__ A, const double* __restrict__ inv, const double* __restrict__ cr, S omega,
-                                                       const S* __restrict__ dinv, S* __restrict__ b, S* __restrict__ x0, S* __restrict__ xc,
-                                                       const SolveCtl* __restrict__ ctl)
-{
-    __shared__ double e[64];
-    if (ctl && ctl->done) return;
-    if (threadIdx.x < ns) { double s_ = 0.0; for (int k = 0; k < ns; ++k) s_ += inv[threadIdx.x * ns + k] * cr[k]; e[threadIdx.x] = s_; }
-    __syncthreads();
-    const int row = blockIdx.x * kBlock + threadIdx.x;
-    if (row >= nb) return;
-    const int base = slice_ptr[row >> 6], lane = row & 63;
-    const double w0 = double(w[row]), w1 = double(w[nbp + row]), w2 = double(w[2 * long(nbp) + row]);
-    double acc = 0.0;
-    for (int k = 0, len = rowlen[row]; k < len; ++k) {
-        const long en = long(base + k) * 64 + lane;
-        const S* bl = A + (en >> 6) * 576 + (en & 63);
-        acc += (w0 * double(bl[0]) + w1 * double(bl[192]) + w2 * double(bl[384])) * e[sub[col[en]]];
-    }
-    const S rn = S(double(b[row]) - acc);
-    b[row] = rn; x0[row] = omega * dinv[row] * rn; xc[row] = S(e[sub[row]]);
-}
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_cs_add(int nb, const S* __restrict__ x, const S* __restrict__ xc, S* __restrict__ out, const SolveCtl* __restrict__ ctl)
-{
-    if (ctl && ctl->done) return;
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < nb) out[i] = x[i] + xc[i];
+    OPMGPU_HIP(hipEventRecord(ls.ev_halo[0], ls.stream));
+    OPMGPU_HIP(hipStreamWaitEvent(ls.halo_stream, ls.ev_halo[0], 0));
+    halo(ls.comm, v, ls.halo_stream);
+    OPMGPU_HIP(hipEventRecord(ls.ev_halo[1], ls.halo_stream));
+    launch(1);
+    OPMGPU_HIP(hipStreamWaitEvent(ls.stream, ls.ev_halo[1], 0));
+    launch(2);
 }
 
-// out[row] += (A_c^-1 cr)[sub[row]] on every local row, ghost rows included (their subdomain is their owner's): the additive form of
-// the coarse-space correction behind the cycle (LinSolver::cs_fused_post)
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_cs_add_post(int nb, int ns, const int32_t* __restrict__ sub, const double* __restrict__ inv, const double* __restrict__ cr,
-                                                        S* __restrict__ out, const SolveCtl* __restrict__ ctl)
-{
-    __shared__ double e[64];
-    if (ctl && ctl->done) return;
-    if (int(threadIdx.x) < ns) { double s_ = 0.0; for (int k = 0; k < ns; ++k) s_ += inv[threadIdx.x * ns + k] * cr[k]; e[threadIdx.x] = s_; }
-    __syncthreads();
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < nb) out[i] = S(double(out[i]) + e[sub[i]]);
-}
-
-// level 0 of the decomposed pressure cycle (LinSolver::cpr_l0_halo): the ghost entries of the iterate from the exchanged staging vector;
-// the ghost rows are identity rows, so their right-hand side follows (b = x: zero residual, stationary under the Jacobi sweep)
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_l0_ghosts(int nb, const int8_t* __restrict__ owned, const S* __restrict__ hx, S* __restrict__ x, S* __restrict__ b,
-                                                      const SolveCtl* __restrict__ ctl)
-{
-    if (ctl && ctl->done) return;
-    const int i = blockIdx.x * kBlock + threadIdx.x;
-    if (i < nb && !owned[i]) { const S v = hx[i]; x[i] = v; b[i] = v; }
-}
-
-// real multi-GPU (one subdomain per process): deterministic versions -- per-workgroup partials, re-reduced in a fixed order
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_cs_rsum(int nb, const int8_t* __restrict__ owned, const S* __restrict__ r, double* __restrict__ parts,
-                                                    const SolveCtl* __restrict__ ctl)
-{
-    __shared__ double sm[4];
-    if (ctl && ctl->done) return;
-    double acc[1] = { 0.0 };
-    for (long i = blockIdx.x * long(kBlock) + threadIdx.x; i < nb; i += long(gridDim.x) * kBlock) if (!owned || owned[i]) acc[0] += double(r[i]);
-    block_sum<1>(acc, sm);
-    if (threadIdx.x == 0) parts[blockIdx.x] = acc[0];
-}
-__global__ __launch_bounds__(kBlock) void k_cs_place(int np, const double* __restrict__ parts, int ns, int mine, double* __restrict__ cr,
-                                                     const SolveCtl* __restrict__ ctl)
-{
-    __shared__ double sm[12];
-    if (ctl && ctl->done) return;
-    const double* const arr[1] = { parts };
-    double s_[1];
-    reduce_partials<1>(arr, np, s_, sm);
-    if (threadIdx.x < ns) cr[threadIdx.x] = threadIdx.x == mine ? s_[0] : 0.0;
-}
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_cs_rowparts(int nb, int nbp, LinSolver::CsSlots sl, const int32_t* __restrict__ slice_ptr, const int32_t* __restrict__ col,
-                                                        const int16_t* __restrict__ rowlen, const int32_t* __restrict__ sub, const int8_t* __restrict__ owned,
-                                                        const S* __restrict__ w, const S* __restrict__ A, double* __restrict__ parts, S* __restrict__ T)
-{
-    // T[q][row] = sum_j A_p(row, j) [subdomain(j) == slot q]: what the per-application correction needs of the matrix
-    __shared__ double sm[32];
-    double acc[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    for (long row = blockIdx.x * long(kBlock) + threadIdx.x; row < nb; row += long(gridDim.x) * kBlock) {
-        if (owned && !owned[row]) { for (int q = 0; q < sl.n; ++q) T[long(q) * nbp + row] = S(0); continue; }
-        double mine[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-        const int base = slice_ptr[row >> 6], lane = row & 63;
-        const double w0 = double(w[row]), w1 = double(w[nbp + row]), w2 = double(w[2 * long(nbp) + row]);
-        for (int k = 0, len = rowlen[row]; k < len; ++k) {
-            const long e = long(base + k) * 64 + lane;
-            const S* bl = A + (e >> 6) * 576 + (e & 63);
-            const double v = w0 * double(bl[0]) + w1 * double(bl[192]) + w2 * double(bl[384]);
-            const int s_ = sl.slot_of_sub[sub[col[e]]];
-#pragma unroll
-            for (int q = 0; q < 8; ++q) mine[q] += (q == s_) ? v : 0.0;
-        }
-#pragma unroll
-        for (int q = 0; q < 8; ++q) { acc[q] += mine[q]; if (q < sl.n) T[long(q) * nbp + row] = S(mine[q]); }
-    }
-    block_sum<8>(acc, sm);
-    if (threadIdx.x == 0) for (int q = 0; q < 8; ++q) parts[long(q) * gridDim.x + blockIdx.x] = acc[q];
-}
-// the whole per-row set-up of the pressure stage in ONE pass over the matrix (per Newton iteration): weights (k_cpr_weights), the
-// pressure matrix (k_extract_pressure) and, with CS, the coarse-space row parts (k_cs_rowparts) -- same arithmetic as the three
-template <class S, bool CS, bool WR>
-__global__ __launch_bounds__(kBlock) void k_cpr_rows(int nb, int nbp, int mode, LinSolver::CsSlots sl, const int32_t* __restrict__ slice_ptr, const int32_t* __restrict__ col,
-                                                     const int16_t* __restrict__ rowlen, const int16_t* __restrict__ nlower, const int32_t* __restrict__ tpos,
-                                                     const int32_t* __restrict__ sub, const int8_t* __restrict__ owned, const S* __restrict__ A,
-                                                     S* __restrict__ w, S* __restrict__ Ap, double* __restrict__ parts, S* __restrict__ T)
-{
-    __shared__ double sm[32];
-    double acc[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    for (long row = blockIdx.x * long(kBlock) + threadIdx.x; row < nbp; row += long(gridDim.x) * kBlock) {
-        const int base = slice_ptr[row >> 6], width = slice_ptr[(row >> 6) + 1] - base, lane = row & 63;
-        if (row >= nb) { for (int k = 0; k < width; ++k) Ap[long(base + k) * 64 + lane] = S(0); continue; }
-        const int len = rowlen[row];
-        S ww[3];
-        if (WR) { ww[0] = w[row]; ww[1] = w[nbp + row]; ww[2] = w[2 * long(nbp) + row]; }       // written by the assembly (k_flux)
-        else {
-            cpr_row_weights<S>(lane, base, len, nlower[row], tpos, A, mode, ww);
-            w[row] = ww[0]; w[nbp + row] = ww[1]; w[2 * long(nbp) + row] = ww[2];
-        }
-        const bool cs = CS && !(owned && !owned[row]);
-        const double w0 = double(ww[0]), w1 = double(ww[1]), w2 = double(ww[2]);
-        double mine[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-        for (int k = 0; k < width; ++k) {
-            const long e = long(base + k) * 64 + lane;
-            const S* bl = A + (e >> 6) * 576 + (e & 63);
-            const S b0 = bl[0], b1 = bl[192], b2 = bl[384];
-            Ap[e] = ww[0] * b0 + ww[1] * b1 + ww[2] * b2;
-            if (cs && k < len) {
-                const double v = w0 * double(b0) + w1 * double(b1) + w2 * double(b2);
-                const int s_ = sl.slot_of_sub[sub[col[e]]];
-#pragma unroll
-                for (int q = 0; q < 8; ++q) mine[q] += (q == s_) ? v : 0.0;
-            }
-        }
-        if (CS) {
-#pragma unroll
-            for (int q = 0; q < 8; ++q) { acc[q] += mine[q]; if (q < sl.n) T[long(q) * nbp + row] = S(mine[q]); }
-        }
-    }
-    if (CS) {
-        block_sum<8>(acc, sm);
-        if (threadIdx.x == 0) for (int q = 0; q < 8; ++q) parts[long(q) * gridDim.x + blockIdx.x] = acc[q];
-    }
-}
-__global__ __launch_bounds__(kBlock) void k_cs_place_row(int np, const double* __restrict__ parts, LinSolver::CsSlots sl, int ns, int mine, double* __restrict__ cA)
-{
-    __shared__ double sm[4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int q = 0; q < sl.n; ++q) {
-        double v = 0.0;
-        for (int i = threadIdx.x; i < np; i += kBlock) v += parts[long(q) * np + i];
-        const double s_ = wave_sum(v);
-        __syncthreads();
-        if (lane == 0) sm[wv] = s_;
-        __syncthreads();
-        if (threadIdx.x == 0) cA[mine * ns + sl.sub_of_slot[q]] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-    }
-}
-
-// ---- several coarse unknowns per rank (cs_m index-range blocks of the owned cells; own blocks occupy the slots 0 .. m-1) ----
-// A_c(rank*m + b, sub_of_slot[q]) = sum over the owned rows of block b of T[q][row]; one slot per blockIdx.y, partials per workgroup
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_cs_block_rows(int nb, int nbp, const int8_t* __restrict__ blk, const S* __restrict__ T, double* __restrict__ parts)
-{
-    __shared__ double sm[32];
-    const int q = blockIdx.y;
-    double acc[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    for (long row = blockIdx.x * long(kBlock) + threadIdx.x; row < nb; row += long(gridDim.x) * kBlock) {
-        const int b = blk[row];
-        if (b < 0) continue;
-        const double v = double(T[long(q) * nbp + row]);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc[u] += (u == b) ? v : 0.0;
-    }
-    block_sum<8>(acc, sm);
-    if (threadIdx.x == 0) for (int u = 0; u < 8; ++u) parts[(long(q) * 8 + u) * gridDim.x + blockIdx.x] = acc[u];
-}
-__global__ __launch_bounds__(kBlock) void k_cs_place_blocks(int np, const double* __restrict__ parts, LinSolver::CsSlots sl, int ns, int m, int mine, double* __restrict__ cA)
-{
-    __shared__ double sm[4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int q = 0; q < sl.n; ++q)
-        for (int b = 0; b < m; ++b) {
-            double v = 0.0;
-            for (int i = threadIdx.x; i < np; i += kBlock) v += parts[(long(q) * 8 + b) * np + i];
-            const double s_ = wave_sum(v);
-            __syncthreads();
-            if (lane == 0) sm[wv] = s_;
-            __syncthreads();
-            if (threadIdx.x == 0) cA[(mine * m + b) * ns + sl.sub_of_slot[q]] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-        }
-}
-// restricted residual of the own blocks: cr[rank*m + b] = sum over the rows of block b (zeros elsewhere: the all-reduce gathers)
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_cs_rsum_blocks(int nb, const int8_t* __restrict__ blk, const S* __restrict__ r, double* __restrict__ parts,
-                                                           const SolveCtl* __restrict__ ctl)
-{
-    __shared__ double sm[32];
-    if (ctl && ctl->done) return;
-    double acc[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-    for (long i = blockIdx.x * long(kBlock) + threadIdx.x; i < nb; i += long(gridDim.x) * kBlock) {
-        const int b = blk[i];
-        if (b < 0) continue;
-        const double v = double(r[i]);
-#pragma unroll
-        for (int u = 0; u < 8; ++u) acc[u] += (u == b) ? v : 0.0;
-    }
-    block_sum<8>(acc, sm);
-    if (threadIdx.x == 0) for (int u = 0; u < 8; ++u) parts[long(u) * gridDim.x + blockIdx.x] = acc[u];
-}
-__global__ __launch_bounds__(kBlock) void k_cs_place_cr(int np, const double* __restrict__ parts, int ns, int m, int mine, double* __restrict__ cr,
-                                                        const SolveCtl* __restrict__ ctl)
-{
-    __shared__ double sm[4];
-    __shared__ double tot[8];
-    if (ctl && ctl->done) return;
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int b = 0; b < m; ++b) {
-        double v = 0.0;
-        for (int i = threadIdx.x; i < np; i += kBlock) v += parts[long(b) * np + i];
-        const double s_ = wave_sum(v);
-        __syncthreads();
-        if (lane == 0) sm[wv] = s_;
-        __syncthreads();
-        if (threadIdx.x == 0) tot[b] = (sm[0] + sm[1]) + (sm[2] + sm[3]);
-    }
-    __syncthreads();
-    if (threadIdx.x < ns) { const int b = threadIdx.x - mine * m; cr[threadIdx.x] = (b >= 0 && b < m) ? tot[b] : 0.0; }
-}
-// wells with blocks: the pair (perforation i, perforations of block b) adds w_i . P_i . sum_{j in b} Q_j[:, pressure] to T[b][row_i]
-// (own blocks are the slots 0 .. m-1); A_c then takes it from T like every other entry.  One workgroup per well, fixed order.
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_cs_wells_blocks(LowRankOp lr, int nbp, int m, const int8_t* __restrict__ blk, const S* __restrict__ w, S* __restrict__ T)
-{
-    __shared__ double sm[28];
-    __shared__ double q7s[8][7];
-    const int wl = blockIdx.x;
-    for (int b = 0; b < m; ++b) {
-        double q7[7] = { 0, 0, 0, 0, 0, 0, 0 };
-        for (int j = lr.connpos[wl] + threadIdx.x; j < lr.connpos[wl + 1]; j += kBlock)
-            if (blk[lr.perf_row[j]] == b) for (int k = 0; k < 7; ++k) q7[k] += lr.Q[21 * long(j) + 3 * k];
-        __syncthreads();
-        block_sum<7>(q7, sm);
-        if (threadIdx.x == 0) for (int k = 0; k < 7; ++k) q7s[b][k] = q7[k];
-    }
-    __syncthreads();
-    for (int i = lr.connpos[wl] + threadIdx.x; i < lr.connpos[wl + 1]; i += kBlock) {
-        const int row = lr.perf_row[i];
-        const double wa[3] = { double(w[row]), double(w[nbp + row]), double(w[2 * long(nbp) + row]) };
-        for (int b = 0; b < m; ++b) {
-            double t = 0.0;
-            for (int a = 0; a < 3; ++a) { double pa = 0.0; for (int k = 0; k < 7; ++k) pa += lr.P[21 * long(i) + 7 * a + k] * q7s[b][k]; t += wa[a] * pa; }
-            T[long(b) * nbp + row] = S(double(T[long(b) * nbp + row]) + t);
-        }
-    }
-}
-
-// wells (rank-7 operator per well, all perforations on this rank): their part of P^T (A_p + wells) P and of the row sums.  Without it
-// a rate-controlled well's diagonal terms are counted although the Schur complement cancels them for a constant pressure shift.
-// One workgroup per well, fixed reduction order; k_cs_wells_sum then adds the per-well totals to A_c(mine, mine) in well order.
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_cs_wells(LowRankOp lr, int nbp, const S* __restrict__ w, S* __restrict__ T0, double* __restrict__ well_tot)
-{
-    __shared__ double sm[28];
-    __shared__ double q7s[7];
-    const int wl = blockIdx.x;
-    double q7[7] = { 0, 0, 0, 0, 0, 0, 0 };
-    for (int j = lr.connpos[wl] + threadIdx.x; j < lr.connpos[wl + 1]; j += kBlock)
-        for (int k = 0; k < 7; ++k) q7[k] += lr.Q[21 * long(j) + 3 * k];              // pressure column of Q_j
-    block_sum<7>(q7, sm);
-    if (threadIdx.x == 0) for (int k = 0; k < 7; ++k) q7s[k] = q7[k];
-    __syncthreads();
-    double tot[1] = { 0.0 };
-    for (int i = lr.connpos[wl] + threadIdx.x; i < lr.connpos[wl + 1]; i += kBlock) {
-        const int row = lr.perf_row[i];
-        const double wa[3] = { double(w[row]), double(w[nbp + row]), double(w[2 * long(nbp) + row]) };
-        double t = 0.0;
-        for (int a = 0; a < 3; ++a) { double pa = 0.0; for (int k = 0; k < 7; ++k) pa += lr.P[21 * long(i) + 7 * a + k] * q7s[k]; t += wa[a] * pa; }
-        T0[row] = S(double(T0[row]) + t);
-        tot[0] += t;
-    }
-    __syncthreads();
-    block_sum<1>(tot, sm);
-    if (threadIdx.x == 0) well_tot[wl] = tot[0];
-}
-__global__ void k_cs_wells_sum(int nw, const double* __restrict__ well_tot, int mine, int ns, double* __restrict__ cA)
-{
-    double s_ = 0.0;
-    for (int wl = 0; wl < nw; ++wl) s_ += well_tot[wl];
-    cA[mine * ns + mine] += s_;
-}
-
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_cs_correct_fast(int nb, int nbp, int ns, LinSolver::CsSlots sl, const int32_t* __restrict__ sub, const S* __restrict__ T,
-                                                            const double* __restrict__ inv, const double* __restrict__ cr, S omega, const S* __restrict__ dinv,
-                                                            S* __restrict__ b, S* __restrict__ x0, S* __restrict__ xc, const SolveCtl* __restrict__ ctl)
-{
-    __shared__ double e[64];
-    if (ctl && ctl->done) return;
-    if (threadIdx.x < ns) { double s_ = 0.0; for (int k = 0; k < ns; ++k) s_ += inv[threadIdx.x * ns + k] * cr[k]; e[threadIdx.x] = s_; }
-    __syncthreads();
-    const int row = blockIdx.x * kBlock + threadIdx.x;
-    if (row >= nb) return;
-    double acc = 0.0;
-    for (int q = 0; q < sl.n; ++q) acc += e[sl.sub_of_slot[q]] * double(T[long(q) * nbp + row]);
-    const S rn = S(double(b[row]) - acc);
-    b[row] = rn; x0[row] = omega * dinv[row] * rn; xc[row] = S(e[sub[row]]);
-}
-
-template <class S> void LinSolver::coarse_setup(bool rowparts_done)
-{
-    SolverWork<S>& w = work<S>();
-    const int ns = coarse_nsub;
-    const bool emulated = !comm && emulate_ranks > 1;
-    const int mine = comm ? comm->my_rank() : 0;
-    double* cA = cs_buf.p; double* inv = cA + ns * ns;
-    if (!emulated && cs_m > 1) {
-        // several coarse unknowns per rank: T is complete (fused row pass or k_cs_rowparts below), the rows of A_c are block sums of it
-        double* rparts = cs_buf.p + size_t(2) * ns * ns + ns;
-        if (!rowparts_done) {
-            const int gp0 = std::min(grid_for(plan.nb), kMaxPart);
-            hipLaunchKernelGGL((k_cs_rowparts<S>), dim3(gp0), dim3(kBlock), 0, stream, plan.nb, plan.nbp, cs_slots, dp.slice_ptr.p, dp.col.p, dp.rowlen.p, cs_sub.p,
-                               comm ? comm->owner_mask() : (const int8_t*)nullptr, (const S*)w.cprw.p, matrix<S>(), rparts, w.csT.p);
-        }
-        if (lowrank.nw > 0)
-            hipLaunchKernelGGL((k_cs_wells_blocks<S>), dim3(lowrank.nw), dim3(kBlock), 0, stream, lowrank, plan.nbp, cs_m, (const int8_t*)cs_blk.p, (const S*)w.cprw.p, w.csT.p);
-        const int gp = std::min(grid_for(plan.nb), 128);           // 64 partial arrays (slot x block) of gp entries in the scratch
-        hipLaunchKernelGGL((k_cs_block_rows<S>), dim3(gp, cs_slots.n), dim3(kBlock), 0, stream, plan.nb, plan.nbp, (const int8_t*)cs_blk.p, (const S*)w.csT.p, rparts);
-        hipLaunchKernelGGL(k_cs_place_blocks, dim3(1), dim3(kBlock), 0, stream, gp, (const double*)rparts, cs_slots, ns, cs_m, mine, cA);
-        if (comm) comm->allreduce_sum(cA, ns * ns, stream);
-    } else if (!emulated) {
-        const int gp = rowparts_done ? std::min(grid_for(plan.nbp), kCsRowParts) : std::min(grid_for(plan.nb), kMaxPart);
-        double* rparts = cs_buf.p + size_t(2) * ns * ns + ns;      // 8 slots x gp partials
-        if (!rowparts_done)
-            hipLaunchKernelGGL((k_cs_rowparts<S>), dim3(gp), dim3(kBlock), 0, stream, plan.nb, plan.nbp, cs_slots, dp.slice_ptr.p, dp.col.p, dp.rowlen.p, cs_sub.p,
-                               comm ? comm->owner_mask() : (const int8_t*)nullptr, (const S*)w.cprw.p, matrix<S>(), rparts, w.csT.p);
-        hipLaunchKernelGGL(k_cs_place_row, dim3(1), dim3(kBlock), 0, stream, gp, (const double*)rparts, cs_slots, ns, mine, cA);
-        if (lowrank.nw > 0) {
-            cs_well_tot.alloc(lowrank.nw);
-            hipLaunchKernelGGL((k_cs_wells<S>), dim3(lowrank.nw), dim3(kBlock), 0, stream, lowrank, plan.nbp, (const S*)w.cprw.p, w.csT.p, cs_well_tot.p);
-            hipLaunchKernelGGL(k_cs_wells_sum, dim3(1), dim3(1), 0, stream, lowrank.nw, (const double*)cs_well_tot.p, mine, ns, cA);
-        }
-        if (comm) comm->allreduce_sum(cA, ns * ns, stream);
-    } else {
-        hipLaunchKernelGGL((k_cs_matrix<S>), dim3(grid_for(plan.nb)), dim3(kBlock), 0, stream, plan.nb, plan.nbp, ns, dp.slice_ptr.p, dp.col.p, dp.rowlen.p, cs_sub.p,
-                           (const int8_t*)nullptr, (const S*)w.cprw.p, matrix<S>(), cA);
-    }
-    hipLaunchKernelGGL(k_cs_invert, dim3(1), dim3(1), size_t(2) * ns * ns * sizeof(double), stream, ns, (const double*)cA, inv);
-}
-// subdomain map, slots and buffers of the coarse space (before the fused row pass writes into them)
-// Subdomains of the coarse space (real ranks or one GPU): m coarse unknowns per rank -- index-range blocks of its owned cells; a single
-// GPU keeps the one global constant -- the largest m <= requested that every rank can hold (own blocks + the neighbours' blocks seen
-// in ghost rows <= 8 slots, n_ranks * m <= 64), agreed collectively.  Cached per communicator / plan.  COLLECTIVE when stale.
-void LinSolver::coarse_domains()
-{
-    const void* key = comm ? static_cast<const void*>(comm) : static_cast<const void*>(this);
-    if (cs_sub.p && cs_sub.n == size_t(plan.nbp) && cs_for == key && cs_blk.p) return;
-    const int mine = comm ? comm->my_rank() : 0;
-    std::vector<int32_t> sub;
-    std::vector<int8_t> blk;
-    // with wells ONE unknown per rank: measured with real ranks, blocks and the wells' rank-7 operator do not mix (2 ranks: 35 -> 77
-    // iterations over six Newton iterations, 4 ranks: 43 -> 96), while one unknown per rank still pays there (4 ranks: 67 -> 43)
-    // ... unless the CALLER supplies the blocks (opmgpu_comm_set_coarse_blocks: sub-slabs along the cut direction keep vertical wells whole)
-    int m = (comm && comm->user_coarse_blocks() > 0) ? comm->user_coarse_blocks() : (comm && !run_has_wells) ? std::max(1, std::min(cs_blocks_req, 8)) : 1;
-    while (m > 1 && comm->num_ranks() * m > 64) m /= 2;
-    for (;; m /= 2) {
-        if (comm) comm->coarse_blocks_of_rows(plan, m, stream, sub, blk); else { sub.assign(plan.nbp, 0); blk.assign(plan.nbp, int8_t(0)); }
-        cs_slots.n = 0;
-        for (int i = 0; i < 64; ++i) cs_slots.slot_of_sub[i] = 0;
-        bool overflow = false;
-        auto add = [&](int sd) {
-            for (int q = 0; q < cs_slots.n; ++q) if (cs_slots.sub_of_slot[q] == sd) return;
-            if (cs_slots.n < 8 && sd >= 0 && sd < 64) { cs_slots.slot_of_sub[sd] = int8_t(cs_slots.n); cs_slots.sub_of_slot[cs_slots.n++] = sd; }
-            else overflow = true;
-        };
-        for (int b = 0; b < m; ++b) add(mine * m + b);             // own blocks: slots 0 .. m-1
-        for (int32_t sd : sub) add(sd);
-        double flag = overflow ? 1.0 : 0.0;
-        if (comm) {
-            DevArray<double> f; f.alloc(1);
-            OPMGPU_HIP(hipMemcpyAsync(f.p, &flag, sizeof(double), hipMemcpyHostToDevice, stream));
-            comm->allreduce_max(f.p, 1, stream);
-            OPMGPU_HIP(hipMemcpyAsync(&flag, f.p, sizeof(double), hipMemcpyDeviceToHost, stream));
-            OPMGPU_HIP(hipStreamSynchronize(stream));
-        }
-        if (flag == 0.0) break;
-        if (m == 1) throw HipError(OPMGPU_EINVAL, "coarse space: more than 7 neighbour ranks or more than 64 ranks (set OPMGPU_COARSE=0)");
-    }
-    cs_m = m;
-    for (int r = plan.nb; r < plan.nbp; ++r) blk[r] = int8_t(-1);
-    cs_sub.alloc(plan.nbp); cs_sub.upload(sub, stream);
-    cs_blk.alloc(plan.nbp); cs_blk.upload(blk, stream);
-    OPMGPU_HIP(hipStreamSynchronize(stream));
-    cs_for = key;
-}
-
-// buffers of the coarse space (before the fused row pass writes into them); the emulated subdomain map
-template <class S> void LinSolver::coarse_begin()
-{
-    SolverWork<S>& w = work<S>();
-    const int ns = coarse_nsub;
-    const bool emulated = !comm && emulate_ranks > 1;
-    if (emulated) {
-        const void* key = static_cast<const void*>(this);
-        if (!cs_sub.p || cs_sub.n != size_t(plan.nbp) || cs_for != key || cs_emulated_ns != ns) {
-            cs_sub.alloc(plan.nbp);
-            hipLaunchKernelGGL(k_cs_sub_emulated, dim3(grid_for(plan.nbp)), dim3(kBlock), 0, stream, plan.nb, plan.nbp, ns, dp.nat.p, cs_sub.p);
-            cs_for = key; cs_emulated_ns = ns; cs_blk.release();
-        }
-    }
-    cs_buf.alloc(size_t(2) * ns * ns + ns + size_t(8) * kCsRowParts);          // scratch: 8 x 8192 partials (also 64 arrays of 128 for the blocks)
-    OPMGPU_HIP(hipMemsetAsync(cs_buf.p, 0, (size_t(2) * ns * ns + ns) * sizeof(double), stream));
-    w.cxc.alloc(plan.nbp);
-    if (!emulated) w.csT.alloc(size_t(cs_slots.n) * plan.nbp);
-}
-
-template <class S> void LinSolver::cpr_reweigh_rows(const int32_t* d_rows, int nrows)
-{
-    if (nrows <= 0 || !weights_from_assembly) return;
-    hipLaunchKernelGGL((k_cpr_weights_rows<S>), dim3((nrows + 3) / 4), dim3(kBlock), 0, stream, nrows, d_rows, plan.nbp, dp.slice_ptr.p, dp.rowlen.p, dp.nlower.p,
-                       dp.tpos.p, matrix<S>(), work<S>().cprw.p, cpr_weight_mode);
-}
-
-// ---- the reference's CPR formulation as an option (opmgpu_params.cpr_reference_transform) ----
-// L of a row from its 0/1 dominance weights (formEllipticSystem's l1, l21 / l22, l31 / l33, NewtonIterationUtilities.cpp:218-262, in this
-// library's equation order water, oil, gas; the reference swaps oil to the front first, so "the first equation" there is the oil slot):
-//   row 0 = pscale * sum of the dominant equations                              (pressure equation; pscale = 200 bar, CPR.cpp:117-121)
-//   row 1 = the water equation -- or the oil equation, if oil is weak and water at least as dominant as gas (l21)
-//   row 2 = the gas equation   -- or the oil equation, if oil is weak and gas more dominant than water (l31)
-// (a weak oil equation with nothing else dominant stays in the sum alone: the weights already say so, no swap)
-template <class S>
-__device__ __forceinline__ void ref_L(const S* __restrict__ w, int nbp, int row, double pscale, double (&L)[9])
-{
-    const double w0 = double(w[row]), w1 = double(w[nbp + row]), w2 = double(w[2 * long(nbp) + row]);
-    const bool oil_weak = w1 == 0.0;
-    const bool l21 = oil_weak && w0 >= w2, l31 = oil_weak && !(w0 >= w2);
-    L[0] = pscale * w0; L[1] = pscale * w1; L[2] = pscale * w2;
-    L[3] = l21 ? 0.0 : 1.0; L[4] = l21 ? 1.0 : 0.0; L[5] = 0.0;
-    L[6] = 0.0; L[7] = l31 ? 1.0 : 0.0; L[8] = l31 ? 0.0 : 1.0;
-}
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_ref_transform_rows(int nb, int nbp, double pscale, const int32_t* __restrict__ slice_ptr, const int16_t* __restrict__ rowlen,
-                                                               const S* __restrict__ w, S* __restrict__ A)
-{
-    const int row = blockIdx.x * kBlock + threadIdx.x;
-    if (row >= nb) return;
-    double L[9];
-    ref_L<S>(w, nbp, row, pscale, L);
-    const int base = slice_ptr[row >> 6], lane = row & 63, len = rowlen[row];
-    for (int k = 0; k < len; ++k) {
-        S* b = A + long(base + k) * 576 + lane;
-        double m[9], o[9];
-#pragma unroll
-        for (int q = 0; q < 9; ++q) m[q] = double(b[q * 64]);
-#pragma unroll
-        for (int i = 0; i < 3; ++i)
-#pragma unroll
-            for (int v = 0; v < 3; ++v) o[3 * i + v] = L[3 * i] * m[v] + L[3 * i + 1] * m[3 + v] + L[3 * i + 2] * m[6 + v];
-#pragma unroll
-        for (int q = 0; q < 9; ++q) b[q * 64] = S(o[q]);
-    }
-}
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_ref_transform_vec(int nb, int nbp, double pscale, const S* __restrict__ w, S* __restrict__ b)
-{
-    const int row = blockIdx.x * kBlock + threadIdx.x;
-    if (row >= nb) return;
-    double L[9];
-    ref_L<S>(w, nbp, row, pscale, L);
-    const double r0 = double(b[row]), r1 = double(b[nbp + row]), r2 = double(b[2 * long(nbp) + row]);
-    b[row] = S(L[0] * r0 + L[1] * r1 + L[2] * r2); b[nbp + row] = S(L[3] * r0 + L[4] * r1 + L[5] * r2); b[2 * long(nbp) + row] = S(L[6] * r0 + L[7] * r1 + L[8] * r2);
-}
-// the wells' low-rank part A += P_w Q_w: the rows of P ([nperf][3][7]) belong to the perforated cells' equations
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_ref_transform_lowrank(LowRankOp lr, int nbp, double pscale, const S* __restrict__ w, double* __restrict__ P)
-{
-    const int j = blockIdx.x * kBlock + threadIdx.x;
-    if (j >= lr.nperf) return;
-    double L[9];
-    ref_L<S>(w, nbp, lr.perf_row[j], pscale, L);
-    double* p = P + 21 * long(j);
-    double m[21];
-    for (int q = 0; q < 21; ++q) m[q] = p[q];
-    for (int i = 0; i < 3; ++i) for (int k = 0; k < 7; ++k) p[7 * i + k] = L[3 * i] * m[k] + L[3 * i + 1] * m[7 + k] + L[3 * i + 2] * m[14 + k];
-}
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_unit_weights(int nbp, S* __restrict__ w)
-{
-    const int row = blockIdx.x * kBlock + threadIdx.x;
-    if (row >= nbp) return;
-    w[row] = S(1); w[nbp + row] = S(0); w[2 * long(nbp) + row] = S(0);
-}
-
-template <class S> void LinSolver::cpr_reference_transform()
-{
-    SolverWork<S>& w = work<S>();
-    const double pscale = 200.0e5;               // 200 * unit::barsa (NewtonIterationBlackoilCPR.cpp:117)
-    const int g = grid_for(plan.nb);
-    if (!ref_transformed) {
-        w.cprw.alloc(3 * size_t(plan.nbp)); w.cprw_orig.alloc(3 * size_t(plan.nbp));
-        if (!weights_from_assembly)
-            hipLaunchKernelGGL((k_cpr_weights<S>), dim3(g), dim3(kBlock), 0, stream, plan.nb, plan.nbp, dp.slice_ptr.p, dp.rowlen.p, dp.nlower.p,
-                               dp.tpos.p, matrix<S>(), w.cprw.p, cpr_weight_mode);
-        OPMGPU_HIP(hipMemcpyAsync(w.cprw_orig.p, w.cprw.p, 3 * size_t(plan.nbp) * sizeof(S), hipMemcpyDeviceToDevice, stream));
-        hipLaunchKernelGGL((k_ref_transform_rows<S>), dim3(g), dim3(kBlock), 0, stream, plan.nb, plan.nbp, pscale, dp.slice_ptr.p, dp.rowlen.p, (const S*)w.cprw_orig.p,
-                           const_cast<S*>(matrix<S>()));
-        if (lowrank.nw > 0 && lowrank.P)
-            hipLaunchKernelGGL((k_ref_transform_lowrank<S>), dim3(grid_for(lowrank.nperf)), dim3(kBlock), 0, stream, lowrank, plan.nbp, pscale, (const S*)w.cprw_orig.p,
-                               const_cast<double*>(lowrank.P));
-        // the pressure equation is row 0 of every transformed block: unit weights for the pressure stage (its extraction, restriction and
-        // coarse space); the bordered well column is formed from the ORIGINAL weights and carries the pressure row's scaling
-        hipLaunchKernelGGL((k_unit_weights<S>), dim3(grid_for(plan.nbp)), dim3(kBlock), 0, stream, plan.nbp, w.cprw.p);
-        weights_from_assembly = true;
-        border_weights = w.cprw_orig.p; border_colscale = pscale;
-        ref_transformed = true;
-        pre_stale = true;
-        pilu.stale = true;
-    }
-    hipLaunchKernelGGL((k_ref_transform_vec<S>), dim3(g), dim3(kBlock), 0, stream, plan.nb, plan.nbp, pscale, (const S*)w.cprw_orig.p, w.b.p);
-}
-
-template <class S> void LinSolver::cpr_prepare()
-{
-    SolverWork<S>& w = work<S>();
-    KtScope kts(kt, KT_CPR_SETUP);
-    const long ne = plan.nentries;
-    if (!w.amg) w.amg.reset(new AmgHierarchy<S>(stream));
-    // OPMGPU_AMG_LAG=k (experiment): refresh the pressure hierarchy's numbers only on every k-th matrix
-    if (amg_lag > 1 && w.amg->ready() && w.cprw.p && (++amg_age % amg_lag) != 0) return;
-    w.cprw.alloc(3 * size_t(plan.nbp));
-    // global coarse space: real ranks, or the emulated ones
-    // one subdomain (single GPU) is the global constant: the near-null-space vector of a closed, slightly compressible system
-    // (wells with a pressure control anchor the level: measured, the constant then costs more than it gains -- so with one
-    // subdomain it is used for well-free systems only; coarse_mode 2 forces it, 0 switches the whole coarse space off)
-    static const int cs_split = std::getenv("OPMGPU_COARSE_SPLIT") ? std::max(1, std::atoi(std::getenv("OPMGPU_COARSE_SPLIT"))) : 1;   // emulation only: coarse unknowns per rank
-    const bool emulated_cs = !comm && emulate_ranks > 1;
-    if (coarse_mode != 0 && !emulated_cs) coarse_domains();
-    const int nsub = comm ? comm->num_ranks() * cs_m : (emulate_ranks > 1 ? emulate_ranks * cs_split : 1);
-    const bool single_ok = coarse_mode == 2 || (coarse_single_ok && lowrank.nw == 0);
-    coarse_nsub = coarse_mode != 0 && (nsub >= 2 || single_ok) ? nsub : 0;
-    if (coarse_nsub > 64) coarse_nsub = 0;        // table sizes of the kernels
-    if (ell.inner) coarse_nsub = 0;               // the inner Krylov method of the elliptic part works on A_p itself (rank-local when decomposed)
-    if (dist_hierarchy()) coarse_nsub = 0;        // the distributed hierarchy reaches the whole domain itself
-    // Scaling of the coarse-grid corrections: 1.9 in general; the correction into level 0 by 2.2 when ONE subdomain carries the coarse
-    // space (one GPU, no wells) -- the global constant is then removed exactly for the whole domain and the hierarchy is global:
-    // measured +4 % (100^3), +9 % (200^3), +7 % (300^3) throughput, 0 % on the sigma = 2 deck (2.2 on every level: better at 100^3 /
-    // 200^3, -15 % at 300^3).  Not with wells (3.7 -> 4.4 iterations on the 5-spot deck) and not decomposed (emulated 8 ranks: 4.8 ->
-    // 5.6; real 4 ranks: unchanged).
-    // Everywhere else the best factor depends on the deck (round 3, profiles/r03_sweep_headline.log: the 5-spot deck wants 2.2-2.6 under
-    // GMRES -- 4.6 -> 3.6 iterations --, the SPE10-like deck and 200^3 want 1.9): the policy below picks between two settings by the
-    // iteration counts they produce.
-    corr_policy.active = false;
-    if (!w.amg->pdamp_user) {
-        const bool global_constant = coarse_nsub == 1 && lowrank.nw == 0;
-        if (global_constant || !corr_policy.on || corr_policy.external || amg_autotune) {
-            if (!w.amg->tuned) { w.amg->pdamp0 = global_constant ? 2.2 : 1.9; w.amg->pdamp = 1.9; }       // (cpr_tune marks the hierarchy; with the autotune experiment it also chose the factors)
-        } else { w.amg->pdamp0 = w.amg->pdamp = corr_policy.arm[corr_policy.cur]; corr_policy.active = true; }
-    }
-    const bool emulated = !comm && emulate_ranks > 1;
-    if (w.amg->ready() && !emulated) {
-        // the usual case: one pass over the matrix does weights + pressure matrix (+ coarse-space row parts)
-        const int gp = std::min(grid_for(plan.nbp), kCsRowParts);
-        if (coarse_nsub >= 1) {
-            coarse_begin<S>();
-            auto kern = weights_from_assembly ? k_cpr_rows<S, true, true> : k_cpr_rows<S, true, false>;
-            hipLaunchKernelGGL(kern, dim3(gp), dim3(kBlock), 0, stream, plan.nb, plan.nbp, cpr_weight_mode, cs_slots, dp.slice_ptr.p, dp.col.p, dp.rowlen.p,
-                               dp.nlower.p, dp.tpos.p, cs_sub.p, comm ? comm->owner_mask() : (const int8_t*)nullptr, matrix<S>(), w.cprw.p,
-                               w.amg->levels[0]->val.p, cs_buf.p + size_t(2) * coarse_nsub * coarse_nsub + coarse_nsub, w.csT.p);
-        } else {
-            auto kern = weights_from_assembly ? k_cpr_rows<S, false, true> : k_cpr_rows<S, false, false>;
-            hipLaunchKernelGGL(kern, dim3(gp), dim3(kBlock), 0, stream, plan.nb, plan.nbp, cpr_weight_mode, cs_slots, dp.slice_ptr.p, dp.col.p, dp.rowlen.p,
-                               dp.nlower.p, dp.tpos.p, (const int32_t*)nullptr, (const int8_t*)nullptr, matrix<S>(), w.cprw.p,
-                               w.amg->levels[0]->val.p, (double*)nullptr, (S*)nullptr);
-        }
-        // Coarse operators (levels >= 1 and the coarsest inverse, 0.18 of the 0.27 ms set-up) follow the first TWO matrices of a time
-        // step (the first update moves the state most; the second solve is also the reference for the guard below): level 0 (weights,
-        // A_p, its Jacobi diagonal) is rebuilt for every matrix, the coarse-grid corrections of the Newton iterations 3.. of a step
-        // come from the operators of its second matrix.  Measured on both bench decks: same iteration
-        // counts even with operators frozen for 20 iterations, -4..7 % time per Newton iteration.  Two guards:
-        //  * only with the global coarse space active (it is rebuilt for every matrix and corrects the pressure level / the subdomain
-        //    constants exactly): without it -- one GPU with wells -- the hierarchy alone carries the near-null pressure-level mode,
-        //    and a lagged one left 5e-6 relative error in that mode at a 1e-12 residual (tests/test_gpu_dist.py, wells case);
-        //  * a lagged solve that needs clearly more iterations than the solve on the fresh operators (a step far from equilibrium:
-        //    measured 13 instead of 8 iterations over six Newton iterations of such a deck) switches the lag off for the rest of
-        //    this time step and the next 8 (bicgstab's epilogue sets lag_block);
-        //  * only for the loose reductions of Newton solves (>= 1e-4): at 1e-11 a lagged hierarchy stagnated on a grid with isolated
-        //    cells (several near-null modes; tests/test_gpu_fullsize.py, Norne-like); and a lagged solve that fails is repeated once
-        //    on fresh operators before the failure is reported (solve_loaded in capi.hip).
-        // OPMGPU_AMG_LAG_COARSE: 0 = refresh for every matrix, 1 = this policy (default), k > 1 = every k-th matrix, no guards.
-        bool refresh;
-        if (coarse_lag == 0) refresh = true;
-        else if (coarse_lag > 1) refresh = (coarse_age++ % coarse_lag) == 0;
-        else {
-            if (new_step_hint) { if (lag_block > 0) --lag_block; step_matrix = 0; } else ++step_matrix;
-            static const bool lag_without_cs = std::getenv("OPMGPU_AMG_LAG_NOCS") && std::atoi(std::getenv("OPMGPU_AMG_LAG_NOCS")) != 0;
-            refresh = step_matrix <= 1 || (coarse_nsub == 0 && !lag_without_cs) || lag_block > 0 || !lag_allowed || force_refresh;
-        }
-        force_refresh = false;
-        new_step_hint = false;
-        refreshed = refresh;
-        if (w.amg->border_nw() > 0)
-            hipLaunchKernelGGL((k_cpr_border<S>), dim3(lowrank.nw), dim3(kBlock), 0, stream, lowrank, plan.nbp, border_weights ? (const S*)border_weights : (const S*)w.cprw.p, w.amg->levels[0]->val.p + w.amg->levels[0]->nentries, border_colscale);
-        // The factorisation (HBM-bound, 140 us, on its own stream) is needed by the first ILU0 sweep only, i.e. behind the hierarchy set-up
-        // AND the first V-cycle.  It starts when the level 0 -> 1 Galerkin sums are done -- the one bandwidth-heavy kernel of the chain,
-        // which it would slow from 60 to 100 us -- and runs next to the small levels' sums and the first cycle (latency-bound launches).
-        w.amg->galerkin(refresh && !(ell.inner && !ell.use_amg), [&] { if (factor_deferred) { factor_deferred = false; factor_async<S>(); } });
-        if (ell.inner && !ell.use_amg) elliptic_factor<S>();
-        if (coarse_nsub >= 1) coarse_setup<S>(true);
-        return;
-    }
-    if (!weights_from_assembly)
-        hipLaunchKernelGGL((k_cpr_weights<S>), dim3(grid_for(plan.nb)), dim3(kBlock), 0, stream, plan.nb, plan.nbp, dp.slice_ptr.p, dp.rowlen.p, dp.nlower.p,
-                           dp.tpos.p, ((emulate_what & 2) ? pre_matrix<S>() : matrix<S>()), w.cprw.p, cpr_weight_mode);
-    if (!w.amg->ready()) {
-        // first matrix with this pattern: pressure values to the host, aggregation hierarchy (structure only) built there
-        DevArray<S> tmp; tmp.alloc(ne);
-        hipLaunchKernelGGL((k_extract_pressure<S>), dim3(grid_for(plan.nbp)), dim3(kBlock), 0, stream, plan.nb, plan.nbp, dp.slice_ptr.p, (const S*)w.cprw.p, ((emulate_what & 2) ? pre_matrix<S>() : matrix<S>()), tmp.p);
-        std::vector<S> h(ne);
-        tmp.download(h.data(), ne, stream);
-        OPMGPU_HIP(hipStreamSynchronize(stream));
-        std::vector<double> hd(h.begin(), h.end());
-        // wells: the pressure system gets one bordering unknown per well (OPMGPU_CPR_WELL_BORDER=0: the wells stay invisible to the AMG)
-        static const bool border_on = !(std::getenv("OPMGPU_CPR_WELL_BORDER") && std::atoi(std::getenv("OPMGPU_CPR_WELL_BORDER")) == 0);
-        AmgBorderSpec bs;
-        if (border_on && lowrank.nw > 0 && lowrank.Fsave && lowrank.ctrl_row && emulate_ranks <= 1) {
-            bs.nw = lowrank.nw; bs.nperf = lowrank.nperf;
-            bs.connpos.resize(bs.nw + 1); bs.perf_row.resize(bs.nperf);
-            OPMGPU_HIP(hipMemcpyAsync(bs.connpos.data(), lowrank.connpos, (bs.nw + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-            OPMGPU_HIP(hipMemcpyAsync(bs.perf_row.data(), lowrank.perf_row, bs.nperf * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
-            DevArray<S> bt; bt.alloc(2 * size_t(bs.nperf) + bs.nw);
-            hipLaunchKernelGGL((k_cpr_border<S>), dim3(lowrank.nw), dim3(kBlock), 0, stream, lowrank, plan.nbp, border_weights ? (const S*)border_weights : (const S*)w.cprw.p, bt.p, border_colscale);
-            std::vector<S> hb(bt.n);
-            bt.download(hb.data(), bt.n, stream);
-            OPMGPU_HIP(hipStreamSynchronize(stream));
-            bs.bcol.assign(hb.begin(), hb.begin() + bs.nperf); bs.crow.assign(hb.begin() + bs.nperf, hb.begin() + 2 * bs.nperf); bs.dw.assign(hb.begin() + 2 * bs.nperf, hb.end());
-            bs.d_connpos = lowrank.connpos; bs.d_perf_row = lowrank.perf_row; bs.d_perf_of_row = lowrank.perf_of_row; bs.d_perf_well = lowrank.perf_well;
-        }
-        w.amg->dcomm = dist_hierarchy() ? comm : nullptr;
-        w.amg->setup(plan, dp.slice_ptr.p, dp.col.p, hd, bs.nw > 0 ? &bs : nullptr);
-    }
-    hipLaunchKernelGGL((k_extract_pressure<S>), dim3(grid_for(plan.nbp)), dim3(kBlock), 0, stream, plan.nb, plan.nbp, dp.slice_ptr.p, (const S*)w.cprw.p, ((emulate_what & 2) ? pre_matrix<S>() : matrix<S>()),
-                       w.amg->levels[0]->val.p);
-    if (w.amg->border_nw() > 0)
-        hipLaunchKernelGGL((k_cpr_border<S>), dim3(lowrank.nw), dim3(kBlock), 0, stream, lowrank, plan.nbp, border_weights ? (const S*)border_weights : (const S*)w.cprw.p, w.amg->levels[0]->val.p + w.amg->levels[0]->nentries, border_colscale);
-    w.amg->galerkin();
-    {
-        // EXPERIMENT (emulated decomposition only, OPMGPU_EMULATE_L0_GLOBAL=1): the coarse operators come from the cut copy (rank-local
-        // Galerkin sums, as a decomposed run builds them), but LEVEL 0 -- smoothing and residual -- works on the uncut pressure matrix, which
-        // is what halo-exchanged level-0 vectors inside the cycle would give a real decomposed run
-        static const bool l0_global = std::getenv("OPMGPU_EMULATE_L0_GLOBAL") && std::atoi(std::getenv("OPMGPU_EMULATE_L0_GLOBAL")) != 0;
-        if (l0_global && emulated && (emulate_what & 2)) {
-            hipLaunchKernelGGL((k_extract_pressure<S>), dim3(grid_for(plan.nbp)), dim3(kBlock), 0, stream, plan.nb, plan.nbp, dp.slice_ptr.p, (const S*)w.cprw.p, matrix<S>(), w.amg->levels[0]->val.p);
-            w.amg->galerkin(false);
-        }
-    }
-    {
-        // EXPERIMENT (emulated decomposition only, OPMGPU_EMULATE_GLOBAL_LEVELS=q): the q COARSEST levels of the hierarchy take the Galerkin
-        // operators of the UNCUT pressure matrix (through the same aggregates, which never cross a cut: cut entries are not strong), the finer
-        // levels keep the cut ones -- what a decomposed run with replicated / all-gathered coarse levels would cycle through.  How many
-        // levels have to be global before the single-domain iteration counts come back tells how far a distributed hierarchy has to reach.
-        static const int gq = std::getenv("OPMGPU_EMULATE_GLOBAL_LEVELS") ? std::atoi(std::getenv("OPMGPU_EMULATE_GLOBAL_LEVELS")) : 0;
-        if (gq > 0 && emulated && (emulate_what & 2) && w.amg->levels.size() >= 2) {
-            AmgHierarchy<S>& A = *w.amg;
-            const int nl = int(A.levels.size()), k = std::max(1, nl - gq);          // levels k .. nl-1 become global
-            std::vector<std::unique_ptr<DevArray<S>>> keep;
-            for (int l = 0; l < k; ++l)
-                for (DevArray<S>* src : { &A.levels[l]->val, &A.levels[l]->dinv }) {
-                    keep.emplace_back(new DevArray<S>()); keep.back()->alloc(src->n);
-                    OPMGPU_HIP(hipMemcpyAsync(keep.back()->p, src->p, src->n * sizeof(S), hipMemcpyDeviceToDevice, stream));
-                }
-            A.join_inverse();
-            hipLaunchKernelGGL((k_extract_pressure<S>), dim3(grid_for(plan.nbp)), dim3(kBlock), 0, stream, plan.nb, plan.nbp, dp.slice_ptr.p, (const S*)w.cprw.p, matrix<S>(), A.levels[0]->val.p);
-            A.galerkin();
-            size_t q = 0;
-            for (int l = 0; l < k; ++l)
-                for (DevArray<S>* dst : { &A.levels[l]->val, &A.levels[l]->dinv }) {
-                    OPMGPU_HIP(hipMemcpyAsync(dst->p, keep[q]->p, dst->n * sizeof(S), hipMemcpyDeviceToDevice, stream)); ++q;
-                }
-            OPMGPU_HIP(hipStreamSynchronize(stream));          // (the stash is freed on return)
-        }
-    }
-    if (ell.inner && !ell.use_amg) elliptic_factor<S>();
-    new_step_hint = false; refreshed = true;
-    if (coarse_nsub >= 1) { coarse_begin<S>(); coarse_setup<S>(false); }
-}
-
-void LinSolver::drop_hierarchies() { wd.amg.reset(); wf.amg.reset(); }
-
-// EXPERIMENT (off by default, OPMGPU_AMG_AUTOTUNE=1).  The plain-aggregation cycle under-corrects by a factor that depends on the matrix:
-// the measured optimum of the two correction factors is 2.2-2.7 on the sigma_lnK = 0.5 decks and <= 1.9 on the SPE10-like one, and either
-// choice costs 15-40 % on the other.  This chooses them per hierarchy from one stationary cycle per candidate on a test right-hand side
-// (A s for a pseudo-random s after OPMGPU_AMG_TUNE_SWEEPS Jacobi sweeps; 0 = the solve's first right-hand side), smallest ||b - A x|| wins,
-// coordinate search over {1.5, 1.9, 2.3, 2.7}^2.  Measured over eleven decks: the choice swings with the smoothness of the test vector
-// (4 sweeps: +9 / +14 % at 100^3 / 150^3 but 2.4 -> 3.3 iterations at 60^3; 6 sweeps picks (2.7, 1.5), on which GMRES fails to converge;
-// the real first right-hand side picks (1.5, 1.5): 3.75 -> 5.25 iterations) -- the stationary cycle's contraction is not what a Krylov
-// method around the cycle needs minimised.  Kept for further work, not used.
-// Multi-GPU: the norms are all-reduced, so every rank would take the same decision.  Leaves levels[0].x = omega0 D^-1 b as the caller's
-// fused kernel wrote it.
-template <class S> void LinSolver::cpr_tune()
-{
-    SolverWork<S>& w = work<S>();
-    AmgHierarchy<S>& A = *w.amg;
-    A.tuned = true;
-    if (!amg_autotune || A.pdamp_user || A.levels.size() < 2) return;
-    static const double cand[4] = { 1.5, 1.9, 2.3, 2.7 };
-    double* d_n2 = partials.p + size_t(6) * npart;          // scratch: the all-reduce slots (no solve is running a reduction now)
-    auto measure = [&](double p0, double pd) {
-        A.pdamp0 = p0; A.pdamp = pd;
-        A.vcycle(nullptr, false);
-        A.residual_norm2(d_n2);
-        if (comm) comm->allreduce_sum(d_n2, 1, stream);
-        double h = 0.0;
-        OPMGPU_HIP(hipMemcpyAsync(&h, d_n2, sizeof(double), hipMemcpyDeviceToHost, stream));
-        OPMGPU_HIP(hipStreamSynchronize(stream));
-        return (h == h) ? h : 1e300;
-    };
-    static const int tune_sweeps = std::getenv("OPMGPU_AMG_TUNE_SWEEPS") ? std::atoi(std::getenv("OPMGPU_AMG_TUNE_SWEEPS")) : 10;
-    if (tune_sweeps > 0) A.smooth_test_rhs(tune_sweeps);          // 0: the solve's own first right-hand side
-    const double p0_start = A.pdamp0;
-    double best_pd = A.pdamp, best = 1e300;
-    for (double c : cand) { const double v = measure(p0_start, c); if (v < best) { best = v; best_pd = c; } }
-    double best_p0 = p0_start; best = 1e300;
-    for (double c : cand) { const double v = measure(c, best_pd); if (v < best) { best = v; best_p0 = c; } }
-    A.pdamp0 = best_p0; A.pdamp = best_pd;
-    if (tune_sweeps > 0) A.restore_rhs();
-    if (std::getenv("OPMGPU_VERBOSE")) std::fprintf(stderr, "[amg] correction factors chosen for this matrix: %.1f into level 0, %.1f below\n", best_p0, best_pd);
-    AmgLevel<S>& L0 = *A.levels[0];
-    hipLaunchKernelGGL((k_amg_restore_x0<S>), dim3(grid_for(L0.ntot())), dim3(kBlock), 0, stream, L0.ntot(), S(A.omega0()), (const S*)L0.dinv.p, (const S*)L0.b.p, L0.x.p);
-}
-
-void LinSolver::CorrectionPolicy::fail_at_current(int iterations)
-{
-    avg[cur] = avg[cur] < 0.0 ? 4.0 * std::max(iterations, 1) : 2.0 * avg[cur];
-    for (int k = cur; k < kArms; ++k) banned_until[k] = steps + ban;
-    step_its = step_solves = 0; step_failed = false;
-    cur = 0;
-}
-
-void LinSolver::correction_policy_choose()
-{
-    CorrectionPolicy& P = corr_policy;
-    if (!P.on || P.external || !new_step_hint) return;            // the setting changes at time-step boundaries only
-    if (P.step_solves >= 2 || P.step_failed) {      // score the step that has just ended
-        const double score = (P.step_failed ? 4.0 : 1.0) * double(P.step_its) / double(std::max(P.step_solves, 1));
-        P.avg[P.cur] = P.avg[P.cur] < 0.0 ? score : 0.5 * P.avg[P.cur] + 0.5 * score;
-        ++P.steps;
-        if (P.step_failed && P.cur > 0) for (int k = P.cur; k < P.kArms; ++k) P.banned_until[k] = P.steps + P.ban;
-    }
-    P.step_its = P.step_solves = 0; P.step_failed = false;
-    // best of what was tried and is allowed: a larger factor has to beat a smaller one by the margin
-    int best = -1;
-    for (int k = 0; k < P.kArms; ++k)
-        if (P.allowed(k) && P.avg[k] >= 0.0 && (best < 0 || P.avg[k] < P.margin * P.avg[best])) best = k;
-    if (best < 0) {          // nothing scored yet (or everything scored is banned): the base setting, else the largest allowed below it
-        int k = P.kBase; while (k > 0 && !P.allowed(k)) --k;
-        P.cur = k;
-        return;
-    }
-    int next = best;
-    if (best == P.kBase && P.allowed(P.kBase + 1) && P.avg[P.kBase + 1] < 0.0) next = P.kBase + 1;           // the pair of round 3: the larger factor once
-    else if (P.avg[best] > P.trouble_its && best > 0 && P.avg[best - 1] < 0.0) next = best - 1;              // many iterations: one arm down, once
-    else if (P.steps % P.period == P.period - 1) {                                                            // periodic second look at a neighbour
-        if (best == P.kBase + 1) next = P.kBase;
-        else if (P.allowed(best + 1)) next = best + 1;
-    }
-    P.cur = next;
-}
-void LinSolver::correction_policy_report(int iterations, bool converged)
-{
-    CorrectionPolicy& P = corr_policy;
-    if (!P.on || !P.active) return;
-    P.step_its += iterations; ++P.step_solves;
-    if (!converged) P.step_failed = true;
-}
-
-static void allreduce_halo(CommBase* c, double* d, int n, float* v, hipStream_t s);
-static void allreduce_halo(CommBase* c, double* d, int n, double* v, hipStream_t s);
-
+#include "coarse_space.inl"
 #include "elliptic.inl"
 #include "fillilu.inl"
 #include "pointilu.inl"
-
-// M^-1 d = [x_p;0;0] + ILU0^-1 (d - A [x_p;0;0]),  x_p = Vcycle(sum of the equations of d) -- or the inner Krylov solve of elliptic.inl
-template <class S> void LinSolver::cpr_apply(const S* d, S* v, double relax, const SolveCtl* ctl, const double* cr_given)
-{
-    SolverWork<S>& w = work<S>();
-    AmgLevel<S>& L0 = *w.amg->levels[0];
-    const int g = grid_for(plan.nb);
-    const bool coarse = coarse_nsub >= 1;
-    const bool fused_post = coarse && cs_fused_post && comm && cpr_halo_xp && !cr_given;        // coarse correction behind the cycle (see linsolver.hpp)
-    const bool fused_rsum = coarse && !fused_post && !(!comm && emulate_ranks > 1) && g <= kCsRowParts;       // real coarse space: restriction fused into the kernel below
-    hipEvent_t kt_a = kt.begin();
-    double* const cs_parts = coarse ? cs_buf.p + size_t(2) * coarse_nsub * coarse_nsub + coarse_nsub : nullptr;   // own scratch (the BiCGStab partial arrays are live across an application)
-    S* const xw = L0.nw > 0 ? L0.x.p + L0.n : (S*)nullptr;        // the wells' unknowns start from zero (their right-hand side is zero): k_cpr_sum_eqs clears them
-    if (!fused_rsum)
-        hipLaunchKernelGGL((k_cpr_sum_eqs<S, 0>), dim3(g), dim3(kBlock), 0, stream, plan.nb, plan.nbp, d, (const S*)w.cprw.p, L0.b.p, S(w.amg->omega0()), (const S*)L0.dinv.p, L0.x.p, ctl,
-                           (const int8_t*)nullptr, (const int8_t*)nullptr, (double*)nullptr, xw, L0.nw);
-    else if (cs_m > 1)
-        hipLaunchKernelGGL((k_cpr_sum_eqs<S, 2>), dim3(g), dim3(kBlock), 0, stream, plan.nb, plan.nbp, d, (const S*)w.cprw.p, L0.b.p, S(w.amg->omega0()), (const S*)L0.dinv.p, L0.x.p, ctl,
-                           (const int8_t*)nullptr, (const int8_t*)cs_blk.p, cs_parts, xw, L0.nw);
-    else
-        hipLaunchKernelGGL((k_cpr_sum_eqs<S, 1>), dim3(g), dim3(kBlock), 0, stream, plan.nb, plan.nbp, d, (const S*)w.cprw.p, L0.b.p, S(w.amg->omega0()), (const S*)L0.dinv.p, L0.x.p, ctl,
-                           comm ? comm->owner_mask() : (const int8_t*)nullptr, (const int8_t*)nullptr, cs_parts, xw, L0.nw);
-    if (!w.amg->tuned) cpr_tune<S>();          // first right-hand side of this hierarchy: choose its correction factors
-    if (coarse && !fused_post) {
-        const int ns = coarse_nsub;
-        double* inv = cs_buf.p + ns * ns; double* cr = inv + ns * ns;
-        const bool emulated = !comm && emulate_ranks > 1;
-        if (cr_given) cr = const_cast<double*>(cr_given);       // the caller's recurrences hold the all-reduced restriction of d already
-        else if (!emulated) {
-            const int gp = fused_rsum ? g : std::min(grid_for(plan.nb), kMaxPart);
-            double* parts = cs_parts;
-            if (cs_m > 1) {
-                if (!fused_rsum) hipLaunchKernelGGL((k_cs_rsum_blocks<S>), dim3(gp), dim3(kBlock), 0, stream, plan.nb, (const int8_t*)cs_blk.p, (const S*)L0.b.p, parts, ctl);
-                hipLaunchKernelGGL(k_cs_place_cr, dim3(1), dim3(kBlock), 0, stream, gp, (const double*)parts, ns, cs_m, comm ? comm->my_rank() : 0, cr, ctl);
-            } else {
-                if (!fused_rsum) hipLaunchKernelGGL((k_cs_rsum<S>), dim3(gp), dim3(kBlock), 0, stream, plan.nb, comm ? comm->owner_mask() : (const int8_t*)nullptr, (const S*)L0.b.p, parts, ctl);
-                hipLaunchKernelGGL(k_cs_place, dim3(1), dim3(kBlock), 0, stream, gp, (const double*)parts, ns, comm ? comm->my_rank() : 0, cr, ctl);
-            }
-            if (comm) comm->allreduce_sum(cr, ns, stream);
-        } else {
-            OPMGPU_HIP(hipMemsetAsync(cr, 0, ns * sizeof(double), stream));
-            hipLaunchKernelGGL((k_cs_restrict<S>), dim3(g), dim3(kBlock), 0, stream, plan.nb, cs_sub.p, (const int8_t*)nullptr, (const S*)L0.b.p, cr, ctl);
-        }
-        if (!emulated)
-            hipLaunchKernelGGL((k_cs_correct_fast<S>), dim3(g), dim3(kBlock), 0, stream, plan.nb, plan.nbp, ns, cs_slots, cs_sub.p, (const S*)w.csT.p, (const double*)inv,
-                               (const double*)cr, S(w.amg->omega0()), (const S*)L0.dinv.p, L0.b.p, L0.x.p, w.cxc.p, ctl);
-        else
-            hipLaunchKernelGGL((k_cs_correct<S>), dim3(g), dim3(kBlock), 0, stream, plan.nb, plan.nbp, ns, dp.slice_ptr.p, dp.col.p, dp.rowlen.p, cs_sub.p,
-                               (const S*)w.cprw.p, matrix<S>(), (const double*)inv, (const double*)cr, S(w.amg->omega0()), (const S*)L0.dinv.p, L0.b.p, L0.x.p, w.cxc.p, ctl);
-    }
-    kt.end(KT_CPR_OTHER, kt_a);
-    kt_a = kt.begin();
-    if (comm && cpr_l0_halo && !ell.inner && w.amg->ndist == 0) {
-        S* const hx = w.hx.p; CommBase* const cm = comm; const int nbl = plan.nb; hipStream_t st = stream;
-        w.amg->level0_halo = [=](S* x, S* b) {
-            OPMGPU_HIP(hipMemcpyAsync(hx, x, size_t(nbl) * sizeof(S), hipMemcpyDeviceToDevice, st));
-            halo_dispatch(cm, hx, st);
-            hipLaunchKernelGGL((k_l0_ghosts<S>), dim3(grid_for(nbl)), dim3(kBlock), 0, st, nbl, cm->owner_mask(), (const S*)hx, x, b, ctl);
-        };
-        w.amg->level0_halo_down = cpr_l0_halo_down;
-    } else w.amg->level0_halo = nullptr;
-    if (ell.inner) elliptic_solve<S>(); else w.amg->vcycle_graph(ctl, true);
-    kt.end(KT_VCYCLE, kt_a);
-    kt_a = kt.begin();
-    const S* xp = L0.x.p;
-    // multi-GPU: the AMG is rank-local (additive Schwarz: ghost rows are identity rows); the owners' x_p is copied to the
-    // ghosts before the full-system residual so that stage 2 sees the neighbours' pressure correction on the rows next to the
-    // cut.  Costs two halo exchanges per BiCGStab iteration; without it (OPMGPU_CPR_HALO_XP=0) the one-rank self-halo deck,
-    // where half of the rows touch the cut, needs 25 % more iterations -- and with the coarse space it is essential: the
-    // subdomain constants jump at the cut, and a stage 2 that does not see the jump needs 2.5x the iterations (emulated 8
-    // ranks: 4.4 -> 11.5, OPMGPU_EMULATE_WHAT=7).  The exchange runs on the halo stream behind the rows that read no ghost (as in
-    // bicgstab's products).
-    bool exchange = false;
-    if (fused_post) {
-        // r = b - A_p x of the cycle's result, restricted over this rank's owned rows (its coarse unknowns); hx = x; the halo of hx and the
-        // restricted residual in ONE operation; then the subdomain constants on all rows, ghost rows included
-        const int ns = coarse_nsub;
-        double* inv = cs_buf.p + ns * ns; double* cr = inv + ns * ns;
-        w.amg->residual0(ctl);
-        AmgLevel<S>& F0 = *w.amg->levels[0];
-        const int gp = std::min(grid_for(plan.nb), kMaxPart);
-        if (cs_m > 1) {
-            hipLaunchKernelGGL((k_cs_rsum_blocks<S>), dim3(gp), dim3(kBlock), 0, stream, plan.nb, (const int8_t*)cs_blk.p, (const S*)F0.r.p, cs_parts, ctl);
-            hipLaunchKernelGGL(k_cs_place_cr, dim3(1), dim3(kBlock), 0, stream, gp, (const double*)cs_parts, ns, cs_m, comm->my_rank(), cr, ctl);
-        } else {
-            hipLaunchKernelGGL((k_cs_rsum<S>), dim3(gp), dim3(kBlock), 0, stream, plan.nb, comm->owner_mask(), (const S*)F0.r.p, cs_parts, ctl);
-            hipLaunchKernelGGL(k_cs_place, dim3(1), dim3(kBlock), 0, stream, gp, (const double*)cs_parts, ns, comm->my_rank(), cr, ctl);
-        }
-        OPMGPU_HIP(hipMemcpyAsync(w.hx.p, F0.x.p, size_t(plan.nb) * sizeof(S), hipMemcpyDeviceToDevice, stream));
-        allreduce_halo(comm, cr, ns, w.hx.p, stream);
-        hipLaunchKernelGGL((k_cs_add_post<S>), dim3(g), dim3(kBlock), 0, stream, plan.nb, ns, (const int32_t*)cs_sub.p, (const double*)inv, (const double*)cr, w.hx.p, ctl);
-        xp = w.hx.p;
-    } else if (coarse) {
-        hipLaunchKernelGGL((k_cs_add<S>), dim3(g), dim3(kBlock), 0, stream, plan.nb, (const S*)L0.x.p, (const S*)w.cxc.p, w.hx.p, ctl);
-        xp = w.hx.p;
-        exchange = comm && cpr_halo_xp;
-    } else if (comm && cpr_halo_xp) {
-        OPMGPU_HIP(hipMemcpyAsync(w.hx.p, L0.x.p, size_t(plan.nb) * sizeof(S), hipMemcpyDeviceToDevice, stream));
-        xp = w.hx.p;
-        exchange = true;
-    }
-    const S* amat = (emulate_what & 4) ? pre_matrix<S>() : matrix<S>();
-    const int8_t* own = comm ? comm->owner_mask() : (const int8_t*)nullptr;
-    const bool overlap = exchange && halo_overlap && halo_stream && light_ok_for == comm && light_ok.n == size_t(plan.nbp);
-    if (!overlap) {
-        if (exchange) halo_dispatch(comm, w.hx.p, stream);
-        hipLaunchKernelGGL((k_cpr_presidual<S>), dim3(grid8_for(plan.nb)), dim3(kBlock), 0, stream, xcd_mode(), plan.nb, plan.nbp, dp.slice_ptr.p, dp.col.p, amat, d, xp, w.z.p, own, ctl,
-                           0, (const int8_t*)nullptr);
-    } else {
-        OPMGPU_HIP(hipEventRecord(ev_halo[0], stream));
-        OPMGPU_HIP(hipStreamWaitEvent(halo_stream, ev_halo[0], 0));
-        halo_dispatch(comm, w.hx.p, halo_stream);
-        OPMGPU_HIP(hipEventRecord(ev_halo[1], halo_stream));
-        hipLaunchKernelGGL((k_cpr_presidual<S>), dim3(grid8_for(plan.nb)), dim3(kBlock), 0, stream, xcd_mode(), plan.nb, plan.nbp, dp.slice_ptr.p, dp.col.p, amat, d, xp, w.z.p, own, ctl,
-                           1, (const int8_t*)light_ok.p);
-        OPMGPU_HIP(hipStreamWaitEvent(stream, ev_halo[1], 0));
-        hipLaunchKernelGGL((k_cpr_presidual<S>), dim3(grid8_for(plan.nb)), dim3(kBlock), 0, stream, xcd_mode(), plan.nb, plan.nbp, dp.slice_ptr.p, dp.col.p, amat, d, xp, w.z.p, own, ctl,
-                           2, (const int8_t*)light_ok.p);
-    }
-    kt.end(KT_CPR_OTHER, kt_a);
-    if (point_stage2 && sizeof(S) == 8) point_ilu_apply(reinterpret_cast<const double*>(w.z.p), reinterpret_cast<double*>(v), relax);      // the reference's own stage 2 (pointilu.inl)
-    else ilu_apply<S>(w.z.p, v, relax, ctl);
-    kt_a = kt.begin();
-    if (well_woodbury && wb_active && lowrank.nw > 0 && lowrank.P && !comm && wb_buf.p && fill_level == 0)
-        hipLaunchKernelGGL((k_wb_apply<S>), dim3(lowrank.nw), dim3(kBlock), 0, stream, lowrank, plan.nbp, (const double*)wb_buf.p,
-                           (const double*)(wb_buf.p + size_t(21) * lowrank.nperf), v, ctl);
-    hipLaunchKernelGGL((k_cpr_add_p<S>), dim3(g), dim3(kBlock), 0, stream, plan.nb, xp, v, ctl, S(ell.relax));
-    kt.end(KT_CPR_OTHER, kt_a);
-}
-
-template <class S> static void halo(CommBase* c, S* v, hipStream_t s);
-template <> void halo<float>(CommBase* c, float* v, hipStream_t s) { c->halo_exchange_f(v, s); }
-template <> void halo<double>(CommBase* c, double* v, hipStream_t s) { c->halo_exchange_d(v, s); }
-static void allreduce_halo(CommBase* c, double* d, int n, float* v, hipStream_t s) { c->allreduce_sum_halo_f(d, n, v, s); }
-static void allreduce_halo(CommBase* c, double* d, int n, double* v, hipStream_t s) { c->allreduce_sum_halo_d(d, n, v, s); }
+#include "cpr.inl"
 
 // Wait for the status block of the check kernel just enqueued.  Spinning on a host-mapped word the kernel writes last sees the result
 // a few microseconds after the kernel retires; hipStreamSynchronize takes an interrupt round trip (~20 us of idle GPU per check).
@@ -2369,723 +939,7 @@ template <class S> void LinSolver::precond_apply(const S* d, S* out, double rela
     hipLaunchKernelGGL((k_convert<float, S>), dim3(g), dim3(kBlock), 0, stream, n, (const float*)wf.y.p, out);
 }
 
-template <class S> SolveResult LinSolver::bicgstab(const opmgpu_params& prm)
-{
-    SolverWork<S>& w = work<S>();
-    SolveResult res;
-    wb_active = false;             // (the wells' Woodbury correction of stage 2 runs under GMRES only: the closed-form rows below assume the plain ILU0)
-    cs_fused_post = false;         // (BiCGStab carries the coarse space's restriction along its recurrences: no all-reduce to fuse)
-    const long n = long(3) * plan.nbp;
-    const int gv = std::min(grid_for(n), kMaxPart);            // vector kernels (also the number of their partials)
-    const int gs = std::min(grid8_for(plan.nb), kMaxPart);     // reducing SpMV launches (multiple of 8: XCD-aware chunking)
-    const double eps = sizeof(S) == 8 ? 1e-80 : 0.0;           // dune: real_type EPSILON = 1e-80 (0 in float)
-    const int maxit = prm.linear_solver_maxiter;
-    const int8_t* mask = comm ? comm->owner_mask() : nullptr;
-    // closed form of (A M^-1 p) on the level-0 rows -- valid when M is the ILU0 of exactly this matrix and none of the row's
-    // neighbours is a ghost whose entry of M^-1 p is overwritten by the halo exchange (multi-GPU: light_ok masks those rows out)
-    const bool cpr = prm.use_cpr != 0;                   // multi-GPU: rank-local (additive Schwarz) AMG + block-Jacobi ILU0
-    lag_allowed = prm.linear_solver_reduction >= 1e-4;
-    const bool mx = mixed && sizeof(S) == 8;
-    if (cpr) { if (mx) cpr_prepare_mixed(); else cpr_prepare<S>(); }
-    if (factor_deferred) { factor_deferred = false; if (mx) factor_async<float>(); else factor_async<S>(); }
-    if (cpr) { if (mx) { if (!wf.amg->npost0_user) wf.amg->npost0 = 2; } else if (!w.amg->npost0_user) w.amg->npost0 = 2; }   // post-sweeps on level 0: 2 under BiCGStab, 1 under GMRES (see gmres)
-    // (with cpr_relax != 1 the pressure part of M^-1 p is scaled, which the closed form does not cover)
-    // (mixed precision: the float ILU0 is not the ILU0 of exactly the double matrix -- the closed form would be off by float rounding)
-    const bool closed = closed_form_level0 && emulate_ranks <= 1 && !(cpr && ell.relax != 1.0) && !mx && !(cpr && point_stage2) && fill_level == 0;      // (ell.relax = cpr_relax; under CPR prm.ilu_relaxation holds cpr_relax * cpr_stage2_relax: solve_loaded)
-    const int8_t* lightmask = nullptr;
-    const bool overlap = comm && halo_overlap;
-    if (comm && (closed || overlap)) {
-        if (light_ok_for != comm || light_ok.n != size_t(plan.nbp)) {
-            light_ok.alloc(plan.nbp); light_ok.zero(stream);
-            hipLaunchKernelGGL(k_light_mask, dim3(grid_for(plan.nb)), dim3(kBlock), 0, stream, plan.nb, dp.slice_ptr.p, dp.col.p, dp.rowlen.p, comm->owner_mask(), light_ok.p);
-            light_ok_for = comm;
-        }
-        if (closed) lightmask = light_ok.p;
-    }
-    if (overlap && !halo_stream) {
-        OPMGPU_HIP(hipStreamCreateWithFlags(&halo_stream, hipStreamNonBlocking));
-        for (auto& e : ev_halo) OPMGPU_HIP(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
-    const S* pin_p = closed ? w.p.p : nullptr; const S* pin_r = closed ? w.r.p : nullptr;
-    const S* zin_p = cpr ? w.z.p : pin_p; const S* zin_r = cpr ? w.z.p : pin_r;     // second-stage input of the last M^-1
-    const int n0 = plan.level_ptr[1];
-    // v = A y with the halo exchange of y behind the rows that do not need it; returns the number of partials written
-    auto spmv_halo = [&](auto which, S* yv, S* out, const S* w1, double* q0, double* q1, const S* pin, const S* zin) -> int {
-        constexpr int ND = decltype(which)::value;
-        if (!overlap) {
-            if (comm) halo<S>(comm, yv, stream);
-            lowrank_reduce<S>(yv, (const SolveCtl*)ctl.p);
-            hipLaunchKernelGGL((k_spmv<S, ND>), dim3(gs), dim3(kBlock), 0, stream, xcd_mode(), plan.nb, plan.nbp, dp.slice_ptr.p, dp.col.p, matrix<S>(),
-                               yv, out, w1, mask, (const SolveCtl*)ctl.p, q0, q1, pin, zin, n0, S(prm.ilu_relaxation), lowrank, lightmask, 0, (const int8_t*)nullptr);
-            return gs;
-        }
-        OPMGPU_HIP(hipEventRecord(ev_halo[0], stream));
-        OPMGPU_HIP(hipStreamWaitEvent(halo_stream, ev_halo[0], 0));
-        halo<S>(comm, yv, halo_stream);
-        OPMGPU_HIP(hipEventRecord(ev_halo[1], halo_stream));
-        lowrank_reduce<S>(yv, (const SolveCtl*)ctl.p);                 // wells live on one rank: their perforated cells are owned rows
-        hipLaunchKernelGGL((k_spmv<S, ND>), dim3(gs), dim3(kBlock), 0, stream, xcd_mode(), plan.nb, plan.nbp, dp.slice_ptr.p, dp.col.p, matrix<S>(),
-                           yv, out, w1, mask, (const SolveCtl*)ctl.p, q0, q1, pin, zin, n0, S(prm.ilu_relaxation), lowrank, lightmask, 1, (const int8_t*)light_ok.p);
-        OPMGPU_HIP(hipStreamWaitEvent(stream, ev_halo[1], 0));
-        hipLaunchKernelGGL((k_spmv<S, ND>), dim3(kBndPart), dim3(kBlock), 0, stream, xcd_mode(), plan.nb, plan.nbp, dp.slice_ptr.p, dp.col.p, matrix<S>(),
-                           yv, out, w1, mask, (const SolveCtl*)ctl.p, q0 + gs, q1 ? q1 + gs : (double*)nullptr, pin, zin, n0, S(prm.ilu_relaxation), lowrank, lightmask, 2,
-                           (const int8_t*)light_ok.p);
-        return gs + kBndPart;
-    };
-    double* P_h = partials.p, *P_n1 = P_h + npart, *P_tr = P_n1 + npart, *P_tt = P_tr + npart, *P_n2 = P_tt + npart, *P_rho = P_n2 + npart;
-    double* red = P_rho + npart;                               // 8 all-reduced scalars (multi-GPU)
-    // (multi-GPU) collapse partial arrays of np entries into red[slot..] and all-reduce them; consumers then read 1 entry
-    // defer > 0: no all-reduce now, the NEXT bridge (whose slots follow this one's) reduces `defer` more values in the same call
-    int deferred = 0;
-    // coarse-space restriction by recurrence (see CsRec): active for the real multi-rank coarse space only
-    // The recurrences run in double next to vectors of precision S: every x -= a y of the vectors leaves a rounding error of eps_S |r_k| in
-    // the REAL restricted residual that the recurrence does not see, so once ||r|| has dropped by about sqrt(eps_S) the carried value is
-    // noise and the correction it drives stalls the iteration (seen: float solve asked for 1e-10).  The host reads ||r||^2 after every
-    // CPR iteration anyway (wait_tick): below cs_floor the applications go back to restricting and all-reducing themselves.
-    const bool cs_rec = cpr && comm && cs_recur && !cpr_speculate && coarse_nsub >= 1 && coarse_nsub <= 64;
-    const double cs_floor = sizeof(S) == 4 ? 1e-3 : 1e-11;
-    bool cs_live = cs_rec;
-    const int ns = cs_rec ? coarse_nsub : 0;
-    // position of all-reduce slot s in `red`: the coarse-space vectors follow slot 0 (initial C(r)), slot 1 (C(v)) and slot 4 (C(t))
-    auto pos = [&](int slot) { return slot + (slot >= 1 ? ns : 0) + (slot >= 2 ? ns : 0) + (slot >= 5 ? ns : 0); };
-    CsRec csr = { nullptr, nullptr, nullptr, nullptr, nullptr, 0 };
-    double* cs_wparts = nullptr; int cs_gp = 0;
-    if (cs_rec) {
-        if (cs_state.n < size_t(2) * ns) cs_state.alloc(size_t(2) * ns);
-        csr.Cp = cs_state.p; csr.Cr = cs_state.p + ns; csr.ns = ns;
-        csr.C0 = red + pos(0) + 1; csr.Cv = red + pos(1) + 1; csr.Ct = red + pos(4) + 1;
-        cs_wparts = cs_buf.p + size_t(2) * ns * ns + ns;       // the scratch of cpr_apply's fused restriction: free between applications
-        cs_gp = std::min(grid_for(plan.nb), kMaxPart);
-    }
-    // cs_vec (cs_rec only): the vector whose restriction is appended behind the scalars of this bridge
-    auto bridge = [&](double*& a0, double*& a1, int& np, int slot, bool defer = false, const S* cs_vec = nullptr) {
-        if (!comm) return;
-        double* out = red + pos(slot);
-        const int nv = a1 ? 2 : 1;
-        int extra = 0;
-        if (cs_live && cs_vec) {
-            hipLaunchKernelGGL((k_cs_wdot<S>), dim3(cs_gp), dim3(kBlock), 0, stream, plan.nb, plan.nbp, cs_vec, (const S*)w.cprw.p, cs_m > 1 ? (const int8_t*)nullptr : mask,
-                               cs_m > 1 ? (const int8_t*)cs_blk.p : (const int8_t*)nullptr, cs_m, cs_wparts, (const SolveCtl*)nullptr);
-            if (a1) hipLaunchKernelGGL((k_bridge_cs<2>), dim3(1), dim3(kBlock), 0, stream, a0, a1, np, (const double*)cs_wparts, cs_gp, ns, cs_m, comm->my_rank(), out);
-            else hipLaunchKernelGGL((k_bridge_cs<1>), dim3(1), dim3(kBlock), 0, stream, a0, (const double*)nullptr, np, (const double*)cs_wparts, cs_gp, ns, cs_m, comm->my_rank(), out);
-            extra = ns;
-        } else if (a1) hipLaunchKernelGGL((k_sum_partials<2>), dim3(1), dim3(kBlock), 0, stream, a0, a1, np, out);
-        else hipLaunchKernelGGL((k_sum_partials<1>), dim3(1), dim3(kBlock), 0, stream, a0, (const double*)nullptr, np, out);
-        if (defer) deferred += nv;
-        else { comm->allreduce_sum(out - deferred, nv + deferred + extra, stream); deferred = 0; }
-        a0 = out; if (a1) a1 = out + 1; np = 1;
-    };
-    // x = 0, r = rt = b, p = v = 0
-    w.x.zero(stream);
-    OPMGPU_HIP(hipMemcpyAsync(w.r.p, w.b.p, n * sizeof(S), hipMemcpyDeviceToDevice, stream));
-    OPMGPU_HIP(hipMemcpyAsync(w.rt.p, w.b.p, n * sizeof(S), hipMemcpyDeviceToDevice, stream));
-    SolveCtl* d_ctl = ctl.p;
-    hipLaunchKernelGGL(k_ctl_init, dim3(1), dim3(1), 0, stream, d_ctl, h_ctl_dev, prm.linear_solver_reduction);
-    hipLaunchKernelGGL((k_dot<S>), dim3(gv), dim3(kBlock), 0, stream, n, w.r.p, w.r.p, P_n2);
-    double* a_n2 = P_n2; double* a_rho = P_n2; double* none = nullptr; int np_n2 = gv;
-    bridge(a_n2, none, np_n2, 0, false, w.r.p); a_rho = a_n2;
-    hipLaunchKernelGGL(k_ctl_thresh, dim3(1), dim3(kBlock), 0, stream, d_ctl, prm.linear_solver_reduction, (const double*)a_n2, np_n2);
-    int j = 1, last = 0, target = 0;
-    bool stop = false, checked = false;      // checked: the last enqueued iteration has been tested and the status block is current
-    for (; j <= maxit && !stop; ++j) {
-        checked = false;
-        hipEvent_t kt_a = kt.begin();
-        const CsRec csr_off = { nullptr, nullptr, nullptr, nullptr, nullptr, 0 };
-        const CsRec csr_it = cs_live ? csr : csr_off;
-        hipLaunchKernelGGL((k_update_p<S>), dim3(gv), dim3(kBlock), 0, stream, n, j, eps, d_ctl, h_ctl_dev, (const double*)a_n2, (const double*)a_rho, np_n2,
-                           w.r.p, w.v.p, w.p.p, csr_it);
-        kt.end(KT_VECTOR, kt_a);
-        precond_apply<S>(w.p.p, w.y.p, prm.ilu_relaxation, d_ctl, cpr, csr_it.Cp);
-        kt_a = kt.begin();
-        const int np_spmv1 = spmv_halo(std::integral_constant<int, 1>(), w.y.p, w.v.p, w.rt.p, P_h, (double*)nullptr, pin_p, zin_p);
-        kt.end(KT_SPMV1, kt_a);
-        double* a_h = P_h; int np_h = np_spmv1; none = nullptr;
-        bridge(a_h, none, np_h, 1, false, w.v.p);
-        kt_a = kt.begin();
-        hipLaunchKernelGGL((k_update_xr1<S>), dim3(gv), dim3(kBlock), 0, stream, n, j, eps, d_ctl, h_ctl_dev, (const double*)a_h, np_h, w.y.p, w.v.p,
-                           w.x.p, w.r.p, P_n1, csr_it);
-        kt.end(KT_VECTOR, kt_a);
-        double* a_n1 = P_n1; int np_n1 = gv; none = nullptr;
-        bridge(a_n1, none, np_n1, 2, true);      // ||r||^2 of the half step is consumed by k_update_xr2: reduced together with <t,r>, <t,t> (slots 2..4)
-        precond_apply<S>(w.r.p, w.y.p, prm.ilu_relaxation, d_ctl, cpr, csr_it.Cr);
-        kt_a = kt.begin();
-        const int np_spmv2 = spmv_halo(std::integral_constant<int, 2>(), w.y.p, w.t.p, w.r.p, P_tr, P_tt, pin_r, zin_r);
-        kt.end(KT_SPMV2, kt_a);
-        double* a_tr = P_tr; double* a_tt = P_tt; int np_t = np_spmv2;
-        bridge(a_tr, a_tt, np_t, 3, false, w.t.p);
-        kt_a = kt.begin();
-        hipLaunchKernelGGL((k_update_xr2<S>), dim3(gv), dim3(kBlock), 0, stream, n, j, d_ctl, h_ctl_dev, (const double*)a_n1, (const double*)a_tr,
-                           (const double*)a_tt, np_n1, np_t, w.y.p, w.t.p, w.rt.p, w.x.p, w.r.p, P_n2, P_rho, csr_it);
-        kt.end(KT_VECTOR, kt_a);
-        a_n2 = P_n2; a_rho = P_rho; np_n2 = gv;
-        bridge(a_n2, a_rho, np_n2, 5);
-        last = j;
-        if (cpr && !cpr_speculate) {
-            // CPR iterations are long (~0.6 ms of kernels) and few (~5): a speculative extra iteration of ~50 no-op
-            // launches costs more than one host round trip, so test convergence at the END of the iteration and wait.
-            const int tick = ++tick_seq;
-            hipLaunchKernelGGL(k_final_check, dim3(1), dim3(kBlock), 0, stream, j, d_ctl, h_ctl_dev, (const double*)a_n2, np_n2, poll_status ? h_tick_dev : (int*)nullptr, tick);
-            wait_tick(tick);
-            if (h_ctl->done) stop = true;
-            if (cs_live && !(h_ctl->norm2 > cs_floor * cs_floor * h_ctl->norm0_2)) cs_live = false;      // the same decision on every rank: the norms are collective
-            checked = true;
-            continue;
-        }
-        OPMGPU_HIP(hipEventRecord(ev[j & 1], stream));
-        if (j >= 2 && target == 0) {       // iteration j-1 is complete once its event has fired; iteration j is already queued
-            OPMGPU_HIP(hipEventSynchronize(ev[(j - 1) & 1]));
-            if (h_ctl->done) {
-                // single GPU: stop now.  Multi GPU: every rank must enqueue the SAME number of iterations (their
-                // collectives pair up); `decided` is identical on all ranks, when a rank notices it is not.
-                if (!comm) stop = true;
-                else target = std::min(maxit, h_ctl->decided + 1);
-            }
-        }
-        if (target != 0 && j >= target) stop = true;
-    }
-    if (!checked) {
-        hipLaunchKernelGGL(k_final_check, dim3(1), dim3(kBlock), 0, stream, last, d_ctl, h_ctl_dev, (const double*)a_n2, np_n2);
-        OPMGPU_HIP(hipStreamSynchronize(stream));
-    }
-    if (comm) comm->check_async();          // a collective that failed asynchronously must not pass as a converged solve
-    const double norm0 = std::sqrt(h_ctl->norm0_2), norm = std::sqrt(h_ctl->norm2);
-    res.converged = h_ctl->done && h_ctl->flag == 0;
-    res.iterations = h_ctl->done ? h_ctl->iters : maxit;
-    res.reduction = norm0 > 0 ? norm / norm0 : 0.0;
-    if (h_ctl->flag != 0 || !(norm0 == norm0)) {
-        res.status = OPMGPU_EBREAKDOWN;
-        char buf[160];
-        std::snprintf(buf, sizeof buf, "breakdown in BiCGSTAB (%s; ||r0|| = %.3e)", !(norm0 == norm0) ? "non-finite initial defect" : (h_ctl->flag == 1 ? "|h| < eps" : "|rho| or |omega| <= eps"), norm0);
-        breakdown_note = buf;
-    }
-    else if (!res.converged && !prm.ignore_convergence_failure) res.status = OPMGPU_ELINSOLVE;      // ISTLSolver.hpp:358-368
-    last_its = res.iterations;
-    if (refreshed) its_ref = res.iterations;
-    else if (coarse_lag == 1 && last_its > its_ref + std::max(1, its_ref / 4)) lag_block = 8;     // see cpr_prepare
-    return res;
-}
-
-// ---- restarted GMRES (Dune::RestartedGMResSolver::apply, reached from ISTLSolver.hpp:257-264 with newton_use_gmres) ----
-// LEFT-preconditioned: the residual it measures is M^-1 (b - A x).  Arnoldi with modified Gram-Schmidt: every projection is a
-// k_dot launch whose partials the following k_gm_axpy re-reduces (no reduction launches, deterministic); the Hessenberg
-// column, the Givens rotations and the convergence test live on the device (k_gm_givens, one thread), the host only reads the
-// mapped status block once per iteration like the CPR path does.
-struct GmState { double* H; double* s; double* cs; double* sn; double* y; };      // H[(m+1) x m] row-major, all double
-
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_gm_axpy(long n, int slot, const double* __restrict__ parts, int np, double* __restrict__ H,
-                                                    const S* __restrict__ vk, S* __restrict__ w, const SolveCtl* __restrict__ ctl)
-{
-    __shared__ double sm[12];
-    if (ctl->done) return;
-    const double* const arr[1] = { parts };
-    double s[1];
-    reduce_partials<1>(arr, np, s, sm);
-    if (blockIdx.x == 0 && threadIdx.x == 0) H[slot] = s[0];
-    const S h = S(s[0]);
-    for (long i = blockIdx.x * long(kBlock) + threadIdx.x; i < n; i += long(gridDim.x) * kBlock) w[i] -= h * vk[i];
-}
-// One modified-Gram-Schmidt step fused with the next one's projection: w -= h vk with h = sum(parts_in) (recorded in H[slot]), and in the
-// same pass the partials of <vnext, w> for the updated w (vnext == nullptr: of <w, w>, the norm that ends the column).  The same
-// arithmetic as k_gm_axpy followed by k_dot / k_dot_owned (the partial sums run over 16-byte lanes, a fixed order: deterministic); one pass
-// over w instead of two and half the launches.
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_gm_axpy_dot(long n, int nbp, const int8_t* __restrict__ mask, int slot, const double* __restrict__ parts_in, int np,
-                                                        double* __restrict__ H, const S* __restrict__ vk, S* __restrict__ w, const S* __restrict__ vnext,
-                                                        double* __restrict__ parts_out, const SolveCtl* __restrict__ ctl)
-{
-    __shared__ double sm[12];
-    if (ctl->done) return;
-    const double* const arr[1] = { parts_in };
-    double s[1];
-    reduce_partials<1>(arr, np, s, sm);
-    if (blockIdx.x == 0 && threadIdx.x == 0) H[slot] = s[0];
-    const S h = S(s[0]);
-    double acc[1] = { 0.0 };
-    if (!mask) {
-        // 16-byte lanes: three read streams and one write stream of 12 MB each want more bytes in flight per thread than one scalar
-        constexpr int L = 16 / sizeof(S);
-        struct alignas(16) Pack { S v[L]; };
-        const long nv = n / L;
-        const Pack* __restrict__ vk4 = reinterpret_cast<const Pack*>(vk);
-        const Pack* __restrict__ vn4 = reinterpret_cast<const Pack*>(vnext);
-        Pack* __restrict__ w4 = reinterpret_cast<Pack*>(w);
-        for (long q = blockIdx.x * long(kBlock) + threadIdx.x; q < nv; q += long(gridDim.x) * kBlock) {
-            Pack a = w4[q];
-            const Pack b = vk4[q];
-            Pack c = a;
-            if (vnext) c = vn4[q];
-#pragma unroll
-            for (int u = 0; u < L; ++u) { a.v[u] = a.v[u] - h * b.v[u]; acc[0] += double(vnext ? c.v[u] : a.v[u]) * double(a.v[u]); }
-            w4[q] = a;
-        }
-        for (long i = nv * L + blockIdx.x * long(kBlock) + threadIdx.x; i < n; i += long(gridDim.x) * kBlock) {      // (n is a multiple of 192: empty)
-            const S wn = w[i] - h * vk[i];
-            w[i] = wn;
-            acc[0] += double(vnext ? vnext[i] : wn) * double(wn);
-        }
-    } else
-    for (long i = blockIdx.x * long(kBlock) + threadIdx.x; i < n; i += long(gridDim.x) * kBlock) {
-        const S wn = w[i] - h * vk[i];
-        w[i] = wn;
-        if (mask[i % nbp]) acc[0] += double(vnext ? vnext[i] : wn) * double(wn);
-    }
-    __syncthreads();
-    block_sum<1>(acc, sm);
-    if (threadIdx.x == 0) parts_out[blockIdx.x] = acc[0];
-}
-// ---- decomposed runs: classical Gram-Schmidt.  Modified Gram-Schmidt (dune's, above) projects on v_0 .. v_i one after the other and
-// needs an all-reduce per projection -- i + 2 sequential ones in column i, ~13 us each over RCCL.  Here all projections of a column are
-// taken from the SAME w (one kernel, one all-reduce of i + 1 scalars), then subtracted together, then the norm of what is left (a second
-// all-reduce): 2 per column.  A different rounding path than the reference's -- used only where the preconditioner is decomposed anyway;
-// one GPU keeps dune's order (parity with the oracle's restatement).  The columns of a CPR solve are few (~4), so the weaker
-// orthogonality of the classical form does not show (OPMGPU_GMRES_CGS=0: modified Gram-Schmidt also when decomposed).
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_gm_multidot(long n, int nbp, const int8_t* __restrict__ mask, int cnt, const S* __restrict__ kry, const S* __restrict__ w,
-                                                        double* __restrict__ parts, const SolveCtl* __restrict__ ctl)
-{
-    __shared__ double sm[32];
-    if (ctl->done) return;
-    // slot cnt: the owned part of ||w||^2 -- with the projections h_k of an orthonormal basis, ||w - sum h_k v_k||^2 = ||w||^2 - sum h_k^2
-    // (Pythagoras), so the column's norm needs no second all-reduce (k_gm_cgs_update decides whether the difference is trustworthy)
-    for (int k0 = 0; k0 < cnt + 1; k0 += 8) {
-        double acc[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
-        const int nk = cnt + 1 - k0 < 8 ? cnt + 1 - k0 : 8;
-        for (long i = blockIdx.x * long(kBlock) + threadIdx.x; i < n; i += long(gridDim.x) * kBlock) {
-            if (mask && !mask[i % nbp]) continue;
-            const double wi = double(w[i]);
-#pragma unroll
-            for (int u = 0; u < 8; ++u) if (u < nk) acc[u] += wi * ((k0 + u < cnt) ? double(kry[long(k0 + u) * n + i]) : wi);
-        }
-        block_sum<8>(acc, sm);
-        if (threadIdx.x == 0) for (int u = 0; u < nk; ++u) parts[long(k0 + u) * gridDim.x + blockIdx.x] = acc[u];
-        __syncthreads();
-    }
-}
-__global__ __launch_bounds__(kBlock) void k_sum_partials_multi(const double* __restrict__ parts, int np, double* __restrict__ out, const SolveCtl* __restrict__ ctl)
-{
-    __shared__ double sm[12];
-    if (ctl->done) return;
-    const double* const arr[1] = { parts + long(blockIdx.x) * np };
-    double s[1];
-    reduce_partials<1>(arr, np, s, sm);
-    if (threadIdx.x == 0) out[blockIdx.x] = s[0];
-}
-// w -= sum_k h_k v_k with the all-reduced h; column i of H; partial sums of the owned part of ||w||^2
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_gm_cgs_update(long n, int nbp, const int8_t* __restrict__ mask, int cnt, int m, int col, const double* __restrict__ h,
-                                                          double* __restrict__ H, const S* __restrict__ kry, S* __restrict__ w, double* __restrict__ parts_out,
-                                                          const SolveCtl* __restrict__ ctl, double* __restrict__ pyth = nullptr)
-{
-    __shared__ double sm[8];
-    __shared__ S hs[64];
-    if (ctl->done) return;
-    for (int k = threadIdx.x; k < cnt; k += kBlock) { hs[k] = S(h[k]); if (blockIdx.x == 0) H[k * m + col] = h[k]; }
-    if (pyth && blockIdx.x == 0 && threadIdx.x == 0) {
-        // ||w_new||^2 = ||w||^2 - sum h_k^2 from the all-reduced numbers (h[cnt] = ||w||^2).  The difference loses relative accuracy as
-        // w falls into the span of the basis -- eps ||w||^2 / rest, i.e. ~1 % at rest = 1e-5 ||w||^2 with float vectors -- which is the
-        // column that ends the solve: its entry only feeds the residual estimate |s_{i+1}|, a 1 % error there moves no stopping decision.
-        // (A lucky breakdown, rest <= 0 by rounding, is clamped: the estimate becomes ~0 and the solve stops.)
-        double s2 = 0.0;
-        for (int k = 0; k < cnt; ++k) s2 += h[k] * h[k];
-        const double rest = h[cnt] - s2;
-        pyth[0] = rest > 1e-28 * h[cnt] ? rest : 1e-28 * h[cnt];
-    }
-    __syncthreads();
-    double acc[1] = { 0.0 };
-    for (long i = blockIdx.x * long(kBlock) + threadIdx.x; i < n; i += long(gridDim.x) * kBlock) {
-        S v = w[i];
-        for (int k = 0; k < cnt; ++k) v -= hs[k] * kry[long(k) * n + i];
-        w[i] = v;
-        if (!mask || mask[i % nbp]) acc[0] += double(v) * double(v);
-    }
-    block_sum<1>(acc, sm);
-    if (threadIdx.x == 0) parts_out[blockIdx.x] = acc[0];
-}
-// vout = w / ||w|| with ||w||^2 in parts; slot >= 0: H[slot] = ||w|| (breakdown flag if ~0); slot < 0: the restart normalisation,
-// s[0] = ||w|| and, at the very first one (first != 0), the convergence threshold
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_gm_normalize(long n, int slot, int first, double red, const double* __restrict__ parts, int np,
-                                                         double* __restrict__ H, double* __restrict__ s0, const S* __restrict__ w, S* __restrict__ vout,
-                                                         SolveCtl* __restrict__ ctl, SolveCtl* __restrict__ hst)
-{
-    __shared__ double sm[12];
-    if (ctl->done) return;
-    const double* const arr[1] = { parts };
-    double s[1];
-    reduce_partials<1>(arr, np, s, sm);
-    const double nrm = sqrt(s[0]);
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        if (slot >= 0) H[slot] = nrm; else { s0[0] = nrm; ctl->norm2 = s[0]; }
-        if (first) { ctl->norm0_2 = s[0]; ctl->norm2 = s[0]; ctl->thresh2 = red * red * s[0]; }
-    }
-    if (!(nrm == nrm) || nrm < 1e-80) {
-        if (blockIdx.x == 0 && threadIdx.x == 0) {
-            if (first && nrm == nrm) { ctl->iters = 0; ctl->done = 1; }            // zero right-hand side: converged at once
-            else { ctl->flag = 2; ctl->done = 1; }                                   // breakdown in GMRes - |w| == 0
-            publish(ctl, hst);
-        }
-        return;
-    }
-    const S inv = S(1.0 / nrm);
-    constexpr int L = 16 / sizeof(S);
-    struct alignas(16) Pack { S v[L]; };
-    const long nv = n / L;
-    for (long q = blockIdx.x * long(kBlock) + threadIdx.x; q < nv; q += long(gridDim.x) * kBlock) {
-        Pack a = reinterpret_cast<const Pack*>(w)[q];
-#pragma unroll
-        for (int u = 0; u < L; ++u) a.v[u] *= inv;
-        reinterpret_cast<Pack*>(vout)[q] = a;
-    }
-    for (long i = nv * L + blockIdx.x * long(kBlock) + threadIdx.x; i < n; i += long(gridDim.x) * kBlock) vout[i] = w[i] * inv;
-}
-// column i of the Hessenberg matrix: previous rotations, new rotation (dune generatePlaneRotation / applyPlaneRotation), |s[i+1]|
-__global__ void k_gm_givens(int i, int m, int j, GmState g, SolveCtl* __restrict__ ctl, SolveCtl* __restrict__ hst, int* __restrict__ tick_ptr = nullptr, int tick = 0)
-{
-    if (ctl->done) { publish(ctl, hst); if (tick_ptr) { __threadfence_system(); *(volatile int*)tick_ptr = tick; } return; }
-    double* H = g.H;
-    auto rot = [](double& dx, double& dy, double c, double sN) { const double t = c * dx + sN * dy; dy = -sN * dx + c * dy; dx = t; };
-    for (int k = 0; k < i; ++k) rot(H[k * m + i], H[(k + 1) * m + i], g.cs[k], g.sn[k]);
-    const double dx = H[i * m + i], dy = H[(i + 1) * m + i];
-    const double ndx = fabs(dx), ndy = fabs(dy);
-    double c, sN;
-    if (ndy < 1e-15) { c = 1.0; sN = 0.0; }
-    else if (ndx < 1e-15) { c = 0.0; sN = 1.0; }
-    else if (ndy > ndx) { const double t = ndx / ndy; c = 1.0 / sqrt(1.0 + t * t); sN = c; c *= t; sN *= dx / ndx; sN *= dy / ndy; }
-    else { const double t = ndy / ndx; c = 1.0 / sqrt(1.0 + t * t); sN = c * (dy / dx); }
-    g.cs[i] = c; g.sn[i] = sN;
-    rot(H[i * m + i], H[(i + 1) * m + i], c, sN);
-    rot(g.s[i], g.s[i + 1], c, sN);
-    const double nrm = fabs(g.s[i + 1]);
-    ctl->norm2 = nrm * nrm;
-    ctl->iters = j;
-    if (nrm * nrm < ctl->thresh2) { ctl->done = 1; ctl->decided = j; }
-    publish(ctl, hst);
-    if (tick_ptr) { __threadfence_system(); *(volatile int*)tick_ptr = tick; }      // the host spins on this word instead of synchronising the stream (wait_tick)
-}
-// y = R^-1 s (back-substitution over the first cnt columns)
-__global__ void k_gm_solve_y(int cnt, int m, GmState g)
-{
-    for (int a = cnt - 1; a >= 0; --a) {
-        double rhs = g.s[a];
-        for (int b = a + 1; b < cnt; ++b) rhs -= g.H[a * m + b] * g.y[b];
-        g.y[a] = rhs / g.H[a * m + a];
-    }
-}
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_gm_update_x(long n, int cnt, const double* __restrict__ y, const S* __restrict__ kry, S* __restrict__ x)
-{
-    constexpr int L = 16 / sizeof(S);              // 16-byte lanes (n is a multiple of 192)
-    struct alignas(16) Pack { S v[L]; };
-    const long nv = n / L;
-    Pack* __restrict__ x4 = reinterpret_cast<Pack*>(x);
-    for (long q = blockIdx.x * long(kBlock) + threadIdx.x; q < nv; q += long(gridDim.x) * kBlock) {
-        Pack acc;
-#pragma unroll
-        for (int u = 0; u < L; ++u) acc.v[u] = 0;
-        for (int a = cnt - 1; a >= 0; --a) {                                            // the order of dune's update(): a = i-1 .. 0
-            const Pack k4 = reinterpret_cast<const Pack*>(kry + long(a) * n)[q];
-            const S ya = S(y[a]);
-#pragma unroll
-            for (int u = 0; u < L; ++u) acc.v[u] += ya * k4.v[u];
-        }
-        Pack xv = x4[q];
-#pragma unroll
-        for (int u = 0; u < L; ++u) xv.v[u] += acc.v[u];
-        x4[q] = xv;
-    }
-    for (long i = nv * L + blockIdx.x * long(kBlock) + threadIdx.x; i < n; i += long(gridDim.x) * kBlock) {
-        S acc = 0;
-        for (int a = cnt - 1; a >= 0; --a) acc += S(y[a]) * kry[long(a) * n + i];
-        x[i] += acc;
-    }
-}
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_gm_defect(long n, const S* __restrict__ b, const S* __restrict__ ax, S* __restrict__ out)
-{
-    for (long i = blockIdx.x * long(kBlock) + threadIdx.x; i < n; i += long(gridDim.x) * kBlock) out[i] = b[i] - ax[i];
-}
-__global__ void k_gm_reset_s(int m, GmState g) { for (int i = 1; i < m + 1; ++i) g.s[i] = 0.0; }
-// opmgpu_params.gmres_verify_residual: left-preconditioned GMRES stops on || M^-1 (b - A x) ||; before the solve is reported as converged
-// the TRUE defect r = b - A x is formed (the vector a restart would start from anyway) together with the owned parts of ||r||^2 and ||b||^2
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_gm_defect_norms(long n, int nbp, const int8_t* __restrict__ mask, const S* __restrict__ b, const S* __restrict__ ax,
-                                                            S* __restrict__ out, double* __restrict__ parts_r, double* __restrict__ parts_b)
-{
-    __shared__ double sm[8];
-    double acc[2] = { 0.0, 0.0 };
-    for (long i = blockIdx.x * long(kBlock) + threadIdx.x; i < n; i += long(gridDim.x) * kBlock) {
-        const S bi = b[i], r = bi - ax[i];
-        out[i] = r;
-        if (!mask || mask[i % nbp]) { acc[0] += double(r) * double(r); acc[1] += double(bi) * double(bi); }
-    }
-    block_sum<2>(acc, sm);
-    if (threadIdx.x == 0) { parts_r[blockIdx.x] = acc[0]; parts_b[blockIdx.x] = acc[1]; }
-}
-// verdict of the check: ||r|| <= reduction ||b|| keeps `done`; otherwise the iteration goes on from r with the threshold on the
-// preconditioned residual lowered by the factor the true residual missed its target by (and a safety factor of 2).  vr[0] = ||r||^2 / ||b||^2.
-__global__ __launch_bounds__(kBlock) void k_gm_verify(const double* __restrict__ parts_r, const double* __restrict__ parts_b, int np, double red, double* __restrict__ vr,
-                                                      SolveCtl* __restrict__ ctl, SolveCtl* __restrict__ hst, int* __restrict__ tick_ptr, int tick)
-{
-    __shared__ double sm[12];
-    const double* const arr[2] = { parts_r, parts_b };
-    double s[2];
-    reduce_partials<2>(arr, np, s, sm);
-    if (threadIdx.x == 0) {
-        const double ratio2 = s[1] > 0.0 ? s[0] / s[1] : 0.0;
-        vr[0] = ratio2;
-        if (ratio2 == ratio2 && ratio2 > red * red) {
-            ctl->done = 0;
-            ctl->thresh2 = ctl->norm2 * (red * red / ratio2) * 0.25;
-        } else if (ratio2 == ratio2) ctl->norm2 = ratio2 * ctl->norm0_2;      // the reported reduction is then the TRUE one (what BiCGStab's means)
-        publish(ctl, hst);
-        if (tick_ptr) { __threadfence_system(); *(volatile int*)tick_ptr = tick; }
-    }
-}
-
-template <class S> SolveResult LinSolver::gmres(const opmgpu_params& prm)
-{
-    SolveResult res;
-    // multi-GPU: the basis vector is halo-exchanged before every product (ghost rows of the product are zero, like in bicgstab), the
-    // projections are owner-masked dot products whose partial arrays are collapsed and all-reduced before the axpy reads them: one small
-    // all-reduce per projection + one for the norm with dune's modified Gram-Schmidt (j + 2 in iteration j of a cycle), two per iteration with
-    // the classical form that decomposed runs use by default (k_gm_multidot; a CPR solve takes ~4 iterations).  Every rank sees
-    // the same Hessenberg matrix, so the Givens / convergence decisions and the final combination are identical everywhere, and the
-    // ghost entries of x are the owners' entries bit for bit (they are the same combination of exchanged basis vectors).
-    const int8_t* mask = comm ? comm->owner_mask() : nullptr;
-    SolverWork<S>& w = work<S>();
-    const long n = long(3) * plan.nbp;
-    const int gv = std::min(grid_for(n), kMaxPart);
-    const int m = std::max(1, int(prm.linear_solver_restart));
-    const int maxit = prm.linear_solver_maxiter;
-    const bool cpr = prm.use_cpr != 0;
-    // the GMRES option keeps the pressure hierarchy fresh for every matrix (it is the reference's robustness fallback); OPMGPU_GMRES_LAG=1
-    // applies the lag policy of the BiCGStab path (cpr_prepare) -- measured: no gain on the 5-spot deck
-    static const bool gm_lag = std::getenv("OPMGPU_GMRES_LAG") && std::atoi(std::getenv("OPMGPU_GMRES_LAG")) != 0;
-    lag_allowed = gm_lag && prm.linear_solver_reduction >= 1e-4;
-    const bool mx = mixed && sizeof(S) == 8;
-    if (cpr) { if (mx) cpr_prepare_mixed(); else cpr_prepare<S>(); }
-    if (factor_deferred) { factor_deferred = false; if (mx) factor_async<float>(); else factor_async<S>(); }
-    // one post-smoothing sweep on level 0 instead of two: measured over nine decks with wells +1..+5 % under GMRES (the same iteration
-    // counts within 0.1, a cheaper cycle), -7..0 % under BiCGStab on the well-free decks (profiles/r02_amg_sweep_gmres.log)
-    if (cpr) { if (mx) { if (!wf.amg->npost0_user) wf.amg->npost0 = 1; } else if (!w.amg->npost0_user) w.amg->npost0 = 1; }
-    w.kry.alloc(size_t(m + 1) * n);
-    // newton_use_gmres = 2: flexible (right-preconditioned) GMRES -- z_i = M^-1 v_i is KEPT, w = A z_i is orthogonalised, x += sum y_i z_i.
-    // Not the reference's solver: Dune's RestartedGMResSolver (value 1) applies M from the left, which costs one application more per
-    // solve (M^-1 b before the first column; a CPR solve has ~4 columns) and stops on the PRECONDITIONED residual; this form stops on the
-    // true residual, the criterion of the reference's default BiCGStab.  One more basis of m vectors in memory.
-    const bool flex = prm.newton_use_gmres == 2;
-    wb_active = true;
-    // gmres_verify_residual: the flexible form measures the true residual itself
-    const bool verify = prm.gmres_verify_residual != 0 && !flex;
-    bool verified = false;
-    int verify_rounds = 0;
-    static const bool cgs_on = !(std::getenv("OPMGPU_GMRES_CGS") && std::atoi(std::getenv("OPMGPU_GMRES_CGS")) == 0);
-    // OPMGPU_GMRES_CGS=2 (experiment): the classical form on ONE GPU too (fewer passes over the basis per column; a different rounding
-    // path than dune's modified Gram-Schmidt, which one GPU keeps by default)
-    static const bool cgs_single = std::getenv("OPMGPU_GMRES_CGS") && std::atoi(std::getenv("OPMGPU_GMRES_CGS")) == 2;
-    const bool cgs = (comm != nullptr || cgs_single) && cgs_on && m <= 63;
-    if (cgs) cgs_parts.alloc(size_t(m + 2) * gv + size_t(m + 2));
-    // Decomposed, classical Gram-Schmidt: the halo of the vector a column ends with travels WITH the all-reduce of its projections (one
-    // fused operation, CommBase::allreduce_sum_halo_*): w = M^-1 A v_i gets its ghost entries from the owners, the update w -= sum h_k v_k
-    // and the normalisation run over ghost rows too (the basis vectors' ghost entries are the owners' values by induction), so v_{i+1} needs
-    // no exchange of its own before the next product -- one latency per column less, and one at the start (the first vector's halo rides on
-    // the all-reduce of its norm).  A/B: OPMGPU_GMRES_FUSE_HALO=0
-    static const bool fuse_env = !(std::getenv("OPMGPU_GMRES_FUSE_HALO") && std::atoi(std::getenv("OPMGPU_GMRES_FUSE_HALO")) == 0);
-    const bool fuse_halo = comm != nullptr && cgs && fuse_env && !flex;
-    cs_fused_post = fuse_halo && cs_fused_env;
-    // The column's norm by Pythagoras (one all-reduce per column) -- for the loose reductions of Newton solves only (>= 1e-4, a handful of
-    // columns): the identity needs an orthonormal basis, and classical Gram-Schmidt loses orthogonality as the columns add up -- at a
-    // 1e-10 reduction (~20 columns) the decomposed runs left the single-domain Newton path with it (tests/test_gpu_dist_shm.py, cpr_gmres),
-    // with the explicit norm (a second all-reduce) they do not.  OPMGPU_GMRES_PYTH=0: always the explicit norm.
-    static const bool cgs_pyth_env = !(std::getenv("OPMGPU_GMRES_PYTH") && std::atoi(std::getenv("OPMGPU_GMRES_PYTH")) == 0);
-    const bool cgs_pyth = cgs_pyth_env && prm.linear_solver_reduction >= 1e-4;
-    if (flex) w.kryz.alloc(size_t(m) * n);
-    gmbuf.alloc(size_t(m + 1) * m + (m + 1) + 3 * m + 8);
-    gmbuf.zero(stream);
-    GmState g; g.H = gmbuf.p; g.s = g.H + size_t(m + 1) * m; g.cs = g.s + (m + 1); g.sn = g.cs + m; g.y = g.sn + m;
-    double* parts = partials.p;
-    double* parts2 = partials.p + npart;                             // second partial array: producer and consumer of a fused step differ
-    double* red1 = partials.p + size_t(6) * npart;                   // the all-reduced scalar of a projection (multi-GPU)
-    SolveCtl* d_ctl = ctl.p;
-    // <a, b> into a partial array the consumer kernels re-reduce: np entries on one GPU, one all-reduced entry otherwise
-    const double* dot_arr = parts; int dot_np = gv;
-    auto dot = [&](const S* a_, const S* b_) {
-        if (!comm) { hipLaunchKernelGGL((k_dot<S>), dim3(gv), dim3(kBlock), 0, stream, n, a_, b_, parts); dot_arr = parts; dot_np = gv; return; }
-        hipLaunchKernelGGL((k_dot_owned<S>), dim3(gv), dim3(kBlock), 0, stream, n, plan.nbp, mask, a_, b_, parts);
-        hipLaunchKernelGGL((k_sum_partials<1>), dim3(1), dim3(kBlock), 0, stream, (const double*)parts, (const double*)nullptr, gv, red1);
-        comm->allreduce_sum(red1, 1, stream);
-        dot_arr = red1; dot_np = 1;
-    };
-    auto product = [&](S* vin, S* out, const SolveCtl* c, bool exchange = true) {          // out = A vin (vin's ghost entries refreshed first unless they are current)
-        if (comm && exchange) halo<S>(comm, vin, stream);
-        lowrank_reduce<S>(vin, c);
-        hipLaunchKernelGGL((k_spmv<S, 0>), dim3(std::min(grid8_for(plan.nb), 4 * kMaxPart)), dim3(kBlock), 0, stream, xcd_mode(), plan.nb, plan.nbp,
-                           dp.slice_ptr.p, dp.col.p, matrix<S>(), (const S*)vin, out, (const S*)nullptr, mask, c,
-                           (double*)nullptr, (double*)nullptr, (const S*)nullptr, (const S*)nullptr, 0, S(0), lowrank, (const int8_t*)nullptr);
-    };
-    auto V = [&](int k) { return w.kry.p + size_t(k) * n; };
-    auto precond = [&](const S* d, S* out) { precond_apply<S>(d, out, prm.ilu_relaxation, d_ctl, cpr); };
-    auto Z = [&](int k) { return w.kryz.p + size_t(k) * n; };
-    auto normalize_start = [&](S* src, int first) {          // v0 = src / ||src||, s[0] = ||src||  (src = M^-1 defect, flexible: the defect)
-        if (fuse_halo) {        // ||src||^2 over the owned rows and src's halo in one operation: v0 then carries the owners' ghost values
-            hipLaunchKernelGGL((k_dot_owned<S>), dim3(gv), dim3(kBlock), 0, stream, n, plan.nbp, mask, (const S*)src, (const S*)src, parts);
-            hipLaunchKernelGGL((k_sum_partials<1>), dim3(1), dim3(kBlock), 0, stream, (const double*)parts, (const double*)nullptr, gv, red1);
-            allreduce_halo(comm, red1, 1, src, stream);
-            dot_arr = red1; dot_np = 1;
-        } else
-        dot(src, src);
-        hipLaunchKernelGGL((k_gm_normalize<S>), dim3(gv), dim3(kBlock), 0, stream, n, -1, first, prm.linear_solver_reduction, dot_arr, dot_np,
-                           g.H, g.s, src, V(0), d_ctl, h_ctl_dev);
-        hipLaunchKernelGGL(k_gm_reset_s, dim3(1), dim3(1), 0, stream, m, g);
-    };
-    // x0 = 0: defect = b
-    w.x.zero(stream);
-    hipLaunchKernelGGL(k_ctl_init, dim3(1), dim3(1), 0, stream, d_ctl, h_ctl_dev, prm.linear_solver_reduction);
-    if (flex) normalize_start(w.b.p, 1);
-    else { precond(w.b.p, w.t.p); normalize_start(w.t.p, 1); }
-    // no synchronisation here: the first iteration is enqueued behind the set-up (factorisation, hierarchy, first application); a zero
-    // defect sets `done` on the device, the iteration's kernels then return at once and its status check reports 0 iterations
-    int j = 1;
-    bool stop = false;
-    // the next iteration's product is enqueued BEFORE the host waits for this iteration's verdict (v_{i+1} is complete once k_gm_normalize
-    // ran; if the verdict is "converged" the product's kernels see `done` and return): the device starts on it while the host is still
-    // reading the status word and enqueueing the rest.  Measured +0.4 % (inside the run-to-run noise), and every solve ends with one such
-    // launch that returns at once, which drags the profiler's per-kernel average of the SpMV away from its real duration: off by default
-    // (OPMGPU_GMRES_SPECULATE=1 switches it on)
-    static const bool speculate = std::getenv("OPMGPU_GMRES_SPECULATE") && std::atoi(std::getenv("OPMGPU_GMRES_SPECULATE")) != 0;
-    while (j <= maxit && !stop) {
-        int i = 0, cycle_misses = 0;
-        bool product_enqueued = false;
-        for (; i < m && j <= maxit && !stop; ++i, ++j) {
-            hipEvent_t kt_a;
-            if (flex) {
-                precond(V(i), Z(i));                                   // z_i = M^-1 v_i
-                kt_a = kt.begin();
-                product(Z(i), w.t.p, (const SolveCtl*)d_ctl);          // w = A z_i
-                kt.end(KT_SPMV1, kt_a);
-            } else {
-                if (!product_enqueued) {
-                    kt_a = kt.begin();
-                    product(V(i), w.v.p, (const SolveCtl*)d_ctl, !fuse_halo);
-                    kt.end(KT_SPMV1, kt_a);
-                }
-                product_enqueued = false;
-                precond(w.v.p, w.t.p);                                 // w = M^-1 A v_i
-            }
-            kt_a = kt.begin();
-            if (cgs) {
-                // decomposed: classical Gram-Schmidt, two all-reduces per column (k_gm_multidot)
-                const int cnt = i + 1;
-                hipLaunchKernelGGL((k_gm_multidot<S>), dim3(gv), dim3(kBlock), 0, stream, n, plan.nbp, mask, cnt, (const S*)w.kry.p, (const S*)w.t.p, cgs_parts.p, (const SolveCtl*)d_ctl);
-                double* hsum = cgs_parts.p + size_t(m + 2) * gv;              // cnt projections + ||w||^2, all-reduced together
-                hipLaunchKernelGGL(k_sum_partials_multi, dim3(cnt + 1), dim3(kBlock), 0, stream, (const double*)cgs_parts.p, gv, hsum, (const SolveCtl*)d_ctl);
-                if (comm) { if (fuse_halo && !flex) allreduce_halo(comm, hsum, cnt + 1, w.t.p, stream); else comm->allreduce_sum(hsum, cnt + 1, stream); }
-                double* pyth = cgs_pyth ? g.y + m + 2 : (double*)nullptr;    // norm^2 of what is left, by Pythagoras
-                hipLaunchKernelGGL((k_gm_cgs_update<S>), dim3(gv), dim3(kBlock), 0, stream, n, plan.nbp, mask, cnt, m, i, (const double*)hsum, g.H,
-                                   (const S*)w.kry.p, w.t.p, parts, (const SolveCtl*)d_ctl, pyth);
-                if (cgs_pyth) { dot_arr = pyth; dot_np = 1; }          // one all-reduce per column: the norm of what is left comes from Pythagoras
-                else if (!comm) { dot_arr = parts; dot_np = gv; }
-                else {
-                    hipLaunchKernelGGL((k_sum_partials<1>), dim3(1), dim3(kBlock), 0, stream, (const double*)parts, (const double*)nullptr, gv, red1);
-                    comm->allreduce_sum(red1, 1, stream);
-                    dot_arr = red1; dot_np = 1;
-                }
-            } else {
-            // modified Gram-Schmidt, each step's update fused with the next step's projection (k_gm_axpy_dot)
-            dot((const S*)V(0), (const S*)w.t.p);
-            for (int k = 0; k <= i; ++k) {
-                double* out = (dot_arr == parts) ? parts2 : parts;
-                hipLaunchKernelGGL((k_gm_axpy_dot<S>), dim3(gv), dim3(kBlock), 0, stream, n, plan.nbp, mask, k * m + i, dot_arr, dot_np, g.H, (const S*)V(k), w.t.p,
-                                   k < i ? (const S*)V(k + 1) : (const S*)nullptr, out, (const SolveCtl*)d_ctl);
-                if (!comm) { dot_arr = out; dot_np = gv; }
-                else {
-                    hipLaunchKernelGGL((k_sum_partials<1>), dim3(1), dim3(kBlock), 0, stream, (const double*)out, (const double*)nullptr, gv, red1);
-                    comm->allreduce_sum(red1, 1, stream);
-                    dot_arr = red1; dot_np = 1;
-                }
-            }
-            }
-            hipLaunchKernelGGL((k_gm_normalize<S>), dim3(gv), dim3(kBlock), 0, stream, n, (i + 1) * m + i, 0, 0.0, dot_arr, dot_np, g.H, g.s,
-                               (const S*)w.t.p, V(i + 1), d_ctl, h_ctl_dev);
-            const int tick = ++tick_seq;
-            hipLaunchKernelGGL(k_gm_givens, dim3(1), dim3(1), 0, stream, i, m, j, g, d_ctl, h_ctl_dev, poll_status ? h_tick_dev : (int*)nullptr, tick);
-            kt.end(KT_VECTOR, kt_a);
-            if (speculate && !flex && i + 1 < m && j + 1 <= maxit) {
-                kt_a = kt.begin();
-                product(V(i + 1), w.v.p, (const SolveCtl*)d_ctl, !fuse_halo);
-                kt.end(KT_SPMV1, kt_a);
-                product_enqueued = true;
-            }
-            wait_tick(tick);
-            if (h_ctl->done) stop = true;
-            if (stop && verify && h_ctl->flag == 0 && h_ctl->iters > 0) {
-                // gmres_verify_residual: the preconditioned residual met the threshold -- does the true one?  The candidate x + V y of the
-                // i + 1 completed columns goes into a scratch vector (x itself is only updated when the cycle ends), one product, one pass
-                // for || b - A xt ||^2 and || b ||^2.  If it misses the target, `done` is taken back, the threshold on the preconditioned
-                // residual is lowered in proportion, and the SAME cycle goes on with its next column: the Krylov space is kept.
-                const int cnt = i + 1;
-                hipLaunchKernelGGL(k_gm_solve_y, dim3(1), dim3(1), 0, stream, cnt, m, g);
-                OPMGPU_HIP(hipMemcpyAsync(w.y.p, w.x.p, size_t(n) * sizeof(S), hipMemcpyDeviceToDevice, stream));
-                hipLaunchKernelGGL((k_gm_update_x<S>), dim3(gv), dim3(kBlock), 0, stream, n, cnt, (const double*)g.y, (const S*)w.kry.p, w.y.p);
-                product(w.y.p, w.p.p, (const SolveCtl*)nullptr);
-                hipLaunchKernelGGL((k_gm_defect_norms<S>), dim3(gv), dim3(kBlock), 0, stream, n, plan.nbp, mask, (const S*)w.b.p, (const S*)w.p.p, w.r.p, parts, parts2);
-                const double* pr = parts; const double* pb = parts2; int np_v = gv;
-                if (comm) {
-                    hipLaunchKernelGGL((k_sum_partials<2>), dim3(1), dim3(kBlock), 0, stream, (const double*)parts, (const double*)parts2, gv, red1);
-                    comm->allreduce_sum(red1, 2, stream);
-                    pr = red1; pb = red1 + 1; np_v = 1;
-                }
-                const int vtick = ++tick_seq;
-                hipLaunchKernelGGL(k_gm_verify, dim3(1), dim3(kBlock), 0, stream, pr, pb, np_v, prm.linear_solver_reduction, g.y + m, d_ctl, h_ctl_dev,
-                                   poll_status ? h_tick_dev : (int*)nullptr, vtick);
-                wait_tick(vtick);
-                verified = true;
-                if (!h_ctl->done) {
-                    stop = false; ++verify_rounds;
-                    product_enqueued = false;          // (OPMGPU_GMRES_SPECULATE: the next column's product was enqueued while `done` was up and returned at once)
-                    // a second miss in the same cycle (the first already with float vectors, whose Arnoldi estimate keeps falling while
-                    // b - A x does not: measured on the 1 M-cell deck, in-cycle continuation never reached 1e-5 there): the recurrence's
-                    // estimate has drifted from the real defect -- end the cycle here and restart from the true defect, which the restart
-                    // path forms from the updated x (iterative refinement)
-                    if (++cycle_misses >= (sizeof(S) == 4 ? 1 : 2)) { ++i; ++j; break; }      // (float vectors: refine at the first miss)
-                }
-            }
-        }
-        if (h_ctl->flag != 0) break;                                   // breakdown: dune throws, no update
-        if (h_ctl->done && h_ctl->iters == 0) break;                   // zero defect: x = 0 is the solution, no column was built
-        // x += sum_a y_a v_a with R y = s   (i columns were completed)
-        hipLaunchKernelGGL(k_gm_solve_y, dim3(1), dim3(1), 0, stream, i, m, g);
-        hipLaunchKernelGGL((k_gm_update_x<S>), dim3(gv), dim3(kBlock), 0, stream, n, i, (const double*)g.y, flex ? (const S*)w.kryz.p : (const S*)w.kry.p, w.x.p);
-        if (!stop && j <= maxit) {                                     // restart from the true defect
-            product(w.x.p, w.v.p, (const SolveCtl*)nullptr);
-            hipLaunchKernelGGL((k_gm_defect<S>), dim3(gv), dim3(kBlock), 0, stream, n, (const S*)w.b.p, (const S*)w.v.p, w.r.p);
-            if (flex) normalize_start(w.r.p, 0);
-            else { precond(w.r.p, w.t.p); normalize_start(w.t.p, 0); }
-        }
-    }
-    // the status block is current (the last iteration's tick was waited for); what is still in flight (the combination of the basis
-    // vectors into x) is ordered before everything the caller enqueues next on this stream.  Without polling: synchronise.
-    if (!poll_status || !stop) OPMGPU_HIP(hipStreamSynchronize(stream));
-    if (comm) comm->check_async();
-    const double norm0 = std::sqrt(h_ctl->norm0_2), norm = std::sqrt(h_ctl->norm2);
-    res.converged = h_ctl->done && h_ctl->flag == 0;
-    res.iterations = (h_ctl->done && h_ctl->flag == 0) ? h_ctl->iters : j - 1;
-    res.reduction = norm0 > 0 ? norm / norm0 : 0.0;
-    (void)verified;
-    last_verify_rounds = verify_rounds;
-    if (h_ctl->flag != 0 || !(norm0 == norm0)) {
-        res.status = OPMGPU_EBREAKDOWN;
-        char buf[160];
-        std::snprintf(buf, sizeof buf, "breakdown in GMRes (%s; column %d, ||M^-1 r0|| = %.3e)", !(norm0 == norm0) ? "non-finite initial defect" : (h_ctl->flag == 2 ? "|w| == 0" : "non-finite Hessenberg entry"), j, norm0);
-        breakdown_note = buf;
-    }
-    else if (!res.converged && !prm.ignore_convergence_failure) res.status = OPMGPU_ELINSOLVE;
-    last_its = res.iterations;              // the back-off of the lag policy, as at the end of bicgstab (see cpr_prepare)
-    if (refreshed) its_ref = res.iterations;
-    else if (coarse_lag == 1 && last_its > its_ref + std::max(1, its_ref / 4)) lag_block = 8;
-    return res;
-}
+#include "krylov.inl"
 
 template <class S> void LinSolver::vec_in(const double* dsrc, int layout, S* d)
 {

@@ -177,8 +177,6 @@ public:
     bool ref_transformed = false;      // the resident matrix is L A (reset by whoever writes a new matrix)
     const void* border_weights = nullptr;   // weights of the bordered pressure column when cprw are the transformed system's unit weights
     double border_colscale = 1.0;
-    // coarse-correction factors of the pressure cycle chosen for THIS matrix on the first right-hand side it sees (see cpr_tune)
-    template <class S> void cpr_tune();
     // The scaling of the coarse-grid corrections, chosen per TIME STEP by what it does to the iteration counts (DESIGN sections 4b, 11): two
     // settings; a whole time step runs under one of them and is scored by its linear iterations per Newton iteration (one solve's count
     // follows the Newton iteration's index more than the setting -- round 3's first, per-solve form of this policy was misled by that);
@@ -207,7 +205,6 @@ public:
     } corr_policy;
     void correction_policy_choose();
     void correction_policy_report(int iterations, bool converged);
-    bool amg_autotune = false;      // OPMGPU_AMG_AUTOTUNE=1: experiment, measured NOT robust; default: 1.9 (2.2 into level 0 on one well-free subdomain)
     // x0 = 0; rhs in work<S>().b; solution in work<S>().x
     // opmgpu_params.cpr_reference_transform = 2 (pointilu.inl): the reference's second stage under CPR, a POINT ILU0 of the transformed system as
     // a scalar equation-major matrix, on its own sparsity plan
@@ -353,15 +350,6 @@ public:
     // carried by the BiCGStab recurrences (it is linear in the vector), so only <W_b, A y> has to be summed over the ranks -- together
     // with the scalar products the iteration all-reduces anyway: 3 all-reduces per iteration instead of 5.  A/B: OPMGPU_CS_RECUR=0.
     bool cs_recur = true;
-    // Decomposed GMRES (fused halo operations on): the coarse space's correction moves BEHIND the cycle -- x_p = x + P A_c^-1 R (b - A_p x)
-    // with x = Vcycle(b), still multiplicative -- so that its restricted residual is all-reduced TOGETHER with the halo exchange of x (one
-    // fused operation instead of an all-reduce before the cycle and an exchange after it); costs one residual pass over A_p per application.
-    // MEASURED, NOT ADOPTED (profiles/r04_j_dist_ab.log, r04_i_dist_ab.log): the correction behind the cycle leaves the jumps of the subdomain
-    // constants to stage 2 instead of letting the cycle smooth them -- 12 -> 18 columns on the 2-rank test deck (14.8 operations per Newton
-    // iteration against 15.8: the saved latencies are spent on extra columns), SPE10-like 23.4 -> 25.7 iterations per solve; the additive
-    // form x + P A_c^-1 R b (no residual pass) is unusable: 4 ranks 9.0 -> 13.9 iterations per solve with chopped time steps.
-    // Off by default; OPMGPU_CS_FUSED=1 switches it on for further work.  Set by gmres() per solve.
-    bool cs_fused_post = false, cs_fused_env = false;
     // Decomposed CPR: level 0 of the pressure cycle on the GLOBAL matrix -- the iterate's ghost entries are refreshed from their owners before
     // the down leg's residual and before every post-smoothing sweep (AmgHierarchy::level0_halo; one more halo exchange each, 2 per
     // application under GMRES, 3 under BiCGStab).  The rank-local hierarchy is what fails on heterogeneous decks (SPE10-like: 4.7 -> 46

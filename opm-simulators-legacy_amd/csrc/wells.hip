@@ -1052,7 +1052,7 @@ void BlackoilDevice::wells_prologue()
 // iteration (the pre-solve that follows needs the assembly's 1/b sums anyway) and not with THP controls (connection pressures in between).
 bool BlackoilDevice::wells_prologue_async(bool initial)
 {
-    static const bool on = !(std::getenv("OPMGPU_WELL_PROLOGUE_ASYNC") && std::atoi(std::getenv("OPMGPU_WELL_PROLOGUE_ASYNC")) == 0);
+    static const bool on = env_flag("OPMGPU_WELL_PROLOGUE_ASYNC", true);
     well_prologue_done = false;
     if (!on || !wd || initial || wd->vfp_active) return false;
     if (!well_stream) {

@@ -174,7 +174,7 @@ def test_collective_operations_per_newton_iteration(gpu_lib):
     # round 4: the new basis vector's halo rides on the all-reduce of its projections (one fused operation per column and one at the start):
     # 18.8 -> 15.8.  VERDICT r3 asked for <= 12: the remaining pair per preconditioner application (coarse-space all-reduce before the cycle,
     # halo of the pressure correction after it) can only be fused by moving the coarse correction behind the cycle, which costs more columns
-    # than it saves latencies (LinSolver::cs_fused_post, profiles/r04_j_dist_ab.log) -- the bound asserted here is what is reached
+    # than it saves latencies (measured, profiles/r04_j_dist_ab.log; the switch was removed, see git history) -- the bound asserted here is what is reached
     assert per1 <= 16.0, per1
     assert c1[2] >= lin1                                              # at least one fused operation per column
     assert c0[0] - c1[0] >= lin1 - 2                                  # one all-reduce less per column
