@@ -1,21 +1,16 @@
 // amg.hip -- plain-aggregation AMG for the CPR pressure stage (see amg.hpp).
 #include "amg.hpp"
-#include <functional>
-
-#include <string>
-#include <utility>
 
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
-#include <numeric>
+#include <string>
+#include <utility>
 
 #include "linsolver.hpp"
 
 namespace opmgpu {
-
-namespace {
 
 // ---------------------------------------------------------------- host: hierarchy setup
 struct HostCsr {
@@ -23,6 +18,8 @@ struct HostCsr {
     std::vector<int32_t> rowptr, col, dev;   // dev = device entry id of every csr entry
     std::vector<double> val;
 };
+
+namespace {
 
 // greedy strength-based aggregation (Vanek-style, as in dune-istl's aggregation AMG): a node whose strong
 // neighbours are all free seeds an aggregate with them; leftovers join their strongest aggregated neighbour.
@@ -61,11 +58,13 @@ int aggregate(const HostCsr& A, double theta, std::vector<int32_t>& agg, int npi
     return na;
 }
 
-// Galerkin product of a distributed level: the coarse rows are this rank's aggregates, each sums only this rank's rows (row_agg[i] in
-// [0, na) for an owned row, -1 otherwise); a fine column j goes to coarse column col_agg[j] (a ghost's: the owner's aggregate, numbered
-// by the caller); the diagonal comes first with column diag0 + I.  coarse_of_fine is -1 for the entries of rows that are not owned.
-void coarsen_dist(const HostCsr& A, const std::vector<int32_t>& row_agg, const std::vector<int32_t>& col_agg, int na, int diag0, int ncols,
-                  HostCsr& C, std::vector<int32_t>& coarse_of_fine, std::vector<int32_t>& agg_ptr, std::vector<int32_t>& agg_rows)
+// Galerkin product with piecewise-constant prolongation: Ac(I,J) = sum_{i in I, j in J} A(i,j).  The coarse rows are the na aggregates
+// row_agg[i] of the rows (-1: a row that is not summed, a ghost row of a distributed level); a fine column j goes to coarse column
+// col_agg[j] in [0, ncols) (a ghost's: the owner's aggregate, numbered by the caller); the diagonal comes first with column diag0 + I.
+// A single-domain level has row_agg == col_agg, diag0 = 0 and ncols = na.  Also returns, for every fine csr entry, the coarse csr
+// entry it is added to (-1 for the entries of rows that are not summed).
+void coarsen(const HostCsr& A, const std::vector<int32_t>& row_agg, const std::vector<int32_t>& col_agg, int na, int diag0, int ncols,
+             HostCsr& C, std::vector<int32_t>& coarse_of_fine, std::vector<int32_t>& agg_ptr, std::vector<int32_t>& agg_rows)
 {
     agg_ptr.assign(na + 1, 0);
     for (int i = 0; i < A.n; ++i) if (row_agg[i] >= 0) agg_ptr[row_agg[i] + 1]++;
@@ -82,36 +81,6 @@ void coarsen_dist(const HostCsr& A, const std::vector<int32_t>& row_agg, const s
             const int i = agg_rows[q];
             for (int s = A.rowptr[i]; s < A.rowptr[i + 1]; ++s) {
                 const int J = col_agg[A.col[s]];
-                if (marker[J] < start) { marker[J] = int(C.col.size()); C.col.push_back(J); C.val.push_back(0.0); }
-                C.val[marker[J]] += A.val[s];
-                coarse_of_fine[s] = marker[J];
-            }
-        }
-        C.rowptr[I + 1] = int(C.col.size());
-    }
-}
-
-// Galerkin product with piecewise-constant prolongation: Ac(I,J) = sum_{i in I, j in J} A(i,j).
-// Also returns, for every fine csr entry, the coarse csr entry it is added to.
-void coarsen(const HostCsr& A, const std::vector<int32_t>& agg, int na, HostCsr& C, std::vector<int32_t>& coarse_of_fine,
-             std::vector<int32_t>& agg_ptr, std::vector<int32_t>& agg_rows)
-{
-    agg_ptr.assign(na + 1, 0);
-    for (int i = 0; i < A.n; ++i) agg_ptr[agg[i] + 1]++;
-    for (int I = 0; I < na; ++I) agg_ptr[I + 1] += agg_ptr[I];
-    agg_rows.resize(A.n);
-    { std::vector<int32_t> fill(agg_ptr.begin(), agg_ptr.end() - 1); for (int i = 0; i < A.n; ++i) agg_rows[fill[agg[i]]++] = i; }
-    C.n = na; C.rowptr.assign(na + 1, 0); C.col.clear(); C.val.clear();
-    coarse_of_fine.assign(A.col.size(), -1);
-    std::vector<int32_t> marker(na, -1);
-    for (int I = 0; I < na; ++I) {
-        const int start = int(C.col.size());
-        // diagonal first
-        marker[I] = start; C.col.push_back(I); C.val.push_back(0.0);
-        for (int q = agg_ptr[I]; q < agg_ptr[I + 1]; ++q) {
-            const int i = agg_rows[q];
-            for (int s = A.rowptr[i]; s < A.rowptr[i + 1]; ++s) {
-                const int J = agg[A.col[s]];
                 if (marker[J] < start) { marker[J] = int(C.col.size()); C.col.push_back(J); C.val.push_back(0.0); }
                 C.val[marker[J]] += A.val[s];
                 coarse_of_fine[s] = marker[J];
@@ -622,6 +591,61 @@ void AmgHierarchy<S>::xchg(AmgLevel<S>& F, T* x, T* b, const SolveCtl* ctl)
     if (nr) hipLaunchKernelGGL((k_xchg_unpack<T>), dim3(grid_for(nr)), dim3(kBlock), 0, stream, nr, F.xchg_recv.p, (const T*)rb, x, b, ctl);
 }
 
+// ---- setup helpers shared by the distributed and the single-domain levels
+// a level's values and its vectors of nvec entries, zeroed (a distributed level's ghost entries of dinv stay zero); the values of the
+// first level are the caller's matrix
+template <class S>
+static void alloc_level(AmgLevel<S>& F, int nvec, bool first, hipStream_t st)
+{
+    F.val.alloc(F.nentries + 2 * size_t(F.nperf) + F.nw);
+    if (!first) F.val.zero(st);
+    for (DevArray<S>* v : { &F.dinv, &F.x, &F.b, &F.r, &F.x2 }) { v->alloc(nvec); v->zero(st); }
+}
+// a fresh level from a host csr: its SELL-64 structure on the device (fills C.dev), diagonal entries and row lengths
+template <class S>
+static std::unique_ptr<AmgLevel<S>> level_from_csr(HostCsr& C, hipStream_t st)
+{
+    std::vector<int32_t> sp, scol, dent; int nent = 0;
+    to_sell(C, sp, scol, dent, nent);
+    std::unique_ptr<AmgLevel<S>> L(new AmgLevel<S>());
+    L->n = C.n; L->nslices = (C.n + 63) / 64; L->nentries = nent;
+    L->own_slice_ptr.upload(sp, st); L->own_col.upload(scol, st);
+    L->slice_ptr = L->own_slice_ptr.p; L->col = L->own_col.p;
+    L->diag_entry.upload(dent, st);
+    L->h_rowlen.resize(C.n);
+    for (int r = 0; r < C.n; ++r) L->h_rowlen[r] = C.rowptr[r + 1] - C.rowptr[r];
+    return L;
+}
+// contribution lists per coarse csr entry, in fine DEVICE entry ids and the csr order of the fine entries (coarse_of_fine -1: not summed)
+static void contrib_lists(const HostCsr& A, const std::vector<int32_t>& cof, int nce, std::vector<int32_t>& cptr, std::vector<int32_t>& cidx)
+{
+    cptr.assign(nce + 1, 0);
+    for (size_t s = 0; s < cof.size(); ++s) if (cof[s] >= 0) cptr[cof[s] + 1]++;
+    for (int e = 0; e < nce; ++e) cptr[e + 1] += cptr[e];
+    cidx.resize(cptr[nce]);
+    std::vector<int32_t> fill(cptr.begin(), cptr.end() - 1);
+    for (size_t s = 0; s < cof.size(); ++s) if (cof[s] >= 0) cidx[fill[cof[s]]++] = A.dev[s];
+}
+// work list of k_amg_galerkin from F into the level made of C, indexed by that level's DEVICE slot (SELL-64: slice, position in the row,
+// lane): a wavefront covers 64 neighbouring coarse rows at the same position, and coarsen() puts the diagonal first, so its lanes loop
+// equally often and its stores are one contiguous line; padding slots have empty lists (they get 0).  The order of the sum inside an
+// entry is the csr order of the fine entries.
+template <class S>
+static void upload_galerkin_list(AmgLevel<S>& F, const HostCsr& C, int nent, const std::vector<int32_t>& cptr, const std::vector<int32_t>& cidx, hipStream_t st)
+{
+    const int nce = int(C.col.size());
+    std::vector<int32_t> cptr2(nent + 1, 0), cidx2(cidx.size()), cdiag2(nent, -1);
+    for (int e = 0; e < nce; ++e) cptr2[C.dev[e] + 1] = cptr[e + 1] - cptr[e];
+    for (int d = 0; d < nent; ++d) cptr2[d + 1] += cptr2[d];
+    for (int r = 0; r < C.n; ++r)
+        for (int e = C.rowptr[r]; e < C.rowptr[r + 1]; ++e) {
+            std::copy(cidx.begin() + cptr[e], cidx.begin() + cptr[e + 1], cidx2.begin() + cptr2[C.dev[e]]);
+            if (C.col[e] == r) cdiag2[C.dev[e]] = r;
+        }
+    F.contrib_ptr.upload(cptr2, st); F.contrib_idx.upload(cidx2, st); F.contrib_diag.upload(cdiag2, st);
+    F.nentries_coarse = nent; F.galerkin_lpe = galerkin_lanes(nce);
+}
+
 // Distributed levels of a decomposed hierarchy (amg.hpp), once per sparsity pattern.  Level l's owned rows are aggregated by the
 // single-domain rule (ghost rows excluded, wells pinned); the global numbering of level l + 1 is a rank offset (one all-reduce of the
 // per-rank counts) plus the local index; one exchange of the aggregate ids over level l's lists tells every rank the coarse ids of its
@@ -630,16 +654,16 @@ void AmgHierarchy<S>::xchg(AmgLevel<S>& F, T* x, T* b, const SolveCtl* ctl)
 // most tail_rows (or the coarsening stalls), that level is gathered onto every rank: row lengths, columns and first values through
 // zero-padded all-reduces; A, L, npin and pinmark are left describing it for the single-domain loop of setup().
 template <class S>
-static void setup_dist(AmgHierarchy<S>& H, const Plan& P, HostCsr& A, std::unique_ptr<AmgLevel<S>>& L, int& npin, std::vector<int8_t>& pinmark, int max_levels)
+void AmgHierarchy<S>::setup_dist(const Plan& P, HostCsr& A, std::unique_ptr<AmgLevel<S>>& L, int& npin, std::vector<int8_t>& pinmark, int max_levels)
 {
-    CommBase& cm = *H.dcomm;
-    const hipStream_t st = H.stream;
+    CommBase& cm = *dcomm;
+    const hipStream_t st = stream;
     const int rank = cm.my_rank(), nranks = cm.num_ranks();
     DevArray<double> red;
     auto allsum = [&](std::vector<double>& v) {
         if (v.empty()) return;
         red.upload(v, st);
-        H.allreduce_chunked(red.p, int64_t(v.size()));
+        allreduce_chunked(red.p, int64_t(v.size()));
         red.download(v.data(), v.size(), st);
         OPMGPU_HIP(hipStreamSynchronize(st));
     };
@@ -680,21 +704,19 @@ static void setup_dist(AmgHierarchy<S>& H, const Plan& P, HostCsr& A, std::uniqu
             F.xchg_sbuf.alloc(std::max<size_t>(si.size(), 1)); F.xchg_rbuf.alloc(std::max<size_t>(ri.size(), 1));
         }
         const int nvec = F.next();
-        F.val.alloc(F.nentries + 2 * size_t(F.nperf) + F.nw); F.dinv.alloc(nvec); F.x.alloc(nvec); F.b.alloc(nvec); F.r.alloc(nvec); F.x2.alloc(nvec);
-        F.x.zero(st); F.b.zero(st); F.r.zero(st); F.x2.zero(st); F.dinv.zero(st);
-        if (level > 0) F.val.zero(st);
-        H.level_sizes.push_back(F.ntot());
+        alloc_level(F, nvec, level == 0, st);
+        level_sizes.push_back(F.ntot());
         std::vector<int32_t> agg;
         const int na = aggregate(A, 0.25, agg, npin, level == 0 ? &mark0 : nullptr);
         int64_t coff = 0, nc = 0;
         offsets(na, coff, nc);
-        const bool tail = nc <= H.tail_rows || nc * 10 > F.nglobal * 8 || int(H.levels.size()) + 2 >= max_levels;
+        const bool tail = nc <= tail_rows || nc * 10 > F.nglobal * 8 || int(levels.size()) + 2 >= max_levels;
         // global coarse id of every entry: own rows from agg, ghosts from their owners
         std::vector<double> gv(nvec, -1.0);
         for (int i = 0; i < A.n; ++i) if (agg[i] >= 0) gv[i] = double(coff + agg[i]);
         {
             DevArray<double> d; d.upload(gv, st);
-            H.template xchg<double>(F, d.p, (double*)nullptr, (const SolveCtl*)nullptr);
+            xchg<double>(F, d.p, (double*)nullptr, (const SolveCtl*)nullptr);
             d.download(gv.data(), gv.size(), st);
             OPMGPU_HIP(hipStreamSynchronize(st));
         }
@@ -721,37 +743,17 @@ static void setup_dist(AmgHierarchy<S>& H, const Plan& P, HostCsr& A, std::uniqu
             nsp.push_back(int32_t(nsi.size()));
         }
         HostCsr C; std::vector<int32_t> cof, aptr, arows;
-        coarsen_dist(A, row_agg, col_agg, na, tail ? int(coff) : 0, tail ? int(nc) : na + ng, C, cof, aptr, arows);
+        coarsen(A, row_agg, col_agg, na, tail ? int(coff) : 0, tail ? int(nc) : na + ng, C, cof, aptr, arows);
         F.agg.upload(col_agg, st); F.agg_ptr.upload(aptr, st); F.agg_rows.upload(arows, st);
         F.n_coarse = na;
         const int nce = int(C.col.size());
-        std::vector<int32_t> cptr(nce + 1, 0), cidx;
-        for (size_t q = 0; q < cof.size(); ++q) if (cof[q] >= 0) cptr[cof[q] + 1]++;
-        for (int e = 0; e < nce; ++e) cptr[e + 1] += cptr[e];
-        cidx.resize(cptr[nce]);
-        { std::vector<int32_t> fill(cptr.begin(), cptr.end() - 1); for (size_t q = 0; q < cof.size(); ++q) if (cof[q] >= 0) cidx[fill[cof[q]]++] = A.dev[q]; }
-        std::unique_ptr<AmgLevel<S>> Lc(new AmgLevel<S>());
+        std::vector<int32_t> cptr, cidx;
+        contrib_lists(A, cof, nce, cptr, cidx);
         if (!tail) {
-            std::vector<int32_t> sp, scol, dent; int nent = 0;
-            to_sell(C, sp, scol, dent, nent);
-            std::vector<int32_t> cptr2(nent + 1, 0), cidx2(cidx.size()), cdiag2(nent, -1);
-            for (int e = 0; e < nce; ++e) cptr2[C.dev[e] + 1] = cptr[e + 1] - cptr[e];
-            for (int d = 0; d < nent; ++d) cptr2[d + 1] += cptr2[d];
-            for (int r = 0; r < C.n; ++r)
-                for (int e = C.rowptr[r]; e < C.rowptr[r + 1]; ++e) {
-                    std::copy(cidx.begin() + cptr[e], cidx.begin() + cptr[e + 1], cidx2.begin() + cptr2[C.dev[e]]);
-                    if (C.col[e] == r) cdiag2[C.dev[e]] = r;
-                }
-            F.contrib_ptr.upload(cptr2, st); F.contrib_idx.upload(cidx2, st); F.contrib_diag.upload(cdiag2, st);
-            F.nentries_coarse = nent; F.galerkin_lpe = galerkin_lanes(nce);
-            Lc->n = na; Lc->nslices = (na + 63) / 64; Lc->nentries = nent;
-            Lc->own_slice_ptr.upload(sp, st); Lc->own_col.upload(scol, st);
-            Lc->slice_ptr = Lc->own_slice_ptr.p; Lc->col = Lc->own_col.p;
-            Lc->diag_entry.upload(dent, st);
-            Lc->h_rowlen.resize(C.n);
-            for (int r = 0; r < C.n; ++r) Lc->h_rowlen[r] = C.rowptr[r + 1] - C.rowptr[r];
+            std::unique_ptr<AmgLevel<S>> Lc = level_from_csr<S>(C, st);
+            upload_galerkin_list(F, C, Lc->nentries, cptr, cidx, st);
             Lc->nghost = ng; Lc->goff = coff; Lc->nglobal = nc; Lc->h_gid = gid_next;
-            H.levels.push_back(std::move(L));
+            levels.push_back(std::move(L));
             L = std::move(Lc);
             A = std::move(C);
             lsp.swap(nsp); lsi.swap(nsi); lrp.swap(nrp); lri.swap(nri);
@@ -775,22 +777,15 @@ static void setup_dist(AmgHierarchy<S>& H, const Plan& P, HostCsr& A, std::uniqu
         allsum(cc); allsum(vv);
         T.col.resize(nnz); T.val = vv;
         for (int64_t k = 0; k < nnz; ++k) T.col[k] = int32_t(std::llround(cc[k]));
-        std::vector<int32_t> sp, scol, dent; int nent = 0;
-        to_sell(T, sp, scol, dent, nent);
-        F.contrib_ptr.upload(cptr, st); F.contrib_idx.upload(cidx, st);
+        std::unique_ptr<AmgLevel<S>> Lc = level_from_csr<S>(T, st);
+        F.contrib_ptr.upload(cptr, st); F.contrib_idx.upload(cidx, st);          // csr order: k_tail_galerkin indexes them by csr entry
         F.nentries_coarse = nce;
-        H.tail_pos.upload(pos, st); H.tail_dev.upload(T.dev, st);
-        H.tail_nnz = nnz; H.tail_off = coff; H.tail_own = na;
-        H.tail_buf.alloc(size_t(std::max<int64_t>(std::max<int64_t>(nnz, nc), 1)));
-        Lc->n = int(nc); Lc->nslices = (Lc->n + 63) / 64; Lc->nentries = nent;
-        Lc->own_slice_ptr.upload(sp, st); Lc->own_col.upload(scol, st);
-        Lc->slice_ptr = Lc->own_slice_ptr.p; Lc->col = Lc->own_col.p;
-        Lc->diag_entry.upload(dent, st);
-        Lc->h_rowlen.resize(T.n);
-        for (int r = 0; r < T.n; ++r) Lc->h_rowlen[r] = T.rowptr[r + 1] - T.rowptr[r];
+        tail_pos.upload(pos, st); tail_dev.upload(T.dev, st);
+        tail_nnz = nnz; tail_off = coff; tail_own = na;
+        tail_buf.alloc(size_t(std::max<int64_t>(std::max<int64_t>(nnz, nc), 1)));
         Lc->goff = 0; Lc->nglobal = nc;
-        H.levels.push_back(std::move(L));
-        H.ndist = int(H.levels.size());
+        levels.push_back(std::move(L));
+        ndist = int(levels.size());
         L = std::move(Lc);
         A = std::move(T);
         npin = 0;
@@ -867,12 +862,10 @@ void AmgHierarchy<S>::setup(const Plan& P, const int32_t* d_slice_ptr, const int
     tail_rows = kTailRows;
     tail_rows = std::max(1, env_int("OPMGPU_AMG_TAIL_ROWS", tail_rows));
     std::vector<int8_t> pinmark;            // replicated tail: the wells' rows stay singletons (aggregate(): mark 2)
-    if (dcomm) setup_dist(*this, P, A, L, npin, pinmark, kMaxLevels);
+    if (dcomm) setup_dist(P, A, L, npin, pinmark, kMaxLevels);
     while (true) {
         const int n = A.n;              // unknowns of this level (a bordered level 0: cells + wells)
-        L->val.alloc(L->nentries + 2 * size_t(L->nperf) + L->nw); L->dinv.alloc(n); L->x.alloc(n); L->b.alloc(n); L->r.alloc(n); L->x2.alloc(n);
-        L->x.zero(stream); L->b.zero(stream); L->r.zero(stream); L->x2.zero(stream);
-        if (!levels.empty()) L->val.zero(stream);
+        alloc_level(*L, n, levels.empty(), stream);
         level_sizes.push_back(n);
         std::vector<int32_t> agg;
         int na = 0;
@@ -883,43 +876,18 @@ void AmgHierarchy<S>::setup(const Plan& P, const int32_t* d_slice_ptr, const int
             break;
         }
         HostCsr C; std::vector<int32_t> cof, aptr, arows;
-        coarsen(A, agg, na, C, cof, aptr, arows);
+        coarsen(A, agg, agg, na, 0, na, C, cof, aptr, arows);
         if (!pinmark.empty()) {
             std::vector<int8_t> cm(na, 0);
             for (int i = 0; i < n; ++i) if (pinmark[i] == 2) cm[agg[i]] = 2;
             pinmark.swap(cm);
         }
-        std::vector<int32_t> sp, scol, dent; int nent = 0;
-        to_sell(C, sp, scol, dent, nent);
-        // contribution lists per coarse csr entry, in fine DEVICE entry ids
-        const int nce = int(C.col.size());
-        std::vector<int32_t> cptr(nce + 1, 0), cidx(A.col.size());
-        for (size_t s = 0; s < A.col.size(); ++s) cptr[cof[s] + 1]++;
-        for (int e = 0; e < nce; ++e) cptr[e + 1] += cptr[e];
-        { std::vector<int32_t> fill(cptr.begin(), cptr.end() - 1); for (size_t s = 0; s < A.col.size(); ++s) cidx[fill[cof[s]]++] = A.dev[s]; }
         L->agg.upload(agg, stream); L->agg_ptr.upload(aptr, stream); L->agg_rows.upload(arows, stream);
-        // work list of k_amg_galerkin, indexed by the coarse level's DEVICE slot (SELL-64: slice, position in the row, lane): a wavefront
-        // covers 64 neighbouring coarse rows at the same position, and coarsen() puts the diagonal first, so its lanes loop equally often
-        // and its stores are one contiguous line; padding slots have empty lists (they get 0).  The order of the sum inside an entry is
-        // the csr order of the fine entries, as before.
-        const int lpe = galerkin_lanes(nce);
-        std::vector<int32_t> cptr2(nent + 1, 0), cidx2(cidx.size()), cdiag2(nent, -1);
-        for (int e = 0; e < nce; ++e) cptr2[C.dev[e] + 1] = cptr[e + 1] - cptr[e];
-        for (int d = 0; d < nent; ++d) cptr2[d + 1] += cptr2[d];
-        for (int r = 0; r < C.n; ++r)
-            for (int e = C.rowptr[r]; e < C.rowptr[r + 1]; ++e) {
-                std::copy(cidx.begin() + cptr[e], cidx.begin() + cptr[e + 1], cidx2.begin() + cptr2[C.dev[e]]);
-                if (C.col[e] == r) cdiag2[C.dev[e]] = r;
-            }
-        L->contrib_ptr.upload(cptr2, stream); L->contrib_idx.upload(cidx2, stream); L->contrib_diag.upload(cdiag2, stream);
-        L->n_coarse = na; L->nentries_coarse = nent; L->galerkin_lpe = lpe;
-        std::unique_ptr<AmgLevel<S>> Lc(new AmgLevel<S>());
-        Lc->n = na; Lc->nslices = (na + 63) / 64; Lc->nentries = nent;
-        Lc->own_slice_ptr.upload(sp, stream); Lc->own_col.upload(scol, stream);
-        Lc->slice_ptr = Lc->own_slice_ptr.p; Lc->col = Lc->own_col.p;
-        Lc->diag_entry.upload(dent, stream);
-        Lc->h_rowlen.resize(C.n);
-        for (int r = 0; r < C.n; ++r) Lc->h_rowlen[r] = C.rowptr[r + 1] - C.rowptr[r];
+        L->n_coarse = na;
+        std::vector<int32_t> cptr, cidx;
+        contrib_lists(A, cof, int(C.col.size()), cptr, cidx);
+        std::unique_ptr<AmgLevel<S>> Lc = level_from_csr<S>(C, stream);
+        upload_galerkin_list(*L, C, Lc->nentries, cptr, cidx, stream);
         levels.push_back(std::move(L));
         L = std::move(Lc);
         A = std::move(C);
@@ -1008,19 +976,67 @@ template <class S> static bool sub_rows(const AmgLevel<S>& F)
     return F.nw == 0 && F.n > lo && F.n <= hi;
 }
 
+// x = w D^-1 b: the first sweep from a zero guess
+template <class S>
+void AmgHierarchy<S>::smooth0(AmgLevel<S>& F, S w, const SolveCtl* ctl)
+{
+    hipLaunchKernelGGL((k_amg_smooth0<S>), dim3(grid_for(F.ntot())), dim3(kBlock), 0, stream, F.ntot(), w, F.dinv.p, F.b.p, F.x.p, ctl);
+}
+
+// One row operation on a level, by the kernel that suits its size: kSubLanes lanes per row on the middle levels (sub_rows), a thread per
+// row above 20000 rows, a wavefront per row below; a bordered level 0 gets one more workgroup per well (see Border).
+// MODE 0: r = b - A x;  MODE 1: x2 = x + omega D^-1 (b - A x);  MODE 2: x = omega D^-1 b, r = b - A x (the thread-per-row kernel of it is
+// k_amg_smooth0_residual);  MODE 3: the sweep of MODE 1 on the prolongated iterate x + pdamp P xc
+template <class S>
+template <int MODE>
+void AmgHierarchy<S>::row_op(AmgLevel<S>& F, const SolveCtl* ctl, const S* xc, S pdamp)
+{
+    const S om = S(omega);
+    S* out = (MODE == 0 || MODE == 2) ? F.r.p : F.x2.p;
+    S* xout = MODE == 2 ? F.x.p : nullptr;
+    const int32_t* agg = MODE == 3 ? F.agg.p : nullptr;
+    if (sub_rows(F)) {
+        hipLaunchKernelGGL((k_amg_row_sub<S, MODE, kSubLanes>), dim3(sub_grid(F.n)), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, (const S*)F.x.p, om, F.dinv.p, out,
+                           xout, ctl, agg, xc, pdamp);
+    } else if (F.n > 20000) {
+        const int g = grid_for(F.n);
+        if constexpr (MODE == 2)
+            hipLaunchKernelGGL((k_amg_smooth0_residual<S>), dim3(g + F.nw), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, om, F.dinv.p, xout, out, ctl, border_of(F, g));
+        else
+            hipLaunchKernelGGL((k_amg_residual<S, MODE>), dim3(g + F.nw), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, F.x.p, om, F.dinv.p, out, ctl,
+                               agg, xc, pdamp, border_of(F, g));
+    } else {
+        const int g = (F.n + 3) / 4;
+        hipLaunchKernelGGL((k_amg_row_wave<S, MODE>), dim3(g + F.nw), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, (const S*)F.x.p, om, F.dinv.p, out,
+                           xout, ctl, agg, xc, pdamp, border_of(F, g));
+    }
+}
+
+// one damped-Jacobi sweep x <- x + omega D^-1 (b - A x) (ping-pong between x and x2)
+template <class S>
+void AmgHierarchy<S>::sweep(AmgLevel<S>& F, const SolveCtl* ctl)
+{
+    row_op<1>(F, ctl);
+    std::swap(F.x.p, F.x2.p);       // the swept iterate becomes x (buffers are the same size)
+}
+
+// first residual of the down leg: x = omega D^-1 b, then r = b - A x, fused in one launch (MODE 2) except above 50000 rows, where
+// k_amg_smooth0 and the plain residual are faster.  presmoothed: F.x holds omega D^-1 b already; only the levels that would launch
+// k_amg_smooth0 or run kSubLanes lanes per row make use of it, the others form it again on the fly.
+template <class S>
+void AmgHierarchy<S>::first_residual(AmgLevel<S>& F, bool presmoothed, const SolveCtl* ctl)
+{
+    const bool split = !sub_rows(F) && F.n > 50000;
+    if (split && !presmoothed) smooth0(F, S(omega), ctl);
+    if (split || (presmoothed && sub_rows(F))) row_op<0>(F, ctl);
+    else row_op<2>(F, ctl);
+}
+
 template <class S>
 void AmgHierarchy<S>::vcycle(const SolveCtl* ctl, bool level0_presmoothed)
 {
     const S om = S(omega);
     const int nl = int(levels.size());
-    // bordered level 0: `gcells` workgroups for the cell rows + one per well (see Border)
-    auto bord = [&](const AmgLevel<S>& F, int gcells) {
-        Border<S> B;
-        if (F.nw == 0) return B;
-        B.nw = F.nw; B.n = F.n; B.gcells = gcells; B.connpos = F.b_connpos; B.perf_row = F.b_perf_row; B.perf_of_row = F.b_perf_of_row; B.perf_well = F.b_perf_well;
-        B.bcol = F.val.p + F.nentries; B.crow = B.bcol + F.nperf; B.dw = B.crow + F.nperf;
-        return B;
-    };
     // OPMGPU_AMG_TIME=1: HIP events between the launches of ONE cycle, printed to stderr (diagnostic; no profiler distortion)
     static const bool timing = std::getenv("OPMGPU_AMG_TIME") != nullptr;
     std::vector<std::pair<std::string, hipEvent_t>> marks;
@@ -1028,21 +1044,21 @@ void AmgHierarchy<S>::vcycle(const SolveCtl* ctl, bool level0_presmoothed)
         if (!timing) return;
         hipEvent_t e; (void)hipEventCreate(&e); (void)hipEventRecord(e, stream); marks.emplace_back(name, e);
     };
+    // the ghost entries of level l's iterate from their owners: a distributed level's own exchange, or the caller's halo exchange on level 0
+    auto refresh = [&](AmgLevel<S>& F, int l) {
+        if (l < ndist) xchg<S>(F, F.x.p, l == 0 ? F.b.p : (S*)nullptr, ctl);
+        else level0_halo(F.x.p, F.b.p);
+    };
     mark("start");
     bool presmoothed = level0_presmoothed && fuse;  // F.x already holds omega D^-1 b (fused into the kernel that produced b)
     for (int l = 0; l < nl - 1; ++l) {
         AmgLevel<S>& F = *levels[l]; AmgLevel<S>& C = *levels[l + 1];
-        const int g = grid_for(F.n);
         if (l < ndist) {
             // distributed level: unfused launches, the ghost entries of the iterate from their owners before every operation that reads them
-            if (!presmoothed) hipLaunchKernelGGL((k_amg_smooth0<S>), dim3(grid_for(F.ntot())), dim3(kBlock), 0, stream, F.ntot(), om, F.dinv.p, F.b.p, F.x.p, ctl);
-            xchg<S>(F, F.x.p, l == 0 ? F.b.p : (S*)nullptr, ctl);
-            residual_level(F, ctl);
-            for (int sw = 1; sw < npre; ++sw) {
-                sweep(F, ctl);
-                xchg<S>(F, F.x.p, l == 0 ? F.b.p : (S*)nullptr, ctl);
-                residual_level(F, ctl);
-            }
+            if (!presmoothed) smooth0(F, om, ctl);
+            refresh(F, l);
+            row_op<0>(F, ctl);
+            for (int sw = 1; sw < npre; ++sw) { sweep(F, ctl); refresh(F, l); row_op<0>(F, ctl); }
             if (l + 1 == ndist) {           // into the replicated tail: one all-reduce of the zero-padded aggregate sums
                 const int nc = C.n;
                 hipLaunchKernelGGL((k_tail_restrict<S>), dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, int(tail_off), int(tail_own), F.agg_ptr.p, F.agg_rows.p,
@@ -1059,43 +1075,24 @@ void AmgHierarchy<S>::vcycle(const SolveCtl* ctl, bool level0_presmoothed)
         }
         if (l == 0 && level0_halo) {
             // decomposed run: x0 = omega D^-1 b, ghost entries from their owners, then the residual on the global level-0 matrix
-            if (!presmoothed) hipLaunchKernelGGL((k_amg_smooth0<S>), dim3(grid_for(F.ntot())), dim3(kBlock), 0, stream, F.ntot(), om, F.dinv.p, F.b.p, F.x.p, ctl);
-            if (level0_halo_down) level0_halo(F.x.p, F.b.p);
+            // (always a thread per row, whatever the level's size)
+            const int g = grid_for(F.n);
+            if (!presmoothed) smooth0(F, om, ctl);
+            if (level0_halo_down) refresh(F, l);
             hipLaunchKernelGGL((k_amg_residual<S, 0>), dim3(g + F.nw), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, F.x.p, om, F.dinv.p, F.r.p, ctl,
-                               (const int32_t*)nullptr, (const S*)nullptr, S(0), bord(F, g));
+                               (const int32_t*)nullptr, (const S*)nullptr, S(0), border_of(F, g));
         } else if (l == 0 && gs_level0() && F.nw == 0) {
             // x = D^-1 b (the first colour's sweep from zero; the caller's fused kernel did it with omega0() = 1), second colour in place,
             // then the residual: zero on the rows just solved, b - A x on the first colour
             const int n0 = gs_n0;
-            if (!presmoothed) hipLaunchKernelGGL((k_amg_smooth0<S>), dim3(g), dim3(kBlock), 0, stream, F.n, S(1), F.dinv.p, F.b.p, F.x.p, ctl);
+            if (!presmoothed) smooth0(F, S(1), ctl);
             hipLaunchKernelGGL((k_amg_gs<S, 1>), dim3(grid_for(F.n - n0)), dim3(kBlock), 0, stream, n0, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, F.dinv.p, F.x.p, (S*)nullptr, ctl);
             hipLaunchKernelGGL((k_amg_gs<S, 0>), dim3(grid_for(n0)), dim3(kBlock), 0, stream, 0, n0, F.slice_ptr, F.col, F.val.p, F.b.p, F.dinv.p, F.x.p, F.r.p, ctl);
             OPMGPU_HIP(hipMemsetAsync(F.r.p + n0, 0, size_t(F.n - n0) * sizeof(S), stream));
-        } else if (sub_rows(F)) {
-            // x = omega D^-1 b came with the restriction (presmoothed) or is formed on the fly (MODE 2)
-            if (presmoothed) hipLaunchKernelGGL((k_amg_row_sub<S, 0, kSubLanes>), dim3(sub_grid(F.n)), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, (const S*)F.x.p, om, F.dinv.p, F.r.p, (S*)nullptr, ctl);
-            else hipLaunchKernelGGL((k_amg_row_sub<S, 2, kSubLanes>), dim3(sub_grid(F.n)), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, (const S*)F.x.p, om, F.dinv.p, F.r.p, F.x.p, ctl);
-        } else if (F.n > 50000) {
-            if (!presmoothed) hipLaunchKernelGGL((k_amg_smooth0<S>), dim3(grid_for(F.ntot())), dim3(kBlock), 0, stream, F.ntot(), om, F.dinv.p, F.b.p, F.x.p, ctl);
-            hipLaunchKernelGGL((k_amg_residual<S, 0>), dim3(g + F.nw), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, F.x.p, om, F.dinv.p, F.r.p, ctl,
-                               (const int32_t*)nullptr, (const S*)nullptr, S(0), bord(F, g));
-        } else if (F.n > 20000) {
-            hipLaunchKernelGGL((k_amg_smooth0_residual<S>), dim3(g + F.nw), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, om, F.dinv.p, F.x.p, F.r.p, ctl, bord(F, g));
         } else {
-            hipLaunchKernelGGL((k_amg_row_wave<S, 2>), dim3((F.n + 3) / 4 + F.nw), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, (const S*)F.x.p, om, F.dinv.p, F.r.p, F.x.p, ctl,
-                               (const int32_t*)nullptr, (const S*)nullptr, S(0), bord(F, (F.n + 3) / 4));
+            first_residual(F, presmoothed, ctl);
         }
-        for (int sw = 1; sw < npre; ++sw) {      // further pre-smoothing sweeps, then the residual again
-            sweep(F, ctl);
-            if (sub_rows(F))
-                hipLaunchKernelGGL((k_amg_row_sub<S, 0, kSubLanes>), dim3(sub_grid(F.n)), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, (const S*)F.x.p, om, F.dinv.p, F.r.p, (S*)nullptr, ctl);
-            else if (F.n > 20000)
-                hipLaunchKernelGGL((k_amg_residual<S, 0>), dim3(g + F.nw), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, F.x.p, om, F.dinv.p, F.r.p, ctl,
-                                   (const int32_t*)nullptr, (const S*)nullptr, S(0), bord(F, g));
-            else
-                hipLaunchKernelGGL((k_amg_row_wave<S, 0>), dim3((F.n + 3) / 4 + F.nw), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, (const S*)F.x.p, om, F.dinv.p, F.r.p, (S*)nullptr, ctl,
-                                   (const int32_t*)nullptr, (const S*)nullptr, S(0), bord(F, (F.n + 3) / 4));
-        }
+        for (int sw = 1; sw < npre; ++sw) { sweep(F, ctl); row_op<0>(F, ctl); }      // further pre-smoothing sweeps, then the residual again
         // the restriction also performs the coarse level's first sweep when that level would launch a separate kernel for it
         presmoothed = fuse && (l + 1 < nl - 1) && C.n > 50000;
         hipLaunchKernelGGL((k_amg_restrict<S>), dim3(grid_for(C.n)), dim3(kBlock), 0, stream, C.n, F.agg_ptr.p, F.agg_rows.p, F.r.p, C.b.p, om,
@@ -1108,61 +1105,41 @@ void AmgHierarchy<S>::vcycle(const SolveCtl* ctl, bool level0_presmoothed)
         hipLaunchKernelGGL((k_dense_apply<S>), dim3((n_coarsest + 3) / 4), dim3(kBlock), 0, stream, n_coarsest, dense_inv.p, B.b.p, B.x.p, ctl);
     } else {        // coarsening stalled above the dense limit: a few Jacobi sweeps stand in for the coarse solve (on the border too when it is level 0)
         const int gb = grid_for(B.n);
-        hipLaunchKernelGGL((k_amg_smooth0<S>), dim3(grid_for(B.ntot())), dim3(kBlock), 0, stream, B.ntot(), om, B.dinv.p, B.b.p, B.x.p, ctl);
-        for (int s = 0; s < coarse_sweeps; ++s) {
-            hipLaunchKernelGGL((k_amg_residual<S, 1>), dim3(gb + B.nw), dim3(kBlock), 0, stream, B.n, B.slice_ptr, B.col, B.val.p, B.b.p, B.x.p, om, B.dinv.p, B.x2.p, ctl,
+        smooth0(B, om, ctl);
+        S* from = B.x.p; S* to = B.x2.p;          // pairs of sweeps (always a thread per row): the iterate ends in x
+        for (int s = 0; s < 2 * coarse_sweeps; ++s, std::swap(from, to))
+            hipLaunchKernelGGL((k_amg_residual<S, 1>), dim3(gb + B.nw), dim3(kBlock), 0, stream, B.n, B.slice_ptr, B.col, B.val.p, B.b.p, from, om, B.dinv.p, to, ctl,
                                (const int32_t*)nullptr, (const S*)nullptr, S(0), border_of(B, gb));
-            hipLaunchKernelGGL((k_amg_residual<S, 1>), dim3(gb + B.nw), dim3(kBlock), 0, stream, B.n, B.slice_ptr, B.col, B.val.p, B.b.p, B.x2.p, om, B.dinv.p, B.x.p, ctl,
-                               (const int32_t*)nullptr, (const S*)nullptr, S(0), border_of(B, gb));
-        }
     }
     mark("coarsest");
     for (int l = nl - 2; l >= 0; --l) {
         AmgLevel<S>& F = *levels[l]; AmgLevel<S>& C = *levels[l + 1];
-        const int g = grid_for(F.n);
         int done_sweeps = 0;
         const int npost = l == 0 ? this->npost0 : this->npost;
         const double pdamp = l == 0 ? this->pdamp0 : this->pdamp;          // (shadows the member: the correction INTO level l)
-        if (l < ndist) {
-            hipLaunchKernelGGL((k_amg_prolong<S>), dim3(grid_for(F.ntot())), dim3(kBlock), 0, stream, F.ntot(), F.agg.p, C.x.p, F.x.p, S(pdamp), ctl);
-            for (int sw = 0; sw < npost; ++sw) { xchg<S>(F, F.x.p, l == 0 ? F.b.p : (S*)nullptr, ctl); sweep(F, ctl); }
-            mark("up L" + std::to_string(l));
-            continue;
-        }
-        if (l == 0 && level0_halo) {
-            // decomposed run: prolongation, then every post-smoothing sweep on an iterate whose ghost entries are the owners'
-            hipLaunchKernelGGL((k_amg_prolong<S>), dim3(grid_for(F.ntot())), dim3(kBlock), 0, stream, F.ntot(), F.agg.p, C.x.p, F.x.p, S(pdamp), ctl);
-            for (int sw = 0; sw < npost; ++sw) { level0_halo(F.x.p, F.b.p); sweep(F, ctl); }
-            mark("up L0");
-            continue;
-        }
-        if (l == 0 && gs_level0() && F.nw == 0) {
+        auto prolong = [&] { hipLaunchKernelGGL((k_amg_prolong<S>), dim3(grid_for(F.ntot())), dim3(kBlock), 0, stream, F.ntot(), F.agg.p, C.x.p, F.x.p, S(pdamp), ctl); };
+        if (l < ndist || (l == 0 && level0_halo)) {
+            // distributed level or decomposed run: prolongation, then every post-smoothing sweep on an iterate whose ghost entries are the owners'
+            prolong();
+            for (int sw = 0; sw < npost; ++sw) { refresh(F, l); sweep(F, ctl); }
+        } else if (l == 0 && gs_level0() && F.nw == 0) {
             const int n0 = gs_n0;
-            hipLaunchKernelGGL((k_amg_prolong<S>), dim3(g), dim3(kBlock), 0, stream, F.n, F.agg.p, C.x.p, F.x.p, S(pdamp), ctl);
+            prolong();
             for (int sw = 0; sw < npost; ++sw) {          // colours in reverse order
                 hipLaunchKernelGGL((k_amg_gs<S, 1>), dim3(grid_for(F.n - n0)), dim3(kBlock), 0, stream, n0, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, F.dinv.p, F.x.p, (S*)nullptr, ctl);
                 hipLaunchKernelGGL((k_amg_gs<S, 1>), dim3(grid_for(n0)), dim3(kBlock), 0, stream, 0, n0, F.slice_ptr, F.col, F.val.p, F.b.p, F.dinv.p, F.x.p, (S*)nullptr, ctl);
             }
-            mark("up L0");
-            continue;
-        }
-        if (fuse && npost >= 1 && F.n <= 200000) {
-            // small and medium levels: the prolongation is gathered inside the first post-smoothing sweep (one launch less)
-            if (sub_rows(F))
-                hipLaunchKernelGGL((k_amg_row_sub<S, 3, kSubLanes>), dim3(sub_grid(F.n)), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, (const S*)F.x.p, om, F.dinv.p, F.x2.p,
-                                   (S*)nullptr, ctl, (const int32_t*)F.agg.p, (const S*)C.x.p, S(pdamp));
-            else if (F.n > 20000)
-                hipLaunchKernelGGL((k_amg_residual<S, 3>), dim3(g + F.nw), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, (const S*)F.x.p, om, F.dinv.p, F.x2.p, ctl,
-                                   (const int32_t*)F.agg.p, (const S*)C.x.p, S(pdamp), bord(F, g));
-            else
-                hipLaunchKernelGGL((k_amg_row_wave<S, 3>), dim3((F.n + 3) / 4 + F.nw), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, (const S*)F.x.p, om, F.dinv.p, F.x2.p,
-                                   (S*)nullptr, ctl, (const int32_t*)F.agg.p, (const S*)C.x.p, S(pdamp), bord(F, (F.n + 3) / 4));
-            std::swap(F.x.p, F.x2.p);
-            done_sweeps = 1;
         } else {
-            hipLaunchKernelGGL((k_amg_prolong<S>), dim3(grid_for(F.ntot())), dim3(kBlock), 0, stream, F.ntot(), F.agg.p, C.x.p, F.x.p, S(pdamp), ctl);
+            if (fuse && npost >= 1 && F.n <= 200000) {
+                // small and medium levels: the prolongation is gathered inside the first post-smoothing sweep (one launch less)
+                row_op<3>(F, ctl, C.x.p, S(pdamp));
+                std::swap(F.x.p, F.x2.p);
+                done_sweeps = 1;
+            } else {
+                prolong();
+            }
+            for (int sw = done_sweeps; sw < npost; ++sw) sweep(F, ctl);
         }
-        for (int sw = done_sweeps; sw < npost; ++sw) sweep(F, ctl);
         mark("up L" + std::to_string(l));
     }
     if (timing && !marks.empty()) {
@@ -1199,54 +1176,6 @@ void AmgHierarchy<S>::vcycle_graph(const SolveCtl* ctl, bool level0_presmoothed)
         graph_ctl = ctl; graph_pre = level0_presmoothed;
     }
     OPMGPU_HIP(hipGraphLaunch(graph_exec, stream));
-}
-
-// r = b - A x on one level (unfused: the distributed levels)
-template <class S>
-void AmgHierarchy<S>::residual_level(AmgLevel<S>& F, const SolveCtl* ctl)
-{
-    const S om = S(omega);
-    const int g = grid_for(F.n);
-    Border<S> B;
-    if (F.nw) {
-        B.nw = F.nw; B.n = F.n; B.connpos = F.b_connpos; B.perf_row = F.b_perf_row; B.perf_of_row = F.b_perf_of_row; B.perf_well = F.b_perf_well;
-        B.bcol = F.val.p + F.nentries; B.crow = B.bcol + F.nperf; B.dw = B.crow + F.nperf;
-    }
-    if (sub_rows(F)) {
-        hipLaunchKernelGGL((k_amg_row_sub<S, 0, kSubLanes>), dim3(sub_grid(F.n)), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, (const S*)F.x.p, om, F.dinv.p, F.r.p, (S*)nullptr, ctl);
-    } else if (F.n > 20000) {
-        B.gcells = g;
-        hipLaunchKernelGGL((k_amg_residual<S, 0>), dim3(g + F.nw), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, F.x.p, om, F.dinv.p, F.r.p, ctl,
-                           (const int32_t*)nullptr, (const S*)nullptr, S(0), B);
-    } else {
-        B.gcells = (F.n + 3) / 4;
-        hipLaunchKernelGGL((k_amg_row_wave<S, 0>), dim3((F.n + 3) / 4 + F.nw), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, (const S*)F.x.p, om, F.dinv.p, F.r.p, (S*)nullptr, ctl,
-                           (const int32_t*)nullptr, (const S*)nullptr, S(0), B);
-    }
-}
-
-// one damped-Jacobi sweep x <- x + omega D^-1 (b - A x) (ping-pong between x and x2)
-template <class S>
-void AmgHierarchy<S>::sweep(AmgLevel<S>& F, const SolveCtl* ctl)
-{
-    const S om = S(omega);
-    Border<S> B;
-    if (F.nw) {
-        B.nw = F.nw; B.n = F.n; B.connpos = F.b_connpos; B.perf_row = F.b_perf_row; B.perf_of_row = F.b_perf_of_row; B.perf_well = F.b_perf_well;
-        B.bcol = F.val.p + F.nentries; B.crow = B.bcol + F.nperf; B.dw = B.crow + F.nperf;
-    }
-    if (sub_rows(F)) {
-        hipLaunchKernelGGL((k_amg_row_sub<S, 1, kSubLanes>), dim3(sub_grid(F.n)), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, (const S*)F.x.p, om, F.dinv.p, F.x2.p, (S*)nullptr, ctl);
-    } else if (F.n > 20000) {
-        B.gcells = grid_for(F.n);
-        hipLaunchKernelGGL((k_amg_residual<S, 1>), dim3(grid_for(F.n) + F.nw), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, F.x.p, om, F.dinv.p, F.x2.p, ctl,
-                           (const int32_t*)nullptr, (const S*)nullptr, S(0), B);
-    } else {
-        B.gcells = (F.n + 3) / 4;
-        hipLaunchKernelGGL((k_amg_row_wave<S, 1>), dim3((F.n + 3) / 4 + F.nw), dim3(kBlock), 0, stream, F.n, F.slice_ptr, F.col, F.val.p, F.b.p, (const S*)F.x.p, om, F.dinv.p, F.x2.p, (S*)nullptr, ctl,
-                           (const int32_t*)nullptr, (const S*)nullptr, S(0), B);
-    }
-    std::swap(F.x.p, F.x2.p);       // the swept iterate becomes x (buffers are the same size)
 }
 
 template class AmgHierarchy<float>;

@@ -25,6 +25,7 @@ namespace opmgpu {
 
 struct SolveCtl;
 struct CommBase;
+struct HostCsr;          // host csr of one level during setup (amg.hip)
 
 template <class S>
 struct AmgLevel {
@@ -143,7 +144,6 @@ public:
     int gs_n0 = 0;                // rows [0, gs_n0) are the first colour (0 = no two-colour order)
     bool gs_level0() const { return use_gs && gs_n0 > 0 && npre == 1; }
     double omega0() const { return gs_level0() ? 1.0 : omega; }      // weight of the caller's fused first sweep on level 0
-    void sweep(AmgLevel<S>& F, const SolveCtl* ctl);
     // Distributed hierarchy (opmgpu_comm_set_pressure_hierarchy mode 1): set dcomm before setup().  Levels [0, ndist) are distributed
     // (aggregates inside a rank, Galerkin products keep the couplings to the neighbours' aggregates); level ndist, the first whose global
     // size is at most kTailRows, and all coarser ones are replicated on every rank (the tail).  ndist = 0: the rank-local hierarchy.
@@ -156,10 +156,16 @@ public:
     DevArray<int32_t> tail_pos;              // per own Galerkin entry of the last distributed level: its csr position in the first tail level
     DevArray<int32_t> tail_dev;              // [tail_nnz] SELL slot of every csr entry of the first tail level
     DevArray<double> tail_buf;               // zero-padded partial sums: Galerkin values / restricted right-hand side of the tail
-    void allreduce_chunked(double* d, int64_t n);      // all-reduces of at most kReduceChunk doubles (32 KiB messages)
     static constexpr int kReduceChunk = 4096;
+private:
+    void setup_dist(const Plan& P, HostCsr& A, std::unique_ptr<AmgLevel<S>>& L, int& npin, std::vector<int8_t>& pinmark, int max_levels);
+    void allreduce_chunked(double* d, int64_t n);      // all-reduces of at most kReduceChunk doubles (32 KiB messages)
     template <class T> void xchg(AmgLevel<S>& F, T* x, T* b, const SolveCtl* ctl);
-    void residual_level(AmgLevel<S>& F, const SolveCtl* ctl);
+    // the launches of the cycle (amg.hip): row_op chooses the row kernel of a level, the others are built on it
+    template <int MODE> void row_op(AmgLevel<S>& F, const SolveCtl* ctl, const S* xc = nullptr, S pdamp = S(0));
+    void smooth0(AmgLevel<S>& F, S w, const SolveCtl* ctl);
+    void first_residual(AmgLevel<S>& F, bool presmoothed, const SolveCtl* ctl);
+    void sweep(AmgLevel<S>& F, const SolveCtl* ctl);
 };
 
 } // namespace opmgpu
