@@ -42,18 +42,6 @@ __device__ __forceinline__ V4 vchain2(double f, double dfa, const V4& a, double 
     return mk(f, dfa * a.p + dfb * b.p, dfa * a.w + dfb * b.w, dfa * a.x + dfb * b.x);
 }
 
-// saturation tables: constant extrapolation; LEFT = segment x[i] < xv <= x[i+1] (SWOF by Sw),
-// RIGHT = x[i] <= xv < x[i+1] (SGOF by Sg: opm-material tabulates those against So).
-template <bool RIGHT>
-__device__ __forceinline__ void sat_eval(const double* __restrict__ x, const double* __restrict__ y, int n, double xv, double& f, double& df)
-{
-    if (xv <= x[0]) { f = y[0]; df = 0.0; return; }
-    if (xv >= x[n - 1]) { f = y[n - 1]; df = 0.0; return; }
-    int i = 0;
-    for (int k = 1; k < n - 1; ++k) i += (RIGHT ? (x[k] <= xv) : (x[k] < xv)) ? 1 : 0;
-    df = (y[i + 1] - y[i]) / (x[i + 1] - x[i]);
-    f = y[i] + df * (xv - x[i]);
-}
 // PVT tables: linear extrapolation, opm-material Tabulated1DFunction segment rule
 __device__ __forceinline__ int pvt_seg(const double* __restrict__ x, int n, double xv)
 {
@@ -61,39 +49,6 @@ __device__ __forceinline__ int pvt_seg(const double* __restrict__ x, int n, doub
     if (n > 2) i = (x[1] < xv) ? 1 : 0;
     for (int k = 2; k <= n - 2; ++k) i += (x[k] <= xv) ? 1 : 0;
     return i;
-}
-__device__ __forceinline__ void pvt1(const double* __restrict__ x, const double* __restrict__ y, int n, double xv, double& f, double& df)
-{
-    const int i = pvt_seg(x, n, xv);
-    df = (y[i + 1] - y[i]) / (x[i + 1] - x[i]);
-    f = y[i] + df * (xv - x[i]);
-}
-// UniformXTabulated2DFunction::eval: f(xnode, ycol)
-__device__ __forceinline__ void pvt2(const double* __restrict__ xs, int nn, const int32_t* __restrict__ cp, const double* __restrict__ cy,
-                                     const double* __restrict__ cv, double xv, double yv, double& f, double& dfx, double& dfy)
-{
-    const int i = pvt_seg(xs, nn, xv);
-    const double h = xs[i + 1] - xs[i];
-    const double alpha = (xv - xs[i]) / h;
-    double s1, d1, s2, d2;
-    pvt1(cy + cp[i], cv + cp[i], cp[i + 1] - cp[i], yv, s1, d1);
-    pvt1(cy + cp[i + 1], cv + cp[i + 1], cp[i + 2] - cp[i + 1], yv, s2, d2);
-    f = s1 * (1.0 - alpha) + s2 * alpha;
-    dfx = (s2 - s1) / h;
-    dfy = d1 * (1.0 - alpha) + d2 * alpha;
-}
-
-__device__ __forceinline__ void rs_sat_d(const opmgpu_tables& T, int reg, double p, double& f, double& df)
-{
-    if (!T.has_disgas) { f = 0.0; df = 0.0; return; }
-    const int a = T.oil_node_ptr[reg];
-    pvt1(T.oil_psat + a, T.oil_rs + a, T.oil_node_ptr[reg + 1] - a, p, f, df);
-}
-__device__ __forceinline__ void rv_sat_d(const opmgpu_tables& T, int reg, double p, double& f, double& df)
-{
-    if (!T.has_vapoil) { f = 0.0; df = 0.0; return; }
-    const int a = T.gas_node_ptr[reg];
-    pvt1(T.gas_pg + a, T.gas_rvsat + a, T.gas_node_ptr[reg + 1] - a, p, f, df);
 }
 
 // ENDSCALE: per curve S_unscaled = u0 + (S - s0) * k (two-point, k = (u2 - u0) / (s2 - s0)); with SCALECRS the relative-permeability
@@ -132,14 +87,6 @@ __device__ __forceinline__ double eps_unmap(const EpsD& e, int c, double su)    
 {
     return su >= e.u1[c] && e.s1[c] < 1e30 ? e.s1[c] + (su - e.u1[c]) / e.k1[c] : e.s0[c] + (su - e.u0[c]) / e.k[c];
 }
-template <bool RIGHT>
-__device__ __forceinline__ void sat_curve(const double* __restrict__ x, const double* __restrict__ y, int n, double sv, const EpsD& e, int c, double& f, double& df)
-{
-    if (!e.on) { sat_eval<RIGHT>(x, y, n, sv, f, df); return; }
-    double slope;
-    sat_eval<RIGHT>(x, y, n, eps_map(e, c, sv, slope), f, df);
-    f *= e.v[c]; df *= slope * e.v[c];
-}
 // Relative-permeability hysteresis of a cell (EclHysteresisTwoPhaseLaw, Carlson for the non-wetting phases, KR only): the history
 // planes hold the smallest wetting saturation each two-phase system has seen (2.0 = none) and the shift of the imbibition curve.
 struct HystD { bool on; int ireg; double mdc_ow, mdc_go, d_ow, d_go; };
@@ -150,26 +97,6 @@ __device__ __forceinline__ void hyst_load(const int32_t* __restrict__ imbnum, co
     if (!h.on) return;
     h.ireg = imbnum[row];
     h.mdc_ow = hist[row]; h.mdc_go = hist[nbp + row]; h.d_ow = hist[2 * nbp + row]; h.d_go = hist[3 * nbp + row];
-}
-
-// Tables in LDS: every table function is two dependent memory round trips (find the segment, read its end points) and a cell
-// evaluates ~14 of them; from L1/L2 that chain is ~10 us of pure latency per wave, from LDS a tenth of it.  The whole blob is
-// copied by the workgroup (words > 0; the host passes 0 when it does not fit) and the struct's pointers are rebased onto it.
-__device__ __forceinline__ void stage_tables(opmgpu_tables& T, const double* __restrict__ blob, int words, double* lds)
-{
-    if (words <= 0) return;
-    for (int i = threadIdx.x; i < words; i += blockDim.x) lds[i] = blob[i];
-    __syncthreads();
-    auto rd = [&](const double*& p) { if (p) p = lds + (p - blob); };
-    auto ri = [&](const int32_t*& p) { if (p) p = reinterpret_cast<const int32_t*>(lds + (reinterpret_cast<const double*>(p) - blob)); };
-    rd(T.surface_density); rd(T.pvtw);
-    ri(T.oil_node_ptr); rd(T.oil_rs); rd(T.oil_psat); rd(T.oil_invb_sat); rd(T.oil_invbmu_sat);
-    ri(T.oil_col_ptr); rd(T.oil_col_p); rd(T.oil_col_invb); rd(T.oil_col_invbmu);
-    ri(T.gas_node_ptr); rd(T.gas_pg); rd(T.gas_rvsat); rd(T.gas_invb_sat); rd(T.gas_invbmu_sat);
-    ri(T.gas_col_ptr); rd(T.gas_col_rv); rd(T.gas_col_invb); rd(T.gas_col_invbmu);
-    ri(T.swof_ptr); rd(T.swof_sw); rd(T.swof_krw); rd(T.swof_krow); rd(T.swof_pcow);
-    ri(T.sgof_ptr); rd(T.sgof_sg); rd(T.sgof_krg); rd(T.sgof_krog); rd(T.sgof_pcgo);
-    rd(T.rocktab_p); rd(T.rocktab_pvmult); rd(T.rocktab_transmult);
 }
 
 // VAPPARS (applyVap, BlackoilPropsAdFromDeck.cpp:1052-1078): factor (so/soMax)^vap and its so-derivative
@@ -191,16 +118,41 @@ __device__ __forceinline__ void rocktab_eval(const double* __restrict__ x, const
     f = y[i] + df * (xv - x[i]);
 }
 
-// Device-internal companions of the tables: the slope (y[i+1] - y[i]) / (x[i+1] - x[i]) of every segment of every 1-D table, formed once
-// on the host by the same IEEE division the kernels used to repeat per cell and per table (an f64 division is ~12 quarter-rate-class
-// instructions on gfx950 and eval_cell made ~50 of them; it runs twice per cell and assembly now, and it is VALU-bound: 3 800 static
-// instructions in its value-only form).  Arrays are as long as their table (the last entry of a table is unused).
-// (struct TabX / DevTables: blackoil.hpp)
+// Device form of the tables (struct DevTables, blackoil.hpp): the caller's arrays and, as their device-internal companions, the slope
+// (y[i+1] - y[i]) / (x[i+1] - x[i]) of every segment of every 1-D table, formed once on the host by the same IEEE division a kernel
+// would repeat per cell and per table (an f64 division is ~12 quarter-rate-class instructions on gfx950 and eval_cell made ~50 of them;
+// it runs twice per cell and assembly, and it is VALU-bound: 3 800 static instructions in its value-only form).  Slope arrays are as
+// long as their table (the last entry of a table is unused).  Every evaluator below reads the slopes: there is one family of them.
 
-// The hot kernels take the tables with every pointer field holding a WORD OFFSET into the blob and resolve them here against the blob's
-// copy in LDS (LDS = true: the workgroup stages it first) or against the blob itself.  With the base a compile-time choice every table
-// access of the LDS instantiation is a ds_read at a 32-bit offset (the round-2 form rebased generic pointers at run time: flat loads
-// with 64-bit address arithmetic, 284 v_lshl_add_u64 in the value-only kernel).
+// THE list of the pointer fields of a DevTables: fd sees every `const double*&`, fi every `const int32_t*&`.  Whatever turns one form of
+// the tables into another (word offsets -> device pointers on the host, -> pointers into LDS or the blob in a kernel) goes through here;
+// upload_tables() is the only other place that names every array, because it alone knows their lengths.
+template <class FD, class FI>
+__host__ __device__ __forceinline__ void for_each_table(DevTables& D, FD&& fd, FI&& fi)
+{
+    opmgpu_tables& T = D.t; TabX& X = D.x;
+    fd(T.surface_density); fd(T.pvtw);
+    fi(T.oil_node_ptr); fd(T.oil_rs); fd(T.oil_psat); fd(T.oil_invb_sat); fd(T.oil_invbmu_sat);
+    fi(T.oil_col_ptr); fd(T.oil_col_p); fd(T.oil_col_invb); fd(T.oil_col_invbmu);
+    fi(T.gas_node_ptr); fd(T.gas_pg); fd(T.gas_rvsat); fd(T.gas_invb_sat); fd(T.gas_invbmu_sat);
+    fi(T.gas_col_ptr); fd(T.gas_col_rv); fd(T.gas_col_invb); fd(T.gas_col_invbmu);
+    fi(T.swof_ptr); fd(T.swof_sw); fd(T.swof_krw); fd(T.swof_krow); fd(T.swof_pcow);
+    fi(T.sgof_ptr); fd(T.sgof_sg); fd(T.sgof_krg); fd(T.sgof_krog); fd(T.sgof_pcgo);
+    fd(T.rocktab_p); fd(T.rocktab_pvmult); fd(T.rocktab_transmult);
+    fd(X.swof_dkrw); fd(X.swof_dkrow); fd(X.swof_dpcow); fd(X.sgof_dkrg); fd(X.sgof_dkrog); fd(X.sgof_dpcgo);
+    fd(X.oil_drs); fd(X.oil_dinvb_sat); fd(X.oil_dinvbmu_sat); fd(X.oil_col_dinvb); fd(X.oil_col_dinvbmu);
+    fd(X.gas_drvsat); fd(X.gas_dinvb_sat); fd(X.gas_dinvbmu_sat); fd(X.gas_col_dinvb); fd(X.gas_col_dinvbmu);
+}
+// the table word at offset `off` of `base` (pointer fields of the offset form hold the offset itself)
+template <class P>
+__host__ __device__ __forceinline__ void rebase(P*& p, const double* base) { p = reinterpret_cast<P*>(base + reinterpret_cast<size_t>(p)); }
+
+// Tables in LDS: every table function is two dependent memory round trips (find the segment, read its end points) and a cell evaluates
+// ~14 of them; from L1/L2 that chain is ~10 us of pure latency per wave, from LDS a tenth of it.  The kernels on the Newton path take the
+// tables with every pointer field holding a WORD OFFSET into the blob and resolve them here against the blob's copy in LDS (LDS = true:
+// the workgroup stages it first; the host chooses it when the blob fits) or against the blob itself.  With the base a compile-time choice
+// every table access of the LDS instantiation is a ds_read at a 32-bit offset (rebasing generic pointers at run time, the round-2 form,
+// gave flat loads with 64-bit address arithmetic: 284 v_lshl_add_u64 in the value-only kernel).
 template <bool LDS>
 __device__ __forceinline__ void resolve_tables(DevTables& D, const double* __restrict__ blob, int words, double* lds)
 {
@@ -210,24 +162,13 @@ __device__ __forceinline__ void resolve_tables(DevTables& D, const double* __res
         __syncthreads();
         base = lds;
     }
-    auto rd = [&](const double*& p) { p = base + reinterpret_cast<size_t>(p); };
-    auto ri = [&](const int32_t*& p) { p = reinterpret_cast<const int32_t*>(base + reinterpret_cast<size_t>(p)); };
-    opmgpu_tables& T = D.t; TabX& X = D.x;
-    rd(T.surface_density); rd(T.pvtw);
-    ri(T.oil_node_ptr); rd(T.oil_rs); rd(T.oil_psat); rd(T.oil_invb_sat); rd(T.oil_invbmu_sat);
-    ri(T.oil_col_ptr); rd(T.oil_col_p); rd(T.oil_col_invb); rd(T.oil_col_invbmu);
-    ri(T.gas_node_ptr); rd(T.gas_pg); rd(T.gas_rvsat); rd(T.gas_invb_sat); rd(T.gas_invbmu_sat);
-    ri(T.gas_col_ptr); rd(T.gas_col_rv); rd(T.gas_col_invb); rd(T.gas_col_invbmu);
-    ri(T.swof_ptr); rd(T.swof_sw); rd(T.swof_krw); rd(T.swof_krow); rd(T.swof_pcow);
-    ri(T.sgof_ptr); rd(T.sgof_sg); rd(T.sgof_krg); rd(T.sgof_krog); rd(T.sgof_pcgo);
-    rd(T.rocktab_p); rd(T.rocktab_pvmult); rd(T.rocktab_transmult);
-    rd(X.swof_dkrw); rd(X.swof_dkrow); rd(X.swof_dpcow); rd(X.sgof_dkrg); rd(X.sgof_dkrog); rd(X.sgof_dpcgo);
-    rd(X.oil_drs); rd(X.oil_dinvb_sat); rd(X.oil_dinvbmu_sat); rd(X.oil_col_dinvb); rd(X.oil_col_dinvbmu);
-    rd(X.gas_drvsat); rd(X.gas_dinvb_sat); rd(X.gas_dinvbmu_sat); rd(X.gas_col_dinvb); rd(X.gas_col_dinvbmu);
+    auto rb = [&](auto*& p) { rebase(p, base); };
+    for_each_table(D, rb, rb);
 }
 
-// saturation table with the segment's slope tabulated: the segment search (sat_eval's rule) and the evaluation are separate so that
-// curves over the same abscissa share one search.  clamp: -1 / +1 = constant extrapolation below / above the table.
+// saturation tables: LEFT = segment x[i] < xv <= x[i+1] (SWOF by Sw), RIGHT = x[i] <= xv < x[i+1] (SGOF by Sg: opm-material tabulates
+// those against So).  The segment search and the evaluation are separate so that curves over the same abscissa share one search.
+// clamp: -1 / +1 = constant extrapolation below / above the table.
 template <bool RIGHT>
 __device__ __forceinline__ int sat_seg(const double* __restrict__ x, int n, double xv, int& clamp)
 {
@@ -275,6 +216,51 @@ __device__ __forceinline__ void pvt2_pair(const double* __restrict__ xs, int i, 
     f1 = s1 * oma + s2 * alpha; dfx1 = (s2 - s1) * ih; dfy1 = d1 * oma + d2 * alpha;
     lin_at(cy + c0, cv2 + c0, dcv2 + c0, j0, yv, s1, d1); lin_at(cy + c1, cv2 + c1, dcv2 + c1, j1, yv, s2, d2);
     f2 = s1 * oma + s2 * alpha; dfx2 = (s2 - s1) * ih; dfy2 = d1 * oma + d2 * alpha;
+}
+// the same for ONE function, value only (perforation and voidage PVT).  alpha keeps its division: pvt2_pair's reciprocal rounds differently
+__device__ __forceinline__ double pvt2_value(const double* __restrict__ xs, int nn, const int32_t* __restrict__ cp, const double* __restrict__ cy,
+                                             const double* __restrict__ cv, const double* __restrict__ dcv, double xv, double yv)
+{
+    const int i = pvt_seg(xs, nn, xv);
+    const double alpha = (xv - xs[i]) / (xs[i + 1] - xs[i]);
+    const int c0 = cp[i], c1 = cp[i + 1];
+    double s1, s2, d;
+    lin_at(cy + c0, cv + c0, dcv + c0, pvt_seg(cy + c0, c1 - c0, yv), yv, s1, d);
+    lin_at(cy + c1, cv + c1, dcv + c1, pvt_seg(cy + c1, cp[i + 2] - c1, yv), yv, s2, d);
+    return s1 * (1.0 - alpha) + s2 * alpha;
+}
+// saturated rs(p) / rv(p_g) of a PVT region's curve (0 without DISGAS / VAPOIL)
+__device__ __forceinline__ double rs_sat_d(const DevTables& D, int reg, double p)
+{
+    if (!D.t.has_disgas) return 0.0;
+    const int a = D.t.oil_node_ptr[reg];
+    double f, df;
+    lin_at(D.t.oil_psat + a, D.t.oil_rs + a, D.x.oil_drs + a, pvt_seg(D.t.oil_psat + a, D.t.oil_node_ptr[reg + 1] - a, p), p, f, df);
+    return f;
+}
+__device__ __forceinline__ double rv_sat_d(const DevTables& D, int reg, double p)
+{
+    if (!D.t.has_vapoil) return 0.0;
+    const int a = D.t.gas_node_ptr[reg];
+    double f, df;
+    lin_at(D.t.gas_pg + a, D.t.gas_rvsat + a, D.x.gas_drvsat + a, pvt_seg(D.t.gas_pg + a, D.t.gas_node_ptr[reg + 1] - a, p), p, f, df);
+    return f;
+}
+// b_w, b_o, b_g of a PVT region at (p, rs, rv), all phases at the SAME pressure; sat_o / sat_g: oil / gas from its saturated curve
+// (ConstantCompressibilityWaterPvt, LiveOilPvt, WetGasPvt: inverseFormationVolumeFactor / saturatedInverseFormationVolumeFactor)
+__device__ __forceinline__ void b_values(const DevTables& D, int preg, double p, double rs, double rv, bool sat_o, bool sat_g, double& bw, double& bo, double& bg)
+{
+    const opmgpu_tables& T = D.t; const TabX& X = D.x;
+    const double* w = T.pvtw + 5 * preg;
+    const double Xc = w[2] * (p - w[0]);
+    bw = (1.0 + Xc * (1.0 + Xc / 2.0)) / w[1];
+    double df;
+    const int oa = T.oil_node_ptr[preg], on = T.oil_node_ptr[preg + 1] - oa;
+    if (sat_o) lin_at(T.oil_psat + oa, T.oil_invb_sat + oa, X.oil_dinvb_sat + oa, pvt_seg(T.oil_psat + oa, on, p), p, bo, df);
+    else bo = pvt2_value(T.oil_rs + oa, on, T.oil_col_ptr + oa, T.oil_col_p, T.oil_col_invb, X.oil_col_dinvb, rs, p);
+    const int ga = T.gas_node_ptr[preg], gn = T.gas_node_ptr[preg + 1] - ga;
+    if (sat_g) lin_at(T.gas_pg + ga, T.gas_invb_sat + ga, X.gas_dinvb_sat + ga, pvt_seg(T.gas_pg + ga, gn, p), p, bg, df);
+    else bg = pvt2_value(T.gas_pg + ga, gn, T.gas_col_ptr + ga, T.gas_col_rv, T.gas_col_invb, X.gas_col_dinvb, p, rv);
 }
 // a / b with ONE division (the reciprocal), value and derivatives
 __device__ __forceinline__ V4 vdiv1(const V4& a, const V4& b)
@@ -456,6 +442,20 @@ __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int
     q.accum[0] = aw;
     q.accum[1] = vadd(ao, vmul(q.rv, ag));
     q.accum[2] = vadd(ag, vmul(q.rs, ao));
+}
+// eval_cell of a row's cell with what surrounds it: the cell's end-point scaling, its hysteresis history and, with one, the end points of
+// its imbibition curves
+__device__ __forceinline__ void eval_row(const DevTables& DT, int row, long nbp, double so_max, const int32_t* __restrict__ pvtnum, const int32_t* __restrict__ satnum,
+                                         const double* __restrict__ p, const double* __restrict__ sw, const double* __restrict__ sg, const double* __restrict__ rs,
+                                         const double* __restrict__ rv, const int8_t* __restrict__ hc, const double* __restrict__ eps, const double* __restrict__ eps_u0,
+                                         const HystArgs& hy, CellEval& q)
+{
+    EpsD E, EI;
+    HystD H;
+    eps_load(eps, eps_u0, nbp, row, satnum[row], E);
+    hyst_load(hy.imbnum, hy.hist, nbp, row, H);
+    if (H.on) eps_load(hy.ieps, hy.iureg, nbp, row, H.ireg, EI);
+    eval_cell(DT, E, so_max, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], q, H, &EI);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -798,7 +798,8 @@ __global__ __launch_bounds__(kBlock) void k_conv_gather(int phase, int nv, int n
 }
 
 // updateState (BlackoilModelBase_impl.hpp:1147-1389), one thread per cell
-__global__ __launch_bounds__(kBlock) void k_update_state(int nb, int nbp, opmgpu_tables T, const int32_t* __restrict__ pvtnum,
+template <bool LDS>
+__global__ __launch_bounds__(kBlock) void k_update_state(int nb, int nbp, DevTables D, const int32_t* __restrict__ pvtnum,
                                                          const int32_t* __restrict__ satnum, const double* __restrict__ dx, double relax,
                                                          double dp_max_rel, double ds_max, double dr_max_rel,
                                                          double* __restrict__ p, double* __restrict__ sw, double* __restrict__ so,
@@ -807,7 +808,8 @@ __global__ __launch_bounds__(kBlock) void k_update_state(int nb, int nbp, opmgpu
                                                          const double* __restrict__ somax, const double* __restrict__ tab_blob, int tab_words)
 {
     extern __shared__ double tab_lds[];
-    stage_tables(T, tab_blob, tab_words, tab_lds);
+    resolve_tables<LDS>(D, tab_blob, tab_words, tab_lds);
+    const opmgpu_tables& T = D.t;
     const int c = blockIdx.x * kBlock + threadIdx.x;
     if (c >= nb) return;
     const double eps = 1.4901161193847656e-08;      // sqrt(DBL_EPSILON)
@@ -844,8 +846,7 @@ __global__ __launch_bounds__(kBlock) void k_update_state(int nb, int nbp, opmgpu
         double v0, v1;
         vap_factor(T.vap2, so_old, somax[c], v0, df);
         vap_factor(T.vap2, o_, somax[c], v1, df);
-        rs_sat_d(T, preg, p_old, f, df); const double rsSat0 = v0 * f;
-        rs_sat_d(T, preg, pn, f, df); const double rsSat = v1 * f;
+        const double rsSat0 = v0 * rs_sat_d(D, preg, p_old), rsSat = v1 * rs_sat_d(D, preg, pn);
         const bool hasGas = (g_ > 0 && !isRs);
         const bool gasVaporized = ((rsn > rsSat * (1 + eps) && isRs) && (rs_old > rsSat0 * (1 - eps)));
         if (watOnly || hasGas || gasVaporized) { rsn = rsSat; if (watOnly) { o_ = 0; g_ = 0; rsn = 0; } }
@@ -855,13 +856,12 @@ __global__ __launch_bounds__(kBlock) void k_update_state(int nb, int nbp, opmgpu
         const int ga = T.sgof_ptr[sreg], ng = T.sgof_ptr[sreg + 1] - ga;
         EpsD E;
         eps_load(eps_planes, eps_u0, nbp, c, sreg, E);
-        sat_curve<true>(T.sgof_sg + ga, T.sgof_pcgo + ga, ng, sg_old, E, EC_PCGO, f, df); const double pg_old = p_old + f;
-        sat_curve<true>(T.sgof_sg + ga, T.sgof_pcgo + ga, ng, g_, E, EC_PCGO, f, df); const double pg_new = pn + f;
+        sat_curve_s<true>(T.sgof_sg + ga, T.sgof_pcgo + ga, D.x.sgof_dpcgo + ga, ng, sg_old, E, EC_PCGO, f, df); const double pg_old = p_old + f;
+        sat_curve_s<true>(T.sgof_sg + ga, T.sgof_pcgo + ga, D.x.sgof_dpcgo + ga, ng, g_, E, EC_PCGO, f, df); const double pg_new = pn + f;
         double v0, v1;
         vap_factor(T.vap1, so_old, somax[c], v0, df);
         vap_factor(T.vap1, o_, somax[c], v1, df);
-        rv_sat_d(T, preg, pg_old, f, df); const double rvSat0 = v0 * f;
-        rv_sat_d(T, preg, pg_new, f, df); const double rvSat = v1 * f;
+        const double rvSat0 = v0 * rv_sat_d(D, preg, pg_old), rvSat = v1 * rv_sat_d(D, preg, pg_new);
         const bool hasOil = (o_ > 0 && !isRv);
         const bool oilCondensed = ((rvn > rvSat * (1 + eps) && isRv) && (rv_old > rvSat0 * (1 - eps)));
         if (watOnly || hasOil || oilCondensed) { rvn = rvSat; if (watOnly) { o_ = 0; g_ = 0; rvn = 0; } }
@@ -905,12 +905,7 @@ __global__ __launch_bounds__(kBlock) void k_perf_props(int nperf, DevTables T, c
     if (i >= nperf) return;
     const int c = cells[i];
     CellEval q;
-    EpsD E, EI;
-    HystD H;
-    eps_load(eps, eps_u0, nbp, c, satnum[c], E);
-    hyst_load(hy.imbnum, hy.hist, nbp, c, H);
-    if (H.on) eps_load(hy.ieps, hy.iureg, nbp, c, H.ireg, EI);
-    eval_cell(T, E, somax[c], pvtnum[c], satnum[c], p[c], sw[c], sg[c], rs[c], rv[c], hc[c], q, H, &EI);
+    eval_row(T, c, nbp, somax[c], pvtnum, satnum, p, sw, sg, rs, rv, hc, eps, eps_u0, hy, q);
     const V4 list[9] = { mk(p[c], 1, 0, 0), q.rs, q.rv, q.b[0], q.b[1], q.b[2], q.mob[0], q.mob[1], q.mob[2] };
     double* o = out + long(i) * OPMGPU_PERF_K;
 #pragma unroll
@@ -930,12 +925,7 @@ __global__ __launch_bounds__(kBlock) void k_fip_cells(int nc, DevTables T, const
     const int c = blockIdx.x * kBlock + threadIdx.x;
     if (c >= nc) return;
     CellEval q;
-    EpsD E, EI;
-    HystD H;
-    eps_load(eps, eps_u0, nbp, c, satnum[c], E);
-    hyst_load(hy.imbnum, hy.hist, nbp, c, H);
-    if (H.on) eps_load(hy.ieps, hy.iureg, nbp, c, H.ireg, EI);
-    eval_cell(T, E, somax[c], pvtnum[c], satnum[c], p[c], sw[c], sg[c], rs[c], rv[c], hc[c], q, H, &EI);
+    eval_row(T, c, nbp, somax[c], pvtnum, satnum, p, sw, sg, rs, rv, hc, eps, eps_u0, hy, q);
     const long n = nat[c];
     const double so = so_[c], sgv = sg[c], swv = sw[c];          // the state's saturations, as the reference takes them
     const double fw = ((q.pvm.v * q.b[0].v) * swv) * pv[c];
@@ -948,7 +938,7 @@ __global__ __launch_bounds__(kBlock) void k_fip_cells(int nc, DevTables T, const
 
 // computePropertiesForWellConnectionPressures (StandardWells_impl.hpp:218-296): b_w, b_o, b_g, rsSat, rvSat of the perforated cells at
 // GIVEN pressures (the average well-block pressures) with the cells' own rs / rv / phase condition / oil saturation
-__global__ __launch_bounds__(kBlock) void k_perf_pvt(int nperf, opmgpu_tables T, const int32_t* __restrict__ cells, const int32_t* __restrict__ pvtnum,
+__global__ __launch_bounds__(kBlock) void k_perf_pvt(int nperf, DevTables D, const int32_t* __restrict__ cells, const int32_t* __restrict__ pvtnum,
                                                      const double* __restrict__ so, const double* __restrict__ rs, const double* __restrict__ rv,
                                                      const int8_t* __restrict__ hc, const double* __restrict__ somax, const double* __restrict__ press,
                                                      const int32_t* __restrict__ gate, double* __restrict__ out)
@@ -956,33 +946,16 @@ __global__ __launch_bounds__(kBlock) void k_perf_pvt(int nperf, opmgpu_tables T,
     if (gate && !*gate) return;
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= nperf) return;
+    const opmgpu_tables& T = D.t;
     const int c = cells[i], preg = pvtnum[c], h = hc[c];
     const bool freeGas = h != OPMGPU_HC_OIL_ONLY, freeOil = h != OPMGPU_HC_GAS_ONLY;
     const double p = press[i];
-    double f, df, d2;
     double* o = out + 5 * long(i);
-    {
-        const double* w = T.pvtw + 5 * preg;
-        const double Xc = w[2] * (p - w[0]);
-        o[0] = (1.0 + Xc * (1.0 + Xc / 2.0)) / w[1];
-    }
-    {
-        const int a = T.oil_node_ptr[preg], nn = T.oil_node_ptr[preg + 1] - a;
-        if (freeGas || !T.has_disgas) pvt1(T.oil_psat + a, T.oil_invb_sat + a, nn, p, f, df);
-        else pvt2(T.oil_rs + a, nn, T.oil_col_ptr + a, T.oil_col_p, T.oil_col_invb, rs[c], p, f, d2, df);
-        o[1] = f;
-    }
-    {
-        const int a = T.gas_node_ptr[preg], nn = T.gas_node_ptr[preg + 1] - a;
-        if (freeOil || !T.has_vapoil) pvt1(T.gas_pg + a, T.gas_invb_sat + a, nn, p, f, df);
-        else pvt2(T.gas_pg + a, nn, T.gas_col_ptr + a, T.gas_col_rv, T.gas_col_invb, p, rv[c], f, df, d2);
-        o[2] = f;
-    }
-    double v;
-    rs_sat_d(T, preg, p, f, df);
+    b_values(D, preg, p, rs[c], rv[c], freeGas || !T.has_disgas, freeOil || !T.has_vapoil, o[0], o[1], o[2]);
+    double f = rs_sat_d(D, preg, p), v, df;
     if (T.vap2 > 0.0) { vap_factor(T.vap2, so[c], somax[c], v, df); f *= v; }
     o[3] = f;
-    rv_sat_d(T, preg, p, f, df);
+    f = rv_sat_d(D, preg, p);
     if (T.vap1 > 0.0) { vap_factor(T.vap1, so[c], somax[c], v, df); f *= v; }
     o[4] = f;
 }
@@ -990,31 +963,14 @@ __global__ __launch_bounds__(kBlock) void k_perf_pvt(int nperf, opmgpu_tables T,
 // RateConverter::SurfaceToReservoirVoidage::calcCoeff (RateConverterLegacy.hpp:495-548): coefficients c with q_rT = sum_p c[p] q_s[p] at a
 // region's average state (p, rs, rv) -- b_w(p), the UNDERSATURATED b_o(p, rs) and b_g(p, rv) (FluidSystem::oilPvt().inverseFormationVolumeFactor(
 // region, T, p, Rs): the tables are evaluated at the given ratios whatever the saturated curve says), detR = 1 - rs rv.
-__global__ __launch_bounds__(kBlock) void k_voidage_coeff(int n, opmgpu_tables T, const double* __restrict__ press, const double* __restrict__ rs_,
+__global__ __launch_bounds__(kBlock) void k_voidage_coeff(int n, DevTables D, const double* __restrict__ press, const double* __restrict__ rs_,
                                                           const double* __restrict__ rv_, const int32_t* __restrict__ pvtreg, double* __restrict__ coeff)
 {
     const int i = blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    const int preg = pvtreg ? pvtreg[i] : 0;
-    const double p = press[i], rs = rs_[i], rv = rv_[i];
-    double f, df, d2, bw, bo, bg;
-    {
-        const double* w = T.pvtw + 5 * preg;
-        const double Xc = w[2] * (p - w[0]);
-        bw = (1.0 + Xc * (1.0 + Xc / 2.0)) / w[1];
-    }
-    {
-        const int a = T.oil_node_ptr[preg], nn = T.oil_node_ptr[preg + 1] - a;
-        if (!T.has_disgas) pvt1(T.oil_psat + a, T.oil_invb_sat + a, nn, p, f, df);
-        else pvt2(T.oil_rs + a, nn, T.oil_col_ptr + a, T.oil_col_p, T.oil_col_invb, rs, p, f, d2, df);
-        bo = f;
-    }
-    {
-        const int a = T.gas_node_ptr[preg], nn = T.gas_node_ptr[preg + 1] - a;
-        if (!T.has_vapoil) pvt1(T.gas_pg + a, T.gas_invb_sat + a, nn, p, f, df);
-        else pvt2(T.gas_pg + a, nn, T.gas_col_ptr + a, T.gas_col_rv, T.gas_col_invb, p, rv, f, df, d2);
-        bg = f;
-    }
+    const double rs = rs_[i], rv = rv_[i];
+    double bw, bo, bg;
+    b_values(D, pvtreg ? pvtreg[i] : 0, press[i], rs, rv, !D.t.has_disgas, !D.t.has_vapoil, bw, bo, bg);
     const double detR = 1.0 - (rs * rv);
     double cw = 0.0, co = 0.0, cg = 0.0;
     cw = 1.0 / bw;                                  // q[w]_r = q[w]_s / bw
@@ -1125,102 +1081,74 @@ BlackoilDevice::~BlackoilDevice()
 
 void BlackoilDevice::upload_tables(const opmgpu_tables* t)
 {
-    dt_ = *t;
-    // all table arrays live in ONE device blob (8-byte words) so that a kernel can stage them in LDS with one cooperative copy
+    // all table arrays live in ONE device blob (8-byte words) so that a kernel can stage them in LDS with one cooperative copy.  Built here
+    // is the OFFSET form: every pointer field holds the word offset of its array in the blob (resolve_tables)
+    DevTables& o = dto_;
+    o.t = *t;
     std::vector<double> blob;
-    auto upd = [&](const double* src, size_t n) -> const double* {
+    auto upd = [&](const double* src, size_t n) {
         const size_t off = blob.size();
         blob.insert(blob.end(), src, src + n);
         if (n == 0) blob.push_back(0.0);
-        return reinterpret_cast<const double*>(off + 1);         // encoded offset (+1: never null), resolved below
+        return reinterpret_cast<const double*>(off);
     };
-    auto upi = [&](const int32_t* src, size_t n) -> const int32_t* {
+    auto upi = [&](const int32_t* src, size_t n) {
         const size_t off = blob.size();
         blob.resize(off + (n + 1) / 2 + 1, 0.0);
         std::memcpy(&blob[off], src, n * sizeof(int32_t));
-        return reinterpret_cast<const int32_t*>(off + 1);
+        return reinterpret_cast<const int32_t*>(off);
     };
     const int np = t->n_pvt_regions, ns = t->n_sat_regions;
     const int non = t->oil_node_ptr[np], ngn = t->gas_node_ptr[np];
     const int noc = t->oil_col_ptr[non], ngc = t->gas_col_ptr[ngn];
     const int nsw = t->swof_ptr[ns], nsg = t->sgof_ptr[ns];
     h_surface_density.assign(t->surface_density, t->surface_density + 3 * size_t(np));
-    dt_.surface_density = upd(t->surface_density, 3 * np); dt_.pvtw = upd(t->pvtw, 5 * np);
-    dt_.oil_node_ptr = upi(t->oil_node_ptr, np + 1);
-    dt_.oil_rs = upd(t->oil_rs, non); dt_.oil_psat = upd(t->oil_psat, non);
-    dt_.oil_invb_sat = upd(t->oil_invb_sat, non); dt_.oil_invbmu_sat = upd(t->oil_invbmu_sat, non);
-    dt_.oil_col_ptr = upi(t->oil_col_ptr, non + 1);
-    dt_.oil_col_p = upd(t->oil_col_p, noc); dt_.oil_col_invb = upd(t->oil_col_invb, noc); dt_.oil_col_invbmu = upd(t->oil_col_invbmu, noc);
-    dt_.gas_node_ptr = upi(t->gas_node_ptr, np + 1);
-    dt_.gas_pg = upd(t->gas_pg, ngn); dt_.gas_rvsat = upd(t->gas_rvsat, ngn);
-    dt_.gas_invb_sat = upd(t->gas_invb_sat, ngn); dt_.gas_invbmu_sat = upd(t->gas_invbmu_sat, ngn);
-    dt_.gas_col_ptr = upi(t->gas_col_ptr, ngn + 1);
-    dt_.gas_col_rv = upd(t->gas_col_rv, ngc); dt_.gas_col_invb = upd(t->gas_col_invb, ngc); dt_.gas_col_invbmu = upd(t->gas_col_invbmu, ngc);
-    dt_.swof_ptr = upi(t->swof_ptr, ns + 1);
-    dt_.swof_sw = upd(t->swof_sw, nsw); dt_.swof_krw = upd(t->swof_krw, nsw); dt_.swof_krow = upd(t->swof_krow, nsw); dt_.swof_pcow = upd(t->swof_pcow, nsw);
-    dt_.sgof_ptr = upi(t->sgof_ptr, ns + 1);
-    dt_.sgof_sg = upd(t->sgof_sg, nsg); dt_.sgof_krg = upd(t->sgof_krg, nsg); dt_.sgof_krog = upd(t->sgof_krog, nsg); dt_.sgof_pcgo = upd(t->sgof_pcgo, nsg);
+    o.t.surface_density = upd(t->surface_density, 3 * np); o.t.pvtw = upd(t->pvtw, 5 * np);
+    o.t.oil_node_ptr = upi(t->oil_node_ptr, np + 1);
+    o.t.oil_rs = upd(t->oil_rs, non); o.t.oil_psat = upd(t->oil_psat, non);
+    o.t.oil_invb_sat = upd(t->oil_invb_sat, non); o.t.oil_invbmu_sat = upd(t->oil_invbmu_sat, non);
+    o.t.oil_col_ptr = upi(t->oil_col_ptr, non + 1);
+    o.t.oil_col_p = upd(t->oil_col_p, noc); o.t.oil_col_invb = upd(t->oil_col_invb, noc); o.t.oil_col_invbmu = upd(t->oil_col_invbmu, noc);
+    o.t.gas_node_ptr = upi(t->gas_node_ptr, np + 1);
+    o.t.gas_pg = upd(t->gas_pg, ngn); o.t.gas_rvsat = upd(t->gas_rvsat, ngn);
+    o.t.gas_invb_sat = upd(t->gas_invb_sat, ngn); o.t.gas_invbmu_sat = upd(t->gas_invbmu_sat, ngn);
+    o.t.gas_col_ptr = upi(t->gas_col_ptr, ngn + 1);
+    o.t.gas_col_rv = upd(t->gas_col_rv, ngc); o.t.gas_col_invb = upd(t->gas_col_invb, ngc); o.t.gas_col_invbmu = upd(t->gas_col_invbmu, ngc);
+    o.t.swof_ptr = upi(t->swof_ptr, ns + 1);
+    o.t.swof_sw = upd(t->swof_sw, nsw); o.t.swof_krw = upd(t->swof_krw, nsw); o.t.swof_krow = upd(t->swof_krow, nsw); o.t.swof_pcow = upd(t->swof_pcow, nsw);
+    o.t.sgof_ptr = upi(t->sgof_ptr, ns + 1);
+    o.t.sgof_sg = upd(t->sgof_sg, nsg); o.t.sgof_krg = upd(t->sgof_krg, nsg); o.t.sgof_krog = upd(t->sgof_krog, nsg); o.t.sgof_pcgo = upd(t->sgof_pcgo, nsg);
+    // no ROCKTAB: offset 0, whatever the caller's fields hold -- a valid address in every form, read by nobody (rocktab_n == 0)
+    o.t.rocktab_p = o.t.rocktab_pvmult = o.t.rocktab_transmult = nullptr;
     if (t->rocktab_n > 0) {
         if (t->rocktab_n < 2) throw HipError(OPMGPU_EINVAL, "ROCKTAB needs at least two rows");
-        dt_.rocktab_p = upd(t->rocktab_p, t->rocktab_n); dt_.rocktab_pvmult = upd(t->rocktab_pvmult, t->rocktab_n);
-        dt_.rocktab_transmult = upd(t->rocktab_transmult, t->rocktab_n);
+        o.t.rocktab_p = upd(t->rocktab_p, t->rocktab_n); o.t.rocktab_pvmult = upd(t->rocktab_pvmult, t->rocktab_n);
+        o.t.rocktab_transmult = upd(t->rocktab_transmult, t->rocktab_n);
     }
     // slopes of every 1-D table (TabX): (y[i+1] - y[i]) / (x[i+1] - x[i]) per segment, segments never cross the tables of a CSR-style array
-    auto slopes = [&](const double* x, const double* y, const int32_t* ptr, int ntab) -> const double* {
+    auto slopes = [&](const double* x, const double* y, const int32_t* ptr, int ntab) {
         const int n = ptr[ntab];
         std::vector<double> d(size_t(std::max(n, 1)), 0.0);
         for (int t_ = 0; t_ < ntab; ++t_)
             for (int i = ptr[t_]; i + 1 < ptr[t_ + 1]; ++i) d[i] = (y[i + 1] - y[i]) / (x[i + 1] - x[i]);
         return upd(d.data(), size_t(n));
     };
-    dx_.swof_dkrw = slopes(t->swof_sw, t->swof_krw, t->swof_ptr, ns); dx_.swof_dkrow = slopes(t->swof_sw, t->swof_krow, t->swof_ptr, ns);
-    dx_.swof_dpcow = slopes(t->swof_sw, t->swof_pcow, t->swof_ptr, ns);
-    dx_.sgof_dkrg = slopes(t->sgof_sg, t->sgof_krg, t->sgof_ptr, ns); dx_.sgof_dkrog = slopes(t->sgof_sg, t->sgof_krog, t->sgof_ptr, ns);
-    dx_.sgof_dpcgo = slopes(t->sgof_sg, t->sgof_pcgo, t->sgof_ptr, ns);
-    dx_.oil_drs = slopes(t->oil_psat, t->oil_rs, t->oil_node_ptr, np); dx_.oil_dinvb_sat = slopes(t->oil_psat, t->oil_invb_sat, t->oil_node_ptr, np);
-    dx_.oil_dinvbmu_sat = slopes(t->oil_psat, t->oil_invbmu_sat, t->oil_node_ptr, np);
-    dx_.oil_col_dinvb = slopes(t->oil_col_p, t->oil_col_invb, t->oil_col_ptr, non); dx_.oil_col_dinvbmu = slopes(t->oil_col_p, t->oil_col_invbmu, t->oil_col_ptr, non);
-    dx_.gas_drvsat = slopes(t->gas_pg, t->gas_rvsat, t->gas_node_ptr, np); dx_.gas_dinvb_sat = slopes(t->gas_pg, t->gas_invb_sat, t->gas_node_ptr, np);
-    dx_.gas_dinvbmu_sat = slopes(t->gas_pg, t->gas_invbmu_sat, t->gas_node_ptr, np);
-    dx_.gas_col_dinvb = slopes(t->gas_col_rv, t->gas_col_invb, t->gas_col_ptr, ngn); dx_.gas_col_dinvbmu = slopes(t->gas_col_rv, t->gas_col_invbmu, t->gas_col_ptr, ngn);
+    o.x.swof_dkrw = slopes(t->swof_sw, t->swof_krw, t->swof_ptr, ns); o.x.swof_dkrow = slopes(t->swof_sw, t->swof_krow, t->swof_ptr, ns);
+    o.x.swof_dpcow = slopes(t->swof_sw, t->swof_pcow, t->swof_ptr, ns);
+    o.x.sgof_dkrg = slopes(t->sgof_sg, t->sgof_krg, t->sgof_ptr, ns); o.x.sgof_dkrog = slopes(t->sgof_sg, t->sgof_krog, t->sgof_ptr, ns);
+    o.x.sgof_dpcgo = slopes(t->sgof_sg, t->sgof_pcgo, t->sgof_ptr, ns);
+    o.x.oil_drs = slopes(t->oil_psat, t->oil_rs, t->oil_node_ptr, np); o.x.oil_dinvb_sat = slopes(t->oil_psat, t->oil_invb_sat, t->oil_node_ptr, np);
+    o.x.oil_dinvbmu_sat = slopes(t->oil_psat, t->oil_invbmu_sat, t->oil_node_ptr, np);
+    o.x.oil_col_dinvb = slopes(t->oil_col_p, t->oil_col_invb, t->oil_col_ptr, non); o.x.oil_col_dinvbmu = slopes(t->oil_col_p, t->oil_col_invbmu, t->oil_col_ptr, non);
+    o.x.gas_drvsat = slopes(t->gas_pg, t->gas_rvsat, t->gas_node_ptr, np); o.x.gas_dinvb_sat = slopes(t->gas_pg, t->gas_invb_sat, t->gas_node_ptr, np);
+    o.x.gas_dinvbmu_sat = slopes(t->gas_pg, t->gas_invbmu_sat, t->gas_node_ptr, np);
+    o.x.gas_col_dinvb = slopes(t->gas_col_rv, t->gas_col_invb, t->gas_col_ptr, ngn); o.x.gas_col_dinvbmu = slopes(t->gas_col_rv, t->gas_col_invbmu, t->gas_col_ptr, ngn);
     d_tab.upload(blob, stream);
     tab_words = int(blob.size());
-    {
-        // offset form for the kernels that resolve the tables against the blob's LDS copy (resolve_tables): pointer fields = word offsets
-        dto_.t = dt_; dto_.x = dx_;
-        auto offd = [&](const double*& p) { p = reinterpret_cast<const double*>(p ? reinterpret_cast<size_t>(p) - 1 : size_t(0)); };
-        auto offi = [&](const int32_t*& p) { p = reinterpret_cast<const int32_t*>(p ? reinterpret_cast<size_t>(p) - 1 : size_t(0)); };
-        opmgpu_tables& o = dto_.t;
-        offd(o.surface_density); offd(o.pvtw);
-        offi(o.oil_node_ptr); offd(o.oil_rs); offd(o.oil_psat); offd(o.oil_invb_sat); offd(o.oil_invbmu_sat);
-        offi(o.oil_col_ptr); offd(o.oil_col_p); offd(o.oil_col_invb); offd(o.oil_col_invbmu);
-        offi(o.gas_node_ptr); offd(o.gas_pg); offd(o.gas_rvsat); offd(o.gas_invb_sat); offd(o.gas_invbmu_sat);
-        offi(o.gas_col_ptr); offd(o.gas_col_rv); offd(o.gas_col_invb); offd(o.gas_col_invbmu);
-        offi(o.swof_ptr); offd(o.swof_sw); offd(o.swof_krw); offd(o.swof_krow); offd(o.swof_pcow);
-        offi(o.sgof_ptr); offd(o.sgof_sg); offd(o.sgof_krg); offd(o.sgof_krog); offd(o.sgof_pcgo);
-        if (t->rocktab_n > 0) { offd(o.rocktab_p); offd(o.rocktab_pvmult); offd(o.rocktab_transmult); }
-        else { o.rocktab_p = nullptr; o.rocktab_pvmult = nullptr; o.rocktab_transmult = nullptr; }
-        const double** xs[] = { &dto_.x.swof_dkrw, &dto_.x.swof_dkrow, &dto_.x.swof_dpcow, &dto_.x.sgof_dkrg, &dto_.x.sgof_dkrog, &dto_.x.sgof_dpcgo, &dto_.x.oil_drs,
-                                &dto_.x.oil_dinvb_sat, &dto_.x.oil_dinvbmu_sat, &dto_.x.oil_col_dinvb, &dto_.x.oil_col_dinvbmu, &dto_.x.gas_drvsat, &dto_.x.gas_dinvb_sat,
-                                &dto_.x.gas_dinvbmu_sat, &dto_.x.gas_col_dinvb, &dto_.x.gas_col_dinvbmu };
-        const double** xg[] = { &dx_.swof_dkrw, &dx_.swof_dkrow, &dx_.swof_dpcow, &dx_.sgof_dkrg, &dx_.sgof_dkrog, &dx_.sgof_dpcgo, &dx_.oil_drs,
-                                &dx_.oil_dinvb_sat, &dx_.oil_dinvbmu_sat, &dx_.oil_col_dinvb, &dx_.oil_col_dinvbmu, &dx_.gas_drvsat, &dx_.gas_dinvb_sat,
-                                &dx_.gas_dinvbmu_sat, &dx_.gas_col_dinvb, &dx_.gas_col_dinvbmu };
-        for (size_t k = 0; k < sizeof(xs) / sizeof(xs[0]); ++k) { offd(*xs[k]); *xg[k] = d_tab.p + (reinterpret_cast<size_t>(*xg[k]) - 1); }
-    }
-    {
-        auto fixd = [&](const double*& p) { if (p) p = d_tab.p + (reinterpret_cast<size_t>(p) - 1); };
-        auto fixi = [&](const int32_t*& p) { if (p) p = reinterpret_cast<const int32_t*>(d_tab.p + (reinterpret_cast<size_t>(p) - 1)); };
-        fixd(dt_.surface_density); fixd(dt_.pvtw);
-        fixi(dt_.oil_node_ptr); fixd(dt_.oil_rs); fixd(dt_.oil_psat); fixd(dt_.oil_invb_sat); fixd(dt_.oil_invbmu_sat);
-        fixi(dt_.oil_col_ptr); fixd(dt_.oil_col_p); fixd(dt_.oil_col_invb); fixd(dt_.oil_col_invbmu);
-        fixi(dt_.gas_node_ptr); fixd(dt_.gas_pg); fixd(dt_.gas_rvsat); fixd(dt_.gas_invb_sat); fixd(dt_.gas_invbmu_sat);
-        fixi(dt_.gas_col_ptr); fixd(dt_.gas_col_rv); fixd(dt_.gas_col_invb); fixd(dt_.gas_col_invbmu);
-        fixi(dt_.swof_ptr); fixd(dt_.swof_sw); fixd(dt_.swof_krw); fixd(dt_.swof_krow); fixd(dt_.swof_pcow);
-        fixi(dt_.sgof_ptr); fixd(dt_.sgof_sg); fixd(dt_.sgof_krg); fixd(dt_.sgof_krog); fixd(dt_.sgof_pcgo);
-        if (t->rocktab_n > 0) { fixd(dt_.rocktab_p); fixd(dt_.rocktab_pvmult); fixd(dt_.rocktab_transmult); }
-        else { dt_.rocktab_p = nullptr; dt_.rocktab_pvmult = nullptr; dt_.rocktab_transmult = nullptr; }
-    }
+    // the device-pointer form for the kernels off the Newton path, which read the blob where it lies
+    dtp_ = dto_;
+    auto rb = [&](auto*& p) { rebase(p, d_tab.p); };
+    for_each_table(dtp_, rb, rb);
     // unscaled end points of every saturation region (what opm-material's EclEpsScalingPointsInfo::extractUnscaled reads off the
     // tables): Swl Swcr Swu Sowcr Sgl Sgcr Sgu Sogcr
     h_unscaled.assign(8 * size_t(ns), 0.0);
@@ -1290,7 +1218,7 @@ void BlackoilDevice::rebuild_structure()
         // per region: unscaled fixed points of every curve (u0 | u1); per cell: the maps and the vertical factors (build_eps_planes)
         // A set of curves WITHOUT scaled end points keeps the saturation exactly (S_u = 0 + (S - 0) * 1: states that sit on a table
         // breakpoint must not move by an ulp), so its region table is zero and build_eps_planes writes s0 = 0, k = 1.
-        const int ns = dt_.n_sat_regions;
+        const int ns = dto_.t.n_sat_regions;
         auto region_table = [&](bool have_points) {
             std::vector<double> ureg(size_t(kEpsRegion) * ns, 0.0);
             for (int r = 0; r < ns && have_points; ++r) {
@@ -1412,7 +1340,7 @@ __device__ double table_inverse(const double* __restrict__ x, const double* __re
 }
 // EclDefaultMaterial::updateHysteresis ("inconsistent" form: krnSw = 1 - So / 1 - Sg) + EclHysteresisTwoPhaseLawParams::update +
 // updateDynamicParams_ (Carlson shift: delta = Sw_imb(krn_drain(mdc)) - mdc), one thread per cell
-__global__ __launch_bounds__(kBlock) void k_hyst_update(int nb, int nbp, opmgpu_tables T, const int32_t* __restrict__ satnum, const int32_t* __restrict__ imbnum,
+__global__ __launch_bounds__(kBlock) void k_hyst_update(int nb, int nbp, DevTables D, const int32_t* __restrict__ satnum, const int32_t* __restrict__ imbnum,
                                                         const double* __restrict__ so, const double* __restrict__ sg, const double* __restrict__ eps,
                                                         const double* __restrict__ ieps, const double* __restrict__ ureg, const double* __restrict__ iureg,
                                                         double* __restrict__ hist, int force)
@@ -1427,6 +1355,7 @@ __global__ __launch_bounds__(kBlock) void k_hyst_update(int nb, int nbp, opmgpu_
         if (1.0 - sgc < mgo) { mgo = 1.0 - sgc; upd = true; }
     }
     if (!upd) return;
+    const opmgpu_tables& T = D.t;
     const int sreg = satnum[c], ireg = imbnum[c];
     EpsD E, EI;
     eps_load(eps, ureg, nbp, c, sreg, E);
@@ -1434,14 +1363,14 @@ __global__ __launch_bounds__(kBlock) void k_hyst_update(int nb, int nbp, opmgpu_
     double dow = 0.0, dgo = 0.0, f, df;
     if (mow < 2.0) {
         const int wa = T.swof_ptr[sreg], wi = T.swof_ptr[ireg];
-        sat_curve<false>(T.swof_sw + wa, T.swof_krow + wa, T.swof_ptr[sreg + 1] - wa, mow, E, EC_KROW, f, df);
+        sat_curve_s<false>(T.swof_sw + wa, T.swof_krow + wa, D.x.swof_dkrow + wa, T.swof_ptr[sreg + 1] - wa, mow, E, EC_KROW, f, df);
         const double ku = f / EI.v[EC_KROW];
         if (ku > 0.0) dow = eps_unmap(EI, EC_KROW, table_inverse(T.swof_sw + wi, T.swof_krow + wi, T.swof_ptr[ireg + 1] - wi, ku, false)) - mow;
     }
     if (mgo < 2.0) {
         const int ga = T.sgof_ptr[sreg], gi = T.sgof_ptr[ireg];
         const double sgm = 1.0 - mgo;
-        sat_curve<true>(T.sgof_sg + ga, T.sgof_krg + ga, T.sgof_ptr[sreg + 1] - ga, sgm, E, EC_KRG, f, df);
+        sat_curve_s<true>(T.sgof_sg + ga, T.sgof_krg + ga, D.x.sgof_dkrg + ga, T.sgof_ptr[sreg + 1] - ga, sgm, E, EC_KRG, f, df);
         const double ku = f / EI.v[EC_KRG];
         if (ku > 0.0) dgo = sgm - eps_unmap(EI, EC_KRG, table_inverse(T.sgof_sg + gi, T.sgof_krg + gi, T.sgof_ptr[ireg + 1] - gi, ku, true));
     }
@@ -1452,7 +1381,7 @@ int BlackoilDevice::update_hysteresis()
 {
     if (!use_hyst) return OPMGPU_OK;
     if (!has_state) return OPMGPU_EINVAL;
-    hipLaunchKernelGGL(k_hyst_update, dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, ls.plan.nbp, dt_, d_satnum.p, d_imbnum.p, d_so.p, d_sg.p,
+    hipLaunchKernelGGL(k_hyst_update, dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, ls.plan.nbp, dtp_, d_satnum.p, d_imbnum.p, d_so.p, d_sg.p,
                        (const double*)d_eps.p, (const double*)d_ieps.p, (const double*)d_eps_u0.p, (const double*)d_ieps_u0.p, d_hist.p, 0);
     return OPMGPU_OK;
 }
@@ -1464,7 +1393,7 @@ int BlackoilDevice::set_hysteresis(const double* mdc_ow, const double* mdc_go)
     for (int r = 0; r < P.nbp; ++r) { hp[r] = r < nc ? mdc_ow[P.nat[r]] : 2.0; hp[size_t(P.nbp) + r] = r < nc ? mdc_go[P.nat[r]] : 2.0; }
     d_hist.upload(hp, stream);
     // the shifts follow from the history
-    hipLaunchKernelGGL(k_hyst_update, dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, P.nbp, dt_, d_satnum.p, d_imbnum.p, d_so.p, d_sg.p,
+    hipLaunchKernelGGL(k_hyst_update, dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, P.nbp, dtp_, d_satnum.p, d_imbnum.p, d_so.p, d_sg.p,
                        (const double*)d_eps.p, (const double*)d_ieps.p, (const double*)d_eps_u0.p, (const double*)d_ieps_u0.p, d_hist.p, 1);
     OPMGPU_HIP(hipStreamSynchronize(stream));
     return OPMGPU_OK;
@@ -1791,14 +1720,14 @@ void BlackoilDevice::attach_comm(CommBase* c, int n_owned)
 void BlackoilDevice::perf_props_device()
 {
     if (nperf == 0) return;
-    hipLaunchKernelGGL(k_perf_props, dim3(grid_for(nperf)), dim3(kBlock), 0, stream, nperf, DevTables{ dt_, dx_ }, d_perf_cells.p, d_pvtnum.p, d_satnum.p,
+    hipLaunchKernelGGL(k_perf_props, dim3(grid_for(nperf)), dim3(kBlock), 0, stream, nperf, dtp_, d_perf_cells.p, d_pvtnum.p, d_satnum.p,
                        d_p.p, d_sw.p, d_sg.p, d_rs.p, d_rv.p, d_hc.p, eps_planes(), d_eps_u0.p, d_somax.p, long(ls.plan.nbp), d_perf.p, hyst_args());
 }
 
 void BlackoilDevice::perf_pvt_device(const double* press_dev, double* out_dev, const int32_t* gate)
 {
     if (nperf == 0) return;
-    hipLaunchKernelGGL(k_perf_pvt, dim3(grid_for(nperf)), dim3(kBlock), 0, stream, nperf, dt_, d_perf_cells.p, d_pvtnum.p, d_so.p, d_rs.p, d_rv.p, d_hc.p,
+    hipLaunchKernelGGL(k_perf_pvt, dim3(grid_for(nperf)), dim3(kBlock), 0, stream, nperf, dtp_, d_perf_cells.p, d_pvtnum.p, d_so.p, d_rs.p, d_rv.p, d_hc.p,
                        d_somax.p, press_dev, gate, out_dev);
 }
 
@@ -1836,7 +1765,7 @@ void BlackoilDevice::average_b(double* B3)
 void BlackoilDevice::perf_props(double* out)
 {
     if (nperf == 0) return;
-    hipLaunchKernelGGL(k_perf_props, dim3(grid_for(nperf)), dim3(kBlock), 0, stream, nperf, DevTables{ dt_, dx_ }, d_perf_cells.p, d_pvtnum.p, d_satnum.p,
+    hipLaunchKernelGGL(k_perf_props, dim3(grid_for(nperf)), dim3(kBlock), 0, stream, nperf, dtp_, d_perf_cells.p, d_pvtnum.p, d_satnum.p,
                        d_p.p, d_sw.p, d_sg.p, d_rs.p, d_rv.p, d_hc.p, eps_planes(), d_eps_u0.p, d_somax.p, long(ls.plan.nbp), d_perf.p, hyst_args());
     OPMGPU_HIP(hipMemcpyAsync(out, d_perf.p, size_t(nperf) * OPMGPU_PERF_K * sizeof(double), hipMemcpyDeviceToHost, stream));
     OPMGPU_HIP(hipStreamSynchronize(stream));
@@ -1931,7 +1860,8 @@ void BlackoilDevice::update_state(const double* dx_host, double relax)
     if (dx_host) { ls.vec_from_host<double>(dx_host, VEC_EQUATION_MAJOR, d_dx.p); OPMGPU_HIP(hipStreamSynchronize(stream)); has_dx = true; }   // caller's buffer: done with it on return
     KtScope kts(ls.kt, KT_UPDATE_STATE);
     if (device_wells) wells_update(relax, dx_host != nullptr);          // updateWellState from the recovered (and possibly relaxed) well increment
-    hipLaunchKernelGGL(k_update_state, dim3(grid_for(nc)), dim3(kBlock), tab_lds_bytes(), stream, nc, P.nbp, dt_, d_pvtnum.p, d_satnum.p, d_dx.p, relax,
+    auto kern = tab_lds_words() > 0 ? k_update_state<true> : k_update_state<false>;
+    hipLaunchKernelGGL(kern, dim3(grid_for(nc)), dim3(kBlock), tab_lds_bytes(), stream, nc, P.nbp, dto_, d_pvtnum.p, d_satnum.p, d_dx.p, relax,
                        prm.dp_max_rel, prm.ds_max, prm.dr_max_rel, d_p.p, d_sw.p, d_so.p, d_sg.p, d_rs.p, d_rv.p, d_hc.p, eps_planes(), d_eps_u0.p, d_somax.p,
                        (const double*)d_tab.p, tab_lds_words());
 }
@@ -1981,7 +1911,7 @@ void BlackoilDevice::fluid_in_place(const int32_t* fipnum, int dims, double* fip
 {
     const Plan& P = ls.plan;
     DevArray<double> dout; dout.alloc(size_t(8) * nc);
-    hipLaunchKernelGGL(k_fip_cells, dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, DevTables{ dt_, dx_ }, ls.dp.nat.p, d_pvtnum.p, d_satnum.p, d_pv.p,
+    hipLaunchKernelGGL(k_fip_cells, dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, dtp_, ls.dp.nat.p, d_pvtnum.p, d_satnum.p, d_pv.p,
                        d_p.p, d_sw.p, d_so.p, d_sg.p, d_rs.p, d_rv.p, d_hc.p, eps_planes(), d_eps_u0.p, d_somax.p, long(P.nbp), dout.p, hyst_args());
     std::vector<double> h(size_t(8) * nc);
     dout.download(h.data(), h.size(), stream);
@@ -2062,14 +1992,14 @@ void BlackoilDevice::region_state_sums(const int32_t* region, int nregions, doub
 void BlackoilDevice::voidage_coefficients(int n, const double* p, const double* rs, const double* rv, const int32_t* pvtreg, double* coeff)
 {
     if (n <= 0) return;
-    if (pvtreg) for (int i = 0; i < n; ++i) if (pvtreg[i] < 0 || pvtreg[i] >= dt_.n_pvt_regions) throw HipError(OPMGPU_EINVAL, "voidage_coefficients: PVT region out of range");
+    if (pvtreg) for (int i = 0; i < n; ++i) if (pvtreg[i] < 0 || pvtreg[i] >= dto_.t.n_pvt_regions) throw HipError(OPMGPU_EINVAL, "voidage_coefficients: PVT region out of range");
     DevArray<double> din, dout; DevArray<int32_t> dreg;
     std::vector<double> h(3 * size_t(n));
     std::copy(p, p + n, h.begin()); std::copy(rs, rs + n, h.begin() + n); std::copy(rv, rv + n, h.begin() + 2 * size_t(n));
     din.upload(h.data(), h.size(), stream);
     if (pvtreg) dreg.upload(pvtreg, size_t(n), stream);
     dout.alloc(3 * size_t(n));
-    hipLaunchKernelGGL(k_voidage_coeff, dim3(grid_for(n)), dim3(kBlock), 0, stream, n, dt_, din.p, din.p + n, din.p + 2 * size_t(n),
+    hipLaunchKernelGGL(k_voidage_coeff, dim3(grid_for(n)), dim3(kBlock), 0, stream, n, dtp_, din.p, din.p + n, din.p + 2 * size_t(n),
                        pvtreg ? (const int32_t*)dreg.p : (const int32_t*)nullptr, dout.p);
     dout.download(coeff, 3 * size_t(n), stream);
     OPMGPU_HIP(hipStreamSynchronize(stream));

@@ -13,6 +13,8 @@
 namespace opmgpu {
 
 struct HystArgs;
+// The device form of the fluid tables: the caller's struct and, next to it, the per-segment slopes of its 1-D tables (TabX), every array
+// in one blob of 8-byte words (BlackoilDevice::d_tab).  The pointer fields hold device pointers, or word offsets into the blob.
 struct TabX {
     const double *swof_dkrw, *swof_dkrow, *swof_dpcow, *sgof_dkrg, *sgof_dkrog, *sgof_dpcgo;
     const double *oil_drs, *oil_dinvb_sat, *oil_dinvbmu_sat, *oil_col_dinvb, *oil_col_dinvbmu;
@@ -145,9 +147,8 @@ private:
     DevArray<int8_t> d_saved_hc;
     const double* eps_planes() const { return use_eps ? d_eps.p : nullptr; }
     // device: tables
-    opmgpu_tables dt_;                       // same struct, device pointers
-    TabX dx_;                                // per-segment slopes of the 1-D tables (device pointers into the same blob)
-    DevTables dto_;                          // tables + slopes with WORD OFFSETS into the blob in the pointer fields (resolve_tables)
+    DevTables dto_;                          // pointer fields = WORD OFFSETS into the blob: for the kernels that may stage it in LDS (resolve_tables)
+    DevTables dtp_;                          // pointer fields = device pointers into the blob: for every other kernel
     DevArray<double> d_tab;                  // all table arrays in one blob of 8-byte words (staged in LDS by the property kernels)
     int tab_words = 0;
     static constexpr int kTabLdsMaxBytes = 24 * 1024;     // 6 workgroups x 24 KiB fit the 160 KiB LDS of a CU: no occupancy lost

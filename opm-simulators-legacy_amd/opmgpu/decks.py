@@ -143,8 +143,9 @@ class FluidTables:
         return self._struct
 
 
-def satfunc_standard_tables(pc_scale=1.0, **extra):
-    """PROPS of the reference's tests/satfuncStandard.DATA (METRIC); extra = vappars= / rocktab= passed on to FluidTables."""
+def satfunc_standard_tables(pc_scale=1.0, regions=1, **extra):
+    """PROPS of the reference's tests/satfuncStandard.DATA (METRIC); extra = vappars= / rocktab= passed on to FluidTables.
+    regions > 1: that many identical PVT and saturation regions (same answers in every region, a larger table set)."""
     pvto = [[(0, [(1., 1.0000, 1.20)]), (20, [(40., 1.0120, 1.17)]), (40, [(80., 1.0255, 1.14)]),
              (60, [(120., 1.0380, 1.11)]), (80, [(160., 1.0510, 1.08)]), (100, [(200., 1.0630, 1.06)]),
              (120, [(240., 1.0750, 1.03)]), (140, [(280., 1.0870, 1.00)]), (160, [(320., 1.0985, .98)]),
@@ -158,8 +159,8 @@ def satfunc_standard_tables(pc_scale=1.0, **extra):
     swof = [[(a, b, c, d * pc_scale) for a, b, c, d in swof[0]]]
     sgof = [[(a, b, c, d * pc_scale) for a, b, c, d in sgof[0]]]
     # DENSITY 700 1000 1 is (oil, water, gas); ours is (water, oil, gas)
-    return FluidTables(density_wog=[[1000.0, 700.0, 1.0]], pvtw=[[1.0, 1.0, 4.0e-5, 0.96, 0.0]],
-                       pvto=pvto, pvtg=pvtg, swof=swof, sgof=sgof, rock=(1.0, 5.0e-5), **extra)
+    return FluidTables(density_wog=[[1000.0, 700.0, 1.0]] * regions, pvtw=[[1.0, 1.0, 4.0e-5, 0.96, 0.0]] * regions,
+                       pvto=pvto * regions, pvtg=pvtg * regions, swof=swof * regions, sgof=sgof * regions, rock=(1.0, 5.0e-5), **extra)
 
 
 def fluid_data_tables():

@@ -645,3 +645,53 @@ def test_compute_fluid_in_place(gpu_lib, oracle):
     out = np.zeros((2, 7))
     assert m.lib.opmgpu_compute_fluid_in_place(m.ctx, capi.iptr(fipnum), 2, None, capi.dptr(out)) == capi.EINVAL
     m.close()
+
+
+def test_table_set_too_large_for_lds(gpu_lib):
+    """A table set past the 24 KiB the property kernels stage in LDS: they then read the tables from the device blob instead, a path
+    of its own in the value pass, the row assembly and updateState.  24 IDENTICAL PVT and saturation regions with random PVTNUM / SATNUM
+    must give what the single-region set gives, whatever path reads them: Jacobian and residual within RTOL_JAC, the updated state
+    within the bounds of test_update_state_parity with hc exactly equal, the perforation PVT and the voidage coefficients within
+    RTOL_JAC (f64 evaluation of equal tables: what may differ is FMA contraction between the instantiations)."""
+    R = 24
+    one, many = decks.satfunc_standard_tables(), decks.satfunc_standard_tables(regions=R)
+    # the device blob holds at least the caller's float64 arrays (then the index arrays and the slopes)
+    assert sum(a.nbytes for a in vars(many).values() if isinstance(a, np.ndarray) and a.dtype == np.float64) > 24 * 1024
+    assert sum(a.nbytes for a in vars(one).values() if isinstance(a, np.ndarray)) * 2 < 24 * 1024      # the single set fits, slopes included
+    g1 = decks.cartesian_grid(7, 6, 5, lognormal_sigma=0.7)
+    nc = g1.nc
+    rng = np.random.default_rng(12)
+    gR = decks.GridData(nc, g1.conn_cells, g1.trans, g1.pv, g1.z, gravity=g1.gravity, dims=g1.dims,
+                        pvtnum=rng.integers(0, R, nc), satnum=rng.integers(0, R, nc))
+    assert len(set(gR.pvtnum)) > 1 and len(set(gR.satnum)) > 1 and (gR.pvtnum != gR.satnum).any()
+    wells = (np.array([0, 3, 8], np.int32), np.array([2, 32, 62, 27, 57, 87, 117, 147], np.int32))
+    prm = capi.default_params()
+    n = 16
+    vp, vrs, vrv = capi.f64((60 + 380 * rng.random(n)) * decks.BAR), capi.f64(250 * rng.random(n)), capi.f64(5e-4 * rng.random(n))
+    for seed in (1, 2):
+        st = decks.random_state(g1, one, seed=seed)
+        dx = np.concatenate([rng.standard_normal(nc) * 30 * decks.BAR, rng.standard_normal(nc) * 0.25,
+                             rng.standard_normal(nc) * np.where(st.hc == capi.HC_OIL_ONLY, 30.0, np.where(st.hc == capi.HC_GAS_ONLY, 1e-4, 0.25))])
+        dx[rng.random(3 * nc) < 0.1] = 0.0
+        press = (60 + 380 * rng.random(8)) * decks.BAR
+        got = []
+        for grid, tab in ((g1, one), (gR, many)):
+            m = GpuBlackoilModel(grid, tab, prm, wells=wells)
+            m.prepareStep(3 * decks.DAY, st)
+            m.assemble(True)
+            jac, res = m.jacobian()[2], m.residual()
+            b, rs_sat, rv_sat = m.perfPvtAt(press)
+            coeff = np.zeros((n, 3))
+            reg = capi.i32(rng.integers(0, tab.n_pvt, n))
+            m._chk(m.lib.opmgpu_voidage_coefficients(m.ctx, n, capi.dptr(vp), capi.dptr(vrs), capi.dptr(vrv), capi.iptr(reg), capi.dptr(coeff)))
+            m.updateState(dx)
+            got.append((jac, res, np.column_stack([b, rs_sat, rv_sat]), coeff, m.getState()))
+            m.close()
+        (j1, r1, pvt1, c1, s1), (jR, rR, pvtR, cR, sR) = got
+        assert rel_err(jR, j1) < RTOL_JAC and rel_err(rR, r1) < RTOL_JAC, seed
+        for k in range(5):
+            assert rel_err(pvtR[:, k], pvt1[:, k]) < RTOL_JAC, (seed, k)
+        assert rel_err(cR, c1) < RTOL_JAC, seed
+        assert np.array_equal(sR.hc, s1.hc)
+        assert np.allclose(sR.p, s1.p, rtol=1e-14, atol=0) and np.allclose(sR.sat, s1.sat, rtol=0, atol=1e-14)
+        assert np.allclose(sR.rs, s1.rs, rtol=1e-13, atol=1e-13) and np.allclose(sR.rv, s1.rv, rtol=1e-13, atol=1e-18)
