@@ -117,8 +117,9 @@ private:
     void wells_update(double relax, bool dx_from_host);
     void wells_stabilize(int sor, double omega);
     void wells_connection_pressures(const int32_t* gate);
-    void wells_save();
-    void wells_restore();
+    void wells_saved_state(bool restore);
+    void wells_save() { wells_saved_state(false); }
+    void wells_restore() { wells_saved_state(true); }
     void wells_rebind();
     void wells_free();
     void vfp_free();

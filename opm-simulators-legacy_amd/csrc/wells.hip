@@ -14,7 +14,7 @@
 // One workgroup per well; derivatives by a small forward-AD type (the work is O(nperf), AD costs nothing here).
 // Round 2: the control logic of the reference runs on the device too --
 //   updateWellControls / updateWellStateWithTarget   StandardWells_impl.hpp:709-800 / :1452-1550   (k_well_controls)
-//   solveWellEq (explicit well pre-solve, default on) BlackoilModelBase_impl.hpp:1018-1133          (k_well_assemble<PRE> + k_well_presolve_step)
+//   solveWellEq (explicit well pre-solve, default on) BlackoilModelBase_impl.hpp:1018-1133          (k_well_presolve_fused / _serial / k_well_assemble<PRE> + k_well_presolve_step)
 //   THP control through VFP tables                   :655-700, :895-960; VFPProd/InjPropertiesLegacy.cpp   (vfp_* below)
 //   PVT at the average well-block pressure           :218-296                                       (k_well_avg_press + k_perf_pvt)
 //   RESERVOIR_RATE conversion coefficients          RateConverterLegacy.hpp:495-548, :718-768        (k_voidage_coeff, region_state_sums in blackoil.hip)
@@ -344,15 +344,18 @@ __device__ void well_apply_increment(const WellArgs& A, int w, const double dy[4
     }
 }
 
-// flags[]: 0 = error bits (2: singular D, 4: no consistent control, 8: NaN / too large well residual), 1 = pre-solve done,
-// 2 = pre-solve converged, 3 = pre-solve iterations
+// flags[]: 0 = error bits (WE_*), 1 = pre-solve done, 2 = pre-solve converged, 3 = pre-solve iterations
 enum { WF_ERR = 0, WF_DONE, WF_CONV, WF_ITS, WF_COUNT };
+// error bits: singular D of a well; updateWellControls found no consistent control; NaN / too large well residual in the pre-solve; the
+// fused pre-solve's barrier gave up (presolve_barrier raises it, k_well_presolve_serial consumes it).  All but the first are what the
+// reference reports as a NumericalIssue.
+enum { WE_SINGULAR = 2, WE_NO_CONTROL = 4, WE_BAD_RESIDUAL = 8, WE_BARRIER = 16, WE_NUMERICAL = WE_NO_CONTROL | WE_BAD_RESIDUAL | WE_BARRIER };
 
 __global__ void k_well_controls(int nw, WellArgs A, int32_t* __restrict__ flags)
 {
     const int w = blockIdx.x * blockDim.x + threadIdx.x;
     if (w >= nw) return;
-    if (!well_update_controls(A, w)) atomicOr(&flags[WF_ERR], 4);
+    if (!well_update_controls(A, w)) atomicOr(&flags[WF_ERR], WE_NO_CONTROL);
 }
 
 // 4x4 inverse with partial pivoting (D of one well); returns false when singular
@@ -516,7 +519,7 @@ __device__ void well_assemble_dev(const WellArgs& A, int w, const int32_t* __res
             D[12] = ds[0]; D[13] = ds[1]; D[14] = ds[2]; D[15] = 0.0;
         }
         double Di[16];
-        if (!inv4(D, Di)) { atomicOr(&flags[WF_ERR], 2); for (int k = 0; k < 16; ++k) Di[k] = 0.0; }
+        if (!inv4(D, Di)) { atomicOr(&flags[WF_ERR], WE_SINGULAR); for (int k = 0; k < 16; ++k) Di[k] = 0.0; }
         for (int k = 0; k < 16; ++k) { wl[20 + k] = Di[k]; A.Dinv[16 * w + k] = Di[k]; }
         if (!PRE) for (int k = 0; k < 4; ++k) A.ctrl_row[4 * w + k] = D[12 + k];      // gradient of the control equation (bordered pressure system, linsolver.hip)
         for (int k = 0; k < 4; ++k) {
@@ -575,6 +578,85 @@ __global__ __launch_bounds__(kBlock) void k_well_assemble(WellArgs A, const int3
     well_assemble_dev<MS, PRE>(A, blockIdx.x, slice_ptr, nlower, s0, s1, s2, R, Amat, rhs_extra, flags, A.wellE + 4 * blockIdx.x, false);
 }
 
+// ---- the explicit well pre-solve (solveWellEq, BlackoilModelBase_impl.hpp:1018-1133) -----------------------------------------------
+// Three forms of one loop -- assemble every well with the reservoir frozen, ONE convergence decision from all wells' residuals, a Newton
+// step of every well -- that share the pieces below and so give the same bits (tests/test_gpu_wells.py, tests/test_gpu_well_sizes.py).
+// bsums = sums of 1/b per phase, ncells = their cell count (B_avg = bsums / ncells)
+struct PresolveParams { const double* bsums; double ncells, tol_wells, tol_ctrl, max_resid, dbhp_max_rel; int max_it; };
+
+struct LoadPlain { __device__ double operator()(const double* p) const { return *p; } };
+// residuals published by other workgroups of a running grid
+struct LoadAgent { __device__ double operator()(const double* p) const { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); } };
+
+// getWellConvergence (:1866-1950) over the residuals E[nw][4] of all wells: B_avg * max |flux eq| < tolerance_wells and max |control eq| <
+// tolerance_well_control; NaN or above max_residual_allowed is a NumericalIssue (:1909-1923).  Called by ALL threads of a workgroup, reduced
+// by its first wavefront (maxima are exact: the lane count does not show in the bits).  Returns 0 continue, 1 converged, 2 numerical failure.
+template <class Load>
+__device__ int presolve_verdict(int nw, const double* E, const PresolveParams& S, Load load)
+{
+    __shared__ int verdict;
+    if (threadIdx.x < 64) {
+        double mx[4] = { 0, 0, 0, 0 }; int bad = 0;
+        for (int v = threadIdx.x; v < nw; v += 64) for (int k = 0; k < 4; ++k) { const double e = fabs(load(&E[4 * v + k])); if (!(e == e)) bad = 1; mx[k] = fmax(mx[k], e); }
+        for (int k = 0; k < 4; ++k) mx[k] = wave_max(mx[k]);
+        bad = __any(bad);
+        if (threadIdx.x == 0) {
+            bool conv = true, toolarge = false;
+            for (int a = 0; a < 3; ++a) { const double wf = (S.bsums[a] / S.ncells) * mx[a]; conv = conv && wf < S.tol_wells; toolarge = toolarge || wf > S.max_resid || !(wf == wf); }
+            conv = conv && mx[3] < S.tol_ctrl;
+            verdict = (bad || toolarge) ? 2 : (conv ? 1 : 0);
+        }
+    }
+    __syncthreads();
+    return verdict;
+}
+// y = D^-1 r of well w
+__device__ __forceinline__ void well_dinv_mul(const WellArgs& A, int w, const double r[4], double y[4])
+{
+    const double* Di = A.Dinv + 16 * w;
+    for (int k = 0; k < 4; ++k) { double d = 0.0; for (int c = 0; c < 4; ++c) d += Di[4 * k + c] * r[c]; y[k] = d; }
+}
+// the Newton step of one well (:1063-1097; the well equations of different wells are independent while the reservoir is frozen):
+// dy = D^-1 E, updateWellState, updateWellControls
+__device__ void presolve_newton_step(const WellArgs& A, int w, const double* E, double dbhp_max_rel, int32_t* __restrict__ flags)
+{
+    const double r[4] = { E[0], E[1], E[2], E[3] };
+    double dy[4];
+    well_dinv_mul(A, w, r, dy);
+    well_apply_increment(A, w, dy, dbhp_max_rel);
+    if (!well_update_controls(A, w)) atomicOr(&flags[WF_ERR], WE_NO_CONTROL);
+}
+// the end of the pre-solve after `it` steps, by ONE thread: verdict 1 or 2 of presolve_verdict, or 0 = max_it steps taken without either
+__device__ void presolve_finish(int32_t* __restrict__ flags, int verdict, int it)
+{
+    if (verdict == 2) atomicOr(&flags[WF_ERR], WE_BAD_RESIDUAL);
+    flags[WF_CONV] = verdict == 1 ? 1 : 0; flags[WF_ITS] = it; flags[WF_DONE] = 1;
+}
+
+// The well state in one place: six arrays of doubles, in the order of AdaptiveTimeStepping's saved copy (wells_saved_state), and `current`.
+// The pre-solve changes four of them: its snapshot ("if (!converged) well_state = well_state0", :1124-1126) is those four in the same order,
+// wstate[4 nw] | thp[nw] | perf_rates[3 np] | perf_press[np], with `current` in isnap.
+constexpr int kWellStateParts = 6;
+struct WellStatePart { double* p; int len; bool presolve; };
+struct WellStateLayout { WellStatePart part[kWellStateParts]; };
+__host__ __device__ inline WellStateLayout well_state_layout(const WellArgs& A, int nw, int np)
+{
+    return { { { A.wstate, 4 * nw, true }, { A.thp, nw, true }, { A.cdp, np, false }, { A.perf_rates, 3 * np, true }, { A.perf_press, np, true },
+               { A.perf_dens, np, false } } };
+}
+// snapshot (restore: put back) of element i of every part the pre-solve changes; i runs up to max(4 nw, 3 np)
+__device__ __forceinline__ void presolve_snapshot(const WellArgs& A, int nw, int np, double* __restrict__ snap, int32_t* __restrict__ isnap, bool restore, int i)
+{
+    const WellStateLayout L = well_state_layout(A, nw, np);
+    int off = 0;
+    for (int k = 0; k < kWellStateParts; ++k) {
+        if (!L.part[k].presolve) continue;
+        if (i < L.part[k].len) { if (restore) L.part[k].p[i] = snap[off + i]; else snap[off + i] = L.part[k].p[i]; }
+        off += L.part[k].len;
+    }
+    if (i < nw) { if (restore) A.current[i] = isnap[i]; else isnap[i] = A.current[i]; }
+}
+
 // The whole pre-solve loop in ONE launch when the wells fit one resident grid (one workgroup per well, nw <= kFusedWells): per
 // iteration every workgroup assembles its well, publishes its four residuals, all meet at a counter barrier, every workgroup takes
 // the SAME convergence decision from all wells' residuals and updates its own well.  The residual buffer alternates with the iteration
@@ -601,52 +683,22 @@ __device__ __forceinline__ bool presolve_barrier(int32_t* counter, int target, i
     return ok != 0;
 }
 __global__ __launch_bounds__(kBlock) void k_well_presolve_fused(int nw, WellArgs A, const int32_t* __restrict__ slice_ptr, const int16_t* __restrict__ nlower,
-                                                                const double* __restrict__ bsums, double ncells, double tol_wells, double tol_ctrl,
-                                                                double max_resid, double dbhp_max_rel, int max_it, int32_t* __restrict__ flags,
-                                                                int32_t* __restrict__ counter, double* __restrict__ Ebuf /* [2][nw][4] */)
+                                                                PresolveParams S, int32_t* __restrict__ flags, int32_t* __restrict__ counter,
+                                                                double* __restrict__ Ebuf /* [2][nw][4] */)
 {
     const int w = blockIdx.x, tid = threadIdx.x;
-    __shared__ int decision;         // 0 continue, 1 converged, 2 numerical failure
-    int it = 0;
-    for (;;) {
-        double* Eme = Ebuf + (size_t(it & 1) * nw + w) * 4;
+    const bool writer = w == 0 && tid == 0;         // every workgroup reaches the same end; one thread of the grid writes it down
+    for (int it = 0;;) {
+        double* Eall = Ebuf + size_t(it & 1) * nw * 4;
+        double* Eme = Eall + 4 * size_t(w);
         well_assemble_dev<double, true>(A, w, slice_ptr, nlower, 1.0, 1.0, 1.0, nullptr, (double*)nullptr, nullptr, flags, Eme, true);
         if (!presolve_barrier(counter, nw * (it + 1), flags)) return;
-        // getWellConvergence over all wells (every workgroup computes the same numbers)
-        if (tid < 64) {
-            double mx[4] = { 0, 0, 0, 0 }; int bad = 0;
-            const double* Eall = Ebuf + size_t(it & 1) * nw * 4;
-            for (int v = tid; v < nw; v += 64) for (int k = 0; k < 4; ++k) {
-                const double e = fabs(__hip_atomic_load(&Eall[4 * v + k], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-                if (!(e == e)) bad = 1; mx[k] = fmax(mx[k], e);
-            }
-            for (int k = 0; k < 4; ++k) mx[k] = wave_max(mx[k]);
-            bad = __any(bad);
-            if (tid == 0) {
-                bool conv = true, toolarge = false;
-                for (int a = 0; a < 3; ++a) { const double wf = (bsums[a] / ncells) * mx[a]; conv = conv && wf < tol_wells; toolarge = toolarge || wf > max_resid || !(wf == wf); }
-                conv = conv && mx[3] < tol_ctrl;
-                decision = (bad || toolarge) ? 2 : (conv ? 1 : 0);
-            }
-        }
-        __syncthreads();
-        const int dec = decision;
-        if (dec != 0) {
-            if (w == 0 && tid == 0) { if (dec == 2) atomicOr(&flags[WF_ERR], 8); flags[WF_CONV] = dec == 1 ? 1 : 0; flags[WF_ITS] = it; flags[WF_DONE] = 1; }
-            return;
-        }
+        const int verdict = presolve_verdict(nw, Eall, S, LoadAgent());
+        if (verdict != 0) { if (writer) presolve_finish(flags, verdict, it); return; }
         ++it;
-        if (tid == 0) {
-            const double* Di = A.Dinv + 16 * w;
-            double E[4], dy[4];
-            for (int k = 0; k < 4; ++k) E[k] = Eme[k];
-            for (int k = 0; k < 4; ++k) { dy[k] = 0.0; for (int c = 0; c < 4; ++c) dy[k] += Di[4 * k + c] * E[c]; }
-            well_apply_increment(A, w, dy, dbhp_max_rel);
-            if (!well_update_controls(A, w)) atomicOr(&flags[WF_ERR], 4);
-            __threadfence();
-        }
+        if (tid == 0) { presolve_newton_step(A, w, Eme, S.dbhp_max_rel, flags); __threadfence(); }
         __syncthreads();
-        if (it >= max_it) { if (w == 0 && tid == 0) { flags[WF_CONV] = 0; flags[WF_ITS] = it; flags[WF_DONE] = 1; } return; }
+        if (it >= S.max_it) { if (writer) presolve_finish(flags, 0, it); return; }
     }
 }
 
@@ -655,64 +707,36 @@ __global__ void k_well_flag_or(int32_t* f, int bits) { atomicOr(f, bits); }
 // the kernel's own occupancy (fused_presolve_capacity) -- other streams' and other processes' kernels give their slots back, but slowly enough
 // under co-tenancy (several ranks rehearsing on one GPU) for a workgroup's bounded spin to give up (error bit 16).  That is a SCHEDULING
 // condition, not a numerical one: this kernel, launched right behind the fused one, does nothing unless bit 16 is up; then it clears the
-// bit, restores the well state the pre-solve started from and runs the whole loop (the same arithmetic: assemble every well, one decision
-// from all residuals, update every well) inside ONE workgroup, wells one after the other.  Slow, correct, and never a NumericalIssue.
+// bit, restores the well state the pre-solve started from and runs the whole loop inside ONE workgroup, wells one after the other.  Slow,
+// correct, and never a NumericalIssue.
 __global__ __launch_bounds__(kBlock) void k_well_presolve_serial(int nw, int np, WellArgs A, const int32_t* __restrict__ slice_ptr, const int16_t* __restrict__ nlower,
-                                                                 const double* __restrict__ bsums, double ncells, double tol_wells, double tol_ctrl,
-                                                                 double max_resid, double dbhp_max_rel, int max_it, int32_t* __restrict__ flags,
-                                                                 const double* __restrict__ snap, const int32_t* __restrict__ isnap, double* __restrict__ Ebuf /* [nw][4] */)
+                                                                 PresolveParams S, int32_t* __restrict__ flags, double* __restrict__ snap,
+                                                                 int32_t* __restrict__ isnap, double* __restrict__ Ebuf /* [nw][4] */)
 {
     const int tid = threadIdx.x;
-    __shared__ int go, decision;
-    if (tid == 0) go = (flags[WF_ERR] & 16) ? 1 : 0;
+    __shared__ int go;
+    if (tid == 0) go = (flags[WF_ERR] & WE_BARRIER) ? 1 : 0;
     __syncthreads();
     if (!go) return;
-    // back to the state the pre-solve started from (layout of snap: k_well_snapshot)
-    {
-        double* parts[4] = { A.wstate, A.thp, A.perf_rates, A.perf_press };
-        const int len[4] = { 4 * nw, nw, 3 * np, np };
-        int off = 0;
-        for (int k = 0; k < 4; ++k) { for (int i = tid; i < len[k]; i += kBlock) parts[k][i] = snap[off + i]; off += len[k]; }
-        for (int i = tid; i < nw; i += kBlock) A.current[i] = isnap[i];
-        if (tid == 0) { flags[WF_ERR] = isnap[nw] & ~16; flags[WF_DONE] = 0; flags[WF_CONV] = 0; flags[WF_ITS] = 0; }     // the whole word as snapshot before the fused attempt
-    }
+    for (int i = tid; i < max(4 * nw, 3 * np); i += kBlock) presolve_snapshot(A, nw, np, snap, isnap, true, i);
+    // the whole error word as snapshot before the fused attempt (isnap[nw]): a half-run attempt may have left control-switch / assembly bits
+    // behind that are not the pre-solve's verdict
+    if (tid == 0) { flags[WF_ERR] = isnap[nw] & ~WE_BARRIER; flags[WF_DONE] = 0; flags[WF_CONV] = 0; flags[WF_ITS] = 0; }
     __threadfence();
     __syncthreads();
-    for (int it = 0;; ) {
+    for (int it = 0;;) {
         for (int w = 0; w < nw; ++w) {
             well_assemble_dev<double, true>(A, w, slice_ptr, nlower, 1.0, 1.0, 1.0, nullptr, (double*)nullptr, nullptr, flags, Ebuf + 4 * size_t(w), false);
             __threadfence();
             __syncthreads();
         }
-        if (tid < 64) {
-            double mx[4] = { 0, 0, 0, 0 }; int bad = 0;
-            for (int v = tid; v < nw; v += 64) for (int k = 0; k < 4; ++k) { const double e = fabs(Ebuf[4 * v + k]); if (!(e == e)) bad = 1; mx[k] = fmax(mx[k], e); }
-            for (int k = 0; k < 4; ++k) mx[k] = wave_max(mx[k]);
-            bad = __any(bad);
-            if (tid == 0) {
-                bool conv = true, toolarge = false;
-                for (int a = 0; a < 3; ++a) { const double wf = (bsums[a] / ncells) * mx[a]; conv = conv && wf < tol_wells; toolarge = toolarge || wf > max_resid || !(wf == wf); }
-                conv = conv && mx[3] < tol_ctrl;
-                decision = (bad || toolarge) ? 2 : (conv ? 1 : 0);
-            }
-        }
-        __syncthreads();
-        const int dec = decision;
-        if (dec != 0) {
-            if (tid == 0) { if (dec == 2) atomicOr(&flags[WF_ERR], 8); flags[WF_CONV] = dec == 1 ? 1 : 0; flags[WF_ITS] = it; flags[WF_DONE] = 1; }
-            return;
-        }
+        const int verdict = presolve_verdict(nw, Ebuf, S, LoadPlain());
+        if (verdict != 0) { if (tid == 0) presolve_finish(flags, verdict, it); return; }
         ++it;
-        for (int w = tid; w < nw; w += kBlock) {
-            const double* Di = A.Dinv + 16 * w;
-            double dy[4];
-            for (int k = 0; k < 4; ++k) { dy[k] = 0.0; for (int c = 0; c < 4; ++c) dy[k] += Di[4 * k + c] * Ebuf[4 * w + c]; }
-            well_apply_increment(A, w, dy, dbhp_max_rel);
-            if (!well_update_controls(A, w)) atomicOr(&flags[WF_ERR], 4);
-        }
+        for (int w = tid; w < nw; w += kBlock) presolve_newton_step(A, w, Ebuf + 4 * size_t(w), S.dbhp_max_rel, flags);
         __threadfence();
         __syncthreads();
-        if (it >= max_it) { if (tid == 0) { flags[WF_CONV] = 0; flags[WF_ITS] = it; flags[WF_DONE] = 1; } return; }
+        if (it >= S.max_it) { if (tid == 0) presolve_finish(flags, 0, it); return; }
     }
 }
 // how many workgroups of the fused pre-solve the device holds at once (occupancy query x compute units, halved as a margin for the side
@@ -727,65 +751,26 @@ static int fused_presolve_capacity()
     return cap = std::max(0, (ncu * per_cu) / 2);
 }
 
-// one step of the pre-solve loop (BlackoilModelBase_impl.hpp:1063-1097), ONE workgroup for all wells: getWellConvergence over all
-// wells (B_avg * max |flux eq| < tolerance_wells, max |control eq| < tolerance_well_control); if not converged every well takes the
-// Newton update dy = D^-1 E of its own 4x4 system (the well equations of different wells are independent while the reservoir is
-// frozen), updateWellState, updateWellControls.  bsums = sums of 1/b per phase, ncells = their cell count.
-__global__ __launch_bounds__(kBlock) void k_well_presolve_step(int nw, WellArgs A, const double* __restrict__ bsums, double ncells, double tol_wells,
-                                                               double tol_ctrl, double max_resid, double dbhp_max_rel, int max_it, int32_t* __restrict__ flags)
+// one step of the pre-solve loop behind k_well_assemble<double, true>, ONE workgroup for all wells; the iteration count lives in
+// flags[WF_ITS] between the launches, and every launch is a no-op once flags[WF_DONE] is up
+__global__ __launch_bounds__(kBlock) void k_well_presolve_step(int nw, WellArgs A, PresolveParams S, int32_t* __restrict__ flags)
 {
     if (flags[WF_DONE]) return;
-    __shared__ double sm[16];
-    __shared__ int bad;
     const int tid = threadIdx.x;
-    if (tid == 0) bad = 0;
-    __syncthreads();
-    double mx[4] = { 0, 0, 0, 0 };
-    for (int w = tid; w < nw; w += kBlock) for (int k = 0; k < 4; ++k) { const double e = fabs(A.wellE[4 * w + k]); if (!(e == e)) bad = 1; mx[k] = fmax(mx[k], e); }
-    for (int k = 0; k < 4; ++k) {
-        const double m = wave_max(mx[k]);
-        if ((tid & 63) == 0) sm[4 * k + (tid >> 6)] = m;
-    }
-    __syncthreads();
-    bool conv = true, toolarge = false;
-    for (int a = 0; a < 3; ++a) {
-        const double wf = (bsums[a] / ncells) * fmax(fmax(sm[4 * a], sm[4 * a + 1]), fmax(sm[4 * a + 2], sm[4 * a + 3]));
-        conv = conv && wf < tol_wells;
-        toolarge = toolarge || wf > max_resid || !(wf == wf);
-    }
-    conv = conv && fmax(fmax(sm[12], sm[13]), fmax(sm[14], sm[15])) < tol_ctrl;
-    if (bad || toolarge) {          // NaN / too large well residual: NumericalIssue (:1909-1923), reported by opmgpu_well_convergence
-        if (tid == 0) { atomicOr(&flags[WF_ERR], 8); flags[WF_DONE] = 1; flags[WF_CONV] = 0; }
-        return;
-    }
-    if (conv) { if (tid == 0) { flags[WF_DONE] = 1; flags[WF_CONV] = 1; } return; }
-    for (int w = tid; w < nw; w += kBlock) {
-        const double* Di = A.Dinv + 16 * w; const double* E = A.wellE + 4 * w;
-        double dy[4];
-        for (int k = 0; k < 4; ++k) { dy[k] = 0.0; for (int c = 0; c < 4; ++c) dy[k] += Di[4 * k + c] * E[c]; }
-        well_apply_increment(A, w, dy, dbhp_max_rel);
-        if (!well_update_controls(A, w)) atomicOr(&flags[WF_ERR], 4);
-    }
-    if (tid == 0) { const int it = flags[WF_ITS] + 1; flags[WF_ITS] = it; if (it >= max_it) flags[WF_DONE] = 1; }
+    const int verdict = presolve_verdict(nw, A.wellE, S, LoadPlain());
+    if (verdict != 0) { if (tid == 0) presolve_finish(flags, verdict, flags[WF_ITS]); return; }
+    for (int w = tid; w < nw; w += kBlock) presolve_newton_step(A, w, A.wellE + 4 * size_t(w), S.dbhp_max_rel, flags);
+    if (tid == 0) { const int it = flags[WF_ITS] + 1; if (it >= S.max_it) presolve_finish(flags, 0, it); else flags[WF_ITS] = it; }
 }
 
-// well state snapshot / restore around the pre-solve ("if (!converged) well_state = well_state0", :1124-1126); layout of snap:
-// wstate[4 nw] | thp[nw] | perf_rates[3 np] | perf_press[np], current in isnap
+// snapshot of the well state before the pre-solve / restore after one that did not converge
 __global__ __launch_bounds__(kBlock) void k_well_snapshot(int nw, int np, WellArgs A, double* __restrict__ snap, int32_t* __restrict__ isnap, int restore,
                                                           const int32_t* __restrict__ flags)
 {
     if (restore && flags[WF_CONV]) return;          // a converged pre-solve keeps its solution
     const int i = blockIdx.x * kBlock + threadIdx.x;
-    double* parts[4] = { A.wstate, A.thp, A.perf_rates, A.perf_press };
-    const int len[4] = { 4 * nw, nw, 3 * np, np };
-    int off = 0;
-    for (int k = 0; k < 4; ++k) {
-        if (i < len[k]) { if (restore) parts[k][i] = snap[off + i]; else snap[off + i] = parts[k][i]; }
-        off += len[k];
-    }
-    if (i < nw) { if (restore) A.current[i] = isnap[i]; else isnap[i] = A.current[i]; }
-    // the error word as it stood before the pre-solve (isnap[nw]): the serial fallback puts it back WHOLE -- a half-run fused attempt may have
-    // left control-switch / assembly bits behind that are not the pre-solve's verdict
+    presolve_snapshot(A, nw, np, snap, isnap, restore != 0, i);
+    // the error word as it stood before the pre-solve: the serial fallback puts it back WHOLE
     if (!restore && i == 0) isnap[nw] = flags[WF_ERR];
 }
 
@@ -804,8 +789,9 @@ __global__ __launch_bounds__(kBlock) void k_well_recover(WellArgs A, const doubl
     }
     block_sum<4>(acc, sm);
     if (tid == 0) {
-        const double* Di = A.Dinv + 16 * w; const double* E = A.wellE + 4 * w;
-        for (int k = 0; k < 4; ++k) { double d = 0.0; for (int c = 0; c < 4; ++c) d += Di[4 * k + c] * (E[c] - acc[c]); A.wdy[4 * w + k] = d; }
+        const double* E = A.wellE + 4 * w;
+        const double r[4] = { E[0] - acc[0], E[1] - acc[1], E[2] - acc[2], E[3] - acc[3] };
+        well_dinv_mul(A, w, r, A.wdy + 4 * w);
     }
 }
 // stabilizeNonlinearUpdate on the well part: dy_old <- dy; dy <- omega dy (+ (1 - omega) previous dy_old for SOR)
@@ -1095,7 +1081,7 @@ void BlackoilDevice::wells_assemble(bool initial)
             OPMGPU_HIP(hipMemsetAsync(W.flags.p + WF_DONE, 0, 3 * sizeof(int32_t), stream));
             binv_sums_device(W.bsums.p, W.bscratch.p);
             const double ncg = ls.comm ? double(ls.comm->n_owned_global) : double(nc);
-            const int max_it = 15;
+            const PresolveParams S = { W.bsums.p, ncg, prm.tolerance_wells, prm.tolerance_well_control, prm.max_residual_allowed, prm.dbhp_max_rel, 15 };
             // OPMGPU_WELL_PRESOLVE_FUSED: 1 (default) one launch with a counter barrier; 0 two launches per iteration; 2 (tests) the serial
             // fallback that takes over when the fused kernel's barrier gives up.  Read per call: once per time step.
             const char* fenv = std::getenv("OPMGPU_WELL_PRESOLVE_FUSED");
@@ -1104,21 +1090,19 @@ void BlackoilDevice::wells_assemble(bool initial)
                 // one launch: one workgroup per well, counter barrier per iteration -- all nw workgroups fit the device together
                 // (fused_presolve_capacity: the kernel's occupancy x compute units, with a margin)
                 W.presolve_sync.alloc(4 + 8 * size_t(W.nw)); W.presolve_sync.zero(stream);
-                if (fmode == 2) hipLaunchKernelGGL(k_well_flag_or, dim3(1), dim3(1), 0, stream, W.flags.p + WF_ERR, 16 | 4);      // (tests) the give-up bit AND a stray control bit of a half-run attempt: the fallback must wipe both
+                // (tests) the give-up bit AND a stray control bit of a half-run attempt: the fallback must wipe both
+                if (fmode == 2) hipLaunchKernelGGL(k_well_flag_or, dim3(1), dim3(1), 0, stream, W.flags.p + WF_ERR, WE_BARRIER | WE_NO_CONTROL);
                 else
-                hipLaunchKernelGGL(k_well_presolve_fused, dim3(W.nw), dim3(kBlock), 0, stream, W.nw, A, ls.dp.slice_ptr.p, ls.dp.nlower.p, (const double*)W.bsums.p, ncg,
-                                   prm.tolerance_wells, prm.tolerance_well_control, prm.max_residual_allowed, prm.dbhp_max_rel, max_it, W.flags.p,
+                hipLaunchKernelGGL(k_well_presolve_fused, dim3(W.nw), dim3(kBlock), 0, stream, W.nw, A, ls.dp.slice_ptr.p, ls.dp.nlower.p, S, W.flags.p,
                                    reinterpret_cast<int32_t*>(W.presolve_sync.p), W.presolve_sync.p + 4);
                 // does nothing unless the barrier gave up (error bit 16): then the loop once more from the snapshot, in one workgroup
-                hipLaunchKernelGGL(k_well_presolve_serial, dim3(1), dim3(kBlock), 0, stream, W.nw, np, A, ls.dp.slice_ptr.p, ls.dp.nlower.p, (const double*)W.bsums.p, ncg,
-                                   prm.tolerance_wells, prm.tolerance_well_control, prm.max_residual_allowed, prm.dbhp_max_rel, max_it, W.flags.p,
-                                   (const double*)W.snap.p, (const int32_t*)W.isnap.p, W.presolve_sync.p + 4);
+                hipLaunchKernelGGL(k_well_presolve_serial, dim3(1), dim3(kBlock), 0, stream, W.nw, np, A, ls.dp.slice_ptr.p, ls.dp.nlower.p, S, W.flags.p,
+                                   W.snap.p, W.isnap.p, W.presolve_sync.p + 4);
             } else
-            for (int it = 0; it <= max_it; ++it) {
+            for (int it = 0; it <= S.max_it; ++it) {
                 hipLaunchKernelGGL((k_well_assemble<double, true>), dim3(W.nw), dim3(kBlock), 0, stream, A, ls.dp.slice_ptr.p, ls.dp.nlower.p, sc[0], sc[1], sc[2],
                                    (double*)nullptr, (double*)nullptr, (double*)nullptr, W.flags.p);
-                hipLaunchKernelGGL(k_well_presolve_step, dim3(1), dim3(kBlock), 0, stream, W.nw, A, (const double*)W.bsums.p, ncg, prm.tolerance_wells,
-                                   prm.tolerance_well_control, prm.max_residual_allowed, prm.dbhp_max_rel, max_it, W.flags.p);
+                hipLaunchKernelGGL(k_well_presolve_step, dim3(1), dim3(kBlock), 0, stream, W.nw, A, S, W.flags.p);
             }
             // converged: connection pressures from the new well state (:1122); otherwise the well state is restored (:1124-1126)
             wells_connection_pressures(W.flags.p + WF_CONV);
@@ -1157,8 +1141,8 @@ __global__ __launch_bounds__(kBlock) void k_well_conv_pack(int nw, const double*
     if (threadIdx.x == 0) {
         for (int k = 0; k < 6; ++k) out[k] = fmax(fmax(sm[0][k], sm[1][k]), fmax(sm[2][k], sm[3][k]));
         const int32_t fl = flags ? flags[0] : 0;
-        if (fl & (4 | 8 | 16)) out[4] = 1.0;
-        if (fl & 2) out[5] = 1.0;
+        if (fl & WE_NUMERICAL) out[4] = 1.0;
+        if (fl & WE_SINGULAR) out[5] = 1.0;
         if (fl) flags[0] = 0;
     }
 }
@@ -1210,8 +1194,8 @@ int BlackoilDevice::well_convergence(double* flux3, double* ctrl)
             const double e = std::fabs(W.h_pinned[4 * w + 3]); if (!(e == e)) bad = true; c = std::max(c, e);
         }
         if (fl) OPMGPU_HIP(hipMemsetAsync(W.flags.p + WF_ERR, 0, sizeof(int32_t), stream));
-        if (fl & 2) singular = true;
-        if (fl & (4 | 8 | 16)) bad = true;  // no consistent control / NaN or too large residual in the pre-solve / its barrier gave up: NumericalIssue
+        if (fl & WE_SINGULAR) singular = true;
+        if (fl & WE_NUMERICAL) bad = true;
     }
     if (ls.comm) {      // collective: every rank calls it, also the ones without wells
         double loc[6] = { f[0], f[1], f[2], c, bad ? 1.0 : 0.0, singular ? 1.0 : 0.0 };
@@ -1256,29 +1240,20 @@ void BlackoilDevice::wells_update(double relax, bool dx_from_host)
     W.dy_valid = false;
 }
 
-// device-side last_state of AdaptiveTimeStepping: wstate | thp | cdp | perf_rates | perf_press | perf_dens, current
-void BlackoilDevice::wells_save()
+// device-side last_state of AdaptiveTimeStepping: every part of the well state and `current`, saved or (restore) put back
+void BlackoilDevice::wells_saved_state(bool restore)
 {
-    if (!wd) return;
+    if (!wd || (restore && !wd->saved.p)) return;
     WellsDev& W = *wd;
-    const size_t nw = size_t(W.nw), np = W.h_cells.size();
-    W.saved.alloc(5 * nw + 6 * np);
-    double* parts[6] = { W.wstate.p, W.thp.p, W.cdp.p, W.perf_rates.p, W.perf_press.p, W.perf_dens.p };
-    const size_t len[6] = { 4 * nw, nw, np, 3 * np, np, np };
+    const int nw = W.nw, np = int(W.h_cells.size());
+    if (!restore) W.saved.alloc(5 * size_t(nw) + 6 * size_t(np));
+    auto copy = [&](void* state, void* saved, size_t bytes) {
+        OPMGPU_HIP(hipMemcpyAsync(restore ? state : saved, restore ? saved : state, bytes, hipMemcpyDeviceToDevice, stream));
+    };
+    const WellStateLayout L = well_state_layout(args_of(W, vfp, ls.plan.nbp, d_perf.p, gravity), nw, np);
     size_t off = 0;
-    for (int k = 0; k < 6; ++k) { OPMGPU_HIP(hipMemcpyAsync(W.saved.p + off, parts[k], len[k] * sizeof(double), hipMemcpyDeviceToDevice, stream)); off += len[k]; }
-    OPMGPU_HIP(hipMemcpyAsync(W.isaved.p, W.current.p, nw * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
-}
-void BlackoilDevice::wells_restore()
-{
-    if (!wd || !wd->saved.p) return;
-    WellsDev& W = *wd;
-    const size_t nw = size_t(W.nw), np = W.h_cells.size();
-    double* parts[6] = { W.wstate.p, W.thp.p, W.cdp.p, W.perf_rates.p, W.perf_press.p, W.perf_dens.p };
-    const size_t len[6] = { 4 * nw, nw, np, 3 * np, np, np };
-    size_t off = 0;
-    for (int k = 0; k < 6; ++k) { OPMGPU_HIP(hipMemcpyAsync(parts[k], W.saved.p + off, len[k] * sizeof(double), hipMemcpyDeviceToDevice, stream)); off += len[k]; }
-    OPMGPU_HIP(hipMemcpyAsync(W.current.p, W.isaved.p, nw * sizeof(int32_t), hipMemcpyDeviceToDevice, stream));
+    for (const WellStatePart& part : L.part) { copy(part.p, W.saved.p + off, part.len * sizeof(double)); off += part.len; }
+    copy(W.current.p, W.isaved.p, nw * sizeof(int32_t));
 }
 
 int BlackoilDevice::well_controls_set(const int32_t* current, const double* thp)

@@ -245,6 +245,79 @@ def test_well_presolve_forms_agree(gpu_lib, monkeypatch, case):
         assert np.array_equal(a[5].p, b[5].p) and np.array_equal(a[5].sat, b[5].sat), mode
 
 
+# bhp step limit of test_well_presolve_without_convergence
+PRESOLVE_DBHP_MAX_REL = 1e-4
+
+
+@pytest.mark.parametrize("name", ["presolve_switch", "many65"])
+def test_well_presolve_without_convergence(gpu_lib, oracle, monkeypatch, name):
+    """solveWellEq that does NOT converge, in its three forms: the exit after max_it = 15 steps and "well_state = well_state0"
+    (BlackoilModelBase_impl.hpp:1124-1126).  dbhp_max_rel = 1e-4 lets the bottom-hole pressure move by 0.025 bar per step, so the rate
+    controlled injectors cannot reach their rates.  The host restatement (solve_well_eq, checked here too) returns (False, 15) with finite
+    residuals on both decks: last B_avg * max |flux eq| = 1.6e-2 on presolve_switch, 6.7e-2 on many65 (65 wells: one past the 64-lane stride
+    of the maxima loop), against tolerance_wells = 1e-4.  With 1e-3, the first value tried, presolve_switch converges in 10 iterations
+    (many65: (False, 15)); 5e-4 and 3e-4 give (False, 15) on both.
+    Every form must report not converged after 15 iterations, raise no error bit and leave the well state as it was.  bhp, qs, thp and
+    current are compared with the state handed to the device.  perf_rates and perf_press are rewritten by the assembly that follows the
+    pre-solve in the same call, from the restored state: they are compared with a run whose pre-solve is switched off
+    (solve_welleq_initially = 0), and so are the other four.  After the Newton update the three forms agree bit for bit."""
+    from test_wells_host import _limits_setup
+    import well_size_decks as D
+    if name == "many65":
+        deck = D.many_deck(65)
+        grid, tab, st, wl, dt = deck.grid, deck.tab, deck.st, deck.wl, deck.dt
+    else:
+        grid, tab, st, wl, _ = _limits_setup(inj_bhp_limit_bar=255.0)
+        dt = 5 * decks.DAY
+    rel = PRESOLVE_DBHP_MAX_REL
+    fields = ("bhp", "qs", "thp", "perf_rates", "perf_press", "current")
+
+    class Host(W.StandardWellsHost):
+        def solve_well_eq(self, *a, **kw):
+            self.presolve = super().solve_well_eq(*a, **kw)
+            self.presolve_residuals = np.concatenate([self.flux_eq.ravel(), self.ctrl_eq.ravel()])
+            return self.presolve
+
+    wh = Host(wl, grid.z, tab.surface_density[0], dbhp_max_rel=rel)
+    mo = W.WellCoupledModel(OracleBackend(oracle, grid, tab, capi.default_params(dbhp_max_rel=rel), wells=wl.arrays()), wh, W.WellState(wl, st.p))
+    mo.prepareStep(dt, st)
+    mo.assemble(True)
+    assert wh.presolve == (False, 15) and np.isfinite(wh.presolve_residuals).all(), wh.presolve
+
+    def first_assembly(mode, presolve=1):
+        monkeypatch.setenv("OPMGPU_WELL_PRESOLVE_FUSED", mode)
+        gm = GpuBlackoilModel(grid, tab, capi.default_params(linear_solver_reduction=1e-11, linear_solver_maxiter=2000, dbhp_max_rel=rel,
+                                                            solve_welleq_initially=presolve))
+        md = W.DeviceWellModel(gm, wl, W.WellState(wl, st.p))
+        md.prepareStep(dt, st)
+        gm.setSolvePrecision(False)
+        gm.assemble(True)
+        return gm, md, md.pull_well_state().copy()
+
+    gm, md, ref = first_assembly("1", presolve=0)
+    gm.close()
+    start = W.WellState(wl, st.p)
+    out = {}
+    for mode in ("1", "0", "2"):
+        gm, md, ws = first_assembly(mode)
+        assert not md.presolve_converged and md.presolve_iterations == 15, (mode, md.presolve_converged, md.presolve_iterations)
+        for f in ("bhp", "qs", "thp", "current"):
+            assert np.array_equal(getattr(ws, f), getattr(start, f)), (mode, f)
+        for f in fields:
+            assert np.array_equal(getattr(ws, f), getattr(ref, f)), (mode, f)
+        gm.getConvergence()
+        md.wellConvergence()                 # raises on a stray error bit (opmgpu_well_convergence != OPMGPU_OK)
+        gm.solveJacobianSystem(single_precision=False)
+        gm.updateState()
+        ws = md.pull_well_state()
+        out[mode] = ([getattr(ws, f).copy() for f in fields], gm.getState())
+        gm.close()
+    for mode in ("0", "2"):
+        a, b = out["1"], out[mode]
+        assert all(np.array_equal(x, y) for x, y in zip(a[0], b[0])), mode
+        assert np.array_equal(a[1].p, b[1].p) and np.array_equal(a[1].sat, b[1].sat), mode
+
+
 @pytest.mark.parametrize("gmres", [0, 1])
 def test_reference_cpr_formulation_with_device_wells(gpu_lib, gmres):
     """cpr_reference_transform on the model path with the device well model: the matrix, the wells' rank-7 rows P_w and the right-hand side are
