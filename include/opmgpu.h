@@ -449,6 +449,32 @@ int opmgpu_voidage_coefficients(opmgpu_ctx* ctx, int n, const double* p, const d
  * receives the global values (fip_cells: this rank's cells, zeros in the pv / weighted-pressure rows of its ghosts). */
 int opmgpu_compute_fluid_in_place(opmgpu_ctx* ctx, const int32_t* fipnum, int nregions, double* fip_cells, double* values);
 
+/* BlackoilModelBase's SimulatorData (BlackoilModelBase_impl.hpp:662-683, rq_[].b/rho/mu/kr; turned into named restart arrays by
+ * SimulatorFullyImplicitBlackoilOutput.hpp:512-567 and written per RPTRST mnemonic by getRestartData, :585-845) of the RESIDENT state,
+ * evaluated as the assembly evaluates it (end-point and vertical scaling, hysteresis, VAPPARS, ROCKTAB).  out is [OPMGPU_SIMDATA_K][nc],
+ * SI units, the same cells in the same order as opmgpu_get_state (decomposed runs: the rank's local cells; no communication):
+ *   b, rho, mu of water / oil / gas   rq_[phase].b / .rho (fluidDensity, :2009-2027) / .mu
+ *   kr                                rq_[phase].kr: the relative permeability itself, no transmissibility multiplier, not over mu
+ *   RSSAT, RVSAT                      sd_.rsSat = fluidRsSat(p_o, so), sd_.rvSat = fluidRvSat(p_g, so) (:662, :668): the saturated
+ *                                     ratios, VAPPARS factor included, of EVERY cell whatever its phase state; 0 without DISGAS / VAPOIL
+ *   PBUB, PDEW                        bubblePointPressure(rs), dewPointPressure(rv) of the solution state's rs / rv (:678-683,
+ *                                     BlackoilPropsAdFromDeck.cpp:959-1004).  The inversion itself is opm-material's; OUR rule: the
+ *                                     pressure at which the PVT region's plain tabulated saturated curve (piecewise linear, end segments
+ *                                     extrapolated, no VAPPARS factor) takes the value, first matching segment from the lowest pressure
+ *                                     upwards; 0 when no segment contains it, the segment is flat or the result is not finite, and 0
+ *                                     everywhere without DISGAS (PBUB) / VAPOIL (PDEW).
+ * One launch and one device-to-host copy on the context's stream; nothing an assembly relies on is touched.  OPMGPU_EINVAL for a NULL
+ * pointer or before a state has been set. */
+#define OPMGPU_SIMDATA_K 16
+enum {
+    OPMGPU_SD_BW = 0, OPMGPU_SD_BO, OPMGPU_SD_BG,                       /* "1OVERBW", "1OVERBO", "1OVERBG" */
+    OPMGPU_SD_WAT_DEN, OPMGPU_SD_OIL_DEN, OPMGPU_SD_GAS_DEN,            /* "WAT_DEN", "OIL_DEN", "GAS_DEN" */
+    OPMGPU_SD_WAT_VISC, OPMGPU_SD_OIL_VISC, OPMGPU_SD_GAS_VISC,         /* "WAT_VISC", "OIL_VISC", "GAS_VISC" */
+    OPMGPU_SD_WATKR, OPMGPU_SD_OILKR, OPMGPU_SD_GASKR,                  /* "WATKR", "OILKR", "GASKR" */
+    OPMGPU_SD_RSSAT, OPMGPU_SD_RVSAT, OPMGPU_SD_PBUB, OPMGPU_SD_PDEW    /* "RSSAT", "RVSAT", "PBUB", "PDEW" */
+};
+int opmgpu_get_simulator_data(opmgpu_ctx* ctx, double* out /* [OPMGPU_SIMDATA_K * nc] */);
+
 /* Maximum historical oil saturation per cell (BlackoilPropsAdFromDeck::satOilMax_, used by VAPPARS).
  * set: explicit values (nc, caller order; restart).  update: soMax = max(soMax, so of the resident state) --
  * what SimulatorBase_impl.hpp:192 does at the start of every report step (updateSatOilMax, :933-945).

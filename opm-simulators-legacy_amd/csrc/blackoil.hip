@@ -246,6 +246,41 @@ __device__ __forceinline__ double rv_sat_d(const DevTables& D, int reg, double p
     lin_at(D.t.gas_pg + a, D.t.gas_rvsat + a, D.x.gas_drvsat + a, pvt_seg(D.t.gas_pg + a, D.t.gas_node_ptr[reg + 1] - a, p), p, f, df);
     return f;
 }
+// Bubble- / dew-point pressure (BlackoilPropsAdFromDeck::bubblePointPressure / dewPointPressure, BlackoilPropsAdFromDeck.cpp:959-1004).  The
+// reference calls oilPvt() / gasPvt().saturationPressure of opm-material, which is not part of its tree, so the rule here is OURS: the
+// pressure at which the region's plain tabulated saturated curve y(x) (oil_rs over oil_psat, gas_rvsat over gas_pg; piecewise linear, the
+// end segments extrapolated, exactly what lin_at evaluates; no VAPPARS factor, which the reference applies outside the PVT object) takes
+// the value v.  The segments are scanned from the lowest pressure upwards, the first and the last unbounded on their outer side; the
+// first whose value range contains v gives x_i + (v - y_i) / slope_i.  0 -- the reference's "NumericalIssue: leave 0" -- when no
+// segment contains v, when that segment is flat, or when the result is not finite.
+__device__ __forceinline__ double sat_pressure(const double* __restrict__ x, const double* __restrict__ y, const double* __restrict__ dy, int n, double v)
+{
+    for (int i = 0; i + 1 < n; ++i) {
+        const double y0 = y[i], y1 = y[i + 1];
+        const bool first = i == 0, last = i == n - 2;
+        bool in;
+        if (y1 > y0) in = (first || v >= y0) && (last || v <= y1);
+        else if (y1 < y0) in = (first || v <= y0) && (last || v >= y1);
+        else in = v == y0;
+        if (!in) continue;
+        if (y1 == y0 || dy[i] == 0.0) return 0.0;
+        const double r = x[i] + (v - y0) / dy[i];
+        return isfinite(r) ? r : 0.0;
+    }
+    return 0.0;
+}
+__device__ __forceinline__ double bubble_point_d(const DevTables& D, int reg, double rs)
+{
+    if (!D.t.has_disgas) return 0.0;        // dead oil has no saturation pressure
+    const int a = D.t.oil_node_ptr[reg];
+    return sat_pressure(D.t.oil_psat + a, D.t.oil_rs + a, D.x.oil_drs + a, D.t.oil_node_ptr[reg + 1] - a, rs);
+}
+__device__ __forceinline__ double dew_point_d(const DevTables& D, int reg, double rv)
+{
+    if (!D.t.has_vapoil) return 0.0;        // dry gas neither
+    const int a = D.t.gas_node_ptr[reg];
+    return sat_pressure(D.t.gas_pg + a, D.t.gas_rvsat + a, D.x.gas_drvsat + a, D.t.gas_node_ptr[reg + 1] - a, rv);
+}
 // b_w, b_o, b_g of a PVT region at (p, rs, rv), all phases at the SAME pressure; sat_o / sat_g: oil / gas from its saturated curve
 // (ConstantCompressibilityWaterPvt, LiveOilPvt, WetGasPvt: inverseFormationVolumeFactor / saturatedInverseFormationVolumeFactor)
 __device__ __forceinline__ void b_values(const DevTables& D, int preg, double p, double rs, double rv, bool sat_o, bool sat_g, double& bw, double& bo, double& bg)
@@ -274,10 +309,14 @@ struct CellEval {
     V4 b[3], mob[3], rho[3], accum[3];
     V4 pvm;              // pore-volume multiplier (poroMult)
 };
+// What the output record (k_simulator_data) takes of a cell beyond CellEval: values that are locals of eval_cell.  Only the OUTPUT
+// instantiation hands them out; the one on the Newton path neither computes nor carries anything for them.
+struct CellOutput { double mu[3], kr[3], rsSat, rvSat; };
 
 // SolutionState + ReservoirResidualQuant of one cell (BlackoilModelBase_impl.hpp:614-751, 1484-1497, 2009-2027)
+template <bool OUTPUT = false>
 __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int preg, int sreg, double p, double sw_, double sg_, double rs_, double rv_, int hc,
-                          CellEval& q, const HystD& H = HystD{ false, 0, 2.0, 2.0, 0.0, 0.0 }, const EpsD* EI = nullptr)
+                          CellEval& q, const HystD& H = HystD{ false, 0, 2.0, 2.0, 0.0, 0.0 }, const EpsD* EI = nullptr, CellOutput* out = nullptr)
 {
     const opmgpu_tables& T = DT.t; const TabX& X = DT.x;
     const bool isSg = hc == OPMGPU_HC_GAS_AND_OIL, isRs = hc == OPMGPU_HC_OIL_ONLY, isRv = hc == OPMGPU_HC_GAS_ONLY;
@@ -442,20 +481,26 @@ __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int
     q.accum[0] = aw;
     q.accum[1] = vadd(ao, vmul(q.rv, ag));
     q.accum[2] = vadd(ag, vmul(q.rs, ao));
+    if constexpr (OUTPUT) {
+        out->mu[0] = mu[0].v; out->mu[1] = mu[1].v; out->mu[2] = mu[2].v;
+        out->kr[0] = krw.v; out->kr[1] = kro.v; out->kr[2] = krg.v;
+        out->rsSat = rsSat.v; out->rvSat = rvSat.v;
+    }
 }
 // eval_cell of a row's cell with what surrounds it: the cell's end-point scaling, its hysteresis history and, with one, the end points of
 // its imbibition curves
+template <bool OUTPUT = false>
 __device__ __forceinline__ void eval_row(const DevTables& DT, int row, long nbp, double so_max, const int32_t* __restrict__ pvtnum, const int32_t* __restrict__ satnum,
                                          const double* __restrict__ p, const double* __restrict__ sw, const double* __restrict__ sg, const double* __restrict__ rs,
                                          const double* __restrict__ rv, const int8_t* __restrict__ hc, const double* __restrict__ eps, const double* __restrict__ eps_u0,
-                                         const HystArgs& hy, CellEval& q)
+                                         const HystArgs& hy, CellEval& q, CellOutput* out = nullptr)
 {
     EpsD E, EI;
     HystD H;
     eps_load(eps, eps_u0, nbp, row, satnum[row], E);
     hyst_load(hy.imbnum, hy.hist, nbp, row, H);
     if (H.on) eps_load(hy.ieps, hy.iureg, nbp, row, H.ireg, EI);
-    eval_cell(DT, E, so_max, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], q, H, &EI);
+    eval_cell<OUTPUT>(DT, E, so_max, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], q, H, &EI, out);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -934,6 +979,36 @@ __global__ __launch_bounds__(kBlock) void k_fip_cells(int nc, DevTables T, const
     out[0 * long(nc) + n] = fw; out[1 * long(nc) + n] = fo; out[2 * long(nc) + n] = fg;
     out[3 * long(nc) + n] = rs[c] * fo; out[4 * long(nc) + n] = rv[c] * fg;
     out[5 * long(nc) + n] = pv[c]; out[6 * long(nc) + n] = p[c]; out[7 * long(nc) + n] = so + sgv;
+}
+
+// BlackoilModelBase's SimulatorData, the per-cell output record of a report step (BlackoilModelBase_impl.hpp:662-683 and rq_[].b / rho /
+// mu / kr of the assembly; named in SimulatorFullyImplicitBlackoilOutput.hpp:512-567): eval_row of the RESIDENT state, so end-point and
+// vertical scaling, hysteresis, VAPPARS and ROCKTAB act as in the assembly.  kr is the relative permeability itself (no transmissibility
+// multiplier, not divided by the viscosity); RsSat / RvSat are the saturated values (VAPPARS factor included) of EVERY cell whatever its
+// phase state; Pb / Pd invert the plain curves at the solution state's rs / rv (sat_pressure).  OPMGPU_SIMDATA_K planes in the CALLER's
+// cell order: out[q * nc + nat[row]], slots OPMGPU_SD_* of opmgpu.h.  An output path: once per report step.
+__global__ __launch_bounds__(kBlock) void k_simulator_data(int nc, DevTables T, const int32_t* __restrict__ nat, const int32_t* __restrict__ pvtnum,
+                                                           const int32_t* __restrict__ satnum, const double* __restrict__ p, const double* __restrict__ sw,
+                                                           const double* __restrict__ sg, const double* __restrict__ rs, const double* __restrict__ rv,
+                                                           const int8_t* __restrict__ hc, const double* __restrict__ eps,
+                                                           const double* __restrict__ eps_u0, const double* __restrict__ somax, long nbp,
+                                                           double* __restrict__ out, HystArgs hy)
+{
+    const int c = blockIdx.x * kBlock + threadIdx.x;
+    if (c >= nc) return;
+    CellEval q;
+    CellOutput x;
+    eval_row<true>(T, c, nbp, somax[c], pvtnum, satnum, p, sw, sg, rs, rv, hc, eps, eps_u0, hy, q, &x);
+    const int preg = pvtnum[c];
+    double* o = out + nat[c];
+    const long n = nc;
+#pragma unroll
+    for (int ph = 0; ph < 3; ++ph) {
+        o[(OPMGPU_SD_BW + ph) * n] = q.b[ph].v; o[(OPMGPU_SD_WAT_DEN + ph) * n] = q.rho[ph].v;
+        o[(OPMGPU_SD_WAT_VISC + ph) * n] = x.mu[ph]; o[(OPMGPU_SD_WATKR + ph) * n] = x.kr[ph];
+    }
+    o[OPMGPU_SD_RSSAT * n] = x.rsSat; o[OPMGPU_SD_RVSAT * n] = x.rvSat;
+    o[OPMGPU_SD_PBUB * n] = bubble_point_d(T, preg, q.rs.v); o[OPMGPU_SD_PDEW * n] = dew_point_d(T, preg, q.rv.v);
 }
 
 // computePropertiesForWellConnectionPressures (StandardWells_impl.hpp:218-296): b_w, b_o, b_g, rsSat, rvSat of the perforated cells at
@@ -1902,6 +1977,16 @@ void BlackoilDevice::stabilize_update(int relax_type, double omega)
     if (device_wells) wells_stabilize(relax_type == OPMGPU_RELAX_SOR ? 1 : 0, omega);      // the well part first: it is recovered from the UNRELAXED dx
     hipLaunchKernelGGL(k_stabilize, dim3(unsigned((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream, n, relax_type == OPMGPU_RELAX_SOR ? 1 : 0, omega,
                        d_dx.p, d_dx_old.p);
+}
+
+// the output record of the resident state: one launch, one copy; reads the state and writes a buffer of its own, nothing else
+void BlackoilDevice::simulator_data(double* out)
+{
+    DevArray<double> dout; dout.alloc(size_t(OPMGPU_SIMDATA_K) * nc);
+    hipLaunchKernelGGL(k_simulator_data, dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, dtp_, ls.dp.nat.p, d_pvtnum.p, d_satnum.p,
+                       d_p.p, d_sw.p, d_sg.p, d_rs.p, d_rv.p, d_hc.p, eps_planes(), d_eps_u0.p, d_somax.p, long(ls.plan.nbp), dout.p, hyst_args());
+    dout.download(out, size_t(OPMGPU_SIMDATA_K) * nc, stream);
+    OPMGPU_HIP(hipStreamSynchronize(stream));
 }
 
 // computeFluidInPlace (BlackoilModelBase_impl.hpp:2263-2445, serial and parallel branch): per-cell volumes on the device, the region sums on the host

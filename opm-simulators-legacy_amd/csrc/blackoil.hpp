@@ -38,6 +38,7 @@ public:
     void set_state(const double* p, const double* sat, const double* rs, const double* rv, const int8_t* hc);
     void get_state(double* p, double* sat, double* rs, double* rv, int8_t* hc);
     void fluid_in_place(const int32_t* fipnum, int dims, double* fip_cells, double* values);      // computeFluidInPlace (:2263-2445)
+    void simulator_data(double* out);                                                              // SimulatorData of the resident state (:662-683, rq_[].b/rho/mu/kr)
     void region_state_sums(const int32_t* region, int nregions, double* sums);                   // RateConverter calcAverages (RateConverterLegacy.hpp:718-768)
     void voidage_coefficients(int n, const double* p, const double* rs, const double* rv, const int32_t* pvtreg, double* coeff);   // calcCoeff (:495-548)
     void assemble(double dt, bool initial);

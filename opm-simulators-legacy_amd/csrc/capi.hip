@@ -830,6 +830,11 @@ int opmgpu_compute_fluid_in_place(opmgpu_ctx* c, const int32_t* fipnum, int nreg
     if (fipnum) for (int i = 0; i < c->model->nc; ++i) if (fipnum[i] < 0 || fipnum[i] > nregions) return fail(c, OPMGPU_EINVAL, "fipnum outside [0, nregions]");
     return guarded(c, [&]() { c->model->fluid_in_place(fipnum, nregions, fip_cells, values); return int(OPMGPU_OK); });
 }
+int opmgpu_get_simulator_data(opmgpu_ctx* c, double* out)
+{
+    if (!c || !c->model || !out || !c->model->has_state) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { c->model->simulator_data(out); return int(OPMGPU_OK); });
+}
 
 int opmgpu_region_state_sums(opmgpu_ctx* c, const int32_t* region, int nregions, double* sums)
 {

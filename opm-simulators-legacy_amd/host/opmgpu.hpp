@@ -17,6 +17,7 @@
 #include <array>
 #include <cmath>
 #include <cstdint>
+#include <map>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -216,6 +217,18 @@ public:
         std::vector<std::vector<double>> values(dims, std::vector<double>(7));
         for (int r = 0; r < dims; ++r) for (int k = 0; k < 7; ++k) values[r][k] = flat[std::size_t(r) * 7 + k];
         return values;
+    }
+    /// BlackoilModelBase::getSimulatorData (sd_ of :662-683 and rq_[].b/rho/mu/kr) for the resident state: 16 per-cell arrays in SI under
+    /// the names of SimulatorFullyImplicitBlackoilOutput.hpp:512-567, in the cell order of the state
+    std::map<std::string, std::vector<double>> simulatorData()
+    {
+        static const char* const names[OPMGPU_SIMDATA_K] = { "1OVERBW", "1OVERBO", "1OVERBG", "WAT_DEN", "OIL_DEN", "GAS_DEN", "WAT_VISC", "OIL_VISC",
+                                                             "GAS_VISC", "WATKR", "OILKR", "GASKR", "RSSAT", "RVSAT", "PBUB", "PDEW" };
+        std::vector<double> flat(std::size_t(OPMGPU_SIMDATA_K) * nc_, 0.0);
+        throw_on_status(ctx_, opmgpu_get_simulator_data(ctx_, flat.data()));
+        std::map<std::string, std::vector<double>> sd;
+        for (int k = 0; k < OPMGPU_SIMDATA_K; ++k) sd[names[k]].assign(flat.begin() + std::ptrdiff_t(k) * nc_, flat.begin() + std::ptrdiff_t(k + 1) * nc_);
+        return sd;
     }
     void setStepLength(double dt) { dt_ = dt; }
     double relaxation() const { return current_relaxation_; }

@@ -19,6 +19,10 @@ K_SPMV, K_ILU_APPLY, K_ILU_FACTOR, K_ASSEMBLE, K_DOT, K_AXPY, K_PROPS, K_STREAM_
 KT_NAMES = ["cell_props", "flux", "wells", "convergence", "ilu0_factor", "cpr_setup", "spmv_fused_dot1", "spmv_fused_dot2", "ilu0_apply", "amg_vcycle",
             "cpr_other", "vector_updates", "update_state"]
 PERF_K = 36
+# slots of opmgpu_get_simulator_data (OPMGPU_SD_* of the header, in its order) under the reference's restart-array names
+SIMDATA_NAMES = ("1OVERBW", "1OVERBO", "1OVERBG", "WAT_DEN", "OIL_DEN", "GAS_DEN", "WAT_VISC", "OIL_VISC", "GAS_VISC",
+                 "WATKR", "OILKR", "GASKR", "RSSAT", "RVSAT", "PBUB", "PDEW")
+SIMDATA_K = len(SIMDATA_NAMES)
 UNIQUE_ID_BYTES = 128
 
 _dp = C.POINTER(C.c_double)
@@ -193,6 +197,7 @@ SIGNATURES = {
     "opmgpu_region_state_sums": (C.c_int, [C.c_void_p, _ip, C.c_int, _dp]),
     "opmgpu_voidage_coefficients": (C.c_int, [C.c_void_p, C.c_int, _dp, _dp, _dp, _ip, _dp]),
     "opmgpu_compute_fluid_in_place": (C.c_int, [C.c_void_p, _ip, C.c_int, _dp, _dp]),
+    "opmgpu_get_simulator_data": (C.c_int, [C.c_void_p, _dp]),
     "opmgpu_set_sat_oil_max": (C.c_int, [C.c_void_p, _dp]),
     "opmgpu_update_sat_oil_max": (C.c_int, [C.c_void_p]),
     "opmgpu_get_sat_oil_max": (C.c_int, [C.c_void_p, _dp]),

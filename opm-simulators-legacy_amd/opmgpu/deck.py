@@ -12,11 +12,12 @@ What `flow_legacy` gets from opm-parser + `DerivedGeology` (opm/autodiff/GeoProp
             only -- is the model the device implements)
   REGIONS   PVTNUM SATNUM IMBNUM FIPNUM (fluid-in-place regions of computeFluidInPlace; 1-based in the deck and in `fipnum()`)
   SOLUTION  PRESSURE SWAT SGAS RS RV (explicit initial state; EQUIL is outside the hot path)
+            RPTRST (the mnemonics that select derived per-cell arrays for the restart file, RPTRST_MNEMONICS; also read in SCHEDULE)
 
 Block-centred Cartesian geometry only (corner-point COORD/ZCORN needs opm-grid's processing, out of scope).  TPFA
 transmissibilities as `tpfa_htrans_compute` / `tpfa_trans_compute` do for such cells: half-transmissibility
 K A / (d/2) per side (horizontal ones times NTG, DerivedGeology :135-160), harmonic sum, times the MULT? of the face.
-Everything else (SCHEDULE, SUMMARY, report keywords) is skipped.  METRIC units only.
+Everything else (SUMMARY, other report keywords) is skipped; SCHEDULE is kept in deck order for opmgpu/schedule.py.  METRIC units only.
 """
 import re
 
@@ -28,6 +29,9 @@ from .decks import BAR, DAY, FluidTables, GridData, MD, State
 FLAG_KEYWORDS = {"RUNSPEC", "GRID", "EDIT", "PROPS", "REGIONS", "SOLUTION", "SUMMARY", "SCHEDULE", "END", "NOECHO", "ECHO", "OIL", "WATER",
                  "GAS", "DISGAS", "VAPOIL", "METRIC", "FIELD", "LAB", "FMTOUT", "FMTIN", "UNIFOUT", "UNIFIN", "RUNSUM", "SEPARATE", "ALL",
                  "INIT", "NOSIM", "ENDBOX", "EXCEL", "NOGGF", "NEWTRAN", "OLDTRAN"}
+# RPTRST mnemonics that select arrays of the model's output record (getRestartData, SimulatorFullyImplicitBlackoilOutput.hpp:585-845);
+# BASIC and every other mnemonic are not kept
+RPTRST_MNEMONICS = ("BW", "BO", "BG", "DEN", "VISC", "VWAT", "VOIL", "VGAS", "KRW", "KRO", "KRG", "RSSAT", "RVSAT", "PBPD")
 _KW = re.compile(r"^[A-Z][A-Z0-9_+\-]{0,7}$")
 EPS_NAMES = GridData.EPS_NAMES
 
@@ -68,10 +72,34 @@ def _value(tok):
         return tok
 
 
+def parse_rptrst(record):
+    """One RPTRST record -> {mnemonic: int} over RPTRST_MNEMONICS (absent = 0).  Items are NAME or NAME=int (also written NAME = int); a bare
+    name counts as 1.  A record of integers only (the old positional form) selects none of them."""
+    items, toks, i = {}, [str(t) for t in record if t is not None], 0
+    words = []
+    for t in toks:                       # 'DEN', 'BASIC=2', 'BASIC', '=', '2', 'BASIC=', '2', ...
+        words.extend(w for w in re.split(r"(=)", t) if w != "")
+    while i < len(words):
+        name = words[i].upper()
+        if i + 2 < len(words) and words[i + 1] == "=":
+            value, i = int(float(words[i + 2])), i + 3
+        else:
+            value, i = 1, i + 1
+        if name in RPTRST_MNEMONICS:
+            items[name] = value
+    return {k: items.get(k, 0) for k in RPTRST_MNEMONICS}
+
+
 class Deck:
-    def __init__(self, keywords, schedule=None):
+    def __init__(self, keywords, schedule=None, solution_rptrst=None):
         self.kw = keywords              # name -> list of records (each a list of values), last occurrence wins; BOX-scoped ones keep their box
         self.schedule = schedule or []  # SCHEDULE section in deck order: [(keyword, records)], every occurrence (opmgpu/schedule.py)
+        self._solution_rptrst = solution_rptrst      # records of the last RPTRST before SCHEDULE (self.kw keeps the deck's last one only)
+
+    def rptrst(self):
+        """The RPTRST mnemonics in force when the SCHEDULE begins (parse_rptrst; all 0 without the keyword)."""
+        recs = self._solution_rptrst
+        return parse_rptrst(recs[0] if recs else [])
 
     def has(self, name):
         return name in self.kw
@@ -591,6 +619,7 @@ def read_deck(path):
     box = None
     skip_line = False
     schedule, in_schedule = [], False
+    solution_rptrst = None
     for toks in lines:
         if not toks:
             continue
@@ -609,6 +638,8 @@ def read_deck(path):
                 in_schedule = True
             elif in_schedule:
                 schedule.append((name, cur["records"]))
+            elif name == "RPTRST":
+                solution_rptrst = cur["records"]
             toks = toks[1:]
             if name == "TITLE":
                 cur["closed"] = True
@@ -626,7 +657,7 @@ def read_deck(path):
             else:
                 cur["pending"].extend(_expand(t))
                 open_record = True
-    return Deck(kws, schedule)
+    return Deck(kws, schedule, solution_rptrst)
 
 
 def _is_data(tok):

@@ -15,9 +15,43 @@ import struct
 
 import numpy as np
 
-from .decks import BAR, DAY
+from .decks import BAR, CP, DAY
 
 _TYPES = {"INTE": (">i4", 4, 1000), "REAL": (">f4", 4, 1000), "DOUB": (">f8", 8, 1000), "LOGI": (">i4", 4, 1000), "CHAR": ("S8", 8, 105)}
+
+
+# getRestartData (SimulatorFullyImplicitBlackoilOutput.hpp:585-845): RPTRST mnemonic -> arrays of the model's output record, in the order it
+# inserts them.  VISC selects all three viscosities, VWAT / VOIL / VGAS one each.  RSSAT / RVSAT / PBPD need oil and gas both active, which
+# every deck read here has.
+RPTRST_ARRAYS = (("BW", ("1OVERBW",)), ("BO", ("1OVERBO",)), ("BG", ("1OVERBG",)), ("DEN", ("WAT_DEN", "OIL_DEN", "GAS_DEN")),
+                 ("VISC", ("WAT_VISC", "OIL_VISC", "GAS_VISC")), ("VWAT", ("WAT_VISC",)), ("VOIL", ("OIL_VISC",)), ("VGAS", ("GAS_VISC",)),
+                 ("KRW", ("WATKR",)), ("KRO", ("OILKR",)), ("KRG", ("GASKR",)), ("RSSAT", ("RSSAT",)), ("RVSAT", ("RVSAT",)),
+                 ("PBPD", ("PBUB", "PDEW")))
+_ARRAY_ORDER = ("1OVERBW", "1OVERBO", "1OVERBG", "WAT_DEN", "OIL_DEN", "GAS_DEN", "WAT_VISC", "OIL_VISC", "GAS_VISC", "WATKR", "OILKR", "GASKR",
+                "RSSAT", "RVSAT", "PBUB", "PDEW")
+
+
+def rptrst_arrays(mnemonics):
+    """names of the output-record arrays the RPTRST mnemonics {name: int} select (positive = on), in the order they go to the file"""
+    on = {a for m, arrays in RPTRST_ARRAYS if mnemonics.get(m, 0) > 0 for a in arrays}
+    return [a for a in _ARRAY_ORDER if a in on]
+
+
+def simdata_to_deck_units(name, values):
+    """an array of the output record from SI to the deck's (METRIC) units, as PRESSURE and RS go to the file: pressures in bar, viscosities
+    in cP; densities stay kg/m3, the ratios Sm3/Sm3, 1/B and kr are pure numbers"""
+    v = np.asarray(values, float)
+    if name in ("PBUB", "PDEW"):
+        return v / BAR
+    if name.endswith("_VISC"):
+        return v / CP
+    return v
+
+
+def restart_simulator_data(mnemonics, simulator_data):
+    """{array name: values in deck units} of what the mnemonics select from a model's simulatorData(), in file order: the leading part of
+    write_restart's `extra`"""
+    return {a: simdata_to_deck_units(a, simulator_data[a]) for a in rptrst_arrays(mnemonics)}
 
 
 def _record(f, payload):
@@ -158,7 +192,9 @@ class EclOutput:
 
     # ---------------------------------------------------------------- restart
     def write_restart(self, elapsed_days, state, extra=None, wells=None, well_state=None, next_step_days=None):
-        """one report step: PRESSURE [bar], SWAT, SGAS, RS, RV per ACTIVE cell (the solution section `compareECL` diffs).  With wells the
+        """one report step: PRESSURE [bar], SWAT, SGAS, RS, RV per ACTIVE cell (the solution section `compareECL` diffs), then `extra`
+        {keyword: per-cell array} in its order up to ENDSOL (the arrays RPTRST selects -- restart_simulator_data -- before SOMAX and the
+        hysteresis history, like getRestartData's).  With wells the
         header section also carries what a restarted run needs of the well state, like flow_legacy's OPM_XWEL / OPM_IWEL do -- under this
         library's own keywords, its own layout: OPMGWNAM (names), OPMGXWEL (per well bhp [Pa], thp [Pa], q_s[3] [m3/s], DOUB), OPMGIWEL
         (current control); OPMGDTNX = the time stepper's suggestion for the next sub-step [days] (flow_legacy's restarts begin with the
@@ -248,7 +284,8 @@ def compare(base_a, base_b, abs_tol=2e-2, rel_tol=1e-5, restart_keywords=("PRESS
     compareECLFiles.cmake:83-85: abs 2e-2, rel 1e-5 or 1e-2): every value of every solution array of every report step of the UNRST
     files, and every summary vector of every ministep of the UNSMRY files, may deviate by at most abs_tol OR by at most rel_tol of the
     larger magnitude (opm-common ECLFilesComparator: a deviation counts only when both are exceeded).  Returns the list of violations
-    [(file kind, keyword, occurrence, worst abs deviation, worst rel deviation)]; empty = the runs agree."""
+    [(file kind, keyword, occurrence, worst abs deviation, worst rel deviation)]; empty = the runs agree.  restart_keywords may name the
+    arrays RPTRST selects (1OVERBO, WAT_DEN, PBUB ...) as well."""
     import numpy as np
     bad = []
 

@@ -297,6 +297,15 @@ class GpuBlackoilModel(_CprDiagnostics):
         self._chk(self.lib.opmgpu_compute_fluid_in_place(self.ctx, capi.iptr(fn), dims, capi.dptr(fc), capi.dptr(values)))
         return (values, fc) if cells else values
 
+    def simulatorData(self):
+        """BlackoilModelBase's SimulatorData of the resident state (BlackoilModelBase_impl.hpp:662-683, rq_[].b/rho/mu/kr): dict of 16 [nc]
+        arrays in SI under the names SimulatorFullyImplicitBlackoilOutput.hpp:512-567 gives them -- 1OVERBW/BO/BG, WAT_/OIL_/GAS_DEN,
+        WAT_/OIL_/GAS_VISC, WATKR/OILKR/GASKR (kr itself, not the mobility), RSSAT, RVSAT (saturated, every cell), PBUB, PDEW -- in the
+        cell order of getState()."""
+        out = np.zeros((capi.SIMDATA_K, self.nc))
+        self._chk(self.lib.opmgpu_get_simulator_data(self.ctx, capi.dptr(out)))
+        return {name: out[k] for k, name in enumerate(capi.SIMDATA_NAMES)}
+
     def relativeChange(self):
         """BlackoilModelBase::relativeChange(saved, resident) (BlackoilModelBase_impl.hpp:1595-1631)."""
         v = C.c_double(0.0)

@@ -5,6 +5,8 @@ keywords a standard-well black-oil run needs:
   WCONPROD  name OPEN|SHUT mode ORAT WRAT GRAT LRAT RESV BHP THP VFP ALQ     WCONINJE  name phase OPEN|SHUT mode RATE RESV BHP THP VFP
   WELOPEN   name OPEN|SHUT|STOP [I J K]                            WELTARG  name ORAT|WRAT|GRAT|LRAT|BHP|THP|RATE value
   DATES / TSTEP (report steps), START (RUNSPEC)
+  RPTRST    mnemonic list (opmgpu/deck.py:parse_rptrst): REPLACES the list in force (RestartConfig::getRestartKeywords) for the report steps
+            that follow it; the SOLUTION section's list holds until then
 
 Every report step gets a `Wells` object (opmgpu/wells.py) the way WellsManager builds opm-core's `Wells` struct: one control per limit
 the deck gives, the deck's control mode is the initial current control, the others are the inequality constraints
@@ -20,6 +22,7 @@ import datetime
 import numpy as np
 
 from . import wells as W
+from .deck import parse_rptrst
 from .decks import BAR, DAY
 
 CP_RM3_PER_DAY_BAR = 1e-3 / (DAY * BAR)         # connection factor: cP rm3 / (day bar) -> SI
@@ -51,6 +54,7 @@ class Schedule:
         self.perm, self.dz, self.dxdy, self.ntg = perm_md, dz, dxdy, ntg
         self.start = _date(deck.records("START")[0]) if deck.has("START") else datetime.date(1983, 1, 1)
         self.steps = []                 # [(length in s, {name: WellSpec snapshot})]
+        self.rptrst = []                # per report step: {RPTRST mnemonic: int} in force for the restart file written at its end
         self._build()
 
     def _build(self):
@@ -58,7 +62,11 @@ class Schedule:
         specs = {}
         order = []
         now = self.start
+        rptrst = self.deck.rptrst()
         for name, recs in self.deck.schedule:
+            if name == "RPTRST":
+                rptrst = parse_rptrst(recs[0] if recs else [])
+                continue
             if name == "WELSPECS":
                 for r in recs:
                     if not r:
@@ -133,11 +141,13 @@ class Schedule:
                         continue
                     d = _date(r)
                     self.steps.append(((d - now).days * DAY, copy.deepcopy({n: specs[n] for n in order})))
+                    self.rptrst.append(dict(rptrst))
                     now = d
             elif name == "TSTEP":
                 for r in recs:
                     for dt in r:
                         self.steps.append((float(dt) * DAY, copy.deepcopy({n: specs[n] for n in order})))
+                        self.rptrst.append(dict(rptrst))
                         now = now + datetime.timedelta(days=float(dt))
 
     @staticmethod

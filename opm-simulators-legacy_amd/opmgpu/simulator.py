@@ -142,6 +142,9 @@ class Simulator:
                 self.reports[-1]["fip"] = gm.computeFluidInPlace(self.fipnum)
             if self.out:
                 extra = {}
+                rpt = self.schedule.rptrst[step]
+                if any(v > 0 for v in rpt.values()):      # the arrays RPTRST selects of the output record (getRestartData), one evaluation
+                    extra.update(eclio.restart_simulator_data(rpt, gm.simulatorData()))
                 if hasattr(gm, "satOilMax") and self.tables.vap1 + self.tables.vap2 > 0:
                     extra["SOMAX"] = gm.satOilMax()
                 if hasattr(gm, "getHysteresis") and self.grid.imbnum is not None:
