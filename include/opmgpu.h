@@ -42,6 +42,9 @@ enum {
 /* HydroCarbonState, opm/core/simulator/BlackoilState.hpp:33-37 */
 enum { OPMGPU_HC_GAS_ONLY = 0, OPMGPU_HC_GAS_AND_OIL = 1, OPMGPU_HC_OIL_ONLY = 2 };
 
+/* three-phase oil relative permeability model (opmgpu_tables.threephase_model) */
+enum { OPMGPU_KRO_DEFAULT = 0, OPMGPU_KRO_STONE1 = 1, OPMGPU_KRO_STONE2 = 2 };
+
 /* ILU0 elimination order.  NATURAL reproduces serial dune-istl bilu0 in the caller's
  * row order (level-scheduled on the device); MULTICOLOR is the reference's own
  * ilu_redblack idea (ISTLSolver.hpp:204-209) generalised to greedy colouring. */
@@ -120,6 +123,28 @@ typedef struct opmgpu_tables {
      * extrapolation; rocktab_n == 0 = use the quadratic ROCK form above (trans multiplier 1).    */
     int32_t rocktab_n;
     const double *rocktab_p, *rocktab_pvmult, *rocktab_transmult;
+    /* Three-phase oil relative permeability (the deck's STONE1 / STONE2 = STONE keywords; the reference hands the choice to the
+     * material-law manager at SaturationPropsFromDeck.cpp:74-204).  OPMGPU_KRO_DEFAULT is the ECLIPSE default model, the
+     * saturation-weighted blend of krow and krog.  The arithmetic of the two Stone laws belongs to opm-material, which is not part
+     * of the reference tree, so THE RULE BELOW IS OURS (not pinned against opm-material), per cell and in double:
+     *   Swco  = the connate water saturation of the default model: the cell's scaled SWL with end-point scaling, else the first
+     *           Sw node of the cell's SWOF table;   Sw* = max(Sw, Swco)  (d Sw* / d Sw = 0 for Sw < Swco)
+     *   krocw = krow(Swco) = first krow node of the region's SWOF table x the cell's vertical KRO factor (eps_v[1]) where given
+     *   krw = krw(Sw), krg = krg(Sg) as in every model;  krow = the krow curve at Sw* (the water saturation alone, NOT Sw + Sg);
+     *   krog = the krog curve at oil saturation 1 - Swco - Sg (the gas saturation alone); both with the cell's horizontal and
+     *   vertical scaling as in the default model.
+     *   STONE2:  kro = max(0, krocw [(krow/krocw + krw)(krog/krocw + krg) - krw - krg]);  0 when krocw = 0.
+     *   STONE1:  Som = min(SOWCR, SOGCR) (the cell's scaled values with end-point scaling, else the critical oil saturations read
+     *            off the region's tables), D = 1 - Swco - Som, So* = 1 - Sw* - Sg.  D <= 0 or So* <= Som: kro = 0.  Otherwise
+     *            SSo = (So* - Som)/D, SSw = (Sw* - Swco)/D, SSg = Sg/D, beta = (SSo / ((1 - SSw)(1 - SSg)))^eta,
+     *            kro = max(0, beta krow krog / krocw);  0 when krocw = 0.  eta = stone1_exponent[region] (STONE1EX), > 0.
+     *   Where kro is clamped to 0 all its derivatives are 0.
+     * Both laws give krow(Sw) at Sg = 0 when krog(Sg = 0) = krocw, and krog at Sw = Swco.
+     * Hysteresis (opmgpu_grid.imbnum != NULL) with a Stone model is refused (OPMGPU_EINVAL): how opm-material feeds the Stone laws
+     * into the hysteresis history is not recalled with confidence.  Any other value of threephase_model and an exponent <= 0 are
+     * OPMGPU_EINVAL too; the text of a refused opmgpu_create is opmgpu_last_error(NULL).                                          */
+    int32_t threephase_model;                  /* OPMGPU_KRO_*                                  */
+    const double* stone1_exponent;             /* [n_sat_regions], NULL = 1.0                   */
 } opmgpu_tables;
 
 /* Newton + linear-solver knobs: BlackoilModelParameters.cpp:76-102, BlackoilModelBase_impl.hpp:139,
@@ -273,6 +298,8 @@ int opmgpu_cpr_elliptic_ilu_apply(opmgpu_ctx* ctx, const double* b, double* x);
 int opmgpu_create(opmgpu_ctx** ctx, int device, const opmgpu_grid* grid,
                   const opmgpu_tables* tables, const opmgpu_params* params);
 void opmgpu_destroy(opmgpu_ctx* ctx);
+/* Text of the context's last error.  ctx == NULL: the text of the calling thread's last REFUSED opmgpu_create (which leaves no
+ * context behind), "null context" when there was none. */
 const char* opmgpu_last_error(const opmgpu_ctx* ctx);
 
 /* Wells topology (Wells::well_connpos / well_cells).  The BSR pattern becomes

@@ -139,6 +139,7 @@ __host__ __device__ __forceinline__ void for_each_table(DevTables& D, FD&& fd, F
     fi(T.swof_ptr); fd(T.swof_sw); fd(T.swof_krw); fd(T.swof_krow); fd(T.swof_pcow);
     fi(T.sgof_ptr); fd(T.sgof_sg); fd(T.sgof_krg); fd(T.sgof_krog); fd(T.sgof_pcgo);
     fd(T.rocktab_p); fd(T.rocktab_pvmult); fd(T.rocktab_transmult);
+    fd(T.stone1_exponent);
     fd(X.swof_dkrw); fd(X.swof_dkrow); fd(X.swof_dpcow); fd(X.sgof_dkrg); fd(X.sgof_dkrog); fd(X.sgof_dpcgo);
     fd(X.oil_drs); fd(X.oil_dinvb_sat); fd(X.oil_dinvbmu_sat); fd(X.oil_col_dinvb); fd(X.oil_col_dinvbmu);
     fd(X.gas_drvsat); fd(X.gas_dinvb_sat); fd(X.gas_dinvbmu_sat); fd(X.gas_col_dinvb); fd(X.gas_col_dinvbmu);
@@ -304,6 +305,55 @@ __device__ __forceinline__ V4 vdiv1(const V4& a, const V4& b)
     return mk(q, (a.p - q * b.p) * ib, (a.w - q * b.w) * ib, (a.x - q * b.x) * ib);
 }
 
+// Stone I / II three-phase oil relative permeability (the rule is stated in include/opmgpu.h at opmgpu_tables::threephase_model; it is
+// ours, opm-material's is not in the reference tree).  krw / krg are the cell's two-phase values eval_cell has already; the two curve
+// evaluations at the arguments only these laws use -- krow at Sw* alone, krog at Sg alone -- are made here, through the same scaling as
+// the default model's.  The model is uniform over the deck: the caller's branch is wave-uniform.
+__device__ __forceinline__ V4 stone_kro(const DevTables& DT, const EpsD& E, int sreg, int row, double sw_, const V4& W, const V4& sg, const V4& krw, const V4& krg)
+{
+    const opmgpu_tables& T = DT.t; const TabX& X = DT.x;
+    const int wa = T.swof_ptr[sreg], nw = T.swof_ptr[sreg + 1] - wa;
+    const int ga = T.sgof_ptr[sreg], ng = T.sgof_ptr[sreg + 1] - ga;
+    const double* xsw = T.swof_sw + wa; const double* xsg = T.sgof_sg + ga;
+    const V4 zero = mk(0, 0, 0, 0);
+    const double krocw = T.swof_krow[wa] * (E.on ? E.v[EC_KROW] : 1.0);
+    if (!(krocw > 0.0)) return zero;
+    const bool hscaled = E.on && (E.k[EC_PCOW] != 1.0 || E.s0[EC_PCOW] != 0.0 || E.u0[EC_PCOW] != 0.0);
+    const double swco = hscaled ? E.s0[EC_PCOW] : xsw[0];
+    const V4 swp = (sw_ > swco) ? W : mk(swco, 0, 0, 0);
+    double f, df;
+    sat_curve_s<false>(xsw, T.swof_krow + wa, X.swof_dkrow + wa, nw, swp.v, E, EC_KROW, f, df);
+    const V4 kow = vchain(f, df, swp);
+    int cl;
+    if (E.on) {     // krog is tabulated against the oil saturation 1 - Swco_table - Sg; the scaling acts on that axis (as in eval_cell)
+        double slope;
+        const double so_u = eps_map(E, EC_KROG, 1.0 - (swco + sg.v), slope);
+        const double sgu = 1.0 - xsw[0] - so_u;
+        const int i = sat_seg<true>(xsg, ng, sgu, cl);
+        sat_at(xsg, T.sgof_krog + ga, X.sgof_dkrog + ga, ng, i, cl, sgu, f, df);
+        f *= E.v[EC_KROG]; df *= slope * E.v[EC_KROG];
+    } else { const int i = sat_seg<true>(xsg, ng, sg.v, cl); sat_at(xsg, T.sgof_krog + ga, X.sgof_dkrog + ga, ng, i, cl, sg.v, f, df); }
+    const V4 kgo = vchain(f, df, sg);
+    const double ik = 1.0 / krocw;
+    V4 kro;
+    if (T.threephase_model == OPMGPU_KRO_STONE2) {
+        const V4 ab = vmul(vadd(vscale(ik, kow), krw), vadd(vscale(ik, kgo), krg));
+        kro = vscale(krocw, mk(ab.v - krw.v - krg.v, ab.p - krw.p - krg.p, ab.w - krw.w - krg.w, ab.x - krw.x - krg.x));
+    } else {
+        const double som = DT.stone_som[row], D = 1.0 - swco - som;
+        const V4 sos = mk(1.0 - swp.v - sg.v, 0, -swp.w - sg.w, -sg.x);          // So* = 1 - Sw* - Sg
+        if (!(D > 0.0) || !(sos.v > som)) return zero;
+        const double iD = 1.0 / D;
+        const V4 sso = mk((sos.v - som) * iD, 0, sos.w * iD, sos.x * iD);
+        const V4 omw = mk(1.0 - (swp.v - swco) * iD, 0, -swp.w * iD, 0);          // 1 - SSw
+        const V4 omg = mk(1.0 - sg.v * iD, 0, -sg.w * iD, -sg.x * iD);            // 1 - SSg
+        const V4 r = vdiv1(sso, vmul(omw, omg));
+        const double eta = T.stone1_exponent[sreg], beta = pow(r.v, eta);
+        kro = vscale(ik, vmul(vchain(beta, eta * beta / r.v, r), vmul(kow, kgo)));        // d r^eta = eta r^eta / r dr  (r > 0 here)
+    }
+    return kro.v > 0.0 ? kro : zero;
+}
+
 struct CellEval {
     V4 pw, pg, rs, rv, sw, so, sg;
     V4 b[3], mob[3], rho[3], accum[3];
@@ -314,9 +364,11 @@ struct CellEval {
 struct CellOutput { double mu[3], kr[3], rsSat, rvSat; };
 
 // SolutionState + ReservoirResidualQuant of one cell (BlackoilModelBase_impl.hpp:614-751, 1484-1497, 2009-2027)
-template <bool OUTPUT = false>
+// STONE: the deck's three-phase model is Stone I or II (T.threephase_model says which), else the default one.  A template parameter and
+// not a branch on the field, chosen on the host for every kernel that evaluates cells: with the branch k_assemble_rows' default instantiation went from 7 to 20 spilled VGPRs.
+template <bool OUTPUT = false, bool STONE = false>
 __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int preg, int sreg, double p, double sw_, double sg_, double rs_, double rv_, int hc,
-                          CellEval& q, const HystD& H = HystD{ false, 0, 2.0, 2.0, 0.0, 0.0 }, const EpsD* EI = nullptr, CellOutput* out = nullptr)
+                          int row, CellEval& q, const HystD& H = HystD{ false, 0, 2.0, 2.0, 0.0, 0.0 }, const EpsD* EI = nullptr, CellOutput* out = nullptr)
 {
     const opmgpu_tables& T = DT.t; const TabX& X = DT.x;
     const bool isSg = hc == OPMGPU_HC_GAS_AND_OIL, isRs = hc == OPMGPU_HC_OIL_ONLY, isRv = hc == OPMGPU_HC_GAS_ONLY;
@@ -363,7 +415,8 @@ __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int
         krg = vchain(f, df, sg);
     }
     V4 kro;
-    {   // EclDefaultMaterial::krn
+    if constexpr (STONE) kro = stone_kro(DT, E, sreg, row, sw_, W, sg, krw, krg);      // (never with hysteresis: refused at creation)
+    else {   // EclDefaultMaterial::krn
         // connate water of the three-phase law: the cell's scaled SWL; a set without horizontal scaling (s0 = u0 = 0, k = 1) has the table's
         const bool hscaled = E.on && (E.k[EC_PCOW] != 1.0 || E.s0[EC_PCOW] != 0.0 || E.u0[EC_PCOW] != 0.0);
         const double swco = hscaled ? E.s0[EC_PCOW] : xsw[0];
@@ -489,7 +542,7 @@ __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int
 }
 // eval_cell of a row's cell with what surrounds it: the cell's end-point scaling, its hysteresis history and, with one, the end points of
 // its imbibition curves
-template <bool OUTPUT = false>
+template <bool STONE, bool OUTPUT = false>
 __device__ __forceinline__ void eval_row(const DevTables& DT, int row, long nbp, double so_max, const int32_t* __restrict__ pvtnum, const int32_t* __restrict__ satnum,
                                          const double* __restrict__ p, const double* __restrict__ sw, const double* __restrict__ sg, const double* __restrict__ rs,
                                          const double* __restrict__ rv, const int8_t* __restrict__ hc, const double* __restrict__ eps, const double* __restrict__ eps_u0,
@@ -500,7 +553,7 @@ __device__ __forceinline__ void eval_row(const DevTables& DT, int row, long nbp,
     eps_load(eps, eps_u0, nbp, row, satnum[row], E);
     hyst_load(hy.imbnum, hy.hist, nbp, row, H);
     if (H.on) eps_load(hy.ieps, hy.iureg, nbp, row, H.ireg, EI);
-    eval_cell<OUTPUT>(DT, E, so_max, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], q, H, &EI, out);
+    eval_cell<OUTPUT, STONE>(DT, E, so_max, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], row, q, H, &EI, out);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -516,7 +569,7 @@ __device__ __forceinline__ void eval_row(const DevTables& DT, int row, long nbp,
 //   k_cell_values : state -> the ten value planes (+ 1 / b for getConvergence)                                  [pass 1, all cells]
 //   k_assemble_rows: state -> own derivatives (eval_cell again: arithmetic is free next to the bytes), accumulation term, TPFA fluxes
 //                    from the neighbours' value planes, residual, diagonal block, transposed off-diagonal blocks, CPR weights  [pass 2]
-template <bool LDS>
+template <bool LDS, bool STONE>
 __global__ __launch_bounds__(kBlock) void k_cell_values(int nb, int nbp, DevTables D, const int32_t* __restrict__ pvtnum, const int32_t* __restrict__ satnum,
                                                         const double* __restrict__ p, const double* __restrict__ sw, const double* __restrict__ sg,
                                                         const double* __restrict__ rs, const double* __restrict__ rv, const int8_t* __restrict__ hc,
@@ -536,7 +589,7 @@ __global__ __launch_bounds__(kBlock) void k_cell_values(int nb, int nbp, DevTabl
         eps_load(eps, eps_u0, nbp, row, satnum[row], E);
         hyst_load(hy.imbnum, hy.hist, nbp, row, H);
         if (H.on) eps_load(hy.ieps, hy.iureg, nbp, row, H.ireg, EI);
-        eval_cell(D, E, (D.t.vap1 > 0.0 || D.t.vap2 > 0.0) ? somax[row] : 0.0, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], q, H, &EI);
+        eval_cell<false, STONE>(D, E, (D.t.vap1 > 0.0 || D.t.vap2 > 0.0) ? somax[row] : 0.0, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], row, q, H, &EI);
         vals[long(VP_PW) * nbp + row] = q.pw.v; vals[long(VP_PG) * nbp + row] = q.pg.v;
         const bool owned = !mask || mask[row];
 #pragma unroll
@@ -562,7 +615,7 @@ __global__ __launch_bounds__(kBlock) void k_cell_values(int nb, int nbp, DevTabl
 // bit (+: the row is c1, ngrad coefficient +1; NaN: not a connection -- the fill of an explicit well clique), g (z_c1 - z_c2), the
 // threshold pressure, and the index of the transposed entry (tpos).  All four are read coalesced at known addresses: the only dependent
 // loads of the loop are the neighbour's values.
-template <class MS, int WAVES, bool LDS, bool BATCH, bool DUAL>
+template <class MS, int WAVES, bool LDS, bool BATCH, bool DUAL, bool STONE>
 __global__ __launch_bounds__(kBlock, WAVES) void k_assemble_rows(int xm, int nb, int nbp, DevTables DT, const int32_t* __restrict__ pvtnum, const int32_t* __restrict__ satnum,
                                                           const double* __restrict__ pv, const double* __restrict__ p, const double* __restrict__ sw,
                                                           const double* __restrict__ sg, const double* __restrict__ rs, const double* __restrict__ rv,
@@ -596,7 +649,7 @@ __global__ __launch_bounds__(kBlock, WAVES) void k_assemble_rows(int xm, int nb,
         eps_load(eps, eps_u0, nbp, row, satnum[row], E);
         hyst_load(hy.imbnum, hy.hist, nbp, row, H);
         if (H.on) eps_load(hy.ieps, hy.iureg, nbp, row, H.ireg, EI);
-        eval_cell(DT, E, (DT.t.vap1 > 0.0 || DT.t.vap2 > 0.0) ? somax[row] : 0.0, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], q, H, &EI);
+        eval_cell<false, STONE>(DT, E, (DT.t.vap1 > 0.0 || DT.t.vap2 > 0.0) ? somax[row] : 0.0, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], row, q, H, &EI);
     }
     const double scale[3] = { s0, s1, s2 };
     double op[3], orho[3], oU[3];                          // own values
@@ -939,6 +992,7 @@ __global__ __launch_bounds__(kBlock) void k_gather_perf3(int nperf, int nbp, con
 }
 
 // per-perforation properties for the host well model (extractWellPerfProperties)
+template <bool STONE>
 __global__ __launch_bounds__(kBlock) void k_perf_props(int nperf, DevTables T, const int32_t* __restrict__ cells, const int32_t* __restrict__ pvtnum,
                                                        const int32_t* __restrict__ satnum, const double* __restrict__ p, const double* __restrict__ sw,
                                                        const double* __restrict__ sg, const double* __restrict__ rs, const double* __restrict__ rv,
@@ -950,7 +1004,7 @@ __global__ __launch_bounds__(kBlock) void k_perf_props(int nperf, DevTables T, c
     if (i >= nperf) return;
     const int c = cells[i];
     CellEval q;
-    eval_row(T, c, nbp, somax[c], pvtnum, satnum, p, sw, sg, rs, rv, hc, eps, eps_u0, hy, q);
+    eval_row<STONE>(T, c, nbp, somax[c], pvtnum, satnum, p, sw, sg, rs, rv, hc, eps, eps_u0, hy, q);
     const V4 list[9] = { mk(p[c], 1, 0, 0), q.rs, q.rv, q.b[0], q.b[1], q.b[2], q.mob[0], q.mob[1], q.mob[2] };
     double* o = out + long(i) * OPMGPU_PERF_K;
 #pragma unroll
@@ -960,6 +1014,7 @@ __global__ __launch_bounds__(kBlock) void k_perf_props(int nperf, DevTables T, c
 // computeFluidInPlace, the per-cell part (BlackoilModelBase_impl.hpp:2263-2296): fip[phase] = ((pv_mult * b_phase) * s_phase) * pv with b at the
 // phase pressures and the cell's phase condition, dissolved gas = rs * fip[oil], vaporised oil = rv * fip[gas]; plus what the region
 // loops need of the state (pore volume, pressure, so + sg).  Output in the CALLER's cell order: out[q * nc + nat[row]], q = 0..7.
+template <bool STONE>
 __global__ __launch_bounds__(kBlock) void k_fip_cells(int nc, DevTables T, const int32_t* __restrict__ nat, const int32_t* __restrict__ pvtnum,
                                                       const int32_t* __restrict__ satnum, const double* __restrict__ pv, const double* __restrict__ p,
                                                       const double* __restrict__ sw, const double* __restrict__ so_, const double* __restrict__ sg, const double* __restrict__ rs,
@@ -970,7 +1025,7 @@ __global__ __launch_bounds__(kBlock) void k_fip_cells(int nc, DevTables T, const
     const int c = blockIdx.x * kBlock + threadIdx.x;
     if (c >= nc) return;
     CellEval q;
-    eval_row(T, c, nbp, somax[c], pvtnum, satnum, p, sw, sg, rs, rv, hc, eps, eps_u0, hy, q);
+    eval_row<STONE>(T, c, nbp, somax[c], pvtnum, satnum, p, sw, sg, rs, rv, hc, eps, eps_u0, hy, q);
     const long n = nat[c];
     const double so = so_[c], sgv = sg[c], swv = sw[c];          // the state's saturations, as the reference takes them
     const double fw = ((q.pvm.v * q.b[0].v) * swv) * pv[c];
@@ -987,6 +1042,7 @@ __global__ __launch_bounds__(kBlock) void k_fip_cells(int nc, DevTables T, const
 // multiplier, not divided by the viscosity); RsSat / RvSat are the saturated values (VAPPARS factor included) of EVERY cell whatever its
 // phase state; Pb / Pd invert the plain curves at the solution state's rs / rv (sat_pressure).  OPMGPU_SIMDATA_K planes in the CALLER's
 // cell order: out[q * nc + nat[row]], slots OPMGPU_SD_* of opmgpu.h.  An output path: once per report step.
+template <bool STONE>
 __global__ __launch_bounds__(kBlock) void k_simulator_data(int nc, DevTables T, const int32_t* __restrict__ nat, const int32_t* __restrict__ pvtnum,
                                                            const int32_t* __restrict__ satnum, const double* __restrict__ p, const double* __restrict__ sw,
                                                            const double* __restrict__ sg, const double* __restrict__ rs, const double* __restrict__ rv,
@@ -998,7 +1054,7 @@ __global__ __launch_bounds__(kBlock) void k_simulator_data(int nc, DevTables T, 
     if (c >= nc) return;
     CellEval q;
     CellOutput x;
-    eval_row<true>(T, c, nbp, somax[c], pvtnum, satnum, p, sw, sg, rs, rv, hc, eps, eps_u0, hy, q, &x);
+    eval_row<STONE, true>(T, c, nbp, somax[c], pvtnum, satnum, p, sw, sg, rs, rv, hc, eps, eps_u0, hy, q, &x);
     const int preg = pvtnum[c];
     double* o = out + nat[c];
     const long n = nc;
@@ -1137,6 +1193,12 @@ BlackoilDevice::BlackoilDevice(hipStream_t s, LinSolver& ls_, const opmgpu_grid*
             }
     }
     use_eps = has_endpoints || vert || use_hyst;
+    if (t->threephase_model != OPMGPU_KRO_DEFAULT && t->threephase_model != OPMGPU_KRO_STONE1 && t->threephase_model != OPMGPU_KRO_STONE2)
+        throw HipError(OPMGPU_EINVAL, "threephase_model is none of OPMGPU_KRO_DEFAULT, OPMGPU_KRO_STONE1, OPMGPU_KRO_STONE2");
+    if (t->threephase_model != OPMGPU_KRO_DEFAULT && use_hyst)
+        throw HipError(OPMGPU_EINVAL, "a Stone three-phase model together with hysteresis (imbnum) is not supported");
+    if (t->stone1_exponent)
+        for (int r = 0; r < t->n_sat_regions; ++r) if (!(t->stone1_exponent[r] > 0.0)) throw HipError(OPMGPU_EINVAL, "stone1_exponent must be positive in every saturation region");
     pvsum = 0.0;
     for (int c = 0; c < nc; ++c) pvsum += h_pv[c];
     upload_tables(t);
@@ -1200,6 +1262,12 @@ void BlackoilDevice::upload_tables(const opmgpu_tables* t)
         o.t.rocktab_p = upd(t->rocktab_p, t->rocktab_n); o.t.rocktab_pvmult = upd(t->rocktab_pvmult, t->rocktab_n);
         o.t.rocktab_transmult = upd(t->rocktab_transmult, t->rocktab_n);
     }
+    {   // STONE1EX, one exponent per saturation region (NULL: 1.0)
+        std::vector<double> eta(size_t(ns), 1.0);
+        if (t->stone1_exponent) eta.assign(t->stone1_exponent, t->stone1_exponent + ns);
+        o.t.stone1_exponent = upd(eta.data(), ns);
+    }
+    o.stone_som = nullptr;
     // slopes of every 1-D table (TabX): (y[i+1] - y[i]) / (x[i+1] - x[i]) per segment, segments never cross the tables of a CSR-style array
     auto slopes = [&](const double* x, const double* y, const int32_t* ptr, int ntab) {
         const int n = ptr[ntab];
@@ -1324,6 +1392,17 @@ void BlackoilDevice::rebuild_structure()
                 for (int r = 0; r < nc; ++r) for (int k = 0; k < 4; ++k) hp[size_t(k) * nbp + r] = hist[size_t(k) * nc + P.nat[r]];
             d_hist.upload(hp, stream);
         }
+    }
+    if (dto_.t.threephase_model == OPMGPU_KRO_STONE1) {
+        // Som = min(SOWCR, SOGCR) per cell: its scaled end points, or the critical oil saturations read off its region's tables
+        std::vector<double> som(nbp, 0.0);
+        for (int r = 0; r < nc; ++r) {
+            const int c = P.nat[r];
+            const double* u = &h_unscaled[8 * size_t(h_satnum[c])];
+            som[r] = has_endpoints ? std::min(h_eps[3][c], h_eps[7][c]) : std::min(u[3], u[7]);
+        }
+        d_stone_som.upload(som, stream);
+        dto_.stone_som = dtp_.stone_som = d_stone_som.p;
     }
     std::vector<int32_t> pc(std::max<size_t>(h_well_cells.size(), 1), 0);
     for (size_t i = 0; i < h_well_cells.size(); ++i) pc[i] = P.pos[h_well_cells[i]];
@@ -1536,7 +1615,8 @@ void BlackoilDevice::get_state(double* p, double* sat, double* rs, double* rv, i
 void BlackoilDevice::launch_cell_values()
 {
     const Plan& P = ls.plan;
-    auto kern = tab_lds_words() > 0 ? k_cell_values<true> : k_cell_values<false>;
+    const bool lds = tab_lds_words() > 0, stone = stone_model();
+    auto kern = stone ? (lds ? k_cell_values<true, true> : k_cell_values<false, true>) : (lds ? k_cell_values<true, false> : k_cell_values<false, false>);
     hipLaunchKernelGGL(kern, dim3(grid_for(nc)), dim3(kBlock), tab_lds_bytes(), stream, nc, P.nbp, dto_, d_pvtnum.p, d_satnum.p,
                        d_p.p, d_sw.p, d_sg.p, d_rs.p, d_rv.p, d_hc.p, eps_planes(), d_eps_u0.p, d_somax.p, d_vals.p, d_bpart.p,
                        ls.comm ? ls.comm->owner_mask() : (const int8_t*)nullptr, (const double*)d_tab.p, tab_lds_words(), hyst_args());
@@ -1565,10 +1645,15 @@ template <class MS> void BlackoilDevice::assemble_kernels(double dt, bool initia
     static const bool dual = env_flag("OPMGPU_MIXED_DUALWRITE", true);
     float* a32 = nullptr;
     if (dual && sizeof(MS) == 8 && prm.preconditioner_single && !props_only && ls.emulate_ranks <= 1 && !(prm.use_cpr && prm.cpr_reference_transform)) { a32 = ls.matrix_f(); dual_written = true; }
-    auto kern = !lds ? k_assemble_rows<MS, 2, false, false, false>
-                     : (waves == 3 ? (batch ? k_assemble_rows<MS, 3, true, true, false> : k_assemble_rows<MS, 3, true, false, false>)
-                                   : (batch ? k_assemble_rows<MS, 2, true, true, false> : k_assemble_rows<MS, 2, true, false, false>));
-    if (a32) kern = lds ? k_assemble_rows<MS, 2, true, true, true> : k_assemble_rows<MS, 2, false, false, true>;      // (the dual-write variant: 2 waves per SIMD, no spills)
+    auto kern = !lds ? k_assemble_rows<MS, 2, false, false, false, false>
+                     : (waves == 3 ? (batch ? k_assemble_rows<MS, 3, true, true, false, false> : k_assemble_rows<MS, 3, true, false, false, false>)
+                                   : (batch ? k_assemble_rows<MS, 2, true, true, false, false> : k_assemble_rows<MS, 2, true, false, false, false>));
+    if (a32) kern = lds ? k_assemble_rows<MS, 2, true, true, true, false> : k_assemble_rows<MS, 2, false, false, true, false>;      // (the dual-write variant: 2 waves per SIMD, no spills)
+    // Stone I / II: instantiations of their own, so that the default model's compile to what they were.  Two waves per SIMD and the batched
+    // loads only -- the two knobs above were tuned on the default model
+    if (stone_model())
+        kern = a32 ? (lds ? k_assemble_rows<MS, 2, true, true, true, true> : k_assemble_rows<MS, 2, false, false, true, true>)
+                   : (lds ? k_assemble_rows<MS, 2, true, true, false, true> : k_assemble_rows<MS, 2, false, false, false, true>);
     hipLaunchKernelGGL(kern, dim3(grid8_for(nc)), dim3(kBlock), tab_lds_bytes(), stream, xcd_mode(), nc, P.nbp, dto_, d_pvtnum.p, d_satnum.p, d_pv.p,
                        d_p.p, d_sw.p, d_sg.p, d_rs.p, d_rv.p, d_hc.p, 1.0 / dt, int(initial), sc[0], sc[1], sc[2],
                        ls.dp.slice_ptr.p, ls.dp.col.p, ls.dp.rowlen.p, ls.dp.nlower.p, ls.dp.tpos.p, d_tr_e.p, (const double*)d_zc.p, gravity, use_thpres ? d_thp_e.p : (const double*)nullptr,
@@ -1795,7 +1880,7 @@ void BlackoilDevice::attach_comm(CommBase* c, int n_owned)
 void BlackoilDevice::perf_props_device()
 {
     if (nperf == 0) return;
-    hipLaunchKernelGGL(k_perf_props, dim3(grid_for(nperf)), dim3(kBlock), 0, stream, nperf, dtp_, d_perf_cells.p, d_pvtnum.p, d_satnum.p,
+    hipLaunchKernelGGL(stone_model() ? k_perf_props<true> : k_perf_props<false>, dim3(grid_for(nperf)), dim3(kBlock), 0, stream, nperf, dtp_, d_perf_cells.p, d_pvtnum.p, d_satnum.p,
                        d_p.p, d_sw.p, d_sg.p, d_rs.p, d_rv.p, d_hc.p, eps_planes(), d_eps_u0.p, d_somax.p, long(ls.plan.nbp), d_perf.p, hyst_args());
 }
 
@@ -1840,7 +1925,7 @@ void BlackoilDevice::average_b(double* B3)
 void BlackoilDevice::perf_props(double* out)
 {
     if (nperf == 0) return;
-    hipLaunchKernelGGL(k_perf_props, dim3(grid_for(nperf)), dim3(kBlock), 0, stream, nperf, dtp_, d_perf_cells.p, d_pvtnum.p, d_satnum.p,
+    hipLaunchKernelGGL(stone_model() ? k_perf_props<true> : k_perf_props<false>, dim3(grid_for(nperf)), dim3(kBlock), 0, stream, nperf, dtp_, d_perf_cells.p, d_pvtnum.p, d_satnum.p,
                        d_p.p, d_sw.p, d_sg.p, d_rs.p, d_rv.p, d_hc.p, eps_planes(), d_eps_u0.p, d_somax.p, long(ls.plan.nbp), d_perf.p, hyst_args());
     OPMGPU_HIP(hipMemcpyAsync(out, d_perf.p, size_t(nperf) * OPMGPU_PERF_K * sizeof(double), hipMemcpyDeviceToHost, stream));
     OPMGPU_HIP(hipStreamSynchronize(stream));
@@ -1983,7 +2068,7 @@ void BlackoilDevice::stabilize_update(int relax_type, double omega)
 void BlackoilDevice::simulator_data(double* out)
 {
     DevArray<double> dout; dout.alloc(size_t(OPMGPU_SIMDATA_K) * nc);
-    hipLaunchKernelGGL(k_simulator_data, dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, dtp_, ls.dp.nat.p, d_pvtnum.p, d_satnum.p,
+    hipLaunchKernelGGL(stone_model() ? k_simulator_data<true> : k_simulator_data<false>, dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, dtp_, ls.dp.nat.p, d_pvtnum.p, d_satnum.p,
                        d_p.p, d_sw.p, d_sg.p, d_rs.p, d_rv.p, d_hc.p, eps_planes(), d_eps_u0.p, d_somax.p, long(ls.plan.nbp), dout.p, hyst_args());
     dout.download(out, size_t(OPMGPU_SIMDATA_K) * nc, stream);
     OPMGPU_HIP(hipStreamSynchronize(stream));
@@ -1996,7 +2081,7 @@ void BlackoilDevice::fluid_in_place(const int32_t* fipnum, int dims, double* fip
 {
     const Plan& P = ls.plan;
     DevArray<double> dout; dout.alloc(size_t(8) * nc);
-    hipLaunchKernelGGL(k_fip_cells, dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, dtp_, ls.dp.nat.p, d_pvtnum.p, d_satnum.p, d_pv.p,
+    hipLaunchKernelGGL(stone_model() ? k_fip_cells<true> : k_fip_cells<false>, dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, dtp_, ls.dp.nat.p, d_pvtnum.p, d_satnum.p, d_pv.p,
                        d_p.p, d_sw.p, d_so.p, d_sg.p, d_rs.p, d_rv.p, d_hc.p, eps_planes(), d_eps_u0.p, d_somax.p, long(P.nbp), dout.p, hyst_args());
     std::vector<double> h(size_t(8) * nc);
     dout.download(h.data(), h.size(), stream);

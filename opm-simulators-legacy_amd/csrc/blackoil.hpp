@@ -20,7 +20,10 @@ struct TabX {
     const double *oil_drs, *oil_dinvb_sat, *oil_dinvbmu_sat, *oil_col_dinvb, *oil_col_dinvbmu;
     const double *gas_drvsat, *gas_dinvb_sat, *gas_dinvbmu_sat, *gas_col_dinvb, *gas_col_dinvbmu;
 };
-struct DevTables { opmgpu_tables t; TabX x; };
+// stone_som: Stone I's residual oil saturation Som = min(SOWCR, SOGCR) of every cell (internal numbering), a device pointer in EVERY form of
+// the tables (it is no table: a per-cell plane that rides here so that each launch site of eval_cell sees it); null unless the model is
+// OPMGPU_KRO_STONE1.  The model itself and the per-region exponent are t.threephase_model and t.stone1_exponent (in the blob).
+struct DevTables { opmgpu_tables t; TabX x; const double* stone_som; };
 
 // per-cell VALUE planes a row's neighbours read (doubles, stride nbp): phase pressures p_w, p_g (p_o is the state's pressure), the
 // densities, b * mobility, rs, rv.  No derivative plane exists: a row differentiates its connections with respect to its own
@@ -143,6 +146,7 @@ private:
     std::vector<int32_t> h_imbnum;
     DevArray<double> d_eps, d_eps_u0, d_somax, d_saved, d_ieps, d_ieps_u0, d_hist;     // d_hist: [mdc_ow | mdc_go | d_ow | d_go] planes
     DevArray<int32_t> d_imbnum;
+    DevArray<double> d_stone_som;            // DevTables::stone_som
     HystArgs hyst_args() const;
     void build_eps_planes(const std::vector<double>* ep8, bool have_points, bool imbibition, std::vector<double>& planes) const;
     std::vector<double> h_tabmax;
@@ -154,6 +158,7 @@ private:
     DevArray<double> d_tab;                  // all table arrays in one blob of 8-byte words (staged in LDS by the property kernels)
     int tab_words = 0;
     static constexpr int kTabLdsMaxBytes = 24 * 1024;     // 6 workgroups x 24 KiB fit the 160 KiB LDS of a CU: no occupancy lost
+    bool stone_model() const { return dto_.t.threephase_model != OPMGPU_KRO_DEFAULT; }      // chooses the kernels' STONE instantiations (eval_cell)
     int tab_lds_words() const { return tab_words * 8 <= kTabLdsMaxBytes ? tab_words : 0; }
     size_t tab_lds_bytes() const { return size_t(tab_lds_words()) * 8; }
     // device: static per-cell / per-connection (internal numbering for cells)

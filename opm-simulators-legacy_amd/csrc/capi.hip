@@ -186,6 +186,8 @@ template <class S> int solve_loaded(opmgpu_ctx* c, bool matrix_changed, SolveRes
 
 } // namespace
 
+static thread_local std::string create_err;      // why the thread's last opmgpu_create was refused (that context is gone): opmgpu_last_error(NULL)
+
 extern "C" {
 
 const char* opmgpu_version(void) { return "opmgpu 0.1 (gfx950, HIP, SELL-64 block-ILU0/BiCGStab + black-oil assembly)"; }
@@ -216,12 +218,13 @@ int opmgpu_create_solver(opmgpu_ctx** ctx, int device, const opmgpu_params* para
 
 int opmgpu_create(opmgpu_ctx** ctx, int device, const opmgpu_grid* grid, const opmgpu_tables* tables, const opmgpu_params* params)
 {
+    create_err.clear();
     if (!grid || !tables || grid->nc <= 0 || grid->nconn < 0) return OPMGPU_EINVAL;
     const int st = make_ctx(ctx, device, params);
     if (st != OPMGPU_OK) return st;
     opmgpu_ctx* c = *ctx;
     const int st2 = guarded(c, [&]() { c->model.reset(new BlackoilDevice(c->stream, *c->ls, grid, tables, &c->prm)); return OPMGPU_OK; });
-    if (st2 != OPMGPU_OK) { opmgpu_destroy(c); *ctx = nullptr; }
+    if (st2 != OPMGPU_OK) { create_err = c->err; opmgpu_destroy(c); *ctx = nullptr; }
     return st2;
 }
 
@@ -239,7 +242,7 @@ void opmgpu_destroy(opmgpu_ctx* c)
     delete c;
 }
 
-const char* opmgpu_last_error(const opmgpu_ctx* c) { return c ? c->err.c_str() : "null context"; }
+const char* opmgpu_last_error(const opmgpu_ctx* c) { return c ? c->err.c_str() : (create_err.empty() ? "null context" : create_err.c_str()); }
 
 int opmgpu_set_wells(opmgpu_ctx* c, int nw, const int32_t* well_connpos, const int32_t* well_cells)
 {

@@ -54,6 +54,7 @@ struct Deck {
         t.swof_ptr = swof_ptr.data(); t.swof_sw = sw.data(); t.swof_krw = krw.data(); t.swof_krow = krow.data(); t.swof_pcow = pcow.data();
         t.sgof_ptr = sgof_ptr.data(); t.sgof_sg = sg.data(); t.sgof_krg = krg.data(); t.sgof_krog = krog.data(); t.sgof_pcgo = pcgo.data();
         t.rock_pref = 200e5; t.rock_comp = 4e-10;
+        t.threephase_model = OPMGPU_KRO_DEFAULT; t.stone1_exponent = nullptr;      // the deck names no STONE1 / STONE2
         return t;
     }
 };

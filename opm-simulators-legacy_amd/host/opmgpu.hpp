@@ -102,7 +102,7 @@ public:
         nc_ = grid.nc;
         use_cpr_ = prm && prm->use_cpr;
         const int st = opmgpu_create(&ctx_, device, &grid, &tables, prm);
-        if (st != OPMGPU_OK) throw std::runtime_error("opmgpu_create failed (no GPU? there is no CPU fallback), status " + std::to_string(st));
+        if (st != OPMGPU_OK) throw std::runtime_error("opmgpu_create failed (no GPU? there is no CPU fallback), status " + std::to_string(st) + ": " + opmgpu_last_error(nullptr));
     }
     ~BlackoilModelGpu() { opmgpu_destroy(ctx_); }
     BlackoilModelGpu(const BlackoilModelGpu&) = delete;

@@ -15,6 +15,7 @@ OK, EINVAL, ENODEVICE, ENUMERICAL, ELINSOLVE, EBREAKDOWN, ESINGULAR, ENOMEM, ECO
 HC_GAS_ONLY, HC_GAS_AND_OIL, HC_OIL_ONLY = 0, 1, 2
 RELAX_DAMPEN, RELAX_SOR = 0, 1
 ORDER_NATURAL, ORDER_MULTICOLOR = 0, 1
+KRO_DEFAULT, KRO_STONE1, KRO_STONE2 = 0, 1, 2          # opmgpu_tables.threephase_model
 K_SPMV, K_ILU_APPLY, K_ILU_FACTOR, K_ASSEMBLE, K_DOT, K_AXPY, K_PROPS, K_STREAM_COPY, K_CPR_APPLY, K_VCYCLE, K_CPR_SETUP, K_SPMV_COLD = range(12)
 KT_NAMES = ["cell_props", "flux", "wells", "convergence", "ilu0_factor", "cpr_setup", "spmv_fused_dot1", "spmv_fused_dot2", "ilu0_apply", "amg_vcycle",
             "cpr_other", "vector_updates", "update_state"]
@@ -53,7 +54,8 @@ class Tables(C.Structure):
                 ("sgof_pcgo", _dp),
                 ("rock_pref", C.c_double), ("rock_comp", C.c_double),
                 ("vap1", C.c_double), ("vap2", C.c_double),
-                ("rocktab_n", C.c_int32), ("rocktab_p", _dp), ("rocktab_pvmult", _dp), ("rocktab_transmult", _dp)]
+                ("rocktab_n", C.c_int32), ("rocktab_p", _dp), ("rocktab_pvmult", _dp), ("rocktab_transmult", _dp),
+                ("threephase_model", C.c_int32), ("stone1_exponent", _dp)]
 
 
 class WellsSpec(C.Structure):

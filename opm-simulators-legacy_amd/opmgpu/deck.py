@@ -7,6 +7,8 @@ What `flow_legacy` gets from opm-parser + `DerivedGeology` (opm/autodiff/GeoProp
   GRID      DX DY DZ / DXV DYV DZV, TOPS (+BOX for the top layer) or DEPTHZ (flat) -- or COORD / ZCORN (corner-point, no faults) --, PORO PERMX PERMY PERMZ NTG ACTNUM MINPV, FAULTS + MULTFLT
             MULTX MULTY MULTZ MULTX- MULTY- MULTZ- MULTPV NNC
   PROPS     SWOF SGOF PVTO PVDO PVCDO PVTG PVDG PVTW DENSITY ROCK ROCKTAB VAPPARS SCALECRS (NO and YES) EHYSTR
+            STONE1 STONE2 STONE (= STONE2) STONE1EX: the three-phase oil relative permeability model (none of them: the default model;
+            two of them, or one together with SATOPTS HYSTER, is refused)
             SWL SWCR SWU SOWCR SGL SGCR SGU SOGCR  KRW KRO KRG PCW PCG  ISWL ISWCR ISWU ISOWCR ISGL ISGCR ISGU ISOGCR
             (SATOPTS HYSTER in RUNSPEC switches the hysteresis on; EHYSTR item 2 = 0 and item 5 = KR -- Carlson, relative permeabilities
             only -- is the model the device implements)
@@ -23,12 +25,12 @@ import re
 
 import numpy as np
 
-from . import decks
+from . import capi, decks
 from .decks import BAR, DAY, FluidTables, GridData, MD, State
 
 FLAG_KEYWORDS = {"RUNSPEC", "GRID", "EDIT", "PROPS", "REGIONS", "SOLUTION", "SUMMARY", "SCHEDULE", "END", "NOECHO", "ECHO", "OIL", "WATER",
                  "GAS", "DISGAS", "VAPOIL", "METRIC", "FIELD", "LAB", "FMTOUT", "FMTIN", "UNIFOUT", "UNIFIN", "RUNSUM", "SEPARATE", "ALL",
-                 "INIT", "NOSIM", "ENDBOX", "EXCEL", "NOGGF", "NEWTRAN", "OLDTRAN"}
+                 "INIT", "NOSIM", "ENDBOX", "EXCEL", "NOGGF", "NEWTRAN", "OLDTRAN", "STONE", "STONE1", "STONE2"}
 # RPTRST mnemonics that select arrays of the model's output record (getRestartData, SimulatorFullyImplicitBlackoilOutput.hpp:585-845);
 # BASIC and every other mnemonic are not kept
 RPTRST_MNEMONICS = ("BW", "BO", "BG", "DEN", "VISC", "VWAT", "VOIL", "VGAS", "KRW", "KRO", "KRG", "RSSAT", "RVSAT", "PBPD")
@@ -188,8 +190,32 @@ class Deck:
         if self.has("VAPPARS"):
             r = self.records("VAPPARS")[0]
             vappars = (r[0], r[1])
+        model, eta = self.threephase()
         return FluidTables(density_wog=dens, pvtw=pvtw, pvto=pvto, pvtg=pvtg, swof=swof, sgof=sgof, rock=rock, disgas=disgas, vapoil=vapoil,
-                           vappars=vappars, rocktab=rocktab)
+                           vappars=vappars, rocktab=rocktab, threephase_model=model, stone1_exponent=eta)
+
+    def threephase(self):
+        """(opmgpu_tables.threephase_model, STONE1EX exponents or None): STONE1 -> Stone I with one exponent per saturation region (STONE1EX,
+        default 1), STONE2 or STONE -> Stone II, none of them -> the default model."""
+        named = [k for k in ("STONE1", "STONE2", "STONE") if self.has(k)]
+        if not named:
+            return capi.KRO_DEFAULT, None
+        if len(named) > 1:
+            raise ValueError("more than one three-phase model keyword: " + " ".join(named))
+        if self.hysteresis():
+            raise ValueError("%s together with SATOPTS HYSTER is not supported" % named[0])
+        if named[0] != "STONE1":
+            return capi.KRO_STONE2, None
+        ntsfun = self.tabdims()[0]
+        eta = [1.0] * ntsfun
+        if self.has("STONE1EX"):
+            recs = self.records("STONE1EX")
+            if len(recs) < ntsfun:
+                raise ValueError("STONE1EX holds %d records, expected one per saturation region (%d)" % (len(recs), ntsfun))
+            eta = [float(r[0]) if len(r) > 0 and r[0] is not None else 1.0 for r in recs[:ntsfun]]
+            if any(not e > 0.0 for e in eta):
+                raise ValueError("STONE1EX: the exponent must be positive")
+        return capi.KRO_STONE1, eta
 
     # ---------------------------------------------------------------- GRID
     # ---------------------------------------------------------------- corner-point geometry (COORD / ZCORN)

@@ -27,13 +27,16 @@ GRAVITY = 9.80665
 class FluidTables:
     """Flat table arrays matching `opmgpu_tables` (include/opmgpu.h)."""
 
-    def __init__(self, density_wog, pvtw, pvto, pvtg, swof, sgof, rock, disgas=True, vapoil=True, vappars=(0.0, 0.0), rocktab=None):
+    def __init__(self, density_wog, pvtw, pvto, pvtg, swof, sgof, rock, disgas=True, vapoil=True, vappars=(0.0, 0.0), rocktab=None,
+                 threephase_model=0, stone1_exponent=None):
         """All inputs in deck units (METRIC): lists per region.
 
         pvto: per region, list of (rs, [(p, Bo, muo), ...]) saturated rows with undersaturated
         branches; pvtg: per region, list of (pg, [(rv, Bg, mug), ...]) (first = saturated).
         pvdo / pvdg style dead tables: pass rows with a single column entry and disgas/vapoil False.
         vappars = (vap1, vap2) of VAPPARS; rocktab = rows (p [bar], pv_mult, trans_mult) of ROCKTAB (replaces `rock`).
+        threephase_model = capi.KRO_DEFAULT / KRO_STONE1 / KRO_STONE2 (STONE1, STONE2 = STONE); stone1_exponent = STONE1EX, one per
+        saturation region (None = 1.0).
         """
         self.n_pvt = len(pvtw)
         self.n_sat = len(swof)
@@ -52,6 +55,11 @@ class FluidTables:
             rt = capi.f64(rocktab).reshape(-1, 3)
             self.rocktab_n = rt.shape[0]
             self.rocktab_p, self.rocktab_pvmult, self.rocktab_transmult = capi.f64(rt[:, 0] * BAR), capi.f64(rt[:, 1]), capi.f64(rt[:, 2])
+        self.threephase_model = int(threephase_model)
+        if stone1_exponent is not None:
+            self.stone1_exponent = capi.f64(stone1_exponent)
+            if self.stone1_exponent.shape != (self.n_sat,):
+                raise ValueError("stone1_exponent needs one value per saturation region")
         self._struct = None
 
     # opm-material LiveOilPvt::initFromDeck + extendPvtoTable_ (restated): rows without
@@ -139,6 +147,7 @@ class FluidTables:
                     setattr(t, name, capi.iptr(a) if a.dtype == np.int32 else capi.dptr(a))
             t.rock_pref, t.rock_comp = self.rock_pref, self.rock_comp
             t.vap1, t.vap2, t.rocktab_n = self.vap1, self.vap2, self.rocktab_n
+            t.threephase_model = self.threephase_model
             self._struct = t
         return self._struct
 

@@ -198,7 +198,8 @@ class GpuBlackoilModel(_CprDiagnostics):
         self.ctx = C.c_void_p()
         st = self.lib.opmgpu_create(C.byref(self.ctx), device, C.byref(grid.struct()), C.byref(tables.struct()), C.byref(self.params))
         if st != capi.OK:
-            raise RuntimeError("opmgpu_create failed with status %d (no GPU? there is no CPU fallback)" % st)
+            why = self.lib.opmgpu_last_error(None)
+            raise RuntimeError("opmgpu_create failed with status %d (no GPU? there is no CPU fallback): %s" % (st, why.decode() if why else ""))
         self.nc = grid.nc
         self.max_single_precision_days = 20.0       # BlackoilModelParameters.cpp:95
         self.linear_iterations = 0
