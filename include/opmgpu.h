@@ -45,6 +45,9 @@ enum { OPMGPU_HC_GAS_ONLY = 0, OPMGPU_HC_GAS_AND_OIL = 1, OPMGPU_HC_OIL_ONLY = 2
 /* three-phase oil relative permeability model (opmgpu_tables.threephase_model) */
 enum { OPMGPU_KRO_DEFAULT = 0, OPMGPU_KRO_STONE1 = 1, OPMGPU_KRO_STONE2 = 2 };
 
+/* active phases (opmgpu_tables.active_phases); 0 = water, oil and gas */
+enum { OPMGPU_PHASES_ALL = 0, OPMGPU_PHASES_OIL_WATER = 1 };
+
 /* ILU0 elimination order.  NATURAL reproduces serial dune-istl bilu0 in the caller's
  * row order (level-scheduled on the device); MULTICOLOR is the reference's own
  * ilu_redblack idea (ISTLSolver.hpp:204-209) generalised to greedy colouring. */
@@ -144,6 +147,34 @@ typedef struct opmgpu_tables {
      * into the hysteresis history is not recalled with confidence.  Any other value of threephase_model and an exponent <= 0 are
      * OPMGPU_EINVAL too; the text of a refused opmgpu_create is opmgpu_last_error(NULL).                                          */
     int32_t threephase_model;                  /* OPMGPU_KRO_*                                  */
+    /* Active phases (the deck's OIL / WATER / GAS of RUNSPEC; the reference's phase_usage / active_[], consulted all over
+     * BlackoilModelBase_impl.hpp).  0 = water + oil + gas; OPMGPU_PHASES_OIL_WATER = a deck without a gas phase.  No other set is
+     * supported (oil-gas, gas-water and single-phase decks: OPMGPU_EINVAL).  The field lies in the four bytes that alignment left
+     * free between threephase_model and stone1_exponent: the size of the struct and the offset of every other field are what they
+     * were, and a caller that zero-initialises the struct gets today's three phases.
+     * With OPMGPU_PHASES_OIL_WATER:
+     *   - sgof_*, gas_*, sgof_ptr, gas_node_ptr, gas_col_ptr may be NULL (the caller's arrays are never read; the library keeps a
+     *     two-row stand-in of its own for its host-side bookkeeping, which no oil-water kernel evaluates) and surface_density[..][2] is
+     *     ignored; of opmgpu_grid.eps[] only SWL SWCR SWU SOWCR are read (the gas end points may be NULL; SGL counts as 0) and of
+     *     eps_v[] only KRW KRO PCW.
+     *   - THE LAW (opm-material's EclTwoPhaseMaterial, oil-water approach; opm-material is outside the reference tree, so as with
+     *     Stone's the rule is ours): krw(Sw) and pcow(Sw) exactly as with three phases; kro = krow(Sw), the krow column of SWOF
+     *     at the cell's water saturation with the cell's two- / three-point horizontal scaling and vertical KRO factor, constant
+     *     beyond the table's ends.  There is no connate-water clamp and none of the default three-phase law's 1e-5 blend.
+     *   - The block size stays 3.  The gas unknown is a pinned dummy: the gas equation of every cell is the identity row (diagonal
+     *     entry exactly 1 whatever matbalscale[2] is, off-diagonal entries and residual exactly 0), the third column of every
+     *     water / oil row is exactly 0 and the gas CPR weight is 0, so the third component of every solve's dx is exactly 0.
+     *     Sg, rs and rv of the state are exactly 0 and stay so; the state's hc is ignored on input and reported as
+     *     OPMGPU_HC_GAS_AND_OIL, its oil saturation is taken as given.
+     *   - Where three phases are still indexed (perforation properties, simulator data, convergence, fluid in place) the inactive
+     *     gas phase presents b_g = 1, mob_g = 0, rho_g = 0, p_g = p_o, kr_g = 0, mu_g = 1 (and 1 / b_g = 1 per cell in B_avg);
+     *     opmgpu_voidage_coefficients gives the gas coefficient 0; the gas, dissolved-gas and vaporised-oil rows of
+     *     opmgpu_compute_fluid_in_place are 0.
+     *   - OPMGPU_EINVAL, with the text in opmgpu_last_error(NULL), for: has_disgas, has_vapoil, vap1 or vap2 set;
+     *     threephase_model != OPMGPU_KRO_DEFAULT; hysteresis (opmgpu_grid.imbnum != NULL); any other value of active_phases.
+     *     opmgpu_set_device_wells refuses (OPMGPU_EINVAL, text in opmgpu_last_error(ctx)) a well whose comp_frac has a gas entry, a
+     *     control whose distribution has a gas entry, and a THP control.                                                        */
+    int32_t active_phases;                     /* 0 or OPMGPU_PHASES_OIL_WATER                  */
     const double* stone1_exponent;             /* [n_sat_regions], NULL = 1.0                   */
 } opmgpu_tables;
 

@@ -294,6 +294,7 @@ __device__ __forceinline__ void b_values(const DevTables& D, int preg, double p,
     const int oa = T.oil_node_ptr[preg], on = T.oil_node_ptr[preg + 1] - oa;
     if (sat_o) lin_at(T.oil_psat + oa, T.oil_invb_sat + oa, X.oil_dinvb_sat + oa, pvt_seg(T.oil_psat + oa, on, p), p, bo, df);
     else bo = pvt2_value(T.oil_rs + oa, on, T.oil_col_ptr + oa, T.oil_col_p, T.oil_col_invb, X.oil_col_dinvb, rs, p);
+    if (T.active_phases == OPMGPU_PHASES_OIL_WATER) { bg = 1.0; return; }       // the inactive phase's b (no gas table is read)
     const int ga = T.gas_node_ptr[preg], gn = T.gas_node_ptr[preg + 1] - ga;
     if (sat_g) lin_at(T.gas_pg + ga, T.gas_invb_sat + ga, X.gas_dinvb_sat + ga, pvt_seg(T.gas_pg + ga, gn, p), p, bg, df);
     else bg = pvt2_value(T.gas_pg + ga, gn, T.gas_col_ptr + ga, T.gas_col_rv, T.gas_col_invb, X.gas_col_dinvb, p, rv);
@@ -364,12 +365,15 @@ struct CellEval {
 struct CellOutput { double mu[3], kr[3], rsSat, rvSat; };
 
 // SolutionState + ReservoirResidualQuant of one cell (BlackoilModelBase_impl.hpp:614-751, 1484-1497, 2009-2027)
-// STONE: the deck's three-phase model is Stone I or II (T.threephase_model says which), else the default one.  A template parameter and
-// not a branch on the field, chosen on the host for every kernel that evaluates cells: with the branch k_assemble_rows' default instantiation went from 7 to 20 spilled VGPRs.
-template <bool OUTPUT = false, bool STONE = false>
+// KM: the saturation-function model of the deck -- KM_DEFAULT the default three-phase law, KM_STONE Stone I or II (T.threephase_model says
+// which), KM_OW a deck without a gas phase (T.active_phases == OPMGPU_PHASES_OIL_WATER: eval_cell_ow).  A template parameter and not a
+// branch on the fields, chosen on the host for every kernel that evaluates cells: with the branch k_assemble_rows' default instantiation went from 7 to 20 spilled VGPRs.
+template <bool OUTPUT> __device__ void eval_cell_ow(const DevTables& DT, const EpsD& E, int preg, int sreg, double p, double sw_, CellEval& q, CellOutput* out);
+template <bool OUTPUT = false, int KM = KM_DEFAULT>
 __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int preg, int sreg, double p, double sw_, double sg_, double rs_, double rv_, int hc,
                           int row, CellEval& q, const HystD& H = HystD{ false, 0, 2.0, 2.0, 0.0, 0.0 }, const EpsD* EI = nullptr, CellOutput* out = nullptr)
 {
+    if constexpr (KM == KM_OW) { eval_cell_ow<OUTPUT>(DT, E, preg, sreg, p, sw_, q, out); return; }
     const opmgpu_tables& T = DT.t; const TabX& X = DT.x;
     const bool isSg = hc == OPMGPU_HC_GAS_AND_OIL, isRs = hc == OPMGPU_HC_OIL_ONLY, isRv = hc == OPMGPU_HC_GAS_ONLY;
     const bool freeOil = isSg || isRs, freeGas = isSg || isRv;
@@ -415,7 +419,7 @@ __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int
         krg = vchain(f, df, sg);
     }
     V4 kro;
-    if constexpr (STONE) kro = stone_kro(DT, E, sreg, row, sw_, W, sg, krw, krg);      // (never with hysteresis: refused at creation)
+    if constexpr (KM == KM_STONE) kro = stone_kro(DT, E, sreg, row, sw_, W, sg, krw, krg);      // (never with hysteresis: refused at creation)
     else {   // EclDefaultMaterial::krn
         // connate water of the three-phase law: the cell's scaled SWL; a set without horizontal scaling (s0 = u0 = 0, k = 1) has the table's
         const bool hscaled = E.on && (E.k[EC_PCOW] != 1.0 || E.s0[EC_PCOW] != 0.0 || E.u0[EC_PCOW] != 0.0);
@@ -540,9 +544,95 @@ __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int
         out->rsSat = rsSat.v; out->rvSat = rvSat.v;
     }
 }
+// eval_cell of a deck WITHOUT a gas phase (oil and water active; the law is stated in include/opmgpu.h at opmgpu_tables::active_phases):
+// krw(Sw) and pcow(Sw) as with three phases, kro = krow(Sw) with the EC_KROW scaling -- no connate-water clamp, no blend --, the dead-oil
+// PVT, So = 1 - Sw.  No gas table is touched.  The inactive gas phase presents b_g = 1, mu_g = 1, mob_g = 0, rho_g = 0, p_g = p_o,
+// Sg = rs = rv = 0 with all derivatives 0, so that what still indexes three phases needs no guard; d/dXvar of everything is 0.
+template <bool OUTPUT>
+__device__ void eval_cell_ow(const DevTables& DT, const EpsD& E, int preg, int sreg, double p, double sw_, CellEval& q, CellOutput* out)
+{
+    const opmgpu_tables& T = DT.t; const TabX& X = DT.x;
+    const V4 P = mk(p, 1, 0, 0), W = mk(sw_, 0, 1, 0), zero = mk(0, 0, 0, 0), one = mk(1, 0, 0, 0);
+    const V4 so = mk(1.0 - sw_, 0, -1, 0);
+    q.sw = W; q.so = so; q.sg = zero; q.rs = zero; q.rv = zero; q.pg = P;
+    const int wa = T.swof_ptr[sreg], nw = T.swof_ptr[sreg + 1] - wa;
+    const double* xsw = T.swof_sw + wa;
+    double f, df;
+    V4 krw, kro;
+    if (!E.on) {      // the three curves share the segment of Sw
+        int cw;
+        const int iw = sat_seg<false>(xsw, nw, sw_, cw);
+        sat_at(xsw, T.swof_pcow + wa, X.swof_dpcow + wa, nw, iw, cw, sw_, f, df);
+        q.pw = mk(p - f, 1, -df, 0);
+        sat_at(xsw, T.swof_krw + wa, X.swof_dkrw + wa, nw, iw, cw, sw_, f, df);
+        krw = mk(f, 0, df, 0);
+        sat_at(xsw, T.swof_krow + wa, X.swof_dkrow + wa, nw, iw, cw, sw_, f, df);
+        kro = mk(f, 0, df, 0);
+    } else {
+        sat_curve_s<false>(xsw, T.swof_pcow + wa, X.swof_dpcow + wa, nw, sw_, E, EC_PCOW, f, df);
+        q.pw = mk(p - f, 1, -df, 0);
+        sat_curve_s<false>(xsw, T.swof_krw + wa, X.swof_dkrw + wa, nw, sw_, E, EC_KRW, f, df);
+        krw = mk(f, 0, df, 0);
+        sat_curve_s<false>(xsw, T.swof_krow + wa, X.swof_dkrow + wa, nw, sw_, E, EC_KROW, f, df);
+        kro = mk(f, 0, df, 0);
+    }
+    // water PVT (ConstantCompressibilityWaterPvt), dead-oil PVT (the saturated curve): the arithmetic of eval_cell
+    V4 mu[2];
+    {
+        const double* w = T.pvtw + 5 * preg;
+        const double iw1 = 1.0 / w[1];
+        const double Xc = w[2] * (q.pw.v - w[0]);
+        const double bw = (1.0 + Xc * (1.0 + Xc / 2.0)) * iw1;
+        const double dbw = w[2] * (1.0 + Xc) * iw1;
+        q.b[0] = vchain(bw, dbw, q.pw);
+        const double c = w[2] - w[4];
+        const double Y = c * (q.pw.v - w[0]);
+        const double den = 1.0 + Y * (1.0 + Y / 2.0), iden = 1.0 / den;
+        const double BM = w[3] * w[1];
+        mu[0] = vchain(BM * bw * iden, BM * (dbw * den - bw * c * (1.0 + Y)) * (iden * iden), q.pw);
+    }
+    {
+        const int oa = T.oil_node_ptr[preg], on = T.oil_node_ptr[preg + 1] - oa;
+        const int ip = pvt_seg(T.oil_psat + oa, on, p);
+        double ib, dibp, ibm, dibmp;
+        lin_at(T.oil_psat + oa, T.oil_invb_sat + oa, X.oil_dinvb_sat + oa, ip, p, ib, dibp);
+        lin_at(T.oil_psat + oa, T.oil_invbmu_sat + oa, X.oil_dinvbmu_sat + oa, ip, p, ibm, dibmp);
+        q.b[1] = mk(ib, dibp, 0, 0);
+        const double r = 1.0 / ibm, m = ib * r;
+        mu[1] = mk(m, (dibp - m * dibmp) * r, 0, 0);
+    }
+    q.b[2] = one;
+    const double* rhos = T.surface_density + 3 * preg;
+    q.rho[0] = vscale(rhos[0], q.b[0]);
+    q.rho[1] = vscale(rhos[1], q.b[1]);
+    q.rho[2] = zero;
+    V4 pvm = one;
+    if (T.rocktab_n > 0) {
+        rocktab_eval(T.rocktab_p, T.rocktab_pvmult, T.rocktab_n, p, f, df); pvm = mk(f, df, 0, 0);
+        rocktab_eval(T.rocktab_p, T.rocktab_transmult, T.rocktab_n, p, f, df);
+        const V4 trm = mk(f, df, 0, 0);
+        q.mob[0] = vdiv1(vmul(trm, krw), mu[0]); q.mob[1] = vdiv1(vmul(trm, kro), mu[1]);
+    } else {
+        q.mob[0] = vdiv1(krw, mu[0]); q.mob[1] = vdiv1(kro, mu[1]);
+    }
+    q.mob[2] = zero;
+    if (T.rocktab_n == 0 && T.rock_comp != 0.0) {
+        const double cp = T.rock_comp * (p - T.rock_pref);
+        pvm = mk(1.0 + cp + 0.5 * cp * cp, T.rock_comp + cp * T.rock_comp, 0, 0);
+    }
+    q.pvm = pvm;
+    q.accum[0] = vmul(vmul(pvm, q.b[0]), W);
+    q.accum[1] = vmul(vmul(pvm, q.b[1]), so);
+    q.accum[2] = zero;
+    if constexpr (OUTPUT) {
+        out->mu[0] = mu[0].v; out->mu[1] = mu[1].v; out->mu[2] = 1.0;
+        out->kr[0] = krw.v; out->kr[1] = kro.v; out->kr[2] = 0.0;
+        out->rsSat = 0.0; out->rvSat = 0.0;
+    }
+}
 // eval_cell of a row's cell with what surrounds it: the cell's end-point scaling, its hysteresis history and, with one, the end points of
 // its imbibition curves
-template <bool STONE, bool OUTPUT = false>
+template <int KM, bool OUTPUT = false>
 __device__ __forceinline__ void eval_row(const DevTables& DT, int row, long nbp, double so_max, const int32_t* __restrict__ pvtnum, const int32_t* __restrict__ satnum,
                                          const double* __restrict__ p, const double* __restrict__ sw, const double* __restrict__ sg, const double* __restrict__ rs,
                                          const double* __restrict__ rv, const int8_t* __restrict__ hc, const double* __restrict__ eps, const double* __restrict__ eps_u0,
@@ -553,7 +643,7 @@ __device__ __forceinline__ void eval_row(const DevTables& DT, int row, long nbp,
     eps_load(eps, eps_u0, nbp, row, satnum[row], E);
     hyst_load(hy.imbnum, hy.hist, nbp, row, H);
     if (H.on) eps_load(hy.ieps, hy.iureg, nbp, row, H.ireg, EI);
-    eval_cell<OUTPUT, STONE>(DT, E, so_max, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], row, q, H, &EI, out);
+    eval_cell<OUTPUT, KM>(DT, E, so_max, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], row, q, H, &EI, out);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -569,7 +659,7 @@ __device__ __forceinline__ void eval_row(const DevTables& DT, int row, long nbp,
 //   k_cell_values : state -> the ten value planes (+ 1 / b for getConvergence)                                  [pass 1, all cells]
 //   k_assemble_rows: state -> own derivatives (eval_cell again: arithmetic is free next to the bytes), accumulation term, TPFA fluxes
 //                    from the neighbours' value planes, residual, diagonal block, transposed off-diagonal blocks, CPR weights  [pass 2]
-template <bool LDS, bool STONE>
+template <bool LDS, int KM>
 __global__ __launch_bounds__(kBlock) void k_cell_values(int nb, int nbp, DevTables D, const int32_t* __restrict__ pvtnum, const int32_t* __restrict__ satnum,
                                                         const double* __restrict__ p, const double* __restrict__ sw, const double* __restrict__ sg,
                                                         const double* __restrict__ rs, const double* __restrict__ rv, const int8_t* __restrict__ hc,
@@ -589,16 +679,19 @@ __global__ __launch_bounds__(kBlock) void k_cell_values(int nb, int nbp, DevTabl
         eps_load(eps, eps_u0, nbp, row, satnum[row], E);
         hyst_load(hy.imbnum, hy.hist, nbp, row, H);
         if (H.on) eps_load(hy.ieps, hy.iureg, nbp, row, H.ireg, EI);
-        eval_cell<false, STONE>(D, E, (D.t.vap1 > 0.0 || D.t.vap2 > 0.0) ? somax[row] : 0.0, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], row, q, H, &EI);
-        vals[long(VP_PW) * nbp + row] = q.pw.v; vals[long(VP_PG) * nbp + row] = q.pg.v;
+        eval_cell<false, KM>(D, E, (D.t.vap1 > 0.0 || D.t.vap2 > 0.0) ? somax[row] : 0.0, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], row, q, H, &EI);
+        // (no gas phase: the five water / oil planes only -- nobody reads the other five --, and 1 / b_g = 1 per cell)
+        constexpr int NP = KM == KM_OW ? 2 : 3;
+        vals[long(VP_PW) * nbp + row] = q.pw.v; if constexpr (NP == 3) vals[long(VP_PG) * nbp + row] = q.pg.v;
         const bool owned = !mask || mask[row];
 #pragma unroll
-        for (int a = 0; a < 3; ++a) {
+        for (int a = 0; a < NP; ++a) {
             vals[long(VP_RHO + a) * nbp + row] = q.rho[a].v;
             vals[long(VP_U + a) * nbp + row] = q.b[a].v * q.mob[a].v;
             if (owned) ib[a] = 1.0 / q.b[a].v;
         }
-        vals[long(VP_RS) * nbp + row] = q.rs.v; vals[long(VP_RV) * nbp + row] = q.rv.v;
+        if constexpr (NP == 3) { vals[long(VP_RS) * nbp + row] = q.rs.v; vals[long(VP_RV) * nbp + row] = q.rv.v; }
+        else if (owned) ib[2] = 1.0;
     }
     // getConvergence needs only the SUMS of 1 / b_a over the owned cells (B_avg, BlackoilModelBase_impl.hpp:1650-1660): one partial per
     // workgroup here instead of three planes written now and read back by k_conv_partial (48 MB of traffic at 100^3)
@@ -615,7 +708,7 @@ __global__ __launch_bounds__(kBlock) void k_cell_values(int nb, int nbp, DevTabl
 // bit (+: the row is c1, ngrad coefficient +1; NaN: not a connection -- the fill of an explicit well clique), g (z_c1 - z_c2), the
 // threshold pressure, and the index of the transposed entry (tpos).  All four are read coalesced at known addresses: the only dependent
 // loads of the loop are the neighbour's values.
-template <class MS, int WAVES, bool LDS, bool BATCH, bool DUAL, bool STONE>
+template <class MS, int WAVES, bool LDS, bool BATCH, bool DUAL, int KM>
 __global__ __launch_bounds__(kBlock, WAVES) void k_assemble_rows(int xm, int nb, int nbp, DevTables DT, const int32_t* __restrict__ pvtnum, const int32_t* __restrict__ satnum,
                                                           const double* __restrict__ pv, const double* __restrict__ p, const double* __restrict__ sw,
                                                           const double* __restrict__ sg, const double* __restrict__ rs, const double* __restrict__ rv,
@@ -649,32 +742,37 @@ __global__ __launch_bounds__(kBlock, WAVES) void k_assemble_rows(int xm, int nb,
         eps_load(eps, eps_u0, nbp, row, satnum[row], E);
         hyst_load(hy.imbnum, hy.hist, nbp, row, H);
         if (H.on) eps_load(hy.ieps, hy.iureg, nbp, row, H.ireg, EI);
-        eval_cell<false, STONE>(DT, E, (DT.t.vap1 > 0.0 || DT.t.vap2 > 0.0) ? somax[row] : 0.0, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], row, q, H, &EI);
+        eval_cell<false, KM>(DT, E, (DT.t.vap1 > 0.0 || DT.t.vap2 > 0.0) ? somax[row] : 0.0, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], row, q, H, &EI);
     }
+    // NP == 2, a deck without a gas phase (KM_OW): only water and oil flow.  Neither the own nor the neighbour's p_g, gas density, gas
+    // b * mobility, rs and rv planes are loaded (5 of the 10 dependent loads per connection), the gas equation is the identity row and
+    // the third column of every block is zero (see the end of the loop and of the kernel)
+    constexpr int NP = KM == KM_OW ? 2 : 3;
     const double scale[3] = { s0, s1, s2 };
     double op[3], orho[3], oU[3];                          // own values
     double dP[3][3], dRho[3][3], dU[3][3];                 // own derivatives d/d(P, Sw, Xvar) of phase pressure, density, b * mobility
     // (the row's own VALUES are read from the planes pass 1 wrote -- bit for bit what the neighbours see of this cell.  Taking them from this
     // kernel's own eval_cell instead saves 80 B per cell and was measured SLOWER, 0.239 against 0.202 ms: the values then stay live in
     // registers across the whole evaluation and the loop spills more; profiles/r03_asm_ownvals_ab.log)
-    op[0] = vals[long(VP_PW) * nbp + row]; op[1] = p[row]; op[2] = vals[long(VP_PG) * nbp + row];
+    op[0] = vals[long(VP_PW) * nbp + row]; op[1] = p[row]; if constexpr (NP == 3) op[2] = vals[long(VP_PG) * nbp + row];
     dP[0][0] = 1.0; dP[0][1] = q.pw.w; dP[0][2] = 0.0;
     dP[1][0] = 1.0; dP[1][1] = 0.0; dP[1][2] = 0.0;
     dP[2][0] = 1.0; dP[2][1] = q.pg.w; dP[2][2] = q.pg.x;
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
+    for (int a = 0; a < NP; ++a) {
         orho[a] = vals[long(VP_RHO + a) * nbp + row]; oU[a] = vals[long(VP_U + a) * nbp + row];
         const V4 u = vmul(q.b[a], q.mob[a]);
         dRho[a][0] = q.rho[a].p; dRho[a][1] = q.rho[a].w; dRho[a][2] = q.rho[a].x;
         dU[a][0] = u.p; dU[a][1] = u.w; dU[a][2] = u.x;
     }
-    const double oRs = vals[long(VP_RS) * nbp + row], oRv = vals[long(VP_RV) * nbp + row];
+    double oRs = 0.0, oRv = 0.0;
+    if constexpr (NP == 3) { oRs = vals[long(VP_RS) * nbp + row]; oRv = vals[long(VP_RV) * nbp + row]; }
     const double dRs[3] = { q.rs.p, q.rs.w, q.rs.x }, dRv[3] = { q.rv.p, q.rv.w, q.rv.x };
     // ---- accumulation term pvdt * (accum1 - accum0) and its part of the diagonal block ----
     const double pvdt = pv[row] * inv_dt;
     double Rl[3], D[9];
 #pragma unroll
-    for (int a = 0; a < 3; ++a) {
+    for (int a = 0; a < NP; ++a) {
         if (initial) accum0[long(a) * nbp + row] = q.accum[a].v;
         const double a0 = initial ? q.accum[a].v : accum0[long(a) * nbp + row];
         Rl[a] = pvdt * (q.accum[a].v - a0);
@@ -719,19 +817,19 @@ __global__ __launch_bounds__(kBlock, WAVES) void k_assemble_rows(int xm, int nb,
         const double g = grav * (side ? z_n - z_own : z_own - z_n);          // g (z_c1 - z_c2): the expression the host evaluated per entry in round 3
         // neighbour values that every connection needs: phase pressures and densities
         double np_[3], nrho[3];
-        np_[0] = vals[long(VP_PW) * nbp + nbr]; np_[1] = p[nbr]; np_[2] = vals[long(VP_PG) * nbp + nbr];
+        np_[0] = vals[long(VP_PW) * nbp + nbr]; np_[1] = p[nbr]; if constexpr (NP == 3) np_[2] = vals[long(VP_PG) * nbp + nbr];
 #pragma unroll
-        for (int a = 0; a < 3; ++a) nrho[a] = vals[long(VP_RHO + a) * nbp + nbr];
+        for (int a = 0; a < NP; ++a) nrho[a] = vals[long(VP_RHO + a) * nbp + nbr];
         double nU[3] = { 0.0, 0.0, 0.0 }, nRs = 0.0, nRv = 0.0;
         if (BATCH) {
 #pragma unroll
-            for (int a = 0; a < 3; ++a) nU[a] = vals[long(VP_U + a) * nbp + nbr];
-            nRs = vals[long(VP_RS) * nbp + nbr]; nRv = vals[long(VP_RV) * nbp + nbr];
+            for (int a = 0; a < NP; ++a) nU[a] = vals[long(VP_U + a) * nbp + nbr];
+            if constexpr (NP == 3) { nRs = vals[long(VP_RS) * nbp + nbr]; nRv = vals[long(VP_RV) * nbp + nbr]; }
         }
         double Tdh[3], ddh[3][3];
         bool own_up[3];
 #pragma unroll
-        for (int a = 0; a < 3; ++a) {
+        for (int a = 0; a < NP; ++a) {
             const double p1 = side ? np_[a] : op[a], p2 = side ? op[a] : np_[a];
             const double r1 = side ? nrho[a] : orho[a], r2 = side ? orho[a] : nrho[a];
             double dh = (p1 - p2) - g * (0.5 * r1 + 0.5 * r2);
@@ -749,23 +847,50 @@ __global__ __launch_bounds__(kBlock, WAVES) void k_assemble_rows(int xm, int nb,
         }
         // upwind-dependent values of the neighbour.  BATCH: all five loaded with the pressures and densities above (one dependent round trip
         // per connection instead of two; the lines are fetched by some lane of the wave anyway); otherwise only the ones the upwinding asks for
-        double Uv[3] = { oU[0], oU[1], oU[2] }, rsu = oRs, rvu = oRv;
+        double Uv[3] = { oU[0], oU[1], NP == 3 ? oU[2] : 0.0 }, rsu = oRs, rvu = oRv;
         if (BATCH) {
 #pragma unroll
-            for (int a = 0; a < 3; ++a) Uv[a] = own_up[a] ? oU[a] : nU[a];
-            rsu = own_up[1] ? oRs : nRs; rvu = own_up[2] ? oRv : nRv;
+            for (int a = 0; a < NP; ++a) Uv[a] = own_up[a] ? oU[a] : nU[a];
+            if constexpr (NP == 3) { rsu = own_up[1] ? oRs : nRs; rvu = own_up[2] ? oRv : nRv; }
         } else {
 #pragma unroll
-            for (int a = 0; a < 3; ++a) if (!own_up[a]) Uv[a] = vals[long(VP_U + a) * nbp + nbr];
-            if (!own_up[1]) rsu = vals[long(VP_RS) * nbp + nbr];
-            if (!own_up[2]) rvu = vals[long(VP_RV) * nbp + nbr];
+            for (int a = 0; a < NP; ++a) if (!own_up[a]) Uv[a] = vals[long(VP_U + a) * nbp + nbr];
+            if constexpr (NP == 3) {
+                if (!own_up[1]) rsu = vals[long(VP_RS) * nbp + nbr];
+                if (!own_up[2]) rvu = vals[long(VP_RV) * nbp + nbr];
+            }
         }
         double F[3], dF[3][3];
 #pragma unroll
-        for (int a = 0; a < 3; ++a) {
+        for (int a = 0; a < NP; ++a) {
             F[a] = Uv[a] * Tdh[a];
 #pragma unroll
             for (int v = 0; v < 3; ++v) dF[a][v] = Uv[a] * (Tf * ddh[a][v]) + (own_up[a] ? dU[a][v] * Tdh[a] : 0.0);
+        }
+        if constexpr (NP == 2) {
+            // G_w = F_w, G_o = F_o, nothing depends on the dummy unknown: block (nbr, row) = -s scale dF / d(P, Sw) in its water / oil
+            // rows, exact zeros in its third column and in its gas row
+            const double s = side ? -1.0 : 1.0;
+            const bool nbr_ghost = mask && !mask[nbr];
+            MS* tptr = A + long(tp >> 6) * 576 + (tp & 63);
+            float* tptr32 = DUAL ? A32 + long(tp >> 6) * 576 + (tp & 63) : nullptr;
+#pragma unroll
+            for (int a = 0; a < 3; ++a) {
+                if (a < 2) Rl[a] += s * F[a];
+#pragma unroll
+                for (int v = 0; v < 3; ++v) {
+                    double own = 0.0;
+                    if (a < 2 && v < 2) {
+                        own = s * scale[a] * dF[a][v];
+                        if (v == 0) sod[a] += fabs(own);
+                        D[3 * a + v] += own;
+                    }
+                    const bool z = nbr_ghost || a == 2 || v == 2;
+                    __builtin_nontemporal_store(z ? MS(0) : MS(-own), &tptr[(3 * a + v) * 64]);
+                    if (DUAL) __builtin_nontemporal_store(z ? 0.f : float(-own), &tptr32[(3 * a + v) * 64]);
+                }
+            }
+            continue;
         }
         // G_o = F_o + rv_up(g) F_g ; G_g = F_g + rs_up(o) F_o
         const double G[3] = { F[0], F[1] + rvu * F[2], F[2] + rsu * F[1] };
@@ -803,10 +928,13 @@ __global__ __launch_bounds__(kBlock, WAVES) void k_assemble_rows(int xm, int nb,
         if (wout) { wout[row] = MS(1); wout[nbp + row] = MS(0); wout[2 * long(nbp) + row] = MS(0); }      // identity row: its pressure entry
         return;
     }
+    if constexpr (NP == 2) {      // the pinned gas unknown: identity row (exactly 1, whatever the scale), zero third column, zero residual
+        D[2] = 0.0; D[5] = 0.0; D[6] = 0.0; D[7] = 0.0; D[8] = 1.0; Rl[2] = 0.0;
+    }
 #pragma unroll
     for (int c = 0; c < 9; ++c) { __builtin_nontemporal_store(MS(D[c]), &dptr[c * 64]); if (DUAL) __builtin_nontemporal_store(float(D[c]), &dptr32[c * 64]); }
     if (wout) {
-        const bool w_ = fabs(D[0]) / sod[0] > 0.01, g_ = fabs(D[6]) / sod[2] > 0.01;       // NaN (0/0) compares false like the reference's Eigen cast
+        const bool w_ = fabs(D[0]) / sod[0] > 0.01, g_ = NP == 3 && fabs(D[6]) / sod[2] > 0.01;       // NaN (0/0) compares false like the reference's Eigen cast
         bool o_ = fabs(D[3]) / sod[1] > 0.01;
         if (!o_ && !w_ && !g_) o_ = true;
         wout[row] = w_ ? MS(1) : MS(0); wout[nbp + row] = o_ ? MS(1) : MS(0); wout[2 * long(nbp) + row] = g_ ? MS(1) : MS(0);
@@ -992,7 +1120,7 @@ __global__ __launch_bounds__(kBlock) void k_gather_perf3(int nperf, int nbp, con
 }
 
 // per-perforation properties for the host well model (extractWellPerfProperties)
-template <bool STONE>
+template <int KM>
 __global__ __launch_bounds__(kBlock) void k_perf_props(int nperf, DevTables T, const int32_t* __restrict__ cells, const int32_t* __restrict__ pvtnum,
                                                        const int32_t* __restrict__ satnum, const double* __restrict__ p, const double* __restrict__ sw,
                                                        const double* __restrict__ sg, const double* __restrict__ rs, const double* __restrict__ rv,
@@ -1004,7 +1132,7 @@ __global__ __launch_bounds__(kBlock) void k_perf_props(int nperf, DevTables T, c
     if (i >= nperf) return;
     const int c = cells[i];
     CellEval q;
-    eval_row<STONE>(T, c, nbp, somax[c], pvtnum, satnum, p, sw, sg, rs, rv, hc, eps, eps_u0, hy, q);
+    eval_row<KM>(T, c, nbp, somax[c], pvtnum, satnum, p, sw, sg, rs, rv, hc, eps, eps_u0, hy, q);
     const V4 list[9] = { mk(p[c], 1, 0, 0), q.rs, q.rv, q.b[0], q.b[1], q.b[2], q.mob[0], q.mob[1], q.mob[2] };
     double* o = out + long(i) * OPMGPU_PERF_K;
 #pragma unroll
@@ -1014,7 +1142,7 @@ __global__ __launch_bounds__(kBlock) void k_perf_props(int nperf, DevTables T, c
 // computeFluidInPlace, the per-cell part (BlackoilModelBase_impl.hpp:2263-2296): fip[phase] = ((pv_mult * b_phase) * s_phase) * pv with b at the
 // phase pressures and the cell's phase condition, dissolved gas = rs * fip[oil], vaporised oil = rv * fip[gas]; plus what the region
 // loops need of the state (pore volume, pressure, so + sg).  Output in the CALLER's cell order: out[q * nc + nat[row]], q = 0..7.
-template <bool STONE>
+template <int KM>
 __global__ __launch_bounds__(kBlock) void k_fip_cells(int nc, DevTables T, const int32_t* __restrict__ nat, const int32_t* __restrict__ pvtnum,
                                                       const int32_t* __restrict__ satnum, const double* __restrict__ pv, const double* __restrict__ p,
                                                       const double* __restrict__ sw, const double* __restrict__ so_, const double* __restrict__ sg, const double* __restrict__ rs,
@@ -1025,7 +1153,7 @@ __global__ __launch_bounds__(kBlock) void k_fip_cells(int nc, DevTables T, const
     const int c = blockIdx.x * kBlock + threadIdx.x;
     if (c >= nc) return;
     CellEval q;
-    eval_row<STONE>(T, c, nbp, somax[c], pvtnum, satnum, p, sw, sg, rs, rv, hc, eps, eps_u0, hy, q);
+    eval_row<KM>(T, c, nbp, somax[c], pvtnum, satnum, p, sw, sg, rs, rv, hc, eps, eps_u0, hy, q);
     const long n = nat[c];
     const double so = so_[c], sgv = sg[c], swv = sw[c];          // the state's saturations, as the reference takes them
     const double fw = ((q.pvm.v * q.b[0].v) * swv) * pv[c];
@@ -1042,7 +1170,7 @@ __global__ __launch_bounds__(kBlock) void k_fip_cells(int nc, DevTables T, const
 // multiplier, not divided by the viscosity); RsSat / RvSat are the saturated values (VAPPARS factor included) of EVERY cell whatever its
 // phase state; Pb / Pd invert the plain curves at the solution state's rs / rv (sat_pressure).  OPMGPU_SIMDATA_K planes in the CALLER's
 // cell order: out[q * nc + nat[row]], slots OPMGPU_SD_* of opmgpu.h.  An output path: once per report step.
-template <bool STONE>
+template <int KM>
 __global__ __launch_bounds__(kBlock) void k_simulator_data(int nc, DevTables T, const int32_t* __restrict__ nat, const int32_t* __restrict__ pvtnum,
                                                            const int32_t* __restrict__ satnum, const double* __restrict__ p, const double* __restrict__ sw,
                                                            const double* __restrict__ sg, const double* __restrict__ rs, const double* __restrict__ rv,
@@ -1054,7 +1182,7 @@ __global__ __launch_bounds__(kBlock) void k_simulator_data(int nc, DevTables T, 
     if (c >= nc) return;
     CellEval q;
     CellOutput x;
-    eval_row<STONE, true>(T, c, nbp, somax[c], pvtnum, satnum, p, sw, sg, rs, rv, hc, eps, eps_u0, hy, q, &x);
+    eval_row<KM, true>(T, c, nbp, somax[c], pvtnum, satnum, p, sw, sg, rs, rv, hc, eps, eps_u0, hy, q, &x);
     const int preg = pvtnum[c];
     double* o = out + nat[c];
     const long n = nc;
@@ -1115,6 +1243,7 @@ __global__ __launch_bounds__(kBlock) void k_voidage_coeff(int n, DevTables D, co
         cg += 1.0 / den;
         co -= rs / den;
     }
+    if (D.t.active_phases == OPMGPU_PHASES_OIL_WATER) cg = 0.0;      // no gas phase: no gas voidage
     coeff[3 * long(i) + 0] = cw; coeff[3 * long(i) + 1] = co; coeff[3 * long(i) + 2] = cg;
 }
 
@@ -1171,16 +1300,31 @@ BlackoilDevice::BlackoilDevice(hipStream_t s, LinSolver& ls_, const opmgpu_grid*
     h_pvtnum.assign(nc, 0); h_satnum.assign(nc, 0);
     if (g->pvtnum) h_pvtnum.assign(g->pvtnum, g->pvtnum + nc);
     if (g->satnum) h_satnum.assign(g->satnum, g->satnum + nc);
+    if (t->active_phases != OPMGPU_PHASES_ALL && t->active_phases != OPMGPU_PHASES_OIL_WATER)
+        throw HipError(OPMGPU_EINVAL, "active_phases is neither 0 (water, oil and gas) nor OPMGPU_PHASES_OIL_WATER: oil-gas, gas-water and single-phase decks are not supported");
+    const bool ow = t->active_phases == OPMGPU_PHASES_OIL_WATER;
+    if (ow) {
+        if (t->has_disgas || t->has_vapoil) throw HipError(OPMGPU_EINVAL, "OPMGPU_PHASES_OIL_WATER: has_disgas / has_vapoil (DISGAS / VAPOIL) need a gas phase");
+        if (t->vap1 != 0.0 || t->vap2 != 0.0) throw HipError(OPMGPU_EINVAL, "OPMGPU_PHASES_OIL_WATER: vap1 / vap2 (VAPPARS) need a gas phase");
+        if (t->threephase_model != OPMGPU_KRO_DEFAULT) throw HipError(OPMGPU_EINVAL, "OPMGPU_PHASES_OIL_WATER: threephase_model must be OPMGPU_KRO_DEFAULT (a Stone law needs a gas phase)");
+        if (g->imbnum) throw HipError(OPMGPU_EINVAL, "OPMGPU_PHASES_OIL_WATER together with hysteresis (imbnum) is not supported");
+    }
     has_endpoints = g->eps[0] != nullptr;
     if (has_endpoints)
         for (int k = 0; k < 8; ++k) {
+            if (ow && k >= 4) continue;                   // no gas phase: the gas end points are not read (set below)
             if (!g->eps[k]) throw HipError(OPMGPU_EINVAL, "ENDSCALE needs all eight end-point arrays (SWL SWCR SWU SOWCR SGL SGCR SGU SOGCR)");
             h_eps[k].assign(g->eps[k], g->eps[k] + nc);
         }
+    if (has_endpoints && ow) {
+        // what the gas curves of the internal stand-in tables (upload_tables) would be scaled with; only SGL = 0 enters an oil-water curve
+        h_eps[4].assign(nc, 0.0); h_eps[5].assign(nc, 0.0); h_eps[6].resize(nc); h_eps[7] = h_eps[3];
+        for (int c = 0; c < nc; ++c) h_eps[6][c] = 1.0 - h_eps[0][c];
+    }
     scalecrs = g->scalecrs != 0;
     if (scalecrs && !has_endpoints) throw HipError(OPMGPU_EINVAL, "SCALECRS needs the end-point arrays");
     bool vert = false;
-    for (int k = 0; k < 5; ++k) if (g->eps_v[k]) { h_eps_v[k].assign(g->eps_v[k], g->eps_v[k] + nc); vert = true; }
+    for (int k = 0; k < 5; ++k) if (g->eps_v[k] && !(ow && (k == 2 || k == 4))) { h_eps_v[k].assign(g->eps_v[k], g->eps_v[k] + nc); vert = true; }
     use_hyst = g->imbnum != nullptr;
     if (use_hyst) {
         h_imbnum.assign(g->imbnum, g->imbnum + nc);
@@ -1220,6 +1364,40 @@ void BlackoilDevice::upload_tables(const opmgpu_tables* t)
 {
     // all table arrays live in ONE device blob (8-byte words) so that a kernel can stage them in LDS with one cooperative copy.  Built here
     // is the OFFSET form: every pointer field holds the word offset of its array in the blob (resolve_tables)
+    // A deck without a gas phase brings no gas tables (its pointers may be NULL).  No kernel of the oil-water instantiations reads one,
+    // but the host code below sizes the blob and reads the regions' end points through them: it gets a stand-in of two rows per region,
+    // b_g = mu_g = 1 and SGOF [(0, 0, krow(Swco), 0), (1 - Swco, 0, 0, 0)] (krg = pcgo = 0, Sgl = Sgcr = 0).
+    // Lengths the code below expects (whoever adds a gas array: give it its stand-in here):
+    //   gas_node_ptr [np + 1] -> ngn = gas_node_ptr[np] nodes;  gas_pg, gas_rvsat, gas_invb_sat, gas_invbmu_sat [ngn]
+    //   gas_col_ptr [ngn + 1] -> ngc = gas_col_ptr[ngn] samples; gas_col_rv, gas_col_invb, gas_col_invbmu [ngc]
+    //   sgof_ptr [ns + 1] -> nsg = sgof_ptr[ns] rows;            sgof_sg, sgof_krg, sgof_krog, sgof_pcgo [nsg]
+    // The constant arrays (zeros, ones) are sized from those counts, not from the region numbers.
+    opmgpu_tables standin;
+    std::vector<int32_t> si_node, si_col, si_sg;
+    std::vector<double> sd_pg, sd_zero, sd_one, sd_crv, sd_sg, sd_krog;
+    if (t->active_phases == OPMGPU_PHASES_OIL_WATER) {
+        const int np_ = t->n_pvt_regions, ns_ = t->n_sat_regions;
+        for (int r = 0; r <= np_; ++r) si_node.push_back(2 * r);                     // two nodes per PVT region
+        const int ngn_ = si_node.back();
+        for (int n = 0; n <= ngn_; ++n) si_col.push_back(2 * n);                     // two column samples per node
+        const int ngc_ = si_col.back();
+        for (int r = 0; r <= ns_; ++r) si_sg.push_back(2 * r);                       // two SGOF rows per saturation region
+        const int nsg_ = si_sg.back();
+        sd_zero.assign(size_t(std::max(std::max(ngn_, ngc_), nsg_)), 0.0); sd_one.assign(size_t(std::max(ngn_, ngc_)), 1.0);
+        for (int n = 0; n < ngn_; ++n) { sd_pg.push_back(n % 2 ? 1.0e8 : 1.0e5); sd_crv.push_back(0.0); sd_crv.push_back(1.0); }
+        for (int r = 0; r < ns_; ++r) {
+            const int a = t->swof_ptr[r];
+            sd_sg.push_back(0.0); sd_sg.push_back(1.0 - t->swof_sw[a]);
+            sd_krog.push_back(t->swof_krow[a]); sd_krog.push_back(0.0);
+        }
+        standin = *t;
+        standin.gas_node_ptr = si_node.data(); standin.gas_pg = sd_pg.data(); standin.gas_rvsat = sd_zero.data();
+        standin.gas_invb_sat = sd_one.data(); standin.gas_invbmu_sat = sd_one.data();
+        standin.gas_col_ptr = si_col.data(); standin.gas_col_rv = sd_crv.data(); standin.gas_col_invb = sd_one.data(); standin.gas_col_invbmu = sd_one.data();
+        standin.sgof_ptr = si_sg.data(); standin.sgof_sg = sd_sg.data(); standin.sgof_krg = sd_zero.data(); standin.sgof_krog = sd_krog.data();
+        standin.sgof_pcgo = sd_zero.data();
+        t = &standin;
+    }
     DevTables& o = dto_;
     o.t = *t;
     std::vector<double> blob;
@@ -1460,6 +1638,10 @@ void BlackoilDevice::build_eps_planes(const std::vector<double>* ep8, bool have_
             ep[size_t(k) * nbp + r] = 0.0; ep[size_t(EC_COUNT + k) * nbp + r] = 1.0; ep[size_t(2 * EC_COUNT + k) * nbp + r] = 1e300; ep[size_t(3 * EC_COUNT + k) * nbp + r] = 1.0;
         }
         for (int k = 0; k < EC_COUNT && have_points; ++k) {
+            if (oil_water() && k >= EC_KRG) {       // no gas phase: the gas curves are read by nobody; the identity map, unchecked
+                ep[size_t(k) * nbp + r] = 0.0; ep[size_t(EC_COUNT + k) * nbp + r] = 1.0; ep[size_t(2 * EC_COUNT + k) * nbp + r] = 1e300; ep[size_t(3 * EC_COUNT + k) * nbp + r] = 1.0;
+                continue;
+            }
             if (c >= 0 && !(s2[k] > s0[k])) throw HipError(OPMGPU_EINVAL, "ENDSCALE end points of a cell are not increasing");
             const bool three = scalecrs && have_points && k != EC_PCOW && k != EC_PCGO;
             if (three && c >= 0 && !(s1[k] > s0[k] && s2[k] > s1[k])) throw HipError(OPMGPU_EINVAL, "SCALECRS: a cell's critical saturation is not between its end points");
@@ -1585,6 +1767,10 @@ void BlackoilDevice::set_state(const double* p, const double* sat, const double*
         hbuf[r] = p[c]; hbuf[nbp + r] = sat[3 * size_t(c)]; hbuf[2 * size_t(nbp) + r] = sat[3 * size_t(c) + 1];
         hbuf[3 * size_t(nbp) + r] = sat[3 * size_t(c) + 2]; hbuf[4 * size_t(nbp) + r] = rs[c]; hbuf[5 * size_t(nbp) + r] = rv[c];
         hbuf8[r] = hc[c];
+        if (oil_water()) {        // no gas phase: Sg = rs = rv = 0 exactly, the phase condition is not the caller's
+            hbuf[3 * size_t(nbp) + r] = 0.0; hbuf[4 * size_t(nbp) + r] = 0.0; hbuf[5 * size_t(nbp) + r] = 0.0;
+            hbuf8[r] = int8_t(OPMGPU_HC_GAS_AND_OIL);
+        }
     }
     DevArray<double>* planes[] = { &d_p, &d_sw, &d_so, &d_sg, &d_rs, &d_rv };
     for (int k = 0; k < 6; ++k) OPMGPU_HIP(hipMemcpyAsync(planes[k]->p, hbuf.data() + size_t(k) * nbp, nbp * sizeof(double), hipMemcpyHostToDevice, stream));
@@ -1612,11 +1798,17 @@ void BlackoilDevice::get_state(double* p, double* sat, double* rs, double* rv, i
     }
 }
 
+// the instantiation of a cell-evaluating kernel template <int KM> for this deck's model
+#define OPMGPU_BY_MODEL(kernel) (kmodel() == KM_OW ? kernel<KM_OW> : (kmodel() == KM_STONE ? kernel<KM_STONE> : kernel<KM_DEFAULT>))
+
 void BlackoilDevice::launch_cell_values()
 {
     const Plan& P = ls.plan;
-    const bool lds = tab_lds_words() > 0, stone = stone_model();
-    auto kern = stone ? (lds ? k_cell_values<true, true> : k_cell_values<false, true>) : (lds ? k_cell_values<true, false> : k_cell_values<false, false>);
+    const bool lds = tab_lds_words() > 0;
+    const int km = kmodel();
+    auto kern = km == KM_OW ? (lds ? k_cell_values<true, KM_OW> : k_cell_values<false, KM_OW>)
+              : km == KM_STONE ? (lds ? k_cell_values<true, KM_STONE> : k_cell_values<false, KM_STONE>)
+                               : (lds ? k_cell_values<true, KM_DEFAULT> : k_cell_values<false, KM_DEFAULT>);
     hipLaunchKernelGGL(kern, dim3(grid_for(nc)), dim3(kBlock), tab_lds_bytes(), stream, nc, P.nbp, dto_, d_pvtnum.p, d_satnum.p,
                        d_p.p, d_sw.p, d_sg.p, d_rs.p, d_rv.p, d_hc.p, eps_planes(), d_eps_u0.p, d_somax.p, d_vals.p, d_bpart.p,
                        ls.comm ? ls.comm->owner_mask() : (const int8_t*)nullptr, (const double*)d_tab.p, tab_lds_words(), hyst_args());
@@ -1645,15 +1837,19 @@ template <class MS> void BlackoilDevice::assemble_kernels(double dt, bool initia
     static const bool dual = env_flag("OPMGPU_MIXED_DUALWRITE", true);
     float* a32 = nullptr;
     if (dual && sizeof(MS) == 8 && prm.preconditioner_single && !props_only && ls.emulate_ranks <= 1 && !(prm.use_cpr && prm.cpr_reference_transform)) { a32 = ls.matrix_f(); dual_written = true; }
-    auto kern = !lds ? k_assemble_rows<MS, 2, false, false, false, false>
-                     : (waves == 3 ? (batch ? k_assemble_rows<MS, 3, true, true, false, false> : k_assemble_rows<MS, 3, true, false, false, false>)
-                                   : (batch ? k_assemble_rows<MS, 2, true, true, false, false> : k_assemble_rows<MS, 2, true, false, false, false>));
-    if (a32) kern = lds ? k_assemble_rows<MS, 2, true, true, true, false> : k_assemble_rows<MS, 2, false, false, true, false>;      // (the dual-write variant: 2 waves per SIMD, no spills)
+    auto kern = !lds ? k_assemble_rows<MS, 2, false, false, false, KM_DEFAULT>
+                     : (waves == 3 ? (batch ? k_assemble_rows<MS, 3, true, true, false, KM_DEFAULT> : k_assemble_rows<MS, 3, true, false, false, KM_DEFAULT>)
+                                   : (batch ? k_assemble_rows<MS, 2, true, true, false, KM_DEFAULT> : k_assemble_rows<MS, 2, true, false, false, KM_DEFAULT>));
+    if (a32) kern = lds ? k_assemble_rows<MS, 2, true, true, true, KM_DEFAULT> : k_assemble_rows<MS, 2, false, false, true, KM_DEFAULT>;      // (the dual-write variant: 2 waves per SIMD, no spills)
     // Stone I / II: instantiations of their own, so that the default model's compile to what they were.  Two waves per SIMD and the batched
     // loads only -- the two knobs above were tuned on the default model
-    if (stone_model())
-        kern = a32 ? (lds ? k_assemble_rows<MS, 2, true, true, true, true> : k_assemble_rows<MS, 2, false, false, true, true>)
-                   : (lds ? k_assemble_rows<MS, 2, true, true, false, true> : k_assemble_rows<MS, 2, false, false, false, true>);
+    if (kmodel() == KM_STONE)
+        kern = a32 ? (lds ? k_assemble_rows<MS, 2, true, true, true, KM_STONE> : k_assemble_rows<MS, 2, false, false, true, KM_STONE>)
+                   : (lds ? k_assemble_rows<MS, 2, true, true, false, KM_STONE> : k_assemble_rows<MS, 2, false, false, false, KM_STONE>);
+    // no gas phase: the same four shapes as Stone's (two waves per SIMD, batched loads)
+    if (kmodel() == KM_OW)
+        kern = a32 ? (lds ? k_assemble_rows<MS, 2, true, true, true, KM_OW> : k_assemble_rows<MS, 2, false, false, true, KM_OW>)
+                   : (lds ? k_assemble_rows<MS, 2, true, true, false, KM_OW> : k_assemble_rows<MS, 2, false, false, false, KM_OW>);
     hipLaunchKernelGGL(kern, dim3(grid8_for(nc)), dim3(kBlock), tab_lds_bytes(), stream, xcd_mode(), nc, P.nbp, dto_, d_pvtnum.p, d_satnum.p, d_pv.p,
                        d_p.p, d_sw.p, d_sg.p, d_rs.p, d_rv.p, d_hc.p, 1.0 / dt, int(initial), sc[0], sc[1], sc[2],
                        ls.dp.slice_ptr.p, ls.dp.col.p, ls.dp.rowlen.p, ls.dp.nlower.p, ls.dp.tpos.p, d_tr_e.p, (const double*)d_zc.p, gravity, use_thpres ? d_thp_e.p : (const double*)nullptr,
@@ -1880,7 +2076,7 @@ void BlackoilDevice::attach_comm(CommBase* c, int n_owned)
 void BlackoilDevice::perf_props_device()
 {
     if (nperf == 0) return;
-    hipLaunchKernelGGL(stone_model() ? k_perf_props<true> : k_perf_props<false>, dim3(grid_for(nperf)), dim3(kBlock), 0, stream, nperf, dtp_, d_perf_cells.p, d_pvtnum.p, d_satnum.p,
+    hipLaunchKernelGGL(OPMGPU_BY_MODEL(k_perf_props), dim3(grid_for(nperf)), dim3(kBlock), 0, stream, nperf, dtp_, d_perf_cells.p, d_pvtnum.p, d_satnum.p,
                        d_p.p, d_sw.p, d_sg.p, d_rs.p, d_rv.p, d_hc.p, eps_planes(), d_eps_u0.p, d_somax.p, long(ls.plan.nbp), d_perf.p, hyst_args());
 }
 
@@ -1925,7 +2121,7 @@ void BlackoilDevice::average_b(double* B3)
 void BlackoilDevice::perf_props(double* out)
 {
     if (nperf == 0) return;
-    hipLaunchKernelGGL(stone_model() ? k_perf_props<true> : k_perf_props<false>, dim3(grid_for(nperf)), dim3(kBlock), 0, stream, nperf, dtp_, d_perf_cells.p, d_pvtnum.p, d_satnum.p,
+    hipLaunchKernelGGL(OPMGPU_BY_MODEL(k_perf_props), dim3(grid_for(nperf)), dim3(kBlock), 0, stream, nperf, dtp_, d_perf_cells.p, d_pvtnum.p, d_satnum.p,
                        d_p.p, d_sw.p, d_sg.p, d_rs.p, d_rv.p, d_hc.p, eps_planes(), d_eps_u0.p, d_somax.p, long(ls.plan.nbp), d_perf.p, hyst_args());
     OPMGPU_HIP(hipMemcpyAsync(out, d_perf.p, size_t(nperf) * OPMGPU_PERF_K * sizeof(double), hipMemcpyDeviceToHost, stream));
     OPMGPU_HIP(hipStreamSynchronize(stream));
@@ -2068,7 +2264,7 @@ void BlackoilDevice::stabilize_update(int relax_type, double omega)
 void BlackoilDevice::simulator_data(double* out)
 {
     DevArray<double> dout; dout.alloc(size_t(OPMGPU_SIMDATA_K) * nc);
-    hipLaunchKernelGGL(stone_model() ? k_simulator_data<true> : k_simulator_data<false>, dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, dtp_, ls.dp.nat.p, d_pvtnum.p, d_satnum.p,
+    hipLaunchKernelGGL(OPMGPU_BY_MODEL(k_simulator_data), dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, dtp_, ls.dp.nat.p, d_pvtnum.p, d_satnum.p,
                        d_p.p, d_sw.p, d_sg.p, d_rs.p, d_rv.p, d_hc.p, eps_planes(), d_eps_u0.p, d_somax.p, long(ls.plan.nbp), dout.p, hyst_args());
     dout.download(out, size_t(OPMGPU_SIMDATA_K) * nc, stream);
     OPMGPU_HIP(hipStreamSynchronize(stream));
@@ -2081,7 +2277,7 @@ void BlackoilDevice::fluid_in_place(const int32_t* fipnum, int dims, double* fip
 {
     const Plan& P = ls.plan;
     DevArray<double> dout; dout.alloc(size_t(8) * nc);
-    hipLaunchKernelGGL(stone_model() ? k_fip_cells<true> : k_fip_cells<false>, dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, dtp_, ls.dp.nat.p, d_pvtnum.p, d_satnum.p, d_pv.p,
+    hipLaunchKernelGGL(OPMGPU_BY_MODEL(k_fip_cells), dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, dtp_, ls.dp.nat.p, d_pvtnum.p, d_satnum.p, d_pv.p,
                        d_p.p, d_sw.p, d_so.p, d_sg.p, d_rs.p, d_rv.p, d_hc.p, eps_planes(), d_eps_u0.p, d_somax.p, long(P.nbp), dout.p, hyst_args());
     std::vector<double> h(size_t(8) * nc);
     dout.download(h.data(), h.size(), stream);

@@ -30,6 +30,9 @@ struct DevTables { opmgpu_tables t; TabX x; const double* stone_som; };
 // variables only and writes the neighbour's off-diagonal block itself (k_assemble_rows).
 enum { VP_PW = 0, VP_PG = 1, VP_RHO = 2 /* + phase */, VP_U = 5 /* + phase */, VP_RS = 8, VP_RV = 9, VP_COUNT = 10 };
 
+// the saturation-function model a cell-evaluating kernel is instantiated for (eval_cell), chosen on the host: BlackoilDevice::kmodel()
+enum { KM_DEFAULT = 0, KM_STONE = 1, KM_OW = 2 };
+
 constexpr int kRedPart = 32;        // d_red: [0, 32) results, per-workgroup partials behind them
 
 class BlackoilDevice {
@@ -158,7 +161,9 @@ private:
     DevArray<double> d_tab;                  // all table arrays in one blob of 8-byte words (staged in LDS by the property kernels)
     int tab_words = 0;
     static constexpr int kTabLdsMaxBytes = 24 * 1024;     // 6 workgroups x 24 KiB fit the 160 KiB LDS of a CU: no occupancy lost
-    bool stone_model() const { return dto_.t.threephase_model != OPMGPU_KRO_DEFAULT; }      // chooses the kernels' STONE instantiations (eval_cell)
+    // chooses the kernels' KM instantiations (eval_cell)
+    int kmodel() const { return oil_water() ? KM_OW : (dto_.t.threephase_model != OPMGPU_KRO_DEFAULT ? KM_STONE : KM_DEFAULT); }
+    bool oil_water() const { return dto_.t.active_phases == OPMGPU_PHASES_OIL_WATER; }
     int tab_lds_words() const { return tab_words * 8 <= kTabLdsMaxBytes ? tab_words : 0; }
     size_t tab_lds_bytes() const { return size_t(tab_lds_words()) * 8; }
     // device: static per-cell / per-connection (internal numbering for cells)

@@ -901,6 +901,16 @@ int BlackoilDevice::set_device_wells(const opmgpu_wells* s)
         if (c < 0 || c >= nc || seen[c]) return OPMGPU_EINVAL;         // a cell perforated twice is not supported
         seen[c] = 1;
     }
+    if (oil_water()) {
+        // no gas phase: with the inactive phase's b_g = 1, mob_g = 0, rho_g = 0 the well kernels work as they are -- the gas well equation
+        // reduces to q_g = 0 with unit derivative -- as long as nothing asks for gas (THP: the VFP tables' GFR axis, out of scope)
+        const int nct_ = s->ctrl_ptr ? s->ctrl_ptr[nw] : nw;
+        for (int w = 0; w < nw; ++w) if (s->comp_frac[3 * w + 2] != 0.0) throw HipError(OPMGPU_EINVAL, "a deck without a gas phase: a well's comp_frac has a gas entry");
+        for (int c = 0; c < nct_; ++c) {
+            if (s->ctrl_type[c] == OPMGPU_CTRL_THP) throw HipError(OPMGPU_EINVAL, "a deck without a gas phase: THP controls are not supported");
+            if (s->ctrl_distr && s->ctrl_distr[3 * c + 2] != 0.0) throw HipError(OPMGPU_EINVAL, "a deck without a gas phase: a well control's distribution has a gas entry (gas rate control)");
+        }
+    }
     wells_free();
     wd = new WellsDev();
     WellsDev& W = *wd;

@@ -16,6 +16,7 @@ HC_GAS_ONLY, HC_GAS_AND_OIL, HC_OIL_ONLY = 0, 1, 2
 RELAX_DAMPEN, RELAX_SOR = 0, 1
 ORDER_NATURAL, ORDER_MULTICOLOR = 0, 1
 KRO_DEFAULT, KRO_STONE1, KRO_STONE2 = 0, 1, 2          # opmgpu_tables.threephase_model
+PHASES_ALL, PHASES_OIL_WATER = 0, 1                    # opmgpu_tables.active_phases
 K_SPMV, K_ILU_APPLY, K_ILU_FACTOR, K_ASSEMBLE, K_DOT, K_AXPY, K_PROPS, K_STREAM_COPY, K_CPR_APPLY, K_VCYCLE, K_CPR_SETUP, K_SPMV_COLD = range(12)
 KT_NAMES = ["cell_props", "flux", "wells", "convergence", "ilu0_factor", "cpr_setup", "spmv_fused_dot1", "spmv_fused_dot2", "ilu0_apply", "amg_vcycle",
             "cpr_other", "vector_updates", "update_state"]
@@ -56,6 +57,20 @@ class Tables(C.Structure):
                 ("vap1", C.c_double), ("vap2", C.c_double),
                 ("rocktab_n", C.c_int32), ("rocktab_p", _dp), ("rocktab_pvmult", _dp), ("rocktab_transmult", _dp),
                 ("threephase_model", C.c_int32), ("stone1_exponent", _dp)]
+
+    # opmgpu_tables.active_phases: the int32 of the header that lies in the four bytes alignment leaves free between threephase_model and
+    # stone1_exponent (so _fields_, every offset and the size above stay what they were); 0 in a fresh struct = water, oil and gas
+    @property
+    def active_phases(self):
+        return C.c_int32.from_buffer(self, ACTIVE_PHASES_OFFSET).value
+
+    @active_phases.setter
+    def active_phases(self, v):
+        C.c_int32.from_buffer(self, ACTIVE_PHASES_OFFSET).value = int(v)
+
+
+ACTIVE_PHASES_OFFSET = Tables.threephase_model.offset + 4
+assert ACTIVE_PHASES_OFFSET + 4 <= Tables.stone1_exponent.offset
 
 
 class WellsSpec(C.Structure):

@@ -4,6 +4,11 @@ What `flow_legacy` gets from opm-parser + `DerivedGeology` (opm/autodiff/GeoProp
 (opm/autodiff/BlackoilPropsAdFromDeck.cpp:60-240), restricted to what the device path consumes:
 
   RUNSPEC   DIMENS TABDIMS OIL WATER GAS DISGAS VAPOIL METRIC ENDSCALE
+            The active phases are the ones RUNSPEC names: OIL WATER GAS, or OIL WATER -- a deck without a gas phase (Deck.phases() ==
+            "wo").  Such a deck needs and reads no gas keyword (PVTG / PVDG, SGOF, the gas end points and KRG / PCG, a gas DENSITY);
+            DISGAS, VAPOIL, VAPPARS, STONE / STONE1 / STONE2, SATOPTS HYSTER and SGAS / RS / RV in SOLUTION are refused (ValueError
+            naming the keyword); its initial oil saturation is 1 - Sw.  Oil-gas, gas-water and single-phase decks are refused.  A deck
+            that names none of the three (a fragment) counts as three-phase.
   GRID      DX DY DZ / DXV DYV DZV, TOPS (+BOX for the top layer) or DEPTHZ (flat) -- or COORD / ZCORN (corner-point, no faults) --, PORO PERMX PERMY PERMZ NTG ACTNUM MINPV, FAULTS + MULTFLT
             MULTX MULTY MULTZ MULTX- MULTY- MULTZ- MULTPV NNC
   PROPS     SWOF SGOF PVTO PVDO PVCDO PVTG PVDG PVTW DENSITY ROCK ROCKTAB VAPPARS SCALECRS (NO and YES) EHYSTR
@@ -129,12 +134,33 @@ class Deck:
         get = lambda i, d: int(r[i]) if len(r) > i and r[i] is not None else d
         return get(0, 1), get(1, 1)          # NTSFUN, NTPVT
 
+    def phases(self):
+        """"wog", or "wo" for a deck whose RUNSPEC names OIL and WATER but not GAS; every other set of phases is refused"""
+        if getattr(self, "_phases", None) is None:
+            self._phases = self._find_phases()           # once per deck: the refusals are not re-run by every caller
+        return self._phases
+
+    def _find_phases(self):
+        named = [k for k in ("OIL", "WATER", "GAS") if self.has(k)]
+        if not named or len(named) == 3:
+            return "wog"
+        if named != ["OIL", "WATER"]:
+            raise ValueError("RUNSPEC names the phases %s: only OIL WATER GAS and OIL WATER are supported" % " ".join(named))
+        for k in ("DISGAS", "VAPOIL", "VAPPARS", "STONE", "STONE1", "STONE2"):
+            if self.has(k):
+                raise ValueError("%s in a deck without GAS (RUNSPEC: OIL WATER)" % k)
+        if self.has("SATOPTS") and any(str(x).upper().startswith("HYST") for r in self.records("SATOPTS") for x in r):
+            raise ValueError("SATOPTS HYSTER in a deck without GAS (RUNSPEC: OIL WATER) is not supported")
+        return "wo"
+
     # ---------------------------------------------------------------- PROPS
     def tables(self):
         if self.has("FIELD") or self.has("LAB"):
             raise ValueError("only METRIC decks are supported")
         ntsfun, ntpvt = self.tabdims()
-        dens = [[r[1], r[0], r[2]] for r in self.records("DENSITY")[:ntpvt]]            # deck order oil water gas -> (w, o, g)
+        two_phase = self.phases() == "wo"
+        # deck order oil water gas -> (w, o, g); a deck without GAS may leave the gas density out
+        dens = [[r[1], r[0], r[2] if len(r) > 2 and r[2] is not None else 0.0] for r in self.records("DENSITY")[:ntpvt]]
         pvtw = [[r[0], r[1], r[2], r[3], r[4] if len(r) > 4 and r[4] is not None else 0.0] for r in self.records("PVTW")[:ntpvt]]
         disgas, vapoil = self.has("DISGAS"), self.has("VAPOIL")
         # oil
@@ -162,7 +188,9 @@ class Deck:
         else:
             raise ValueError("no oil PVT keyword (PVTO / PVDO / PVCDO)")
         # gas
-        if self.has("PVTG"):
+        if two_phase:
+            pvtg = None
+        elif self.has("PVTG"):
             pvtg = []
             for tab in _split_tables(self.records("PVTG")):
                 rows = []
@@ -176,7 +204,7 @@ class Deck:
         else:
             raise ValueError("no gas PVT keyword (PVTG / PVDG)")
         swof = [[tuple(rec[i:i + 4]) for i in range(0, len(rec), 4)] for rec in self.records("SWOF")[:ntsfun]]
-        sgof = [[tuple(rec[i:i + 4]) for i in range(0, len(rec), 4)] for rec in self.records("SGOF")[:ntsfun]]
+        sgof = None if two_phase else [[tuple(rec[i:i + 4]) for i in range(0, len(rec), 4)] for rec in self.records("SGOF")[:ntsfun]]
         rock = (1.0, 0.0)
         if self.has("ROCK"):
             r = self.records("ROCK")[0]
@@ -191,6 +219,8 @@ class Deck:
             r = self.records("VAPPARS")[0]
             vappars = (r[0], r[1])
         model, eta = self.threephase()
+        if two_phase:
+            return FluidTables(density_wog=dens, pvtw=pvtw, pvto=pvto, pvtg=None, swof=swof, sgof=None, rock=rock, rocktab=rocktab, phases="wo")
         return FluidTables(density_wog=dens, pvtw=pvtw, pvto=pvto, pvtg=pvtg, swof=swof, sgof=sgof, rock=rock, disgas=disgas, vapoil=vapoil,
                            vappars=vappars, rocktab=rocktab, threephase_model=model, stone1_exponent=eta)
 
@@ -523,7 +553,8 @@ class Deck:
         more = {}
         if eps is not None and self.has("SCALECRS") and str(self.records("SCALECRS")[0][0]).upper().startswith("Y"):
             more["scalecrs"] = True
-        ev = {k: self.array(k, n)[act] * (BAR if k.startswith("PC") else 1.0) for k in GridData.EPSV_NAMES if self.has(k)}
+        ev = {k: self.array(k, n)[act] * (BAR if k.startswith("PC") else 1.0) for k in GridData.EPSV_NAMES
+              if self.has(k) and not (self.phases() == "wo" and k in ("KRG", "PCG"))}
         if ev:
             if any(np.isnan(v).any() for v in ev.values()):
                 raise ValueError("vertical scaling arrays (KRW KRO KRG PCW PCG) must be given for every cell")
@@ -577,14 +608,19 @@ class Deck:
         for r in range(t.n_sat):
             a, b = t.swof_ptr[r], t.swof_ptr[r + 1]
             sw, krw, krow = t.swof_sw[a:b], t.swof_krw[a:b], t.swof_krow[a:b]
+            if t.phases == "wo":
+                un[r, :4] = [sw[0], last_zero(sw, krw), sw[-1], 1.0 - first_zero(sw, krow)]
+                continue
             a, b = t.sgof_ptr[r], t.sgof_ptr[r + 1]
             sg, krg, krog = t.sgof_sg[a:b], t.sgof_krg[a:b], t.sgof_krog[a:b]
             un[r] = [sw[0], last_zero(sw, krw), sw[-1], 1.0 - first_zero(sw, krow), sg[0], last_zero(sg, krg), sg[-1], 1.0 - first_zero(sg, krog)]
         out = {}
         for k, name in enumerate(EPS_NAMES):
-            a = self.array(prefix + name, n, None)
+            a = self.array(prefix + name, n, None) if not (t.phases == "wo" and k >= 4) else None
             dflt = un[sat, k]
             out[name] = dflt if a is None else np.where(np.isnan(a), dflt, a)
+        if t.phases == "wo":        # no gas phase: the gas end points are not the deck's (no gas curve is ever scaled); SGL = 0 is what counts
+            out["SGL"], out["SGCR"], out["SGU"], out["SOGCR"] = np.zeros(n), np.zeros(n), 1.0 - out["SWL"], out["SOWCR"].copy()
         return out
 
     # ---------------------------------------------------------------- SOLUTION
@@ -597,11 +633,18 @@ class Deck:
         nx, ny, nz = self.dims
         n = nx * ny * nz
         act = self.active
+        if tables.phases == "wo":
+            for k in ("SGAS", "RS", "RV"):
+                if self.has(k):
+                    raise ValueError("%s in the SOLUTION section of a deck without GAS (RUNSPEC: OIL WATER)" % k)
+            p = self.array("PRESSURE", n)[act] * BAR
+            sw = self.array("SWAT", n, np.zeros(n))[act]
+            z = np.zeros_like(sw)
+            return State(p, np.stack([sw, 1.0 - sw, z], 1), z, z, np.full(sw.size, capi.HC_GAS_AND_OIL, np.int8))
         p = self.array("PRESSURE", n)[act] * BAR
         sw = self.array("SWAT", n, np.zeros(n))[act]; sg = self.array("SGAS", n, np.zeros(n))[act]
         rs = self.array("RS", n, np.zeros(n))[act]; rv = self.array("RV", n, np.zeros(n))[act]
         sat = np.stack([sw, 1.0 - sw - sg, sg], 1)
-        from . import capi
         hc = np.where(sg > 0, np.where(sat[:, 1] > 0, capi.HC_GAS_AND_OIL, capi.HC_GAS_ONLY), capi.HC_OIL_ONLY).astype(np.int8)
         if not tables.has_disgas:
             hc[hc == capi.HC_OIL_ONLY] = capi.HC_GAS_AND_OIL

@@ -27,8 +27,8 @@ GRAVITY = 9.80665
 class FluidTables:
     """Flat table arrays matching `opmgpu_tables` (include/opmgpu.h)."""
 
-    def __init__(self, density_wog, pvtw, pvto, pvtg, swof, sgof, rock, disgas=True, vapoil=True, vappars=(0.0, 0.0), rocktab=None,
-                 threephase_model=0, stone1_exponent=None):
+    def __init__(self, density_wog, pvtw, pvto, pvtg, swof, sgof, rock, disgas=None, vapoil=None, vappars=(0.0, 0.0), rocktab=None,
+                 threephase_model=0, stone1_exponent=None, phases="wog"):
         """All inputs in deck units (METRIC): lists per region.
 
         pvto: per region, list of (rs, [(p, Bo, muo), ...]) saturated rows with undersaturated
@@ -36,17 +36,35 @@ class FluidTables:
         pvdo / pvdg style dead tables: pass rows with a single column entry and disgas/vapoil False.
         vappars = (vap1, vap2) of VAPPARS; rocktab = rows (p [bar], pv_mult, trans_mult) of ROCKTAB (replaces `rock`).
         threephase_model = capi.KRO_DEFAULT / KRO_STONE1 / KRO_STONE2 (STONE1, STONE2 = STONE); stone1_exponent = STONE1EX, one per
-        saturation region (None = 1.0).
+        saturation region (None = 1.0).  disgas / vapoil default to True with a gas phase.
+        phases = "wog" (water, oil, gas) or "wo": a deck without a gas phase (opmgpu_tables.active_phases = OPMGPU_PHASES_OIL_WATER) --
+        pvtg and sgof are None, pvto is a dead-oil table (PVDO / PVCDO rows), density_wog has two or three columns (a gas density is
+        ignored), and there are no gas arrays at all: the struct's gas pointers are NULL.
         """
+        if phases not in ("wog", "wo"):
+            raise ValueError("phases must be 'wog' or 'wo' (oil-gas, gas-water and single-phase decks are not supported): %r" % (phases,))
+        self.phases = phases
+        self.active_phases = capi.PHASES_OIL_WATER if phases == "wo" else capi.PHASES_ALL
         self.n_pvt = len(pvtw)
         self.n_sat = len(swof)
+        if phases == "wo":
+            if pvtg is not None or sgof is not None:
+                raise ValueError("phases='wo': pvtg and sgof must be None")
+            if disgas or vapoil or any(vappars) or threephase_model != capi.KRO_DEFAULT:
+                raise ValueError("phases='wo': DISGAS, VAPOIL, VAPPARS and the Stone laws need a gas phase")
+            disgas = vapoil = False
+            d = capi.f64(density_wog).reshape(self.n_pvt, -1)
+            density_wog = np.concatenate([d[:, :2], np.zeros((self.n_pvt, 1))], axis=1)
+        else:
+            disgas, vapoil = disgas is None or disgas, vapoil is None or vapoil
         self.has_disgas, self.has_vapoil = int(disgas), int(vapoil)
         self.surface_density = capi.f64(density_wog).reshape(self.n_pvt, 3)
         w = capi.f64(pvtw).reshape(self.n_pvt, 5).copy()
         w[:, 0] *= BAR; w[:, 2] /= BAR; w[:, 3] *= CP; w[:, 4] /= BAR
         self.pvtw = w
         self._build_oil(pvto)
-        self._build_gas(pvtg)
+        if phases != "wo":
+            self._build_gas(pvtg)
         self._build_sat(swof, sgof)
         self.rock_pref, self.rock_comp = rock[0] * BAR, rock[1] / BAR
         self.vap1, self.vap2 = float(vappars[0]), float(vappars[1])
@@ -127,12 +145,16 @@ class FluidTables:
         w, g = [], []
         for tab in swof:
             w.extend(tab); wp.append(len(w))
-        for tab in sgof:
-            g.extend(tab); gp.append(len(g))
-        w = capi.f64(w).reshape(-1, 4); g = capi.f64(g).reshape(-1, 4)
-        self.swof_ptr, self.sgof_ptr = capi.i32(wp), capi.i32(gp)
+        w = capi.f64(w).reshape(-1, 4)
+        self.swof_ptr = capi.i32(wp)
         self.swof_sw, self.swof_krw, self.swof_krow = capi.f64(w[:, 0]), capi.f64(w[:, 1]), capi.f64(w[:, 2])
         self.swof_pcow = capi.f64(w[:, 3] * BAR)
+        if sgof is None:
+            return
+        for tab in sgof:
+            g.extend(tab); gp.append(len(g))
+        g = capi.f64(g).reshape(-1, 4)
+        self.sgof_ptr = capi.i32(gp)
         self.sgof_sg, self.sgof_krg, self.sgof_krog = capi.f64(g[:, 0]), capi.f64(g[:, 1]), capi.f64(g[:, 2])
         self.sgof_pcgo = capi.f64(g[:, 3] * BAR)
 
@@ -148,6 +170,7 @@ class FluidTables:
             t.rock_pref, t.rock_comp = self.rock_pref, self.rock_comp
             t.vap1, t.vap2, t.rocktab_n = self.vap1, self.vap2, self.rocktab_n
             t.threephase_model = self.threephase_model
+            t.active_phases = self.active_phases
             self._struct = t
         return self._struct
 

@@ -21,8 +21,9 @@ _TYPES = {"INTE": (">i4", 4, 1000), "REAL": (">f4", 4, 1000), "DOUB": (">f8", 8,
 
 
 # getRestartData (SimulatorFullyImplicitBlackoilOutput.hpp:585-845): RPTRST mnemonic -> arrays of the model's output record, in the order it
-# inserts them.  VISC selects all three viscosities, VWAT / VOIL / VGAS one each.  RSSAT / RVSAT / PBPD need oil and gas both active, which
-# every deck read here has.
+# inserts them.  VISC selects all three viscosities, VWAT / VOIL / VGAS one each.  RSSAT / RVSAT / PBPD need oil and gas both active: a deck
+# without a gas phase (phases = "wo") writes none of the gas-only arrays (BG VGAS KRG RSSAT RVSAT PBPD select nothing) and DEN / VISC
+# write the two active phases.
 RPTRST_ARRAYS = (("BW", ("1OVERBW",)), ("BO", ("1OVERBO",)), ("BG", ("1OVERBG",)), ("DEN", ("WAT_DEN", "OIL_DEN", "GAS_DEN")),
                  ("VISC", ("WAT_VISC", "OIL_VISC", "GAS_VISC")), ("VWAT", ("WAT_VISC",)), ("VOIL", ("OIL_VISC",)), ("VGAS", ("GAS_VISC",)),
                  ("KRW", ("WATKR",)), ("KRO", ("OILKR",)), ("KRG", ("GASKR",)), ("RSSAT", ("RSSAT",)), ("RVSAT", ("RVSAT",)),
@@ -31,10 +32,14 @@ _ARRAY_ORDER = ("1OVERBW", "1OVERBO", "1OVERBG", "WAT_DEN", "OIL_DEN", "GAS_DEN"
                 "RSSAT", "RVSAT", "PBUB", "PDEW")
 
 
-def rptrst_arrays(mnemonics):
-    """names of the output-record arrays the RPTRST mnemonics {name: int} select (positive = on), in the order they go to the file"""
+_GAS_ARRAYS = ("1OVERBG", "GAS_DEN", "GAS_VISC", "GASKR", "RSSAT", "RVSAT", "PBUB", "PDEW")
+
+
+def rptrst_arrays(mnemonics, phases="wog"):
+    """names of the output-record arrays the RPTRST mnemonics {name: int} select (positive = on), in the order they go to the file;
+    phases = "wo": without the arrays of the gas phase"""
     on = {a for m, arrays in RPTRST_ARRAYS if mnemonics.get(m, 0) > 0 for a in arrays}
-    return [a for a in _ARRAY_ORDER if a in on]
+    return [a for a in _ARRAY_ORDER if a in on and not (phases == "wo" and a in _GAS_ARRAYS)]
 
 
 def simdata_to_deck_units(name, values):
@@ -48,10 +53,10 @@ def simdata_to_deck_units(name, values):
     return v
 
 
-def restart_simulator_data(mnemonics, simulator_data):
+def restart_simulator_data(mnemonics, simulator_data, phases="wog"):
     """{array name: values in deck units} of what the mnemonics select from a model's simulatorData(), in file order: the leading part of
     write_restart's `extra`"""
-    return {a: simdata_to_deck_units(a, simulator_data[a]) for a in rptrst_arrays(mnemonics)}
+    return {a: simdata_to_deck_units(a, simulator_data[a]) for a in rptrst_arrays(mnemonics, phases)}
 
 
 def _record(f, payload):
@@ -112,15 +117,15 @@ def read_arrays(path):
     return out
 
 
-def _intehead(dims, nactive, date, nwells=0, ncwmax=0):
+def _intehead(dims, nactive, date, nwells=0, ncwmax=0, phases="wog"):
     """INTEHEAD (411 entries; the ones readers look at): [2] units (1 METRIC), [8..10] NX NY NZ, [11] NACTIV, [14] phase indicator
-    (7 = oil + water + gas), [16] NWELLS, [17] NCWMAX (most completions of a well), [24..27] NIWELZ NSWELZ NXWELZ NZWELZ,
+    (oil 1 + water 2 + gas 4: 7, or 3 for a deck without a gas phase), [16] NWELLS, [17] NCWMAX (most completions of a well), [24..27] NIWELZ NSWELZ NXWELZ NZWELZ,
     [32..34] NICONZ NSCONZ NXCONZ, [64..66] day month year, [94] simulator (100 = ECLIPSE 100 conventions).  (The report step number is
     the SEQNUM keyword's, not an INTEHEAD entry.)"""
     ih = np.zeros(411, np.int32)
     ih[2] = 1
     ih[8], ih[9], ih[10], ih[11] = dims[0], dims[1], dims[2], nactive
-    ih[14] = 7
+    ih[14] = 3 if phases == "wo" else 7
     ih[16], ih[17] = nwells, ncwmax
     ih[24], ih[25], ih[26], ih[27] = 155, 122, 130, 3
     ih[32], ih[33], ih[34] = 25, 41, 58
@@ -133,9 +138,13 @@ def _intehead(dims, nactive, date, nwells=0, ncwmax=0):
 class EclOutput:
     """BASE.EGRID / .INIT once, then BASE.UNRST / .SMSPEC / .UNSMRY per report step."""
 
-    def __init__(self, base, dims, active_index, start_date, cell_sizes=None, tops=None, porv=None, extra_init=None, coord_zcorn=None):
+    def __init__(self, base, dims, active_index, start_date, cell_sizes=None, tops=None, porv=None, extra_init=None, coord_zcorn=None, phases="wog"):
         """dims (nx, ny, nz); active_index[cartesian cell] = active cell or -1; cell_sizes = (dx, dy, dz) per Cartesian cell and
-        tops [ny*nx] for the EGRID of a block-centred grid; porv per Cartesian cell [m3]; extra_init = {keyword: per-active-cell array}"""
+        tops [ny*nx] for the EGRID of a block-centred grid; porv per Cartesian cell [m3]; extra_init = {keyword: per-active-cell array};
+        phases = "wog" or "wo" (a deck without a gas phase: phase indicator 3, no SGAS / RS / RV in the restart file)"""
+        if phases not in ("wog", "wo"):
+            raise ValueError("phases must be 'wog' or 'wo'")
+        self.phases = phases
         self.base, self.dims = base, tuple(int(d) for d in dims)
         self.act = np.asarray(active_index)
         self.nactive = int((self.act >= 0).sum())
@@ -182,7 +191,7 @@ class EclOutput:
 
     def _write_init(self, porv, extra):
         with open(self.base + ".INIT", "wb") as f:
-            write_array(f, "INTEHEAD", "INTE", _intehead(self.dims, self.nactive, self.start))
+            write_array(f, "INTEHEAD", "INTE", _intehead(self.dims, self.nactive, self.start, phases=self.phases))
             write_array(f, "LOGIHEAD", "LOGI", np.zeros(121, bool))
             write_array(f, "DOUBHEAD", "DOUB", np.zeros(229))
             if porv is not None:
@@ -192,7 +201,7 @@ class EclOutput:
 
     # ---------------------------------------------------------------- restart
     def write_restart(self, elapsed_days, state, extra=None, wells=None, well_state=None, next_step_days=None):
-        """one report step: PRESSURE [bar], SWAT, SGAS, RS, RV per ACTIVE cell (the solution section `compareECL` diffs), then `extra`
+        """one report step: PRESSURE [bar], SWAT, SGAS, RS, RV (without a gas phase: PRESSURE, SWAT) per ACTIVE cell (the solution section `compareECL` diffs), then `extra`
         {keyword: per-cell array} in its order up to ENDSOL (the arrays RPTRST selects -- restart_simulator_data -- before SOMAX and the
         hysteresis history, like getRestartData's).  With wells the
         header section also carries what a restarted run needs of the well state, like flow_legacy's OPM_XWEL / OPM_IWEL do -- under this
@@ -206,7 +215,7 @@ class EclOutput:
             write_array(f, "SEQNUM", "INTE", [self.report])
             nw = wells.nw if wells is not None else 0
             ncw = max((wells.connpos[w + 1] - wells.connpos[w] for w in range(nw)), default=0)
-            write_array(f, "INTEHEAD", "INTE", _intehead(self.dims, self.nactive, date, nwells=nw, ncwmax=ncw))
+            write_array(f, "INTEHEAD", "INTE", _intehead(self.dims, self.nactive, date, nwells=nw, ncwmax=ncw, phases=self.phases))
             write_array(f, "LOGIHEAD", "LOGI", np.zeros(121, bool))
             dh = np.zeros(229); dh[0] = self.elapsed
             write_array(f, "DOUBHEAD", "DOUB", dh)
@@ -220,9 +229,10 @@ class EclOutput:
             write_array(f, "STARTSOL", "MESS", None)
             write_array(f, "PRESSURE", "REAL", state.p / BAR)
             write_array(f, "SWAT", "REAL", state.sat[:, 0])
-            write_array(f, "SGAS", "REAL", state.sat[:, 2])
-            write_array(f, "RS", "REAL", state.rs)
-            write_array(f, "RV", "REAL", state.rv)
+            if self.phases != "wo":
+                write_array(f, "SGAS", "REAL", state.sat[:, 2])
+                write_array(f, "RS", "REAL", state.rs)
+                write_array(f, "RV", "REAL", state.rv)
             for k, v in (extra or {}).items():
                 write_array(f, k, "REAL", v)
             write_array(f, "ENDSOL", "MESS", None)

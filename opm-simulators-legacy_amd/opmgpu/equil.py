@@ -17,6 +17,10 @@ the tree; tolerance 1e-6, EquilibrationHelpers.hpp:646-652) is replaced by an Il
 at once with the same stopping rule, so saturations agree with the reference's to that tolerance, not bit for bit.  SWATINIT is not
 supported (it rescales PCW per cell, EclMaterialLawManager::applySwatinit, outside the tree).
 
+A deck without a gas phase (tables.phases == "wo") takes the branches the reference takes when its gas phase is not active
+(initStateEquil_impl.hpp:436-497, :623-741: `if (gas)`): no gas pressure integration, Sg = 0, Sw from the pcow inversion alone, p_g = p_o;
+the gas-oil contact and pcgo items of the record are not used (the vertical span is not extended to the contact either).
+
 Pins: tests/test_equil.py holds the known answers of the reference's tests/test_equil_legacy.cpp that do not need one of its (absent)
 deck files: PhasePressure :188-218, CellSubset :220-304, RegMapping :309-394, CapillaryInversion :435-498 (tables rebuilt from the
 vectors in the test itself).
@@ -60,6 +64,8 @@ class HostPvt:
         self.o_rs, self.o_psat, self.o_ib = list(t.oil_rs[a:b]), list(t.oil_psat[a:b]), list(t.oil_invb_sat[a:b])
         self.o_cols = [(list(t.oil_col_p[t.oil_col_ptr[k]:t.oil_col_ptr[k + 1]]), list(t.oil_col_invb[t.oil_col_ptr[k]:t.oil_col_ptr[k + 1]]))
                        for k in range(a, b)]
+        if getattr(t, "phases", "wog") == "wo":           # no gas phase: no gas tables
+            return
         a, b = int(t.gas_node_ptr[reg]), int(t.gas_node_ptr[reg + 1])
         self.g_pg, self.g_rv, self.g_ib = list(t.gas_pg[a:b]), list(t.gas_rvsat[a:b]), list(t.gas_invb_sat[a:b])
         self.g_cols = [(list(t.gas_col_rv[t.gas_col_ptr[k]:t.gas_col_ptr[k + 1]]), list(t.gas_col_invb[t.gas_col_ptr[k]:t.gas_col_ptr[k + 1]]))
@@ -197,11 +203,11 @@ def _assign(f, split, z):
     return p
 
 
-def phase_pressures(z, span, reg, grav, nsteps=2000):
+def phase_pressures(z, span, reg, grav, nsteps=2000, gas_active=True):
     """EQUIL::phasePressures (:476-551) for the cells at depths `z` of one region whose cell corners span `span` = (top, bottom).
-    Returns [pw, po, pg]."""
+    Returns [pw, po, pg]; gas_active = False (no gas phase): [pw, po, po], the gas-oil contact is not used."""
     rec, pvt = reg.rec, reg.pvt
-    span = (min(span[0], rec.zgoc), max(span[1], rec.zwoc))             # contacts inside the span (:545-547)
+    span = (min(span[0], rec.zgoc) if gas_active else span[0], max(span[1], rec.zwoc))             # contacts inside the span (:545-547)
     press = [None, None, None]
     st = {"po_woc": -1.0, "po_goc": -1.0}
 
@@ -246,13 +252,13 @@ def phase_pressures(z, span, reg, grav, nsteps=2000):
     def oil():                                                          # :307-362
         if rec.datum > rec.zwoc:
             z0, p0 = rec.zwoc, st["po_woc"]
-        elif rec.datum < rec.zgoc:
+        elif gas_active and rec.datum < rec.zgoc:
             z0, p0 = rec.zgoc, st["po_goc"]
         else:
             z0, p0 = rec.datum, rec.pressure
         o = both(rho_o, z0, p0)
         press[1] = _assign(o, z0, z)
-        for key, c in (("po_woc", rec.zwoc), ("po_goc", rec.zgoc)):
+        for key, c in (("po_woc", rec.zwoc), ("po_goc", rec.zgoc)) if gas_active else (("po_woc", rec.zwoc),):
             st[key] = o[0](c) if z0 > c else (o[1](c) if z0 < c else p0)
 
     def gas():                                                          # :364-407
@@ -265,7 +271,9 @@ def phase_pressures(z, span, reg, grav, nsteps=2000):
         if rec.datum < rec.zgoc:
             st["po_goc"] = g[1](rec.zgoc) - rec.pcgo_goc
 
-    if rec.datum > rec.zwoc:                                            # equilibrateOWG (:410-469): the phase holding the datum first
+    if not gas_active:                                                  # (:447-455, :483-491 without their `if (gas)` parts)
+        order = (water, oil) if rec.datum > rec.zwoc else (oil, water)
+    elif rec.datum > rec.zwoc:                                          # equilibrateOWG (:410-469): the phase holding the datum first
         order = (water, oil, gas)
     elif rec.datum < rec.zgoc:
         order = (gas, oil, water)
@@ -273,6 +281,8 @@ def phase_pressures(z, span, reg, grav, nsteps=2000):
         order = (oil, water, gas)
     for fn in order:
         fn()
+    if not gas_active:
+        press[2] = press[1].copy()
     return press
 
 
@@ -294,15 +304,17 @@ class CapPress:
         self.vw, self.vg = np.ones(self.n), np.ones(self.n)
         for r in np.unique(sat):
             a, b = t.swof_ptr[r], t.swof_ptr[r + 1]
-            c, d = t.sgof_ptr[r], t.sgof_ptr[r + 1]
             self.tab_w[r] = (t.swof_sw[a:b], t.swof_pcow[a:b])
-            self.tab_g[r] = (t.sgof_sg[c:d], t.sgof_pcgo[c:d])
             m = sat == r
             self.swl_t[m], self.swu_t[m] = t.swof_sw[a], t.swof_sw[b - 1]
-            self.sgl_t[m], self.sgu_t[m] = t.sgof_sg[c], t.sgof_sg[d - 1]
             ev = grid.eps_v or {}
             if "PCW" in ev and t.swof_pcow[a] != 0.0:
                 self.vw[m] = ev["PCW"][cells][m] / t.swof_pcow[a]
+            if getattr(t, "phases", "wog") == "wo":       # no gas phase: no SGOF (pcgo is never asked for)
+                continue
+            c, d = t.sgof_ptr[r], t.sgof_ptr[r + 1]
+            self.tab_g[r] = (t.sgof_sg[c:d], t.sgof_pcgo[c:d])
+            self.sgl_t[m], self.sgu_t[m] = t.sgof_sg[c], t.sgof_sg[d - 1]
             if "PCG" in ev and t.sgof_pcgo[d - 1] != 0.0:
                 self.vg[m] = ev["PCG"][cells][m] / t.sgof_pcgo[d - 1]
         if grid.eps is not None:
@@ -384,7 +396,7 @@ def sat_from_sum_of_pcs(cp, target, idx=None):
     return out
 
 
-def phase_saturations(z, reg, cp, press):
+def phase_saturations(z, reg, cp, press, gas_active=True):
     """EQUIL::phaseSaturations (initStateEquil_impl.hpp:566-741); `press` = [pw, po, pg] is adjusted in place.  Returns [sw, so, sg]."""
     rec = reg.rec
     pw, po, pg = press
@@ -392,6 +404,14 @@ def phase_saturations(z, reg, cp, press):
     # water (:637-655)
     const_w = np.abs(cp.pcow(cp.swl) - cp.pcow(cp.swu)) < eps                       # isConstPc (:774-783)
     sw = np.where(const_w, np.where(z < rec.zwoc, cp.swl, cp.swu), sat_from_pc(cp, 0, po - pw))
+    if not gas_active:                                                               # the `if (gas)` parts left out (:658-701, :715, :727-737)
+        thr = 1.0e-6
+        at_swu = sw > cp.swu - thr
+        po[at_swu] = (pw + cp.pcow(cp.swu))[at_swu]
+        at_swl = sw < cp.swl + thr
+        pw[at_swl] = (po - cp.pcow(cp.swl))[at_swl]
+        pg[:] = po
+        return [sw, 1.0 - sw, np.zeros_like(sw)]
     # gas (:657-671); pcog = pg - po increases with Sg
     const_g = np.abs(cp.pcgo(cp.sgl) - cp.pcgo(cp.sgu)) < eps
     sg = np.where(const_g, np.where(z < rec.zgoc, cp.sgu, cp.sgl), sat_from_pc(cp, 2, pg - po, increasing=True))
@@ -470,9 +490,10 @@ def equilibrate(grid, tables, records, eqlnum=None, rsvd=None, rvvd=None, ztop=N
                 rv_fn = _RSatAtContact(pvt.rv_sat, rec.pressure + rec.pcgo_goc)
         reg = EquilReg(rec, rs_fn, rv_fn, pvt)
         z = grid.z[cells]
-        press = phase_pressures(z, (float(ztop[cells].min()), float(zbot[cells].max())), reg, grav, nsteps)
+        gas_active = getattr(tables, "phases", "wog") != "wo"
+        press = phase_pressures(z, (float(ztop[cells].min()), float(zbot[cells].max())), reg, grav, nsteps, gas_active)
         cp = CapPress(tables, grid, cells)
-        s = phase_saturations(z, reg, cp, press)
+        s = phase_saturations(z, reg, cp, press, gas_active)
         p[cells] = press[1]
         phase_p[cells] = np.stack(press, 1)
         sat[cells] = np.stack(s, 1)

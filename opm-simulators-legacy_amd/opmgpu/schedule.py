@@ -16,6 +16,8 @@ computeWellIndices, opm-core, external: restated from the published formula).  M
 Not read: groups (GCONPROD ...), WCONHIST, multi-segment wells, horizontal completions (dir X / Y).  A RESV target becomes a
 RESERVOIR_RATE control with distr {1, 1, 1}; opmgpu/rateconverter.py's computeRESV gives it the conversion coefficients once per report
 step (SimulatorBase_impl.hpp:196, :476-553).
+A deck without a gas phase (RUNSPEC: OIL WATER; Deck.phases() == "wo"): a GRAT target (WCONPROD item 6, WELTARG GRAT), a GAS injector and a
+THP limit are refused with a ValueError naming them; the RESV control's distr is {1, 1, 0}.
 """
 import datetime
 
@@ -53,6 +55,7 @@ class Schedule:
         self.nx, self.ny, self.nz = deck.dims
         self.perm, self.dz, self.dxdy, self.ntg = perm_md, dz, dxdy, ntg
         self.start = _date(deck.records("START")[0]) if deck.has("START") else datetime.date(1983, 1, 1)
+        self.two_phase = deck.phases() == "wo"
         self.steps = []                 # [(length in s, {name: WellSpec snapshot})]
         self.rptrst = []                # per report step: {RPTRST mnemonic: int} in force for the restart file written at its end
         self._build()
@@ -95,6 +98,8 @@ class Schedule:
                         continue
                     lim = {"ORAT": _get(r, 3), "WRAT": _get(r, 4), "GRAT": _get(r, 5), "LRAT": _get(r, 6), "RESV": _get(r, 7), "BHP": _get(r, 8, 1.01325),
                            "THP": _get(r, 9), "VFP": int(_get(r, 10, 0) or 0), "ALQ": _get(r, 11, 0.0)}
+                    if self.two_phase:
+                        self._refuse_gas("WCONPROD", str(r[0]), GRAT=lim["GRAT"], THP=lim["THP"], mode=str(_get(r, 2, "")).upper())
                     for wn in self._match(specs, str(r[0])):
                         specs[wn].control = ("PROD", str(_get(r, 1, "OPEN")).upper() == "OPEN", str(_get(r, 2, "")).upper(), lim)
             elif name == "WCONINJE":
@@ -102,6 +107,9 @@ class Schedule:
                     if not r:
                         continue
                     lim = {"RATE": _get(r, 4), "RESV": _get(r, 5), "BHP": _get(r, 6, 6895.0), "THP": _get(r, 7), "VFP": int(_get(r, 8, 0) or 0)}
+                    if self.two_phase:
+                        self._refuse_gas("WCONINJE", str(r[0]), GAS=True if str(r[1]).upper() == "GAS" else None, THP=lim["THP"],
+                                         mode=str(_get(r, 3, "")).upper())
                     for wn in self._match(specs, str(r[0])):
                         specs[wn].control = ("INJ", str(r[1]).upper(), str(_get(r, 2, "OPEN")).upper() == "OPEN", str(_get(r, 3, "")).upper(), lim)
             elif name == "WELOPEN":          # name OPEN|SHUT|STOP [I J K C1 C2]: the whole well, or the completions that match (defaults / 0 = any)
@@ -124,6 +132,8 @@ class Schedule:
                     if not r:
                         continue
                     key, val = str(r[1]).upper(), float(r[2])
+                    if self.two_phase:
+                        self._refuse_gas("WELTARG", str(r[0]), mode=key)
                     for wn in self._match(specs, str(r[0])):
                         ws = specs[wn]
                         if ws.control is None:
@@ -149,6 +159,13 @@ class Schedule:
                         self.steps.append((float(dt) * DAY, copy.deepcopy({n: specs[n] for n in order})))
                         self.rptrst.append(dict(rptrst))
                         now = now + datetime.timedelta(days=float(dt))
+
+    @staticmethod
+    def _refuse_gas(keyword, well, mode="", **items):
+        """a deck without a gas phase: no gas rate target, no gas injector, no THP limit (its VFP tables have a gas-fraction axis)"""
+        for name, value in list(items.items()) + [(mode, True if mode in ("GRAT", "THP") else None)]:
+            if value is not None:
+                raise ValueError("%s %s: %s in a deck without GAS (RUNSPEC: OIL WATER)" % (keyword, well, name))
 
     @staticmethod
     def _match(specs, pattern):
@@ -193,7 +210,7 @@ class Schedule:
                 if lim["RATE"] is not None:
                     ctrls["RATE"] = (W.SURFACE_RATE, lim["RATE"] / DAY, comp)
                 if lim["RESV"] is not None:          # distr {1, 1, 1} until SimulatorBase::computeRESV fills in the conversion coefficients
-                    ctrls["RESV"] = (W.RESERVOIR_RATE, lim["RESV"] / DAY, (1.0, 1.0, 1.0))
+                    ctrls["RESV"] = (W.RESERVOIR_RATE, lim["RESV"] / DAY, (1.0, 1.0, 0.0 if self.two_phase else 1.0))
                 if lim["BHP"] is not None:
                     ctrls["BHP"] = (W.BHP, lim["BHP"] * BAR)
                 if lim["THP"] is not None and lim["VFP"] > 0:
@@ -209,7 +226,7 @@ class Schedule:
                     if lim[key] is not None:
                         ctrls[key] = (W.SURFACE_RATE, -lim[key] / DAY, distr)
                 if lim["RESV"] is not None:
-                    ctrls["RESV"] = (W.RESERVOIR_RATE, -lim["RESV"] / DAY, (1.0, 1.0, 1.0))
+                    ctrls["RESV"] = (W.RESERVOIR_RATE, -lim["RESV"] / DAY, (1.0, 1.0, 0.0 if self.two_phase else 1.0))
                 if lim["BHP"] is not None:
                     ctrls["BHP"] = (W.BHP, lim["BHP"] * BAR)
                 if lim["THP"] is not None and lim["VFP"] > 0:

@@ -62,13 +62,17 @@ class Simulator:
             tops = self.deck.array("TOPS")[:nx * ny] if self.deck.has("TOPS") and self.deck.array("TOPS").size >= nx * ny else None
             cz = (self.deck.array("COORD"), self.deck.array("ZCORN")) if self.deck.has("ZCORN") else None
             self.out = eclio.EclOutput(output_base, (nx, ny, nz), self.grid.active_index, self.schedule.start, cell_sizes=(dx, dy, dz), tops=tops, porv=porv,
-                                       coord_zcorn=cz)
+                                       coord_zcorn=cz, phases=self.tables.phases)
         self.reports = []
 
     def _load_restart(self, base, report):
         from .decks import BAR, State
         r = eclio.read_restart(base, report)
-        sw, sg = np.asarray(r["SWAT"], float), np.asarray(r["SGAS"], float)
+        sw = np.asarray(r["SWAT"], float)
+        zero = np.zeros_like(sw)
+        if self.tables.phases == "wo":                    # a deck without a gas phase writes no SGAS / RS / RV
+            r = dict(r, SGAS=zero, RS=zero, RV=zero)
+        sg = np.asarray(r["SGAS"], float)
         sat = np.stack([sw, 1.0 - sw - sg, sg], 1)
         hc = np.where(sg > 0, np.where(sat[:, 1] > 0, capi.HC_GAS_AND_OIL, capi.HC_GAS_ONLY), capi.HC_OIL_ONLY).astype(np.int8)     # initHydroCarbonState
         if not self.tables.has_disgas:
@@ -144,7 +148,7 @@ class Simulator:
                 extra = {}
                 rpt = self.schedule.rptrst[step]
                 if any(v > 0 for v in rpt.values()):      # the arrays RPTRST selects of the output record (getRestartData), one evaluation
-                    extra.update(eclio.restart_simulator_data(rpt, gm.simulatorData()))
+                    extra.update(eclio.restart_simulator_data(rpt, gm.simulatorData(), self.tables.phases))
                 if hasattr(gm, "satOilMax") and self.tables.vap1 + self.tables.vap2 > 0:
                     extra["SOMAX"] = gm.satOilMax()
                 if hasattr(gm, "getHysteresis") and self.grid.imbnum is not None:
