@@ -533,6 +533,38 @@ enum {
 };
 int opmgpu_get_simulator_data(opmgpu_ctx* ctx, double* out /* [OPMGPU_SIMDATA_K * nc] */);
 
+/* BlackoilModelBase::setThresholdPressures (BlackoilModelBase_impl.hpp:421-443; called from SimulatorBase_impl.hpp:467-468 once the
+ * initial state exists, because a defaulted THPRES value is computed from it): replaces the threshold pressures of ALL connections, in
+ * the connection order of opmgpu_grid.conn_cells (grid faces, then NNCs); NULL removes them.  Works on a context created with or without
+ * opmgpu_grid.thpres and lasts through later opmgpu_set_wells / opmgpu_set_device_wells calls.  The assembly applies them as before
+ * (applyThresholdPressures, :1518-1545); no kernel of the Newton path changes.  A negative or non-finite value: OPMGPU_EINVAL, text in
+ * opmgpu_last_error(ctx), nothing changed.  Decomposed runs: the rank's local connections, no communication. */
+int opmgpu_set_threshold_pressures(opmgpu_ctx* ctx, const double* thpres /* [nconn] or NULL */);
+
+/* computeMaxDp (opm/simulators/thresholdPressures.hpp:46-298; called at FlowMain.hpp:675-680) for the RESIDENT state: the largest
+ * phase-potential difference across every pair of equilibration regions, which a defaulted THPRES item takes as its value
+ * (thresholdPressures / thresholdPressuresNNC, ibid. :320-369, :383-417).
+ *   eqlnum      [nc] equilibration region of every cell, 1-based, caller's cell order
+ *   n_face_conn the first n_face_conn connections are grid faces and are scanned; the NNCs behind them are not (the reference loops over
+ *               the grid's faces only)
+ *   dp_conn     [nconn] or NULL: per connection the largest |p1 - p2| over the phases that count; 0 when none counts, when both cells lie
+ *               in one region and for f >= n_face_conn
+ *   max_dp      [nregions][nregions], symmetric: the maximum of dp_conn over the face connections joining regions a and b; -1.0 where no
+ *               face connection joins them (the reference's "pair absent from the map"); 0.0 for a joined pair whose phases never count
+ * Per cell and phase (:109-248), by rules that are NOT the Newton path's: p_o = the state's pressure, p_w = p_o - pcow(Sw),
+ * p_g = p_o + pcgo(Sg) at the state's saturations with the cell's end-point and vertical scaling; rho_w = rhoS_w b_w(p_w);
+ * rho_o = (rhoS_o + rhoS_g Rs) b_o with the state's Rs and b_o from the saturated curve at p_o when Rs >= RsSat(p_o), else undersaturated
+ * at (p_o, Rs); rho_g = (rhoS_g + rhoS_o Rv) b_g likewise by Rv >= RvSat(p_g) at p_g.  RsSat / RvSat carry no VAPPARS factor, the phase
+ * condition of the state is not consulted.  Per face and active phase (:278-296): p1 = p(c1), p2 = p(c2) + (rho(c1) + rho(c2))/2 g
+ * (z1 - z2); the phase counts when (p1 > p2 && s1 > sres1) || (p2 > p1 && s2 > sres2), strict, with the residual saturations of satRange
+ * (SaturationPropsFromDeck.cpp:212-250): water the cell's scaled SWL else the first Sw node of its table, gas SGL likewise, oil
+ * max(0, 1 - SWU - SGU).  OPMGPU_PHASES_OIL_WATER: water and oil only, oil residual max(0, 1 - SWU); no gas table is read.
+ * The per-face evaluation runs on the device, the maxima per pair on the host over the downloaded plane.  Decomposed runs: a COLLECTIVE
+ * call; every rank passes its local cells' eqlnum, its local n_face_conn and the GLOBAL number of regions, and receives the maxima over
+ * all ranks (a connection two ranks both hold is harmless to a maximum); dp_conn stays local.
+ * OPMGPU_EINVAL (with text) for a NULL eqlnum / max_dp, a region outside [1, nregions], n_face_conn outside [0, nconn], or no state. */
+int opmgpu_compute_max_dp(opmgpu_ctx* ctx, const int32_t* eqlnum, int nregions, int n_face_conn, double* dp_conn, double* max_dp);
+
 /* Maximum historical oil saturation per cell (BlackoilPropsAdFromDeck::satOilMax_, used by VAPPARS).
  * set: explicit values (nc, caller order; restart).  update: soMax = max(soMax, so of the resident state) --
  * what SimulatorBase_impl.hpp:192 does at the start of every report step (updateSatOilMax, :933-945).

@@ -1195,6 +1195,92 @@ __global__ __launch_bounds__(kBlock) void k_simulator_data(int nc, DevTables T, 
     o[OPMGPU_SD_PBUB * n] = bubble_point_d(T, preg, q.rs.v); o[OPMGPU_SD_PDEW * n] = dew_point_d(T, preg, q.rv.v);
 }
 
+// computeMaxDp, the per-cell part (opm/simulators/thresholdPressures.hpp:109-248): the pressure, density and saturation of every active
+// phase of cell `row` (water, oil, gas) by the rules of THAT function, which are not the Newton path's:
+//   p_o = the state's pressure, p_w = p_o - pcow(Sw), p_g = p_o + pcgo(Sg) with the STATE's saturations (not those implied by the phase
+//   condition) through the cell's end-point and vertical scaling (hysteresis is KR-only here: no capillary-pressure history);
+//   rho_w = rhoS_w b_w(p_w);
+//   rho_o = rhoS_o b_o + rhoS_g Rs b_o with the state's Rs, b_o from the saturated curve at p_o when Rs >= RsSat(p_o), else the
+//   undersaturated value at (p_o, Rs); RsSat is the plain curve (no VAPPARS factor); without DISGAS RsSat = 0: the saturated curve;
+//   rho_g = rhoS_g b_g + rhoS_o Rv b_g the same way by Rv >= RvSat(p_g) at p_g.
+// KM_OW: water and oil only, the dead-oil curve, no gas table and no gas density read; the gas slots come back as p_o, 0, 0.
+template <int KM>
+__device__ void max_dp_cell(const DevTables& D, int row, long nbp, const int32_t* __restrict__ pvtnum, const int32_t* __restrict__ satnum,
+                            const double* __restrict__ p_, const double* __restrict__ sw_, const double* __restrict__ so_, const double* __restrict__ sg_,
+                            const double* __restrict__ rs_, const double* __restrict__ rv_, const double* __restrict__ eps, const double* __restrict__ eps_u0,
+                            double (&pp)[3], double (&rho)[3], double (&s)[3])
+{
+    const opmgpu_tables& T = D.t; const TabX& X = D.x;
+    const int preg = pvtnum[row], sreg = satnum[row];
+    const double p = p_[row];
+    EpsD E;
+    eps_load(eps, eps_u0, nbp, row, sreg, E);
+    s[0] = sw_[row]; s[1] = so_[row]; s[2] = KM == KM_OW ? 0.0 : sg_[row];
+    double f, df;
+    const int wa = T.swof_ptr[sreg], nw = T.swof_ptr[sreg + 1] - wa;
+    sat_curve_s<false>(T.swof_sw + wa, T.swof_pcow + wa, X.swof_dpcow + wa, nw, s[0], E, EC_PCOW, f, df);
+    pp[0] = p - f; pp[1] = p; pp[2] = p;
+    const double* rhos = T.surface_density + 3 * preg;
+    {   // ConstantCompressibilityWaterPvt::inverseFormationVolumeFactor at p_w
+        const double* w = T.pvtw + 5 * preg;
+        const double Xc = w[2] * (pp[0] - w[0]);
+        rho[0] = rhos[0] * ((1.0 + Xc * (1.0 + Xc / 2.0)) / w[1]);
+    }
+    const int oa = T.oil_node_ptr[preg], on = T.oil_node_ptr[preg + 1] - oa;
+    if constexpr (KM == KM_OW) {
+        lin_at(T.oil_psat + oa, T.oil_invb_sat + oa, X.oil_dinvb_sat + oa, pvt_seg(T.oil_psat + oa, on, p), p, f, df);
+        rho[1] = rhos[1] * f; rho[2] = 0.0;
+    } else {
+        const int ga = T.sgof_ptr[sreg], ng = T.sgof_ptr[sreg + 1] - ga;
+        sat_curve_s<true>(T.sgof_sg + ga, T.sgof_pcgo + ga, X.sgof_dpcgo + ga, ng, s[2], E, EC_PCGO, f, df);
+        pp[2] = p + f;
+        const double rs = rs_[row], rv = rv_[row];
+        double b;
+        if (rs >= rs_sat_d(D, preg, p)) lin_at(T.oil_psat + oa, T.oil_invb_sat + oa, X.oil_dinvb_sat + oa, pvt_seg(T.oil_psat + oa, on, p), p, b, df);
+        else b = pvt2_value(T.oil_rs + oa, on, T.oil_col_ptr + oa, T.oil_col_p, T.oil_col_invb, X.oil_col_dinvb, rs, p);
+        rho[1] = rhos[1] * b + rhos[2] * rs * b;
+        const int gna = T.gas_node_ptr[preg], gn = T.gas_node_ptr[preg + 1] - gna;
+        if (rv >= rv_sat_d(D, preg, pp[2])) lin_at(T.gas_pg + gna, T.gas_invb_sat + gna, X.gas_dinvb_sat + gna, pvt_seg(T.gas_pg + gna, gn, pp[2]), pp[2], b, df);
+        else b = pvt2_value(T.gas_pg + gna, gn, T.gas_col_ptr + gna, T.gas_col_rv, T.gas_col_invb, X.gas_col_dinvb, pp[2], rv);
+        rho[2] = rhos[2] * b + rhos[1] * rv * b;
+    }
+}
+
+// computeMaxDp, the per-connection part (thresholdPressures.hpp:252-297): one thread per connection; conn = the connections' two cells in
+// internal numbering, eql = the cells' equilibration regions (internal numbering), sres = the residual saturations of satRange [3][nbp].
+// A thread whose cells share a region -- almost every one -- leaves at once; the others evaluate BOTH end cells (each barrier face
+// is a handful of threads: nothing is exchanged or accumulated).  For every active phase p1 = p(c1), p2 = p(c2) + (rho(c1) + rho(c2))/2 g
+// (z1 - z2); the phase counts when (p1 > p2 && s1 > sres1) || (p2 > p1 && s2 > sres2), strict; out[f] = the largest |p1 - p2| of the
+// phases that count, 0 when none does, on a connection within one region and on f >= nface (NNCs: the reference scans grid faces only).
+// Off every timed path (once per run, before the first step): not tuned, not timed.
+template <int KM>
+__global__ __launch_bounds__(kBlock) void k_max_dp(int nconn, int nface, DevTables T, const int32_t* __restrict__ conn, const int32_t* __restrict__ eql,
+                                                   const int32_t* __restrict__ pvtnum, const int32_t* __restrict__ satnum, const double* __restrict__ p,
+                                                   const double* __restrict__ sw, const double* __restrict__ so, const double* __restrict__ sg,
+                                                   const double* __restrict__ rs, const double* __restrict__ rv, const double* __restrict__ eps,
+                                                   const double* __restrict__ eps_u0, const double* __restrict__ sres, const double* __restrict__ zc,
+                                                   double gravity, long nbp, double* __restrict__ out)
+{
+    const int f = blockIdx.x * kBlock + threadIdx.x;
+    if (f >= nconn) return;
+    double dp = 0.0;
+    const int c1 = conn[2 * long(f)], c2 = conn[2 * long(f) + 1];
+    if (f < nface && eql[c1] != eql[c2]) {
+        double p1[3], p2[3], r1[3], r2[3], s1[3], s2[3];
+        max_dp_cell<KM>(T, c1, nbp, pvtnum, satnum, p, sw, so, sg, rs, rv, eps, eps_u0, p1, r1, s1);
+        max_dp_cell<KM>(T, c2, nbp, pvtnum, satnum, p, sw, so, sg, rs, rv, eps, eps_u0, p2, r2, s2);
+        const double dz = zc[c1] - zc[c2];
+        constexpr int np = KM == KM_OW ? 2 : 3;
+#pragma unroll
+        for (int ph = 0; ph < np; ++ph) {
+            const double rho_avg = (r1[ph] + r2[ph]) / 2;
+            const double pa = p1[ph], pb = p2[ph] + rho_avg * gravity * dz;
+            if ((pa > pb && s1[ph] > sres[ph * nbp + c1]) || (pb > pa && s2[ph] > sres[ph * nbp + c2])) dp = fmax(dp, fabs(pa - pb));
+        }
+    }
+    out[f] = dp;
+}
+
 // computePropertiesForWellConnectionPressures (StandardWells_impl.hpp:218-296): b_w, b_o, b_g, rsSat, rvSat of the perforated cells at
 // GIVEN pressures (the average well-block pressures) with the cells' own rs / rv / phase condition / oil saturation
 __global__ __launch_bounds__(kBlock) void k_perf_pvt(int nperf, DevTables D, const int32_t* __restrict__ cells, const int32_t* __restrict__ pvtnum,
@@ -1514,18 +1600,18 @@ void BlackoilDevice::rebuild_structure()
     // g (z_c1 - z_c2) of the connection, its threshold pressure (k_assemble_rows reads them coalesced next to the column index)
     {
         const double nan = std::numeric_limits<double>::quiet_NaN();
-        std::vector<double> te(P.nentries, 0.0), he;
-        if (use_thpres) he.assign(P.nentries, 0.0);
+        std::vector<double> te(P.nentries, 0.0);
+        h_entry_conn.assign(P.nentries, -1);
         for (int b = 0; b < P.nnzb; ++b) {
             const int e = P.entry_of_block[b], c = code[b];
             if (c >= 0) {
                 const int f = c >> 1;
                 te[e] = std::copysign(h_trans[f], (c & 1) ? -1.0 : 1.0);
-                if (use_thpres) he[e] = h_thpres[f];
+                h_entry_conn[e] = f;
             } else if (c == -2) te[e] = nan;
         }
         d_tr_e.upload(te, stream);
-        if (use_thpres) d_thp_e.upload(he, stream);
+        upload_thpres_plane();
         // cell depths in internal numbering: g (z_c1 - z_c2) of a connection is formed in the kernel (gravity * (z[c1] - z[c2]), the same
         // expression the reference's geometry evaluates once per face)
         std::vector<double> zi(P.nbp, 0.0);
@@ -2328,6 +2414,97 @@ void BlackoilDevice::fluid_in_place(const int32_t* fipnum, int dims, double* fip
         std::copy(fpv.begin(), fpv.end(), fip_cells + size_t(5) * nc);
         std::copy(fwp.begin(), fwp.end(), fip_cells + size_t(6) * nc);
     }
+}
+
+// the per-SELL-entry plane of the connections' threshold pressures (what k_assemble_rows reads next to the column index) from h_thpres
+void BlackoilDevice::upload_thpres_plane()
+{
+    if (!use_thpres) return;
+    std::vector<double> he(h_entry_conn.size(), 0.0);
+    for (size_t e = 0; e < he.size(); ++e) if (h_entry_conn[e] >= 0) he[e] = h_thpres[h_entry_conn[e]];
+    d_thp_e.upload(he, stream);
+    OPMGPU_HIP(hipStreamSynchronize(stream));
+}
+
+// BlackoilModelBase::setThresholdPressures (BlackoilModelBase_impl.hpp:421-443): the thresholds of ALL connections, in the connection order
+// of the grid; nullptr = none.  The host copy is what rebuild_structure() builds the plane from, so a later re-plan (wells) keeps them.
+void BlackoilDevice::set_threshold_pressures(const double* thpres)
+{
+    if (thpres)
+        for (int f = 0; f < nconn; ++f)
+            if (!(thpres[f] >= 0.0) || !std::isfinite(thpres[f]))
+                throw HipError(OPMGPU_EINVAL, "setThresholdPressures: the threshold pressure of connection " + std::to_string(f) + " is negative or not finite");
+    use_thpres = thpres != nullptr;
+    if (use_thpres) h_thpres.assign(thpres, thpres + nconn);
+    else h_thpres.clear();
+    upload_thpres_plane();
+}
+
+// computeMaxDp (opm/simulators/thresholdPressures.hpp:46-298) for the resident state: the per-connection potential differences on the
+// device (k_max_dp), the maxima per pair of regions on the host over the downloaded plane, in connection order like the reference's face
+// loop.  eqlnum: 1-based region per cell, caller order; max_dp: [nregions][nregions], symmetric, -1 = no face connection joins the pair
+// (the reference's "pair absent from the map"), 0 = joined, but no phase ever counts.  The residual saturations are satRange's
+// (SaturationPropsFromDeck.cpp:212-250) from the end points the host holds: SWL, SGL, max(0, 1 - SWU - SGU) -- the cell's scaled values,
+// else its region's table's; with two phases max(0, 1 - SWU).  Decomposed runs: collective; every rank scans its local face connections
+// (one seen from both sides is harmless to a max) and passes the GLOBAL number of regions; the maxima are max-reduced over the ranks.
+void BlackoilDevice::compute_max_dp(const int32_t* eqlnum, int nregions, int n_face_conn, double* dp_conn, double* max_dp)
+{
+    const Plan& P = ls.plan;
+    const int nbp = P.nbp;
+    if (ls.comm) {
+        double dmax = double(nregions);
+        DevArray<double> d;
+        d.upload(&dmax, 1, stream);
+        ls.comm->allreduce_max(d.p, 1, stream);
+        d.download(&dmax, 1, stream);
+        OPMGPU_HIP(hipStreamSynchronize(stream));
+        if (int(dmax + 0.5) != nregions) throw HipError(OPMGPU_EINVAL, "computeMaxDp: pass the GLOBAL number of regions on every rank of a decomposed run");
+    }
+    std::vector<double> dp(std::max(nconn, 1), 0.0);
+    if (nconn > 0) {
+        std::vector<int32_t> hc(2 * size_t(nconn)), he(nbp, 0);
+        for (size_t i = 0; i < hc.size(); ++i) hc[i] = P.pos[h_conn[i]];
+        std::vector<double> sres(3 * size_t(nbp), 0.0);
+        for (int r = 0; r < nc; ++r) {
+            const int c = P.nat[r];
+            he[r] = eqlnum[c];
+            const double* u = &h_unscaled[8 * size_t(h_satnum[c])];
+            auto end_point = [&](int k) { return has_endpoints ? h_eps[k][c] : u[k]; };
+            sres[r] = end_point(0);
+            sres[size_t(2) * nbp + r] = oil_water() ? 0.0 : end_point(4);
+            double so_min = 1.0;
+            so_min -= end_point(2);
+            if (!oil_water()) so_min -= end_point(6);
+            sres[size_t(nbp) + r] = std::max(0.0, so_min);
+        }
+        DevArray<int32_t> d_conn, d_eql;
+        DevArray<double> d_sres, d_out;
+        d_conn.upload(hc, stream); d_eql.upload(he, stream); d_sres.upload(sres, stream);
+        d_out.alloc(size_t(nconn));
+        hipLaunchKernelGGL(OPMGPU_BY_MODEL(k_max_dp), dim3(grid_for(nconn)), dim3(kBlock), 0, stream, nconn, n_face_conn, dtp_, d_conn.p, d_eql.p,
+                           d_pvtnum.p, d_satnum.p, d_p.p, d_sw.p, d_so.p, d_sg.p, d_rs.p, d_rv.p, eps_planes(), d_eps_u0.p, d_sres.p, (const double*)d_zc.p,
+                           gravity, long(nbp), d_out.p);
+        OPMGPU_HIP(hipGetLastError());
+        d_out.download(dp.data(), size_t(nconn), stream);
+        OPMGPU_HIP(hipStreamSynchronize(stream));
+    }
+    const size_t nn = size_t(nregions) * nregions;
+    for (size_t i = 0; i < nn; ++i) max_dp[i] = -1.0;
+    for (int f = 0; f < n_face_conn; ++f) {
+        const int a = eqlnum[h_conn[2 * size_t(f)]] - 1, b = eqlnum[h_conn[2 * size_t(f) + 1]] - 1;
+        if (a == b) continue;
+        double& m = max_dp[size_t(a) * nregions + b];
+        m = std::max(std::max(m, 0.0), dp[f]);
+        max_dp[size_t(b) * nregions + a] = m;
+    }
+    if (ls.comm) {
+        DevArray<double> d;
+        d.upload(max_dp, nn, stream);
+        ls.comm->allreduce_max(d.p, int(nn), stream);
+        d.download(max_dp, nn, stream);
+        OPMGPU_HIP(hipStreamSynchronize(stream));
+    }
+    if (dp_conn) std::copy(dp.begin(), dp.begin() + nconn, dp_conn);
 }
 
 // RateConverter::SurfaceToReservoirVoidage::calcAverages (RateConverterLegacy.hpp:718-768), the sums only: per region sum of p, rs, rv over the

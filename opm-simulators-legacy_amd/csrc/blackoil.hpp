@@ -44,6 +44,8 @@ public:
     void set_state(const double* p, const double* sat, const double* rs, const double* rv, const int8_t* hc);
     void get_state(double* p, double* sat, double* rs, double* rv, int8_t* hc);
     void fluid_in_place(const int32_t* fipnum, int dims, double* fip_cells, double* values);      // computeFluidInPlace (:2263-2445)
+    void set_threshold_pressures(const double* thpres);                                            // setThresholdPressures (:421-443); nullptr = none
+    void compute_max_dp(const int32_t* eqlnum, int nregions, int n_face_conn, double* dp_conn, double* max_dp);      // computeMaxDp (opm/simulators/thresholdPressures.hpp:46-298)
     void simulator_data(double* out);                                                              // SimulatorData of the resident state (:662-683, rq_[].b/rho/mu/kr)
     void region_state_sums(const int32_t* region, int nregions, double* sums);                   // RateConverter calcAverages (RateConverterLegacy.hpp:718-768)
     void voidage_coefficients(int n, const double* p, const double* rs, const double* rv, const int32_t* pvtreg, double* coeff);   // calcCoeff (:495-548)
@@ -134,11 +136,13 @@ private:
     VfpDev* vfp = nullptr;
     std::vector<double> h_surface_density;
     void rebuild_structure();
+    void upload_thpres_plane();
 
     hipStream_t stream;
     LinSolver& ls;
     // host copies of the static inputs (caller numbering)
     std::vector<int32_t> h_conn, h_pvtnum, h_satnum, h_well_connpos, h_well_cells;
+    std::vector<int32_t> h_entry_conn;      // connection of every SELL entry of the current plan, -1 = none (diagonal, padding, well fill)
     std::vector<double> h_trans, h_pv, h_z, h_thpres;
     double gravity = 0.0, pvsum = 0.0, pvsum_global = 0.0;
     bool use_thpres = false;

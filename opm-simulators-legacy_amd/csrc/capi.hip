@@ -833,6 +833,20 @@ int opmgpu_compute_fluid_in_place(opmgpu_ctx* c, const int32_t* fipnum, int nreg
     if (fipnum) for (int i = 0; i < c->model->nc; ++i) if (fipnum[i] < 0 || fipnum[i] > nregions) return fail(c, OPMGPU_EINVAL, "fipnum outside [0, nregions]");
     return guarded(c, [&]() { c->model->fluid_in_place(fipnum, nregions, fip_cells, values); return int(OPMGPU_OK); });
 }
+int opmgpu_set_threshold_pressures(opmgpu_ctx* c, const double* thpres)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { c->model->set_threshold_pressures(thpres); return int(OPMGPU_OK); });
+}
+int opmgpu_compute_max_dp(opmgpu_ctx* c, const int32_t* eqlnum, int nregions, int n_face_conn, double* dp_conn, double* max_dp)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    if (!eqlnum || !max_dp || nregions < 1) return fail(c, OPMGPU_EINVAL, "computeMaxDp: eqlnum and max_dp must be given, nregions >= 1");
+    if (n_face_conn < 0 || n_face_conn > c->model->nconn) return fail(c, OPMGPU_EINVAL, "computeMaxDp: n_face_conn outside [0, nconn]");
+    if (!c->model->has_state) return fail(c, OPMGPU_EINVAL, "no reservoir state on the device");
+    for (int i = 0; i < c->model->nc; ++i) if (eqlnum[i] < 1 || eqlnum[i] > nregions) return fail(c, OPMGPU_EINVAL, "computeMaxDp: eqlnum outside [1, nregions]");
+    return guarded(c, [&]() { c->model->compute_max_dp(eqlnum, nregions, n_face_conn, dp_conn, max_dp); return int(OPMGPU_OK); });
+}
 int opmgpu_get_simulator_data(opmgpu_ctx* c, double* out)
 {
     if (!c || !c->model || !out || !c->model->has_state) return OPMGPU_EINVAL;

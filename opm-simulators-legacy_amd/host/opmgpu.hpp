@@ -100,6 +100,7 @@ public:
     BlackoilModelGpu(const opmgpu_grid& grid, const opmgpu_tables& tables, const opmgpu_params* prm = nullptr, int device = 0)
     {
         nc_ = grid.nc;
+        nconn_ = grid.nconn;
         use_cpr_ = prm && prm->use_cpr;
         const int st = opmgpu_create(&ctx_, device, &grid, &tables, prm);
         if (st != OPMGPU_OK) throw std::runtime_error("opmgpu_create failed (no GPU? there is no CPU fallback), status " + std::to_string(st) + ": " + opmgpu_last_error(nullptr));
@@ -218,6 +219,27 @@ public:
         for (int r = 0; r < dims; ++r) for (int k = 0; k < 7; ++k) values[r][k] = flat[std::size_t(r) * 7 + k];
         return values;
     }
+    /// BlackoilModelBase::setThresholdPressures (:421-443): the thresholds of all connections in the grid's connection order (faces, then
+    /// NNCs); an empty vector removes them.  std::logic_error for a wrong size, a negative or a non-finite value.
+    void setThresholdPressures(const std::vector<double>& threshold_pressures)
+    {
+        if (!threshold_pressures.empty() && int(threshold_pressures.size()) != nconn_)
+            throw std::logic_error("Illegal size of threshold_pressures input, must be equal to number of faces + nncs");
+        throw_on_status(ctx_, opmgpu_set_threshold_pressures(ctx_, threshold_pressures.empty() ? nullptr : threshold_pressures.data()));
+    }
+    /// computeMaxDp (opm/simulators/thresholdPressures.hpp:46-298) for the resident state: max_dp[a][b] over the 1-based regions `eqlnum`,
+    /// scanning the first n_face_conn connections (the grid faces); -1 = no face joins the pair.  dp_conn (optional): per connection.
+    std::vector<std::vector<double>> computeMaxDp(const std::vector<int>& eqlnum, int nregions, int n_face_conn, std::vector<double>* dp_conn = nullptr)
+    {
+        if (int(eqlnum.size()) != nc_ || nregions < 1) throw std::logic_error("computeMaxDp: one region per cell and nregions >= 1");
+        std::vector<int32_t> eq(eqlnum.begin(), eqlnum.end());
+        std::vector<double> flat(std::size_t(nregions) * nregions, -1.0);
+        if (dp_conn) dp_conn->assign(std::size_t(nconn_), 0.0);
+        throw_on_status(ctx_, opmgpu_compute_max_dp(ctx_, eq.data(), nregions, n_face_conn, dp_conn ? dp_conn->data() : nullptr, flat.data()));
+        std::vector<std::vector<double>> m(nregions, std::vector<double>(nregions));
+        for (int a = 0; a < nregions; ++a) for (int b = 0; b < nregions; ++b) m[a][b] = flat[std::size_t(a) * nregions + b];
+        return m;
+    }
     /// BlackoilModelBase::getSimulatorData (sd_ of :662-683 and rq_[].b/rho/mu/kr) for the resident state: 16 per-cell arrays in SI under
     /// the names of SimulatorFullyImplicitBlackoilOutput.hpp:512-567, in the cell order of the state
     std::map<std::string, std::vector<double>> simulatorData()
@@ -239,6 +261,7 @@ public:
 private:
     opmgpu_ctx* ctx_ = nullptr;
     int nc_ = 0;
+    int nconn_ = 0;
     bool use_cpr_ = false;
     double dt_ = 0.0, max_single_precision_days_ = 20.0, linear_reduction_ = 0.0;
     int linear_iterations_ = 0;

@@ -3,7 +3,7 @@
 What `flow_legacy` gets from opm-parser + `DerivedGeology` (opm/autodiff/GeoProps.hpp:84-195) + `BlackoilPropsAdFromDeck`
 (opm/autodiff/BlackoilPropsAdFromDeck.cpp:60-240), restricted to what the device path consumes:
 
-  RUNSPEC   DIMENS TABDIMS OIL WATER GAS DISGAS VAPOIL METRIC ENDSCALE
+  RUNSPEC   DIMENS TABDIMS EQLDIMS OIL WATER GAS DISGAS VAPOIL METRIC ENDSCALE EQLOPTS (THPRES; IRREVERS is refused)
             The active phases are the ones RUNSPEC names: OIL WATER GAS, or OIL WATER -- a deck without a gas phase (Deck.phases() ==
             "wo").  Such a deck needs and reads no gas keyword (PVTG / PVDG, SGOF, the gas end points and KRG / PCG, a gas DENSITY);
             DISGAS, VAPOIL, VAPPARS, STONE / STONE1 / STONE2, SATOPTS HYSTER and SGAS / RS / RV in SOLUTION are refused (ValueError
@@ -18,7 +18,10 @@ What `flow_legacy` gets from opm-parser + `DerivedGeology` (opm/autodiff/GeoProp
             (SATOPTS HYSTER in RUNSPEC switches the hysteresis on; EHYSTR item 2 = 0 and item 5 = KR -- Carlson, relative permeabilities
             only -- is the model the device implements)
   REGIONS   PVTNUM SATNUM IMBNUM FIPNUM (fluid-in-place regions of computeFluidInPlace; 1-based in the deck and in `fipnum()`)
+            EQLNUM (equilibration regions: EQUIL's, and the regions THPRES puts barriers between; 1-based in `eqlnum()`)
   SOLUTION  PRESSURE SWAT SGAS RS RV (explicit initial state; EQUIL is outside the hot path)
+            THPRES (threshold pressures between EQLNUM regions, with EQLOPTS THPRES in RUNSPEC: `thpres()` / `threshold_pressures()`
+            restate opm/simulators/thresholdPressures.hpp:320-417; a defaulted item 3 takes the model's computeMaxDp of the initial state)
             RPTRST (the mnemonics that select derived per-cell arrays for the restart file, RPTRST_MNEMONICS; also read in SCHEDULE)
 
 Block-centred Cartesian geometry only (corner-point COORD/ZCORN needs opm-grid's processing, out of scope).  TPFA
@@ -535,6 +538,7 @@ class Deck:
             cy, ty = faces(idx[:, :-1, :], idx[:, 1:, :], ky, axz, axz, dyr, dyr, True, fm["Y"], fm["Y-"])
             cz, tz = faces(idx[:-1, :, :], idx[1:, :, :], kz, axy, axy, dzr, dzr, False, fm["Z"], fm["Z-"])
         conn = np.concatenate([cx, cy, cz]); trans = np.concatenate([tx, ty, tz])
+        n_faces = conn.shape[0]
         if self.has("NNC"):
             for r in self.records("NNC"):
                 if not r:
@@ -568,6 +572,8 @@ class Deck:
         g = GridData(int(act.sum()), conn, trans, pv[act], zc[act], gravity=gravity, pvtnum=reg("PVTNUM"), satnum=reg("SATNUM"),
                      dims=(nx, ny, nz), eps=eps, **more)
         g.active_index = newid
+        # host-only: the first n_face_conn connections are grid faces (fault overlaps included), the rest NNCs -- what computeMaxDp scans
+        g.n_face_conn = int(np.count_nonzero(keep[:n_faces]))
         self._grid = g
         return g
 
@@ -580,6 +586,88 @@ class Deck:
         self.grid()                                   # (fixes the set of active cells)
         full = self.array("FIPNUM", nx * ny * nz)[self.active]
         return np.where(np.isnan(full), 0, full).astype(np.int32)
+
+    def eqlnum(self):
+        """EQLNUM of the active cells, 1-based (all ones without the keyword), like fipnum()"""
+        nx, ny, nz = self.dims
+        if getattr(self, "active", None) is None:
+            self.grid()                               # (fixes the set of active cells)
+        if not self.has("EQLNUM"):
+            return np.ones(self.active.size, np.int32)
+        full = self.array("EQLNUM", nx * ny * nz)[self.active]
+        if np.isnan(full).any():
+            raise ValueError("EQLNUM must be given for every active cell")
+        return full.astype(np.int32)
+
+    def thpres(self):
+        """The barriers of THPRES: {(r1, r2) with r1 < r2: threshold in Pa, or None when item 3 is defaulted (the value is then the
+        largest phase-potential difference between the two regions in the initial state, computeMaxDp)}; None without the keyword.  A
+        later record for the same pair wins.  The reference keeps them in opm-common's ThresholdPressure, which is outside its tree, so
+        the refusals are OURS -- all ValueErrors naming the keyword: THPRES without EQLOPTS naming THPRES; EQLOPTS naming IRREVERS
+        (directional thresholds, whether or not THPRES follows); a region below 1 or above EQLDIMS item 1; a record with r1 == r2 or
+        fewer than two items; a negative value."""
+        opts = [str(x).upper() for r in (self.records("EQLOPTS") if self.has("EQLOPTS") else []) for x in r if x is not None]
+        if "IRREVERS" in opts:
+            raise ValueError("EQLOPTS IRREVERS (direction-dependent threshold pressures) is not supported")
+        if not self.has("THPRES"):
+            return None
+        if "THPRES" not in opts:
+            raise ValueError("THPRES in SOLUTION needs EQLOPTS naming THPRES in RUNSPEC")
+        r = self.records("EQLDIMS")[0] if self.has("EQLDIMS") and self.records("EQLDIMS") else []
+        ntequl = int(r[0]) if len(r) > 0 and r[0] is not None else 1
+        out = {}
+        for rec in self.records("THPRES"):
+            if not rec:
+                continue
+            if len(rec) < 2 or rec[0] is None or rec[1] is None:
+                raise ValueError("THPRES: a record needs two region numbers")
+            r1, r2 = int(rec[0]), int(rec[1])
+            for reg in (r1, r2):
+                if reg < 1 or reg > ntequl:
+                    raise ValueError("THPRES: region %d outside 1 .. %d (EQLDIMS item 1)" % (reg, ntequl))
+            if r1 == r2:
+                raise ValueError("THPRES: a barrier between region %d and itself" % r1)
+            value = float(rec[2]) * BAR if len(rec) > 2 and rec[2] is not None else None
+            if value is not None and not value >= 0.0:
+                raise ValueError("THPRES: negative threshold pressure between regions %d and %d" % (r1, r2))
+            out[(min(r1, r2), max(r1, r2))] = value
+        return out
+
+    def threshold_pressures(self, grid, max_dp=None):
+        """Threshold pressure [Pa] of every connection of `grid` (this deck's grid()), faces then NNCs: thresholdPressures and
+        thresholdPressuresNNC (opm/simulators/thresholdPressures.hpp:320-369, :383-417).  A connection between two regions with a
+        barrier takes the explicit value; for a defaulted barrier max_dp[pair] -- max_dp is computeMaxDp's [nregions][nregions] table
+        (-1 = no face joins the pair) or a dict {(r1, r2) with r1 < r2: value} -- and a FACE whose pair is absent from it takes 0; every
+        connection without a barrier takes 0.  max_dp may be None when no barrier is defaulted.  None without THPRES.
+        Ours, not the reference's: a defaulted barrier on an NNC whose pair no face joins is a ValueError naming THPRES (the reference's
+        maxDp.at() throws there); and the NNC's pair is looked up ORDERED (r1 < r2), where the reference looks it up as given,
+        (eq1, eq2), in a map that only holds ordered pairs."""
+        barriers = self.thpres()
+        if barriers is None:
+            return None
+        eq = self.eqlnum()
+        c = grid.conn_cells
+        e1, e2 = eq[c[:, 0]], eq[c[:, 1]]
+        lo, hi = np.minimum(e1, e2), np.maximum(e1, e2)
+        nface = grid.n_face_conn
+        out = np.zeros(grid.nconn)
+        for (r1, r2), value in barriers.items():
+            m = (lo == r1) & (hi == r2)
+            if value is None:
+                if max_dp is None:
+                    raise ValueError("THPRES: the barrier between regions %d and %d is defaulted: max_dp is needed" % (r1, r2))
+                if isinstance(max_dp, dict):
+                    value = max_dp.get((r1, r2))
+                else:
+                    value = float(np.asarray(max_dp)[r1 - 1, r2 - 1])
+                    value = None if value < 0.0 else value
+                if value is None:
+                    if m[nface:].any():
+                        raise ValueError("THPRES: the defaulted barrier between regions %d and %d lies on an NNC, but no grid face joins "
+                                         "the two regions: there is no potential difference to take" % (r1, r2))
+                    value = 0.0
+            out[m] = value
+        return out
 
     def hysteresis(self):
         """SATOPTS HYSTER with the EHYSTR model the device implements (item 2 = 0: Carlson / drainage for the wetting phase, item 5 = KR)"""

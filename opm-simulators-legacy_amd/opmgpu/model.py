@@ -307,6 +307,28 @@ class GpuBlackoilModel(_CprDiagnostics):
         self._chk(self.lib.opmgpu_get_simulator_data(self.ctx, capi.dptr(out)))
         return {name: out[k] for k, name in enumerate(capi.SIMDATA_NAMES)}
 
+    def setThresholdPressures(self, thpres):
+        """BlackoilModelBase::setThresholdPressures (BlackoilModelBase_impl.hpp:421-443): the thresholds of ALL connections in the grid's
+        connection order (faces, then NNCs), or None to remove them.  Lasts through later setWells / setDeviceWells calls; a negative or
+        non-finite value is a ValueError."""
+        th = None if thpres is None else capi.f64(thpres)
+        if th is not None and th.shape != (self.grid.nconn,):
+            raise ValueError("setThresholdPressures: %d values for %d connections" % (th.size, self.grid.nconn))
+        self._chk(self.lib.opmgpu_set_threshold_pressures(self.ctx, capi.dptr(th)))
+
+    def computeMaxDp(self, eqlnum, nregions, n_face_conn, conns=False):
+        """computeMaxDp (opm/simulators/thresholdPressures.hpp:46-298) for the resident state: max_dp[nregions][nregions], the largest
+        phase-potential difference over the first n_face_conn connections (the grid faces; NNCs are not scanned) joining each pair of
+        the 1-based equilibration regions `eqlnum`; -1.0 = no face joins the pair, 0.0 = joined but no phase counts.  conns=True also
+        returns the per-connection plane [nconn].  Decomposed runs: collective, nregions is the global number."""
+        eq = capi.i32(eqlnum)
+        if eq.shape != (self.nc,):
+            raise ValueError("computeMaxDp: eqlnum has %d entries for %d cells" % (eq.size, self.nc))
+        out = np.zeros((int(nregions), int(nregions)))
+        dp = np.zeros(self.grid.nconn) if conns else None
+        self._chk(self.lib.opmgpu_compute_max_dp(self.ctx, capi.iptr(eq), int(nregions), int(n_face_conn), capi.dptr(dp), capi.dptr(out)))
+        return (out, dp) if conns else out
+
     def relativeChange(self):
         """BlackoilModelBase::relativeChange(saved, resident) (BlackoilModelBase_impl.hpp:1595-1631)."""
         v = C.c_double(0.0)

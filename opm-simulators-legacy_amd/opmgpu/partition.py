@@ -63,6 +63,8 @@ class LocalDomain:
                              pvtnum=None if grid.pvtnum is None else grid.pvtnum[self.global_of_local],
                              satnum=None if grid.satnum is None else grid.satnum[self.global_of_local],
                              eps=None if grid.eps is None else {k: grid.eps[i][self.global_of_local] for i, k in enumerate(GridData.EPS_NAMES)})
+        if hasattr(grid, "n_face_conn"):          # (host-only, Deck.grid()): the kept connections keep their order, grid faces before NNCs
+            self.grid.n_face_conn = int(np.count_nonzero(self.conn_index < grid.n_face_conn))
         # halo lists
         gown = part[ghosts]
         self.neigh_rank = np.unique(gown).astype(np.int32)

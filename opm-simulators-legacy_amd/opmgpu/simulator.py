@@ -1,8 +1,8 @@
 """Report-step driver on top of the device Newton path: what SimulatorBase::run does around `flow_legacy`'s hot path
 (opm/autodiff/SimulatorBase_impl.hpp:90-324), reduced to what an external diff needs:
 
-    deck -> grid / tables / initial state -> for every report step of the SCHEDULE: wells of the step (WellsManager), well state
-    carried over by name, updateSatOilMax + updateSatHyst (:190-192), AdaptiveTimeStepping.step with the NonlinearSolver (:236-253),
+    deck -> grid / tables / initial state -> [THPRES: computeMaxDp of the initial state, setThresholdPressures] -> for every report
+    step of the SCHEDULE: wells of the step (WellsManager), well state carried over by name, updateSatOilMax + updateSatHyst (:190-192), AdaptiveTimeStepping.step with the NonlinearSolver (:236-253),
     restart + summary output (:300-306).
 
 The physics runs in libopmgpu.so (state resident on the device across sub-steps); this module is host plumbing.  Output goes to
@@ -29,6 +29,7 @@ class Simulator:
         self.tables = self.deck.tables()
         self.grid = self.deck.grid()
         self.state0 = self.deck.initial_state(self.tables)
+        deck_state0 = self.state0                       # a restart replaces state0; the defaulted THPRES values come from the deck's
         self.start_step, self.t0, self._restart_ws = 0, 0.0, None
         if restart is not None:
             self._load_restart(*restart)
@@ -43,10 +44,28 @@ class Simulator:
         self.well_model_factory = well_model_factory
         if model_factory is None:
             self.model = GpuBlackoilModel(self.grid, self.tables, self.params, device=device)
-            self.model.setState(self.state0)
+            set_state = self.model.setState
         else:
             self.model = model_factory(self.grid, self.tables, self.params)
-            self.model.prepareStep(1.0, self.state0)
+            set_state = lambda st: self.model.prepareStep(1.0, st)      # noqa: E731
+        self.threshold_pressures = None
+        barriers = self.deck.thpres()
+        if barriers is None:
+            set_state(self.state0)
+        else:
+            # FlowMain.hpp:675-680 -> SimulatorBase_impl.hpp:467-468: computeMaxDp of the DECK's initial state (setupState runs before a
+            # restart file is loaded), thresholdPressures / thresholdPressuresNNC, setThresholdPressures; then the state the run starts from
+            if not hasattr(self.model, "setThresholdPressures"):
+                raise ValueError("the deck has THPRES, but the model cannot take threshold pressures (setThresholdPressures)")
+            max_dp = None
+            if any(v is None for v in barriers.values()):
+                eql = self.deck.eqlnum()
+                set_state(deck_state0)
+                nregions = max(int(eql.max()), max(r2 for _, r2 in barriers))          # (a barrier may name a region without cells)
+                max_dp = self.model.computeMaxDp(eql, nregions, self.grid.n_face_conn)
+            self.threshold_pressures = self.deck.threshold_pressures(self.grid, max_dp)
+            self.model.setThresholdPressures(self.threshold_pressures)
+            set_state(self.state0)
         self.ats = ats or ts.AdaptiveTimeStepping(initial_timestep_days=1.0)
         if getattr(self, "_restart_dtnx", None) is not None:
             self.ats.suggested_next_timestep = self._restart_dtnx
