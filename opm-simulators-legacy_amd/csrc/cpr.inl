@@ -499,7 +499,7 @@ template <class S> void LinSolver::cpr_prepare()
     if (coarse_nsub >= 1) { coarse_begin<S>(); coarse_setup<S>(false); }
 }
 
-void LinSolver::drop_hierarchies() { wd.amg.reset(); wf.amg.reset(); }
+void LinSolver::drop_hierarchies() { wd.amg.reset(); wf.amg.reset(); gm_light_for = nullptr; }      // (the wells changed: so did the perforated rows)
 
 void LinSolver::CorrectionPolicy::fail_at_current(int iterations)
 {

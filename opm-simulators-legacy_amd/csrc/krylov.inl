@@ -436,7 +436,9 @@ template <class S> SolveResult LinSolver::bicgstab(const opmgpu_params& prm)
 // k_dot launch whose partials the following k_gm_axpy re-reduces (no reduction launches, deterministic); the Hessenberg
 // column, the Givens rotations and the convergence test live on the device (k_gm_givens, one thread), the host only reads the
 // mapped status block once per iteration like the CPR path does.
-struct GmState { double* H; double* s; double* cs; double* sn; double* y; };      // H[(m+1) x m] row-major, all double
+struct GmState { double* H; double* s; double* cs; double* sn; double* y; double* gam; };      // H[(m+1) x m] row-major, all double
+// gam[m+1]: the closed form of the product on the level-0 rows (k_spmv, GM): (A v_i)_row = gam[i] base_row with
+//   gam[0] = 1 / beta,   gam[i+1] = (gam[i] - sum_{k<=i} h_ki gam[k]) / h_{i+1,i}      (h: the UNROTATED Hessenberg column i)
 
 template <class S>
 __global__ __launch_bounds__(kBlock) void k_gm_axpy(long n, int slot, const double* __restrict__ parts, int np, double* __restrict__ H,
@@ -573,7 +575,7 @@ __global__ __launch_bounds__(kBlock) void k_gm_cgs_update(long n, int nbp, const
 template <class S>
 __global__ __launch_bounds__(kBlock) void k_gm_normalize(long n, int slot, int first, double red, const double* __restrict__ parts, int np,
                                                          double* __restrict__ H, double* __restrict__ s0, const S* __restrict__ w, S* __restrict__ vout,
-                                                         SolveCtl* __restrict__ ctl, SolveCtl* __restrict__ hst)
+                                                         SolveCtl* __restrict__ ctl, SolveCtl* __restrict__ hst, double* __restrict__ gam0 = nullptr)
 {
     __shared__ double sm[12];
     if (ctl->done) return;
@@ -582,7 +584,7 @@ __global__ __launch_bounds__(kBlock) void k_gm_normalize(long n, int slot, int f
     reduce_partials<1>(arr, np, s, sm);
     const double nrm = sqrt(s[0]);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
-        if (slot >= 0) H[slot] = nrm; else { s0[0] = nrm; ctl->norm2 = s[0]; }
+        if (slot >= 0) H[slot] = nrm; else { s0[0] = nrm; ctl->norm2 = s[0]; if (gam0) gam0[0] = 1.0 / nrm; }       // (nrm ~ 0: the solve ends below, no product reads it)
         if (first) { ctl->norm0_2 = s[0]; ctl->norm2 = s[0]; ctl->thresh2 = red * red * s[0]; }
     }
     if (!(nrm == nrm) || nrm < 1e-80) {
@@ -610,6 +612,11 @@ __global__ void k_gm_givens(int i, int m, int j, GmState g, SolveCtl* __restrict
 {
     if (ctl->done) { publish(ctl, hst); if (tick_ptr) { __threadfence_system(); *(volatile int*)tick_ptr = tick; } return; }
     double* H = g.H;
+    if (g.gam) {   // the next column's factor on the level-0 rows, from this column's entries BEFORE the old rotations are applied to them
+        double a = g.gam[i];
+        for (int k = 0; k <= i; ++k) a -= H[k * m + i] * g.gam[k];
+        g.gam[i + 1] = a / H[(i + 1) * m + i];
+    }
     auto rot = [](double& dx, double& dy, double c, double sN) { const double t = c * dx + sN * dy; dy = -sN * dx + c * dy; dx = t; };
     for (int k = 0; k < i; ++k) rot(H[k * m + i], H[(k + 1) * m + i], g.cs[k], g.sn[k]);
     const double dx = H[i * m + i], dy = H[(i + 1) * m + i];
@@ -762,9 +769,38 @@ template <class S> SolveResult LinSolver::gmres(const opmgpu_params& prm)
     static const bool cgs_pyth_env = env_flag("OPMGPU_GMRES_PYTH", true);
     const bool cgs_pyth = cgs_pyth_env && prm.linear_solver_reduction >= 1e-4;
     if (flex) w.kryz.alloc(size_t(m) * n);
-    gmbuf.alloc(size_t(m + 1) * m + (m + 1) + 3 * m + 8);
+    gmbuf.alloc(size_t(m + 1) * m + (m + 1) + 3 * m + 8 + (m + 1));
     gmbuf.zero(stream);
-    GmState g; g.H = gmbuf.p; g.s = g.H + size_t(m + 1) * m; g.cs = g.s + (m + 1); g.sn = g.cs + m; g.y = g.sn + m;
+    GmState g; g.H = gmbuf.p; g.s = g.H + size_t(m + 1) * m; g.cs = g.s + (m + 1); g.sn = g.cs + m; g.y = g.sn + m; g.gam = nullptr;
+    // Closed form of the product on the level-0 rows (k_spmv, GM): on the conditions of bicgstab()'s `closed`, and
+    //   double only       -- in float the recurrence of gamma drifts from the explicit product by more than the Arnoldi estimate tolerates
+    //                        (the true preconditioned residual 3x the estimate at a reduction of 4e-7);
+    //   not flexible      -- its product multiplies z_i = M^-1 v_i and its basis is built from A z_i, not M^-1 A v_i;
+    //   not verified      -- the check takes `done` back and may continue a cycle from a threshold the recurrence was not carried for; kept
+    //                        on the explicit product it was validated with;
+    //   one GPU           -- the halo exchange overwrites ghost entries of v_i (bicgstab masks those rows, GMRES' classical Gram-Schmidt path is
+    //                        a different recurrence);
+    //   relaxation 1      -- with w != 1 (A M^-1 d)_i = d_i - (1 - w) z_i needs the second stage's input, which a basis vector does not have;
+    //   no Woodbury       -- the wells' correction behind the ILU0 changes M^-1 d on the perforated rows, which their neighbours' rows of A read: A M^-1
+    //                        is then no longer the identity on the level-0 rows next to a perforation;
+    //   no row transform  -- cpr_reference_transform is the comparison mode against the reference's formulation (L A x = L b, optionally its point
+    //                        ILU0): it keeps the explicit product, the closed form was not validated on the transformed system.
+    // The perforated level-0 rows keep the full product (gm_light).
+    const bool gm_closed = closed_form_level0 && emulate_ranks <= 1 && !(cpr && ell.relax != 1.0) && !mx && !(cpr && point_stage2) && fill_level == 0      // bicgstab()'s `closed`
+                           && sizeof(S) == 8 && !flex && !verify && !comm && prm.ilu_relaxation == 1.0 && !(well_woodbury && wb_active) && prm.cpr_reference_transform == 0;
+    const int8_t* gm_mask = nullptr;
+    if (gm_closed) {
+        g.gam = g.y + m + 8;
+        if (lowrank.perf_of_row) {
+            if (gm_light_for != lowrank.perf_of_row || gm_light_plan != plan_id || gm_light.n != size_t(plan.nbp)) {
+                gm_light.alloc(plan.nbp);
+                hipLaunchKernelGGL(k_unperforated_mask, dim3(grid_for(plan.nbp)), dim3(kBlock), 0, stream, plan.nbp, lowrank.perf_of_row, gm_light.p);
+                gm_light_for = lowrank.perf_of_row; gm_light_plan = plan_id;
+            }
+            gm_mask = gm_light.p;
+        }
+    }
+    const S* gm_base = w.b.p;          // the vector the cycle started from: b, after a restart the true defect
     double* parts = partials.p;
     double* parts2 = partials.p + npart;                             // second partial array: producer and consumer of a fused step differ
     double* red1 = partials.p + size_t(6) * npart;                   // the all-reduced scalar of a projection (multi-GPU)
@@ -789,6 +825,16 @@ template <class S> SolveResult LinSolver::gmres(const opmgpu_params& prm)
                            dp.slice_ptr.p, dp.col.p, matrix<S>(), (const S*)vin, out, (const S*)nullptr, mask, c,
                            (double*)nullptr, (double*)nullptr, (const S*)nullptr, (const S*)nullptr, 0, S(0), lowrank, (const int8_t*)nullptr);
     };
+    // A v_i inside a cycle: the level-0 rows from gam[i] and the cycle's base vector
+    auto product_basis = [&](int i, S* out, const SolveCtl* c, bool exchange) {
+        if (!gm_closed) { product(w.kry.p + size_t(i) * n, out, c, exchange); return; }
+        S* vin = w.kry.p + size_t(i) * n;
+        lowrank_reduce<S>(vin, c);
+        hipLaunchKernelGGL((k_spmv<S, 0, 1>), dim3(std::min(grid8_for(plan.nb), 4 * kMaxPart)), dim3(kBlock), 0, stream, xcd_mode(), plan.nb, plan.nbp,
+                           dp.slice_ptr.p, dp.col.p, matrix<S>(), (const S*)vin, out, (const S*)nullptr, mask, c,
+                           (double*)nullptr, (double*)nullptr, gm_base, (const S*)nullptr, int(plan.level_ptr[1]), S(0), lowrank, gm_mask, 0, (const int8_t*)nullptr,
+                           (const double*)(g.gam + i));
+    };
     auto V = [&](int k) { return w.kry.p + size_t(k) * n; };
     auto precond = [&](const S* d, S* out) { precond_apply<S>(d, out, prm.ilu_relaxation, d_ctl, cpr); };
     auto Z = [&](int k) { return w.kryz.p + size_t(k) * n; };
@@ -799,7 +845,7 @@ template <class S> SolveResult LinSolver::gmres(const opmgpu_params& prm)
         } else
         dot(src, src);
         hipLaunchKernelGGL((k_gm_normalize<S>), dim3(gv), dim3(kBlock), 0, stream, n, -1, first, prm.linear_solver_reduction, dot_arr, dot_np,
-                           g.H, g.s, src, V(0), d_ctl, h_ctl_dev);
+                           g.H, g.s, src, V(0), d_ctl, h_ctl_dev, g.gam);
         hipLaunchKernelGGL(k_gm_reset_s, dim3(1), dim3(1), 0, stream, m, g);
     };
     // x0 = 0: defect = b
@@ -830,7 +876,7 @@ template <class S> SolveResult LinSolver::gmres(const opmgpu_params& prm)
             } else {
                 if (!product_enqueued) {
                     kt_a = kt.begin();
-                    product(V(i), w.v.p, (const SolveCtl*)d_ctl, !fuse_halo);
+                    product_basis(i, w.v.p, (const SolveCtl*)d_ctl, !fuse_halo);
                     kt.end(KT_SPMV1, kt_a);
                 }
                 product_enqueued = false;
@@ -866,7 +912,7 @@ template <class S> SolveResult LinSolver::gmres(const opmgpu_params& prm)
             kt.end(KT_VECTOR, kt_a);
             if (speculate && !flex && i + 1 < m && j + 1 <= maxit) {
                 kt_a = kt.begin();
-                product(V(i + 1), w.v.p, (const SolveCtl*)d_ctl, !fuse_halo);
+                product_basis(i + 1, w.v.p, (const SolveCtl*)d_ctl, !fuse_halo);
                 kt.end(KT_SPMV1, kt_a);
                 product_enqueued = true;
             }
@@ -913,6 +959,7 @@ template <class S> SolveResult LinSolver::gmres(const opmgpu_params& prm)
         if (!stop && j <= maxit) {                                     // restart from the true defect
             product(w.x.p, w.v.p, (const SolveCtl*)nullptr);
             hipLaunchKernelGGL((k_gm_defect<S>), dim3(gv), dim3(kBlock), 0, stream, n, (const S*)w.b.p, (const S*)w.v.p, w.r.p);
+            gm_base = w.r.p;
             if (flex) normalize_start(w.r.p, 0);
             else { precond(w.r.p, w.t.p); normalize_start(w.t.p, 0); }
         }

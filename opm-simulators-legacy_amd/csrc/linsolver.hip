@@ -70,6 +70,13 @@ __device__ __forceinline__ void reduce_partials(const double* const (&arr)[NV], 
 //   (A x)_i = (A c)_i + w z_i = (pin_i - z_i) + w z_i = pin_i - (1 - w) z_i .
 // Those rows (half of all rows with the 2-colour ordering) need no matrix traffic.  Light and heavy rows
 // are chunked separately so that every XCD gets the same share of both.
+//
+// GM == 1 (left-preconditioned GMRES, relaxation 1, see gmres()): x is a basis vector v_i, not M^-1 of a vector in memory.  On a
+// level-0 row A M^-1 is the identity (the formula above with w = 1), so by induction over the Arnoldi recurrence
+//   v_0 = M^-1 b / beta,   v_{i+1} = (M^-1 A v_i - sum_{k<=i} h_ki v_k) / h_{i+1,i}
+// every product is a multiple of the cycle's base vector there: (A v_i)_row = gamma_i base_row (base = b, after a restart the true
+// defect).  pin = base, *gamma = gamma_i (device-resident, k_gm_normalize / k_gm_givens advance it).  A perforated level-0 row is no
+// such row (the well operator adds P_i t_w): lightmask[row] == 0 sends it through the full row product.
 // y_i += P_i t_w on a perforated row (t_w = Q_w x from k_lowrank_reduce)
 template <class S>
 __device__ __forceinline__ void lowrank_add(const LowRankOp& lr, int row, S& y0, S& y1, S& y2)
@@ -117,14 +124,22 @@ __global__ __launch_bounds__(kBlock) void k_light_mask(int nb, const int32_t* __
     ok[row] = good ? 1 : 0;
 }
 
-template <class S, int NDOT>
+// GMRES closed form: level-0 rows that keep it = those without a perforation (1), the others take the full row product (0)
+__global__ __launch_bounds__(kBlock) void k_unperforated_mask(int n, const int32_t* __restrict__ perf_of_row, int8_t* __restrict__ ok)
+{
+    const int row = blockIdx.x * kBlock + threadIdx.x;
+    if (row < n) ok[row] = perf_of_row[row] < 0 ? 1 : 0;
+}
+
+template <class S, int NDOT, int GM = 0>
 __global__ __launch_bounds__(kBlock) void k_spmv(int xm, int nb, int nbp, const int32_t* __restrict__ slice_ptr,
                                                  const int32_t* __restrict__ col, const S* __restrict__ val,
                                                  const S* __restrict__ x, S* __restrict__ y,
                                                  const S* __restrict__ w1, const int8_t* __restrict__ mask,
                                                  const SolveCtl* __restrict__ ctl, double* __restrict__ p0, double* __restrict__ p1,
                                                  const S* __restrict__ pin, const S* __restrict__ zin, int n0, S w, LowRankOp lr,
-                                                 const int8_t* __restrict__ lightmask, int phase = 0, const int8_t* __restrict__ interior = nullptr)
+                                                 const int8_t* __restrict__ lightmask, int phase = 0, const int8_t* __restrict__ interior = nullptr,
+                                                 const double* __restrict__ gamma = nullptr)
 {
     // phase (multi-GPU, halo exchange in flight): 1 = only the rows of `interior` (owned, no ghost neighbour: they read no halo value),
     // 2 = only the others; 0 = all rows.  The partials of the two launches are laid side by side by the caller.
@@ -140,10 +155,16 @@ __global__ __launch_bounds__(kBlock) void k_spmv(int xm, int nb, int nbp, const 
             if (phase && (phase == 1) != (interior[row] != 0)) continue;
             S y0, y1, y2;
             if (!lightmask || lightmask[row]) {
-                const S om = S(1) - w;
-                y0 = pin[row] - om * zin[row]; y1 = pin[nbp + row] - om * zin[nbp + row]; y2 = pin[2 * nbp + row] - om * zin[2 * nbp + row];
+                if (GM) {
+                    const S g = S(*gamma);
+                    y0 = g * pin[row]; y1 = g * pin[nbp + row]; y2 = g * pin[2 * nbp + row];
+                } else {
+                    const S om = S(1) - w;
+                    y0 = pin[row] - om * zin[row]; y1 = pin[nbp + row] - om * zin[nbp + row]; y2 = pin[2 * nbp + row] - om * zin[2 * nbp + row];
+                }
             } else {
-                // multi-GPU: a level-0 row next to a ghost cell (its x was replaced by the owner's value) or a ghost row itself
+                // multi-GPU: a level-0 row next to a ghost cell (its x was replaced by the owner's value) or a ghost row itself;
+                // GMRES: a perforated level-0 row
                 y0 = 0; y1 = 0; y2 = 0;
                 if (!mask || mask[row]) {
                     const int sl = row >> 6, lane = row & 63;

@@ -295,6 +295,8 @@ public:
     LowRankOp lowrank;             // nw == 0: none
     DevArray<int8_t> light_ok;     // multi-GPU: rows that keep the closed form (owned, no ghost neighbour)
     const CommBase* light_ok_for = nullptr;
+    DevArray<int8_t> gm_light;     // GMRES closed form: level-0 rows without a perforation (built once per well plan, gmres())
+    const int32_t* gm_light_for = nullptr; int gm_light_plan = -1;      // the perf_of_row map / plan it was built from (wells_rebind -> drop_hierarchies resets)
     template <class S> void lowrank_reduce(const S* x, const SolveCtl* ctl);
     // Stage 2 of the CPR preconditioner sees the wells: the ILU0 is of A, the operator is A + sum_w P_w Q_w.  Woodbury with
     // the block-diagonal of the ILU0 standing in for its inverse on the (few) perforated rows:
@@ -304,7 +306,11 @@ public:
     DevArray<double> wb_buf;       // [nperf][3][7] Y | [nw][49] inverses
     bool well_woodbury = false, wb_active = false;
     double wb_relax = 0.9;         // the ILU0's relaxation factor (omega above), set by the caller before the factorisation
-    bool closed_form_level0 = true; // k_spmv shortcut on level-0 rows (A/B switch: OPMGPU_CLOSED=0)
+    // k_spmv shortcut on level-0 rows, which have no lower entries (half of all rows with the 2-colour ordering): no matrix traffic there.
+    // BiCGStab: (A M^-1 p)_i from p and the second stage's input; left-preconditioned GMRES in double with relaxation 1: (A v_i)_i =
+    // gamma_i base_i with one device-resident scalar per column (linsolver.hip, k_spmv; the conditions: bicgstab() / gmres()).
+    // A/B switch for both: OPMGPU_CLOSED=0, read when the solver is created
+    bool closed_form_level0 = true;
     bool cpr_halo_xp = true;        // multi-GPU CPR: halo-exchange the pressure correction before stage 2 (A/B: OPMGPU_CPR_HALO_XP=0)
     int amg_lag = 1, amg_age = 0;   // A/B: OPMGPU_AMG_LAG
     // refresh policy of the coarse operators of the pressure hierarchy (see cpr_prepare); OPMGPU_AMG_LAG_COARSE
