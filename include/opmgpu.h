@@ -565,6 +565,39 @@ int opmgpu_set_threshold_pressures(opmgpu_ctx* ctx, const double* thpres /* [nco
  * OPMGPU_EINVAL (with text) for a NULL eqlnum / max_dp, a region outside [1, nregions], n_face_conn outside [0, nconn], or no state. */
 int opmgpu_compute_max_dp(opmgpu_ctx* ctx, const int32_t* eqlnum, int nregions, int n_face_conn, double* dp_conn, double* max_dp);
 
+/* SWATINIT: BlackoilPropsAdFromDeck::setSwatInitScaling (BlackoilPropsAdFromDeck.cpp:1009-1019; called at FlowMain.hpp:683-690 "to match
+ * the scaled capillary pressure in props").  Rescales every cell's maximum oil-water capillary pressure (PCW) so that the imposed water
+ * saturation sw[c] is in equilibrium with the target pcow[c] = p_o - p_w.  The reference hands each cell to
+ * EclMaterialLawManager::applySwatinit, which is opm-material and outside its tree, so THE RULE BELOW IS OURS.  It is pinned by the known
+ * answers of the reference's DeckWithSwatinit test (tests/test_equil_legacy.cpp:916-1060: 60 saturations, 12 scaled capillary pressures),
+ * which it reproduces, and by nothing else.  For cell c with its drainage scaled end points Swl, Swu (the cell's SWL / SWU, else the first /
+ * last Sw node of its SWOF table):
+ *   pcow[c] < 0:  sw_out = Swu, PCW unchanged;
+ *   else          Sw = min(max(sw[c], Swl), Swu), sw_out = Sw (a saturation clamped to Swl is still scaled);
+ *                 pc_at = the cell's oil-water capillary pressure at Sw under its CURRENT end-point and vertical scaling;
+ *                 pc_at > 0: PCW_c *= pcow[c] / pc_at;  pc_at <= 0 (a table without capillary pressure, or a zero at Sw): unchanged.
+ * Applying it again with pcow equal to the scaled curve at sw_out changes nothing (the ratio is 1); calling it twice with the same target
+ * compounds, as the reference's would.  No cap on the scaled PCW (PPCWMAX), no mixed-wettability handling.
+ * pc_at is evaluated on the device by the evaluators of the Newton path (one kernel, one thread per cell); the new PCW is kept on the
+ * host as a pressure and reaches the device as opmgpu_grid.eps_v[3] does at creation.  So a context scaled here, a context created with
+ * eps_v[3] = the array opmgpu_get_pcw returns, and either after opmgpu_set_wells / opmgpu_set_device_wells assemble bit for bit the same.
+ * Works on a context created with or without end points / vertical arrays, with every three-phase model and without a gas phase; the
+ * imbibition curves of a hysteresis context carry no capillary pressure and are untouched.  sw_out may be NULL.
+ * OPMGPU_EINVAL with text in opmgpu_last_error(ctx), nothing changed: a non-finite sw or pcow, sw outside [0, 1], a NULL sw / pcow.
+ * Decomposed runs: the rank's local cells, ghosts included (a ghost's PCW enters the owner's flux); no communication. */
+int opmgpu_set_swatinit_scaling(opmgpu_ctx* ctx, const double* sw /* [nc] */, const double* pcow /* [nc] */, double* sw_out /* [nc] or NULL */);
+
+/* Each cell's current maximum oil-water capillary pressure [Pa]: its PCW (opmgpu_grid.eps_v[3], or what opmgpu_set_swatinit_scaling left);
+ * for a context without vertical scaling of that curve -- and for a cell whose table's first pcow node is zero, which is never scaled --
+ * the first pcow node of the SWOF table of the cell's saturation region. */
+int opmgpu_get_pcw(opmgpu_ctx* ctx, double* pcw /* [nc] */);
+
+/* BlackoilPropsAdFromDeck::capPress: pc[c] = pcow = p_o - p_w and pc[nc + c] = pcgo = p_g - p_o of every cell at the saturations sat
+ * ([nc][3] water, oil, gas) or, sat == NULL, at the resident state's, through the cell's end-point and vertical scaling -- the curves the
+ * assembly evaluates.  OPMGPU_PHASES_OIL_WATER: pcgo = 0.  One kernel; the resident state is only read.  OPMGPU_EINVAL (with text) for a
+ * NULL pc, or a NULL sat before a state has been set. */
+int opmgpu_cap_press(opmgpu_ctx* ctx, const double* sat /* [nc*3] or NULL */, double* pc /* [2*nc] */);
+
 /* Maximum historical oil saturation per cell (BlackoilPropsAdFromDeck::satOilMax_, used by VAPPARS).
  * set: explicit values (nc, caller order; restart).  update: soMax = max(soMax, so of the resident state) --
  * what SimulatorBase_impl.hpp:192 does at the start of every report step (updateSatOilMax, :933-945).

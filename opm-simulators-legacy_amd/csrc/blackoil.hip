@@ -1281,6 +1281,61 @@ __global__ __launch_bounds__(kBlock) void k_max_dp(int nconn, int nface, DevTabl
     out[f] = dp;
 }
 
+// SWATINIT, the per-cell part of BlackoilPropsAdFromDeck::setSwatInitScaling (BlackoilPropsAdFromDeck.cpp:1009-1019): one thread per cell of
+// the plan (row r, caller cell nat[r]; sw_in / pcow_in / the two outputs are in CALLER numbering, everything else internal).  The rule is
+// stated in include/opmgpu.h (opmgpu_set_swatinit_scaling): pcow < 0 -> sw_out = Swu, nothing scaled; else sw_out = the imposed saturation
+// clamped to [Swl, Swu], pc_at = the cell's pcow there under its current scaling (the evaluator every other kernel uses), and where
+// pc_at > 0 the cell's PCW is to be multiplied by ratio = pcow / pc_at.  ratio_out = -1 marks a cell whose PCW stays (a ratio is never
+// negative).  swl / swu: the cell's scaled end points, else its table's first / last Sw node (the host holds them).
+// Off every timed path (once per run, before the first step): not tuned, not timed.
+__global__ __launch_bounds__(kBlock) void k_swatinit(int nb, DevTables D, const int32_t* __restrict__ nat, const int32_t* __restrict__ satnum,
+                                                     const double* __restrict__ eps, const double* __restrict__ eps_u0, long nbp,
+                                                     const double* __restrict__ swl, const double* __restrict__ swu, const double* __restrict__ sw_in,
+                                                     const double* __restrict__ pcow_in, double* __restrict__ sw_out, double* __restrict__ ratio_out)
+{
+    const int r = blockIdx.x * kBlock + threadIdx.x;
+    if (r >= nb) return;
+    const opmgpu_tables& T = D.t;
+    const int c = nat[r], sreg = satnum[r];
+    const double pcow = pcow_in[c];
+    double sw = swu[r], ratio = -1.0;
+    if (!(pcow < 0.0)) {
+        sw = fmin(fmax(sw_in[c], swl[r]), swu[r]);
+        EpsD E;
+        eps_load(eps, eps_u0, nbp, r, sreg, E);
+        const int wa = T.swof_ptr[sreg], nw = T.swof_ptr[sreg + 1] - wa;
+        double f, df;
+        sat_curve_s<false>(T.swof_sw + wa, T.swof_pcow + wa, D.x.swof_dpcow + wa, nw, sw, E, EC_PCOW, f, df);
+        if (f > 0.0) ratio = pcow / f;
+    }
+    sw_out[c] = sw; ratio_out[c] = ratio;
+}
+
+// capPress of the properties object (BlackoilPropsAdFromDeck::capPress): pcow = p_o - p_w at sw[r] and pcgo = p_g - p_o at sg[r] (internal
+// planes) through the cell's end-point and vertical scaling, the curves the Newton path evaluates (eval_cell; hysteresis is KR-only: no
+// capillary-pressure history).  out (caller numbering): [pcow | pcgo] x nc.  No gas phase: pcgo = 0, no gas table read.  Not timed.
+__global__ __launch_bounds__(kBlock) void k_cap_press(int nb, DevTables D, const int32_t* __restrict__ nat, const int32_t* __restrict__ satnum,
+                                                      const double* __restrict__ sw, const double* __restrict__ sg, const double* __restrict__ eps,
+                                                      const double* __restrict__ eps_u0, long nbp, double* __restrict__ out)
+{
+    const int r = blockIdx.x * kBlock + threadIdx.x;
+    if (r >= nb) return;
+    const opmgpu_tables& T = D.t;
+    const int c = nat[r], sreg = satnum[r];
+    EpsD E;
+    eps_load(eps, eps_u0, nbp, r, sreg, E);
+    const int wa = T.swof_ptr[sreg], nw = T.swof_ptr[sreg + 1] - wa;
+    double f, df;
+    sat_curve_s<false>(T.swof_sw + wa, T.swof_pcow + wa, D.x.swof_dpcow + wa, nw, sw[r], E, EC_PCOW, f, df);
+    out[c] = f;
+    f = 0.0;
+    if (T.active_phases != OPMGPU_PHASES_OIL_WATER) {
+        const int ga = T.sgof_ptr[sreg], ng = T.sgof_ptr[sreg + 1] - ga;
+        sat_curve_s<true>(T.sgof_sg + ga, T.sgof_pcgo + ga, D.x.sgof_dpcgo + ga, ng, sg[r], E, EC_PCGO, f, df);
+    }
+    out[long(nb) + c] = f;
+}
+
 // computePropertiesForWellConnectionPressures (StandardWells_impl.hpp:218-296): b_w, b_o, b_g, rsSat, rvSat of the perforated cells at
 // GIVEN pressures (the average well-block pressures) with the cells' own rs / rv / phase condition / oil saturation
 __global__ __launch_bounds__(kBlock) void k_perf_pvt(int nperf, DevTables D, const int32_t* __restrict__ cells, const int32_t* __restrict__ pvtnum,
@@ -1622,27 +1677,10 @@ void BlackoilDevice::rebuild_structure()
     for (int r = 0; r < nc; ++r) { pvi[r] = h_pv[P.nat[r]]; pn[r] = h_pvtnum[P.nat[r]]; sn[r] = h_satnum[P.nat[r]]; }
     d_pv.upload(pvi, stream); d_pvtnum.upload(pn, stream); d_satnum.upload(sn, stream);
     if (use_eps) {
-        // per region: unscaled fixed points of every curve (u0 | u1); per cell: the maps and the vertical factors (build_eps_planes)
-        // A set of curves WITHOUT scaled end points keeps the saturation exactly (S_u = 0 + (S - 0) * 1: states that sit on a table
-        // breakpoint must not move by an ulp), so its region table is zero and build_eps_planes writes s0 = 0, k = 1.
-        const int ns = dto_.t.n_sat_regions;
-        auto region_table = [&](bool have_points) {
-            std::vector<double> ureg(size_t(kEpsRegion) * ns, 0.0);
-            for (int r = 0; r < ns && have_points; ++r) {
-                const double* u = &h_unscaled[8 * size_t(r)];
-                double* o = &ureg[size_t(kEpsRegion) * r];
-                o[EC_KRW] = u[1]; o[EC_KROW] = u[0] + u[4]; o[EC_PCOW] = u[0]; o[EC_KRG] = u[5]; o[EC_KROG] = u[7]; o[EC_PCGO] = u[4];
-                double* m = o + EC_COUNT;   // middle points (SCALECRS): krw 1-Sowcr-Sgl, krow Swcr+Sgl, krg 1-Sogcr-Swl, krog 1-Sgcr-Swl
-                m[EC_KRW] = 1.0 - u[3] - u[4]; m[EC_KROW] = u[1] + u[4]; m[EC_PCOW] = 0.0; m[EC_KRG] = 1.0 - u[7] - u[0]; m[EC_KROG] = 1.0 - u[5] - u[0]; m[EC_PCGO] = 0.0;
-            }
-            return ureg;
-        };
-        d_eps_u0.upload(region_table(has_endpoints), stream);
         std::vector<double> planes;
-        build_eps_planes(h_eps, has_endpoints, false, planes);
-        d_eps.upload(planes, stream);
+        upload_drainage_eps();
         if (use_hyst) {
-            d_ieps_u0.upload(region_table(has_iendpoints || has_endpoints), stream);
+            d_ieps_u0.upload(eps_region_table(has_iendpoints || has_endpoints), stream);
             build_eps_planes(has_iendpoints ? h_ieps : h_eps, has_iendpoints || has_endpoints, true, planes);
             d_ieps.upload(planes, stream);
             std::vector<int32_t> im(nbp, 0);
@@ -1690,6 +1728,104 @@ void BlackoilDevice::rebuild_structure()
     if (!smax.empty()) set_sat_oil_max(smax.data());
     wells_rebind();
     if (has_state) set_state(sp.data(), ssat.data(), srs.data(), srv.data(), shc.data());
+}
+
+// per region: unscaled fixed points of every curve (u0 | u1).  A set of curves WITHOUT scaled end points keeps the saturation exactly
+// (S_u = 0 + (S - 0) * 1: states that sit on a table breakpoint must not move by an ulp), so its region table is zero and
+// build_eps_planes writes s0 = 0, k = 1.
+std::vector<double> BlackoilDevice::eps_region_table(bool have_points) const
+{
+    const int ns = dto_.t.n_sat_regions;
+    std::vector<double> ureg(size_t(kEpsRegion) * ns, 0.0);
+    for (int r = 0; r < ns && have_points; ++r) {
+        const double* u = &h_unscaled[8 * size_t(r)];
+        double* o = &ureg[size_t(kEpsRegion) * r];
+        o[EC_KRW] = u[1]; o[EC_KROW] = u[0] + u[4]; o[EC_PCOW] = u[0]; o[EC_KRG] = u[5]; o[EC_KROG] = u[7]; o[EC_PCGO] = u[4];
+        double* m = o + EC_COUNT;   // middle points (SCALECRS): krw 1-Sowcr-Sgl, krow Swcr+Sgl, krg 1-Sogcr-Swl, krog 1-Sgcr-Swl
+        m[EC_KRW] = 1.0 - u[3] - u[4]; m[EC_KROW] = u[1] + u[4]; m[EC_PCOW] = 0.0; m[EC_KRG] = 1.0 - u[7] - u[0]; m[EC_KROG] = 1.0 - u[5] - u[0]; m[EC_PCGO] = 0.0;
+    }
+    return ureg;
+}
+
+// the drainage curves' region table and per-cell planes (the maps and the vertical factors, build_eps_planes) from the host copies, for
+// the current plan: THE path onto the device for them (rebuild_structure, set_swatinit_scaling)
+void BlackoilDevice::upload_drainage_eps()
+{
+    d_eps_u0.upload(eps_region_table(has_endpoints), stream);
+    std::vector<double> planes;
+    build_eps_planes(h_eps, has_endpoints, false, planes);
+    d_eps.upload(planes, stream);
+    OPMGPU_HIP(hipStreamSynchronize(stream));
+}
+
+// each cell's maximum oil-water capillary pressure (caller numbering): its PCW where the context holds vertical scaling of that curve,
+// else the first pcow node of its region's SWOF table (also where that node is zero: such a curve is not scaled, build_eps_planes)
+void BlackoilDevice::get_pcw(double* pcw) const
+{
+    for (int c = 0; c < nc; ++c) {
+        const double tm = h_tabmax[6 * size_t(h_satnum[c]) + EC_PCOW];
+        pcw[c] = (h_eps_v[3].empty() || tm == 0.0) ? tm : h_eps_v[3][c];
+    }
+}
+
+// setSwatInitScaling (BlackoilPropsAdFromDeck.cpp:1009-1019; the rule: include/opmgpu.h).  The kernel evaluates the curve and returns the
+// ratio per cell; the new PCW goes into the host copy h_eps_v[3] and from there through build_eps_planes like a PCW array given at
+// creation, so a later re-plan keeps it.  A context without any scaling gets identity planes (use_eps: e.on is a run-time pointer).
+void BlackoilDevice::set_swatinit_scaling(const double* sw, const double* pcow, double* sw_out)
+{
+    for (int c = 0; c < nc; ++c) {
+        if (!std::isfinite(sw[c]) || !std::isfinite(pcow[c]))
+            throw HipError(OPMGPU_EINVAL, "setSwatInitScaling: the saturation or capillary pressure of cell " + std::to_string(c) + " is not finite");
+        if (sw[c] < 0.0 || sw[c] > 1.0)
+            throw HipError(OPMGPU_EINVAL, "setSwatInitScaling: the water saturation of cell " + std::to_string(c) + " is outside [0, 1]");
+    }
+    const Plan& P = ls.plan;
+    const int nbp = P.nbp;
+    OPMGPU_HIP(hipStreamSynchronize(stream));
+    std::vector<double> lim(2 * size_t(nbp), 0.0), in(2 * size_t(nc)), out(2 * size_t(nc));
+    for (int r = 0; r < nc; ++r) {
+        const int c = P.nat[r];
+        const double* u = &h_unscaled[8 * size_t(h_satnum[c])];
+        lim[r] = has_endpoints ? h_eps[0][c] : u[0];
+        lim[size_t(nbp) + r] = has_endpoints ? h_eps[2][c] : u[2];
+    }
+    std::copy(sw, sw + nc, in.begin()); std::copy(pcow, pcow + nc, in.begin() + nc);
+    DevArray<double> d_lim, d_in, d_out;
+    d_lim.upload(lim, stream); d_in.upload(in, stream); d_out.alloc(out.size());
+    hipLaunchKernelGGL(k_swatinit, dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, dtp_, ls.dp.nat.p, d_satnum.p, eps_planes(), d_eps_u0.p, long(nbp),
+                       (const double*)d_lim.p, (const double*)d_lim.p + nbp, (const double*)d_in.p, (const double*)d_in.p + nc, d_out.p, d_out.p + nc);
+    OPMGPU_HIP(hipGetLastError());
+    d_out.download(out.data(), out.size(), stream);
+    OPMGPU_HIP(hipStreamSynchronize(stream));
+    std::vector<double> pcw(nc);
+    get_pcw(pcw.data());
+    for (int c = 0; c < nc; ++c) if (out[size_t(nc) + c] >= 0.0) pcw[c] *= out[size_t(nc) + c];
+    h_eps_v[3] = pcw;
+    use_eps = true;
+    upload_drainage_eps();
+    if (sw_out) std::copy(out.begin(), out.begin() + nc, sw_out);
+}
+
+// capPress for given saturations ([nc][3] water, oil, gas; caller numbering) or, sat == nullptr, the resident state's: pc = [pcow | pcgo] x nc
+void BlackoilDevice::cap_press(const double* sat, double* pc)
+{
+    const Plan& P = ls.plan;
+    const int nbp = P.nbp;
+    DevArray<double> d_s, d_out;
+    const double *sw = d_sw.p, *sg = d_sg.p;
+    if (sat) {
+        std::vector<double> s(2 * size_t(nbp), 0.0);
+        for (int r = 0; r < nc; ++r) { s[r] = sat[3 * size_t(P.nat[r])]; s[size_t(nbp) + r] = sat[3 * size_t(P.nat[r]) + 2]; }
+        d_s.upload(s, stream);
+        OPMGPU_HIP(hipStreamSynchronize(stream));
+        sw = d_s.p; sg = d_s.p + nbp;
+    }
+    d_out.alloc(2 * size_t(nc));
+    hipLaunchKernelGGL(k_cap_press, dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, dtp_, ls.dp.nat.p, d_satnum.p, sw, sg, eps_planes(), d_eps_u0.p,
+                       long(nbp), d_out.p);
+    OPMGPU_HIP(hipGetLastError());
+    d_out.download(pc, 2 * size_t(nc), stream);
+    OPMGPU_HIP(hipStreamSynchronize(stream));
 }
 
 HystArgs BlackoilDevice::hyst_args() const

@@ -46,6 +46,9 @@ public:
     void fluid_in_place(const int32_t* fipnum, int dims, double* fip_cells, double* values);      // computeFluidInPlace (:2263-2445)
     void set_threshold_pressures(const double* thpres);                                            // setThresholdPressures (:421-443); nullptr = none
     void compute_max_dp(const int32_t* eqlnum, int nregions, int n_face_conn, double* dp_conn, double* max_dp);      // computeMaxDp (opm/simulators/thresholdPressures.hpp:46-298)
+    void set_swatinit_scaling(const double* sw, const double* pcow, double* sw_out);              // setSwatInitScaling (BlackoilPropsAdFromDeck.cpp:1009-1019)
+    void get_pcw(double* pcw) const;                                                               // each cell's maximum oil-water capillary pressure
+    void cap_press(const double* sat, double* pc);                                                 // capPress: [pcow | pcgo] of given / the resident saturations
     void simulator_data(double* out);                                                              // SimulatorData of the resident state (:662-683, rq_[].b/rho/mu/kr)
     void region_state_sums(const int32_t* region, int nregions, double* sums);                   // RateConverter calcAverages (RateConverterLegacy.hpp:718-768)
     void voidage_coefficients(int n, const double* p, const double* rs, const double* rv, const int32_t* pvtreg, double* coeff);   // calcCoeff (:495-548)
@@ -156,6 +159,8 @@ private:
     DevArray<double> d_stone_som;            // DevTables::stone_som
     HystArgs hyst_args() const;
     void build_eps_planes(const std::vector<double>* ep8, bool have_points, bool imbibition, std::vector<double>& planes) const;
+    std::vector<double> eps_region_table(bool have_points) const;
+    void upload_drainage_eps();
     std::vector<double> h_tabmax;
     DevArray<int8_t> d_saved_hc;
     const double* eps_planes() const { return use_eps ? d_eps.p : nullptr; }

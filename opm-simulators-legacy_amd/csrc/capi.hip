@@ -847,6 +847,25 @@ int opmgpu_compute_max_dp(opmgpu_ctx* c, const int32_t* eqlnum, int nregions, in
     for (int i = 0; i < c->model->nc; ++i) if (eqlnum[i] < 1 || eqlnum[i] > nregions) return fail(c, OPMGPU_EINVAL, "computeMaxDp: eqlnum outside [1, nregions]");
     return guarded(c, [&]() { c->model->compute_max_dp(eqlnum, nregions, n_face_conn, dp_conn, max_dp); return int(OPMGPU_OK); });
 }
+int opmgpu_set_swatinit_scaling(opmgpu_ctx* c, const double* sw, const double* pcow, double* sw_out)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    if (!sw || !pcow) return fail(c, OPMGPU_EINVAL, "setSwatInitScaling: sw and pcow must be given");
+    return guarded(c, [&]() { c->model->set_swatinit_scaling(sw, pcow, sw_out); return int(OPMGPU_OK); });
+}
+int opmgpu_get_pcw(opmgpu_ctx* c, double* pcw)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    if (!pcw) return fail(c, OPMGPU_EINVAL, "get_pcw: pcw must be given");
+    return guarded(c, [&]() { c->model->get_pcw(pcw); return int(OPMGPU_OK); });
+}
+int opmgpu_cap_press(opmgpu_ctx* c, const double* sat, double* pc)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    if (!pc) return fail(c, OPMGPU_EINVAL, "capPress: pc must be given");
+    if (!sat && !c->model->has_state) return fail(c, OPMGPU_EINVAL, "capPress: no saturations given and no reservoir state on the device");
+    return guarded(c, [&]() { c->model->cap_press(sat, pc); return int(OPMGPU_OK); });
+}
 int opmgpu_get_simulator_data(opmgpu_ctx* c, double* out)
 {
     if (!c || !c->model || !out || !c->model->has_state) return OPMGPU_EINVAL;

@@ -240,6 +240,31 @@ public:
         for (int a = 0; a < nregions; ++a) for (int b = 0; b < nregions; ++b) m[a][b] = flat[std::size_t(a) * nregions + b];
         return m;
     }
+    /// BlackoilPropsAdFromDeck::setSwatInitScaling (BlackoilPropsAdFromDeck.cpp:1009-1019; the rule is stated in opmgpu.h): per cell the
+    /// imposed water saturation and the target pcow = p_o - p_w; returns the saturation each cell ends at.  std::logic_error for a wrong
+    /// size, a non-finite value or a saturation outside [0, 1].
+    std::vector<double> setSwatInitScaling(const std::vector<double>& sw, const std::vector<double>& pcow)
+    {
+        if (int(sw.size()) != nc_ || int(pcow.size()) != nc_) throw std::logic_error("setSwatInitScaling: one saturation and one capillary pressure per cell");
+        std::vector<double> sw_out(std::size_t(nc_), 0.0);
+        throw_on_status(ctx_, opmgpu_set_swatinit_scaling(ctx_, sw.data(), pcow.data(), sw_out.data()));
+        return sw_out;
+    }
+    /// each cell's current maximum oil-water capillary pressure (PCW, or the table maximum of its saturation region)
+    std::vector<double> pcw()
+    {
+        std::vector<double> v(std::size_t(nc_), 0.0);
+        throw_on_status(ctx_, opmgpu_get_pcw(ctx_, v.data()));
+        return v;
+    }
+    /// BlackoilPropsAdFromDeck::capPress: [pcow | pcgo] x nc at the saturations `sat` ([nc][3]) or, nullptr, the resident state's
+    std::vector<double> capPress(const std::vector<double>* sat = nullptr)
+    {
+        if (sat && int(sat->size()) != 3 * nc_) throw std::logic_error("capPress: three saturations per cell");
+        std::vector<double> pc(2 * std::size_t(nc_), 0.0);
+        throw_on_status(ctx_, opmgpu_cap_press(ctx_, sat ? sat->data() : nullptr, pc.data()));
+        return pc;
+    }
     /// BlackoilModelBase::getSimulatorData (sd_ of :662-683 and rq_[].b/rho/mu/kr) for the resident state: 16 per-cell arrays in SI under
     /// the names of SimulatorFullyImplicitBlackoilOutput.hpp:512-567, in the cell order of the state
     std::map<std::string, std::vector<double>> simulatorData()

@@ -15,6 +15,8 @@ What `flow_legacy` gets from opm-parser + `DerivedGeology` (opm/autodiff/GeoProp
             STONE1 STONE2 STONE (= STONE2) STONE1EX: the three-phase oil relative permeability model (none of them: the default model;
             two of them, or one together with SATOPTS HYSTER, is refused)
             SWL SWCR SWU SOWCR SGL SGCR SGU SOGCR  KRW KRO KRG PCW PCG  ISWL ISWCR ISWU ISOWCR ISGL ISGCR ISGU ISOGCR
+            SWATINIT (an imposed initial water saturation per cell; read like SWL, `swatinit()`; EQUIL then rescales each cell's PCW,
+            opmgpu/equil.py; needs EQUIL and a water phase)
             (SATOPTS HYSTER in RUNSPEC switches the hysteresis on; EHYSTR item 2 = 0 and item 5 = KR -- Carlson, relative permeabilities
             only -- is the model the device implements)
   REGIONS   PVTNUM SATNUM IMBNUM FIPNUM (fluid-in-place regions of computeFluidInPlace; 1-based in the deck and in `fipnum()`)
@@ -710,6 +712,27 @@ class Deck:
         if t.phases == "wo":        # no gas phase: the gas end points are not the deck's (no gas curve is ever scaled); SGL = 0 is what counts
             out["SGL"], out["SGCR"], out["SGU"], out["SOGCR"] = np.zeros(n), np.zeros(n), 1.0 - out["SWL"], out["SOWCR"].copy()
         return out
+
+    def swatinit(self):
+        """SWATINIT of the active cells (the imposed initial water saturation EQUIL honours by rescaling each cell's PCW); None without
+        the keyword.  Refused with a ValueError naming the keyword: an array that does not hold one value for every cell of the grid or
+        leaves an active cell defaulted, a value outside [0, 1], a deck without EQUIL or without a water phase."""
+        if not self.has("SWATINIT"):
+            return None
+        named = [k for k in ("OIL", "WATER", "GAS") if self.has(k)]
+        if named and "WATER" not in named:
+            raise ValueError("SWATINIT in a deck without a water phase")
+        if not self.has("EQUIL"):
+            raise ValueError("SWATINIT needs EQUIL: it acts on the equilibration, a deck with an explicit initial state has no use for it")
+        nx, ny, nz = self.dims
+        if getattr(self, "active", None) is None:
+            self.grid()                               # (fixes the set of active cells)
+        v = self.array("SWATINIT", nx * ny * nz)[self.active]
+        if np.isnan(v).any():
+            raise ValueError("SWATINIT must be given for every active cell")
+        if (v < 0.0).any() or (v > 1.0).any():
+            raise ValueError("SWATINIT outside [0, 1]")
+        return v
 
     # ---------------------------------------------------------------- SOLUTION
     def initial_state(self, tables):

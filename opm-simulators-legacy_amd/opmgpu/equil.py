@@ -14,8 +14,13 @@ the deck holds EQUIL instead of explicit PRESSURE / SWAT / SGAS arrays (opm/auto
 This runs once per simulation on the host (sequential ODE integration, a few thousand scalar PVT evaluations per region); its product
 is the State the device model starts from.  The scalar root finder of the reference (opm-core RegulaFalsi, a dependency that is not in
 the tree; tolerance 1e-6, EquilibrationHelpers.hpp:646-652) is replaced by an Illinois-type regula falsi run over all cells of a region
-at once with the same stopping rule, so saturations agree with the reference's to that tolerance, not bit for bit.  SWATINIT is not
-supported (it rescales PCW per cell, EclMaterialLawManager::applySwatinit, outside the tree).
+at once with the same stopping rule, so saturations agree with the reference's to that tolerance, not bit for bit.
+
+SWATINIT (initStateEquil_impl.hpp:645-655, :678-688): an imposed water saturation per cell; instead of inverting pcow the cell's maximum
+oil-water capillary pressure (PCW) is rescaled so that the imposed saturation is in equilibrium (CapPress.apply_swatinit).  The reference
+leaves that to EclMaterialLawManager::applySwatinit, which is opm-material and outside the tree: the rule is OURS, stated in
+include/opmgpu.h (opmgpu_set_swatinit_scaling), and pinned by the known answers of DeckWithSwatinit (tests/test_equil_legacy.cpp:916-1060)
+and by nothing else.
 
 A deck without a gas phase (tables.phases == "wo") takes the branches the reference takes when its gas phase is not active
 (initStateEquil_impl.hpp:436-497, :623-741: `if (gas)`): no gas pressure integration, Sg = 0, Sw from the pcow inversion alone, p_g = p_o;
@@ -301,12 +306,14 @@ class CapPress:
         self.sat = sat
         self.tab_w, self.tab_g = {}, {}
         self.swl_t, self.swu_t, self.sgl_t, self.sgu_t = (np.zeros(self.n) for _ in range(4))
-        self.vw, self.vg = np.ones(self.n), np.ones(self.n)
+        self.vw, self.vg = np.ones(self.n), np.ones(self.n)           # vertical factors; vw is what apply_swatinit rescales
+        self.pcw_tab = np.zeros(self.n)                               # the table maximum of pcow (its first node)
         for r in np.unique(sat):
             a, b = t.swof_ptr[r], t.swof_ptr[r + 1]
             self.tab_w[r] = (t.swof_sw[a:b], t.swof_pcow[a:b])
             m = sat == r
             self.swl_t[m], self.swu_t[m] = t.swof_sw[a], t.swof_sw[b - 1]
+            self.pcw_tab[m] = t.swof_pcow[a]
             ev = grid.eps_v or {}
             if "PCW" in ev and t.swof_pcow[a] != 0.0:
                 self.vw[m] = ev["PCW"][cells][m] / t.swof_pcow[a]
@@ -338,6 +345,24 @@ class CapPress:
 
     def pcgo(self, sg, idx=None):
         return self._eval(self.tab_g, sg, self.sgl, self.sgu, self.sgl_t, self.sgu_t, self.vg, idx)
+
+    @property
+    def pcw(self):
+        """the cells' current maximum oil-water capillary pressure [Pa]"""
+        return self.vw * self.pcw_tab
+
+    def apply_swatinit(self, idx, pcow, sw):
+        """SWATINIT for the cells idx (None: all) with the target pcow = p_o - p_w and the imposed saturation sw: returns the saturation
+        the cells end at and rescales their water factor.  The rule (include/opmgpu.h): pcow < 0 -> Swu, nothing scaled; else
+        Sw = min(max(sw, Swl), Swu) and, where the curve is positive at Sw, PCW *= pcow / pcow(Sw)."""
+        idx = np.arange(self.n) if idx is None else np.asarray(idx)
+        pcow = np.broadcast_to(np.asarray(pcow, float), idx.shape)
+        s = np.minimum(np.maximum(np.broadcast_to(np.asarray(sw, float), idx.shape), self.swl[idx]), self.swu[idx])
+        keep = pcow < 0.0
+        pc_at = self.pcow(s, idx)
+        m = ~keep & (pc_at > 0.0)
+        self.vw[idx[m]] *= pcow[m] / pc_at[m]
+        return np.where(keep, self.swu[idx], s)
 
 
 def _root(f, a, b, fa, fb, max_iter, tol):
@@ -396,14 +421,21 @@ def sat_from_sum_of_pcs(cp, target, idx=None):
     return out
 
 
-def phase_saturations(z, reg, cp, press, gas_active=True):
-    """EQUIL::phaseSaturations (initStateEquil_impl.hpp:566-741); `press` = [pw, po, pg] is adjusted in place.  Returns [sw, so, sg]."""
+def phase_saturations(z, reg, cp, press, gas_active=True, swat_init=None):
+    """EQUIL::phaseSaturations (initStateEquil_impl.hpp:566-741); `press` = [pw, po, pg] is adjusted in place.  Returns [sw, so, sg].
+    swat_init (SWATINIT of the cells, or None): the imposed water saturation; cp's oil-water curve is rescaled in place (:645-655,
+    :678-688) and everything after that reads the scaled curve."""
     rec = reg.rec
     pw, po, pg = press
     eps = np.finfo(float).eps
     # water (:637-655)
     const_w = np.abs(cp.pcow(cp.swl) - cp.pcow(cp.swu)) < eps                       # isConstPc (:774-783)
-    sw = np.where(const_w, np.where(z < rec.zwoc, cp.swl, cp.swu), sat_from_pc(cp, 0, po - pw))
+    if swat_init is None:                                                            # invert pc to find sw
+        sw = np.where(const_w, np.where(z < rec.zwoc, cp.swl, cp.swu), sat_from_pc(cp, 0, po - pw))
+    else:                                                                            # scale pc to reflect the imposed sw
+        sw = np.where(z < rec.zwoc, cp.swl, cp.swu)                                  # (constant-pc cells keep satFromDepth)
+        k = np.flatnonzero(~const_w)
+        sw[k] = cp.apply_swatinit(k, (po - pw)[k], np.asarray(swat_init, float)[k])
     if not gas_active:                                                               # the `if (gas)` parts left out (:658-701, :715, :727-737)
         thr = 1.0e-6
         at_swu = sw > cp.swu - thr
@@ -418,6 +450,8 @@ def phase_saturations(z, reg, cp, press, gas_active=True):
     # overlapping transition zones (:672-701): water against gas, oil pressure from the gas pressure
     over = np.flatnonzero(sg + sw > 1.0)
     if over.size:
+        if swat_init is not None:                                                    # "re-scale Pc to reflect imposed sw for vanishing oil phase"
+            cp.apply_swatinit(over, (pg - pw)[over], sw[over])                       # (its saturation is overwritten, as in the reference)
         swo = sat_from_sum_of_pcs(cp, (pg - pw)[over], over)
         sw[over], sg[over] = swo, 1.0 - swo
         po[over] = pg[over] - cp.pcgo(sg[over], over)
@@ -449,19 +483,23 @@ def init_hydrocarbon_state(sat, has_disgas, has_vapoil):
     return hc
 
 
-def equilibrate(grid, tables, records, eqlnum=None, rsvd=None, rvvd=None, ztop=None, zbot=None, grav=None, nsteps=2000):
+def equilibrate(grid, tables, records, eqlnum=None, rsvd=None, rvvd=None, ztop=None, zbot=None, grav=None, nsteps=2000, swatinit=None):
     """InitialStateComputer (initStateEquil.hpp:233-443) + the copy into the reservoir state (FlowMain.hpp:652-659).
 
     records: EquilRecord per EQLNUM region; eqlnum: 0-based region of every cell (None: one region); rsvd / rvvd: per region a
     (depth, value) pair of arrays or None; ztop / zbot: depth of the cells' top and bottom faces (their extremes over a region are the
-    integration span; default: the cell-centre depths)."""
+    integration span; default: the cell-centre depths); swatinit: the imposed water saturation of every cell (SWATINIT) or None.
+    The returned State also carries phase_pressure [n][3], pcw (every cell's maximum oil-water capillary pressure [Pa], rescaled where
+    SWATINIT acted) and pcow (the cells' oil-water capillary pressure at their water saturation on that curve: what
+    FlowMain.hpp:683-690 hands to setSwatInitScaling)."""
     n = grid.nc
     grav = grid.gravity if grav is None else grav
     eqlnum = np.zeros(n, np.int64) if eqlnum is None else np.asarray(eqlnum)
     ztop = grid.z if ztop is None else ztop
     zbot = grid.z if zbot is None else zbot
     p = np.zeros(n); sat = np.zeros((n, 3)); rs = np.zeros(n); rv = np.zeros(n)
-    phase_p = np.zeros((n, 3))
+    phase_p = np.zeros((n, 3)); pcw = np.zeros(n); pcow = np.zeros(n)
+    swatinit = None if swatinit is None else np.asarray(swatinit, float)
     for r, rec in enumerate(records):
         cells = np.flatnonzero(eqlnum == r)
         if cells.size == 0:                                              # "Equilibration region has no active cells" (:403-408)
@@ -493,21 +531,20 @@ def equilibrate(grid, tables, records, eqlnum=None, rsvd=None, rvvd=None, ztop=N
         gas_active = getattr(tables, "phases", "wog") != "wo"
         press = phase_pressures(z, (float(ztop[cells].min()), float(zbot[cells].max())), reg, grav, nsteps, gas_active)
         cp = CapPress(tables, grid, cells)
-        s = phase_saturations(z, reg, cp, press, gas_active)
+        s = phase_saturations(z, reg, cp, press, gas_active, None if swatinit is None else swatinit[cells])
+        pcw[cells], pcow[cells] = cp.pcw, cp.pcow(s[0])
         p[cells] = press[1]
         phase_p[cells] = np.stack(press, 1)
         sat[cells] = np.stack(s, 1)
         rs[cells] = rs_fn(z, press[1], s[2])                             # computeRs (:754-770): oil pressure / gas saturation
         rv[cells] = rv_fn(z, press[2], s[1])                             #                     gas pressure / oil saturation
     st = State(p, sat, rs, rv, init_hydrocarbon_state(sat, tables.has_disgas, tables.has_vapoil))
-    st.phase_pressure = phase_p
+    st.phase_pressure, st.pcw, st.pcow = phase_p, pcw, pcow
     return st
 
 
 def from_deck(deck, grid, tables):
     """EQUIL / EQLNUM / RSVD / RVVD of a parsed deck (opmgpu/deck.py) -> State"""
-    if deck.has("SWATINIT"):
-        raise ValueError("SWATINIT is not supported")
     nx, ny, nz = deck.dims
     n = nx * ny * nz
     act = deck.active
@@ -532,4 +569,4 @@ def from_deck(deck, grid, tables):
     eql = None if not deck.has("EQLNUM") else deck.array("EQLNUM", n)[act].astype(np.int64) - 1
     _, _, dz = deck._cell_sizes()
     half = 0.5 * dz.ravel()[act]
-    return equilibrate(grid, tables, recs, eql, vd("RSVD"), vd("RVVD"), ztop=grid.z - half, zbot=grid.z + half)
+    return equilibrate(grid, tables, recs, eql, vd("RSVD"), vd("RVVD"), ztop=grid.z - half, zbot=grid.z + half, swatinit=deck.swatinit())

@@ -329,6 +329,36 @@ class GpuBlackoilModel(_CprDiagnostics):
         self._chk(self.lib.opmgpu_compute_max_dp(self.ctx, capi.iptr(eq), int(nregions), int(n_face_conn), capi.dptr(dp), capi.dptr(out)))
         return (out, dp) if conns else out
 
+    def setSwatInitScaling(self, sw, pcow):
+        """BlackoilPropsAdFromDeck::setSwatInitScaling (BlackoilPropsAdFromDeck.cpp:1009-1019): per cell the imposed water saturation and
+        the target pcow = p_o - p_w; every cell's maximum oil-water capillary pressure is rescaled by the rule stated in include/opmgpu.h.
+        Returns the saturation each cell ends at.  Lasts through later setWells / setDeviceWells calls; calling it twice compounds.  A
+        non-finite value or a saturation outside [0, 1] is a ValueError and changes nothing."""
+        sw, pcow = capi.f64(sw), capi.f64(pcow)
+        if sw.shape != (self.nc,) or pcow.shape != (self.nc,):
+            raise ValueError("setSwatInitScaling: one saturation and one capillary pressure per cell (%d cells)" % self.nc)
+        out = np.zeros(self.nc)
+        self._chk(self.lib.opmgpu_set_swatinit_scaling(self.ctx, capi.dptr(sw), capi.dptr(pcow), capi.dptr(out)))
+        return out
+
+    def getPcw(self):
+        """each cell's current maximum oil-water capillary pressure [Pa] (PCW, or the table maximum of its saturation region)"""
+        out = np.zeros(self.nc)
+        self._chk(self.lib.opmgpu_get_pcw(self.ctx, capi.dptr(out)))
+        return out
+
+    def capPress(self, sat=None):
+        """BlackoilPropsAdFromDeck::capPress: (pcow = p_o - p_w, pcgo = p_g - p_o) of every cell at the saturations sat [nc][3] or, None, at
+        the resident state's, through the cell's end-point and vertical scaling"""
+        s = None
+        if sat is not None:
+            s = capi.f64(sat)
+            if s.size != 3 * self.nc:
+                raise ValueError("capPress: three saturations per cell (%d cells)" % self.nc)
+        out = np.zeros((2, self.nc))
+        self._chk(self.lib.opmgpu_cap_press(self.ctx, capi.dptr(s), capi.dptr(out)))
+        return out[0], out[1]
+
     def relativeChange(self):
         """BlackoilModelBase::relativeChange(saved, resident) (BlackoilModelBase_impl.hpp:1595-1631)."""
         v = C.c_double(0.0)

@@ -1,7 +1,8 @@
 """Report-step driver on top of the device Newton path: what SimulatorBase::run does around `flow_legacy`'s hot path
 (opm/autodiff/SimulatorBase_impl.hpp:90-324), reduced to what an external diff needs:
 
-    deck -> grid / tables / initial state -> [THPRES: computeMaxDp of the initial state, setThresholdPressures] -> for every report
+    deck -> grid / tables / initial state (EQUIL, with SWATINIT) -> [SWATINIT: setSwatInitScaling] -> [THPRES: computeMaxDp of the
+    initial state, setThresholdPressures] -> set the state (the order of FlowMain::setupState, FlowMain.hpp:636-692) -> for every report
     step of the SCHEDULE: wells of the step (WellsManager), well state carried over by name, updateSatOilMax + updateSatHyst (:190-192), AdaptiveTimeStepping.step with the NonlinearSolver (:236-253),
     restart + summary output (:300-306).
 
@@ -48,6 +49,13 @@ class Simulator:
         else:
             self.model = model_factory(self.grid, self.tables, self.params)
             set_state = lambda st: self.model.prepareStep(1.0, st)      # noqa: E731
+        if self.deck.swatinit() is not None:
+            # FlowMain.hpp:683-690: the capillary pressure of the scaled curve at the initial saturations goes to setSwatInitScaling.  Before
+            # computeMaxDp, which must see the scaled curve (the reference's two property objects share one material-law manager); from the
+            # DECK's equilibration also on a restarted run, like the thresholds.
+            if not hasattr(self.model, "setSwatInitScaling"):
+                raise ValueError("the deck has SWATINIT, but the model cannot take the scaling (setSwatInitScaling)")
+            self.model.setSwatInitScaling(deck_state0.sat[:, 0], deck_state0.pcow)
         self.threshold_pressures = None
         barriers = self.deck.thpres()
         if barriers is None:
