@@ -449,6 +449,14 @@ typedef struct opmgpu_vfp_table {
 
 /* Call BEFORE opmgpu_set_device_wells when a well has a THP control; n == 0 removes the tables. */
 int opmgpu_set_vfp_tables(opmgpu_ctx* ctx, int n, const opmgpu_vfp_table* tables);
+/* diagnostic: the device's VFP evaluators (csrc/vfp.hpp, what the well kernels call) at n points on table number `table` -- its index in the
+ * last opmgpu_set_vfp_tables call, so a producer and an injector table with the same id stay apart.  Per point i: rates q[3i..3i+2] = (aqua,
+ * liquid, vapour) with the well's signs (a producer's are negative), thp[i], alq[i] -> bhp_out[i] and dbhp_dq[3i..3i+2] = d bhp / d q
+ * (VFPProd/InjPropertiesLegacy::bhp); bhp_in[i] -> thp_out[i] (::thp, the inversion along the THP axis at the same rates and alq).  No
+ * hydrostatic correction.  It changes nothing a later solve sees; OPMGPU_EINVAL without tables or for an unknown table.
+ * tests/test_gpu_vfp.py compares it with the host restatement opmgpu/vfp.py. */
+int opmgpu_vfp_evaluate(opmgpu_ctx* ctx, int table, int n, const double* q, const double* thp, const double* alq, const double* bhp_in,
+                        double* bhp_out, double* dbhp_dq, double* thp_out);
 /* nw == 0 removes them.  Multi-GPU: a well lives on ONE rank, and EVERY rank of a run with wells makes this call (nw = 0 where it owns
  * none) -- opmgpu_well_convergence is collective, and the call tells the pressure stage's coarse space that the run has wells. */
 int opmgpu_set_device_wells(opmgpu_ctx* ctx, const opmgpu_wells* wells);

@@ -99,6 +99,7 @@ public:
     bool well_red_valid = false;
     bool has_device_wells() const;        // a device well model is attached (on this or, in a multi-rank run, on any rank)
     int set_vfp_tables(int n, const opmgpu_vfp_table* tabs);
+    int vfp_evaluate(int t, int n, const double* q, const double* thp, const double* alq, const double* bhp_in, double* bhp_out, double* dbhp_dq, double* thp_out);
     int well_controls_set(const int32_t* current, const double* thp);
     int well_controls_set_targets(const double* target, const double* distr);
     int well_controls_get(int32_t* current, double* thp, int32_t* pre_its, int32_t* pre_conv);

@@ -664,6 +664,15 @@ int opmgpu_set_vfp_tables(opmgpu_ctx* c, int n, const opmgpu_vfp_table* tables)
         return st == OPMGPU_OK ? st : fail(c, st, "invalid VFP table (missing axis / data, empty axis, or more than 64 THP values)");
     });
 }
+int opmgpu_vfp_evaluate(opmgpu_ctx* c, int table, int n, const double* q, const double* thp, const double* alq, const double* bhp_in,
+                        double* bhp_out, double* dbhp_dq, double* thp_out)
+{
+    if (!c || !c->model || n < 0 || (n > 0 && (!q || !thp || !alq || !bhp_in || !bhp_out || !dbhp_dq || !thp_out))) return OPMGPU_EINVAL;
+    return guarded(c, [&]() {
+        const int st = c->model->vfp_evaluate(table, n, q, thp, alq, bhp_in, bhp_out, dbhp_dq, thp_out);
+        return st == OPMGPU_OK ? st : fail(c, st, "no VFP tables set, or no table with that index");
+    });
+}
 int opmgpu_well_controls_set(opmgpu_ctx* c, const int32_t* current, const double* thp)
 {
     if (!c || !c->model) return OPMGPU_EINVAL;

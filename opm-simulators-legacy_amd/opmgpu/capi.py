@@ -203,6 +203,7 @@ SIGNATURES = {
     "opmgpu_well_state_get": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp]),
     "opmgpu_well_convergence": (C.c_int, [C.c_void_p, _dp, _dp]),
     "opmgpu_set_vfp_tables": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(VfpTable)]),
+    "opmgpu_vfp_evaluate": (C.c_int, [C.c_void_p, C.c_int, C.c_int, _dp, _dp, _dp, _dp, _dp, _dp, _dp]),
     "opmgpu_well_controls_set": (C.c_int, [C.c_void_p, _ip, _dp]),
     "opmgpu_well_controls_get": (C.c_int, [C.c_void_p, _ip, _dp, _ip, _ip]),
     "opmgpu_perf_pvt": (C.c_int, [C.c_void_p, _dp, _dp]),

@@ -461,6 +461,16 @@ class GpuBlackoilModel(_CprDiagnostics):
         self._chk(self.lib.opmgpu_spmv(self.ctx, capi.dptr(capi.f64(x3)), capi.dptr(y)))
         return y
 
+    def vfp_evaluate(self, table, q, thp, alq, bhp_in):
+        """diagnostic: the device's VFP evaluators on table number `table` of the tables set: (bhp [n], d bhp / d q [n, 3], thp of bhp_in [n])"""
+        q, thp, alq, bhp_in = (capi.f64(a) for a in (q, thp, alq, bhp_in))
+        n = thp.size
+        assert q.size == 3 * n and alq.size == n and bhp_in.size == n
+        bhp, dq, thp_out = np.zeros(n), np.zeros((n, 3)), np.zeros(n)
+        self._status(self.lib.opmgpu_vfp_evaluate(self.ctx, int(table), n, capi.dptr(q), capi.dptr(thp), capi.dptr(alq), capi.dptr(bhp_in),
+                                                  capi.dptr(bhp), capi.dptr(dq), capi.dptr(thp_out)))
+        return bhp, dq, thp_out
+
     def perfProps(self, nperf):
         out = np.zeros((nperf, capi.PERF_K))
         self._chk(self.lib.opmgpu_perf_props(self.ctx, capi.dptr(out)))

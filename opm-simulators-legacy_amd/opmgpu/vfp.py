@@ -10,7 +10,8 @@ tests/test_vfpproperties_legacy.cpp:375-401, see tests/test_vfp.py).
 
 Conventions: producer rates are negative in OPM, the FLO axis of a table is positive (the lookup negates flo for producers);
 the interpolant is multilinear on the table cell found per axis, with LINEAR EXTRAPOLATION outside the axes.
-The device evaluates the same tables in csrc/wells.hip (`opmgpu_set_vfp_tables`).
+The device evaluates the same tables in csrc/vfp.hpp (`opmgpu_set_vfp_tables`; compared with this file by tests/test_vfp_twin.py
+and tests/test_gpu_vfp.py).
 """
 import numpy as np
 

@@ -217,16 +217,22 @@ def test_device_well_controls_match_host(gpu_lib, oracle, case, cpr):
     gm.close()
 
 
-@pytest.mark.parametrize("case", ["presolve_switch", "prod_rate_limit", "thp"])
+@pytest.mark.parametrize("case", ["presolve_switch", "prod_rate_limit", "thp", "thp5"])
 def test_well_presolve_forms_agree(gpu_lib, monkeypatch, case):
     """solveWellEq on the device in its three forms -- one fused launch with a counter barrier per iteration (default), two launches per
     iteration (OPMGPU_WELL_PRESOLVE_FUSED=0) and the single-workgroup fallback that takes over when the fused kernel's barrier gives up
     (forced by OPMGPU_WELL_PRESOLVE_FUSED=2; ADVICE r2: a scheduling condition must not surface as a NumericalIssue) -- must give the same
-    pre-solve iteration count, the same control switches and the same well state, bit for bit."""
+    pre-solve iteration count, the same control switches and the same well state, bit for bit.
+    thp5: the producer on THP control through a 5-axis VFP table, ALQ between nodes (tests/vfp_cases.py, the deck of test_gpu_vfp.py)."""
     from test_wells_host import _limits_setup
-    kw = {"presolve_switch": dict(inj_bhp_limit_bar=255.0), "prod_rate_limit": dict(inj_bhp_limit_bar=600.0, prod_rate_limit=150.0),
-          "thp": dict(inj_bhp_limit_bar=600.0, thp=True)}[case]
-    grid, tab, st, wl, tables = _limits_setup(**kw)
+    if case == "thp5":
+        import vfp_cases
+        c = vfp_cases.lockstep_case("prod_thp5")
+        grid, tab, st, wl, tables = c["grid"], c["tab"], c["st"], c["wells"], c["tables"]
+    else:
+        kw = {"presolve_switch": dict(inj_bhp_limit_bar=255.0), "prod_rate_limit": dict(inj_bhp_limit_bar=600.0, prod_rate_limit=150.0),
+              "thp": dict(inj_bhp_limit_bar=600.0, thp=True)}[case]
+        grid, tab, st, wl, tables = _limits_setup(**kw)
     out = {}
     for mode in ("1", "0", "2"):
         monkeypatch.setenv("OPMGPU_WELL_PRESOLVE_FUSED", mode)
