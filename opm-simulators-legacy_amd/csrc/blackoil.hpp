@@ -13,6 +13,7 @@
 namespace opmgpu {
 
 struct HystArgs;
+struct CellPlanes;      // the resident state as a cell evaluator reads it (fluid_eval.hpp)
 // The device form of the fluid tables: the caller's struct and, next to it, the per-segment slopes of its 1-D tables (TabX), every array
 // in one blob of 8-byte words (BlackoilDevice::d_tab).  The pointer fields hold device pointers, or word offsets into the blob.
 struct TabX {
@@ -141,6 +142,9 @@ private:
     std::vector<double> h_surface_density;
     void rebuild_structure();
     void upload_thpres_plane();
+    // decomposed runs: sum (or max) of v[0..n) over the ranks in place, through the device; nothing without a communicator
+    void host_allreduce(double* v, int n, bool max);
+    void check_global_region_count(int n, const char* who);     // throws unless n is the same (the GLOBAL number) on every rank
 
     hipStream_t stream;
     LinSolver& ls;
@@ -159,6 +163,7 @@ private:
     DevArray<int32_t> d_imbnum;
     DevArray<double> d_stone_som;            // DevTables::stone_som
     HystArgs hyst_args() const;
+    CellPlanes cell_planes() const;
     void build_eps_planes(const std::vector<double>* ep8, bool have_points, bool imbibition, std::vector<double>& planes) const;
     std::vector<double> eps_region_table(bool have_points) const;
     void upload_drainage_eps();

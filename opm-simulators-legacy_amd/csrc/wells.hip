@@ -17,7 +17,7 @@
 //   solveWellEq (explicit well pre-solve, default on) BlackoilModelBase_impl.hpp:1018-1133          (k_well_presolve_fused / _serial / k_well_assemble<PRE> + k_well_presolve_step)
 //   THP control through VFP tables                   :655-700, :895-960; VFPProd/InjPropertiesLegacy.cpp   (vfp_* of vfp.hpp)
 //   PVT at the average well-block pressure           :218-296                                       (k_well_avg_press + k_perf_pvt)
-//   RESERVOIR_RATE conversion coefficients          RateConverterLegacy.hpp:495-548, :718-768        (k_voidage_coeff, region_state_sums in blackoil.hip)
+//   RESERVOIR_RATE conversion coefficients          RateConverterLegacy.hpp:495-548, :718-768        (k_voidage_coeff, region_state_sums in blackoil_output.hip)
 // Not restated: group controls / guide rates, efficiency factors.
 #include "blackoil.hpp"
 #include "vfp.hpp"
