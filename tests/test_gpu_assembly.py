@@ -16,7 +16,11 @@ P_RTOL, S_ATOL = 1e-6, 1e-6   # pressures 1e-6 relative, saturations 1
 
 def _cases():
     act = np.random.default_rng(5).random(7 * 6 * 5) > 0.3
+    # pore volumes that differ from cell to cell: the accumulation term and max |R| / pv read pv by the cell's INTERNAL row
+    g = decks.cartesian_grid(7, 6, 5, lognormal_sigma=0.7)
+    varied = decks.GridData(g.nc, g.conn_cells, g.trans, g.pv * np.random.default_rng(6).uniform(0.5, 2.0, g.nc), g.z, gravity=g.gravity, dims=g.dims)
     return [
+        ("pv", varied, None),
         ("cart", decks.cartesian_grid(7, 6, 5, lognormal_sigma=0.7), None),
         ("nnc", decks.cartesian_grid(6, 6, 4, nnc_fraction=0.06, lognormal_sigma=0.3), None),
         ("actnum+thpres", decks.cartesian_grid(7, 6, 5, actnum=act, thpres=0.05 * decks.BAR), None),

@@ -34,6 +34,18 @@ def test_cart100_full_size_properties(gpu_lib):
         assert abs(ra.sum()) <= 1e-9 * np.abs(ra).sum()
     conv = m.getConvergence()
     assert not conv and np.all(np.isfinite(m.CNV)) and np.all(m.MB < 1e-12)
+    # the same scalars against their float64 restatement at the derived bounds (tests/reductions_reference.py): 3907 partials of sum 1/b,
+    # two full grid-stride trips of the partial kernels, sixteen stride trips of the final ones
+    import reductions_reference as red
+    sd = m.simulatorData()
+    want = red.convergence_scalars(r, np.stack([1.0 / sd["1OVERBW"], 1.0 / sd["1OVERBO"], 1.0 / sd["1OVERBG"]]), grid.pv, dt, prm)
+    tol = red.tolerances(want)
+    assert want.status == capi.OK and conv == want.converged
+    assert np.all(np.abs(m.B_avg - want.B) <= tol.B_rtol * want.B), (m.B_avg, want.B)
+    assert np.array_equal(m.linf, want.linf)
+    assert np.all(np.abs(m.CNV - m.B_avg * dt * want.maxRpv) <= tol.CNV_rtol * m.CNV), (m.CNV, m.B_avg * dt * want.maxRpv)
+    assert np.all(np.abs(m.MB - want.MB) <= tol.MB_atol), (m.MB, want.MB, tol.MB_atol)
+    assert np.array_equal(m.averageB(), m.B_avg)
     # solve, then verify the TRUE residual of the returned increment with an independent SpMV on the same matrix
     rowptr, col, val = m.jacobian()
     assert col.size == 6940000
