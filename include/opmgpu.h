@@ -549,6 +549,23 @@ int opmgpu_get_simulator_data(opmgpu_ctx* ctx, double* out /* [OPMGPU_SIMDATA_K 
  * opmgpu_last_error(ctx), nothing changed.  Decomposed runs: the rank's local connections, no communication. */
 int opmgpu_set_threshold_pressures(opmgpu_ctx* ctx, const double* thpres /* [nconn] or NULL */);
 
+/* PVCDO: the dead oil of constant compressibility and viscosibility.  The reference takes the keyword through opm-material's
+ * ConstantCompressibilityOilPvt (FluidSystem::initFromDeck, BlackoilPropsAdFromDeck.cpp:164), which is outside its tree, so THE RULE
+ * BELOW IS OURS and is pinned against opm-material by nothing.  It is the arithmetic of PVTW (ConstantCompressibilityWaterPvt) with oil's
+ * row at the oil pressure.  Per PVT region one row (p_ref [Pa], B_ref, C_o [1/Pa], mu_ref [Pa s], C_v [1/Pa]):
+ *   X = C_o (p - p_ref)            1 / B_o        = (1 + X (1 + X / 2)) / B_ref
+ *   Y = (C_o - C_v) (p - p_ref)    1 / (B_o mu_o) = (1 + Y (1 + Y / 2)) / (B_ref mu_ref)
+ * with analytic derivatives with respect to p and no dependence on Sw, rs or rv.  The oil is dead: RSSAT and PBUB of the output record
+ * are 0.  The tables a context is created with cannot express this (they are piecewise linear in 1 / B and 1 / (B mu)); the context is
+ * created with any valid dead-oil table in their place, and from this call on every evaluator of the oil -- the assembly, the perforation
+ * properties and PVT, the voidage coefficients, the fluid in place, the output record, computeMaxDp -- takes the form above instead of
+ * that table.  NULL goes back to the tabulated oil.  To be called before an assembly; it lasts through opmgpu_set_wells /
+ * opmgpu_set_device_wells, opmgpu_save_state / opmgpu_restore_state and a change of the solve's precision, and a context re-planned
+ * after the call assembles bit for bit what one re-planned before it does.  has_vapoil (wet gas over dead oil) is allowed.
+ * OPMGPU_EINVAL with text in opmgpu_last_error(ctx), nothing changed: a context with has_disgas != 0, a non-finite entry, B_ref <= 0 or
+ * mu_ref <= 0.  Decomposed runs: every rank sets its own copy; no communication. */
+int opmgpu_set_pvcdo(opmgpu_ctx* ctx, const double* pvcdo /* [n_pvt_regions][5], SI; NULL = back to the tabulated oil */);
+
 /* computeMaxDp (opm/simulators/thresholdPressures.hpp:46-298; called at FlowMain.hpp:675-680) for the RESIDENT state: the largest
  * phase-potential difference across every pair of equilibration regions, which a defaulted THPRES item takes as its value
  * (thresholdPressures / thresholdPressuresNNC, ibid. :320-369, :383-417).

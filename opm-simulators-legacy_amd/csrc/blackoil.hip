@@ -51,7 +51,7 @@ __global__ __launch_bounds__(kBlock) void k_cell_values(int nb, int nbp, DevTabl
         if (H.on) eps_load(hy.ieps, hy.iureg, nbp, row, H.ireg, EI);
         eval_cell<false, KM>(D, E, (D.t.vap1 > 0.0 || D.t.vap2 > 0.0) ? somax[row] : 0.0, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], row, q, H, &EI);
         // (no gas phase: the five water / oil planes only -- nobody reads the other five --, and 1 / b_g = 1 per cell)
-        constexpr int NP = KM == KM_OW ? 2 : 3;
+        constexpr int NP = km_model(KM) == KM_OW ? 2 : 3;
         vals[long(VP_PW) * nbp + row] = q.pw.v; if constexpr (NP == 3) vals[long(VP_PG) * nbp + row] = q.pg.v;
         const bool owned = !mask || mask[row];
 #pragma unroll
@@ -122,7 +122,7 @@ __global__ __launch_bounds__(kBlock, asm_rows_waves(LDS, DUAL, KM)) void k_assem
     // NP == 2, a deck without a gas phase (KM_OW): only water and oil flow.  Neither the own nor the neighbour's p_g, gas density, gas
     // b * mobility, rs and rv planes are loaded (5 of the 10 dependent loads per connection), the gas equation is the identity row and
     // the third column of every block is zero (see the end of the loop and of the kernel)
-    constexpr int NP = KM == KM_OW ? 2 : 3;
+    constexpr int NP = km_model(KM) == KM_OW ? 2 : 3;
     const double scale[3] = { s0, s1, s2 };
     double op[3], orho[3], oU[3];                          // own values
     double dP[3][3], dRho[3][3], dU[3][3];                 // own derivatives d/d(P, Sw, Xvar) of phase pressure, density, b * mobility
@@ -787,8 +787,11 @@ void BlackoilDevice::get_state(double* p, double* sat, double* rs, double* rv, i
 template <class F> static auto kernel_by_shape(bool lds, int km, F&& pick)
 {
     auto by_model = [&](auto L) {
-        return km == KM_OW ? pick(L, std::integral_constant<int, KM_OW>{})
-             : km == KM_STONE ? pick(L, std::integral_constant<int, KM_STONE>{}) : pick(L, std::integral_constant<int, KM_DEFAULT>{});
+        auto by_oil = [&](auto K) {       // the tabulated oil, or the analytic one of opmgpu_set_pvcdo
+            return km_pvcdo(km) ? pick(L, std::integral_constant<int, decltype(K)::value | KM_PVCDO>{}) : pick(L, K);
+        };
+        return km_model(km) == KM_OW ? by_oil(std::integral_constant<int, KM_OW>{})
+             : km_model(km) == KM_STONE ? by_oil(std::integral_constant<int, KM_STONE>{}) : by_oil(std::integral_constant<int, KM_DEFAULT>{});
     };
     return lds ? by_model(std::true_type{}) : by_model(std::false_type{});
 }

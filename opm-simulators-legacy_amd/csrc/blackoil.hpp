@@ -20,6 +20,10 @@ struct TabX {
     const double *swof_dkrw, *swof_dkrow, *swof_dpcow, *sgof_dkrg, *sgof_dkrog, *sgof_dpcgo;
     const double *oil_drs, *oil_dinvb_sat, *oil_dinvbmu_sat, *oil_col_dinvb, *oil_col_dinvbmu;
     const double *gas_drvsat, *gas_dinvb_sat, *gas_dinvbmu_sat, *gas_col_dinvb, *gas_col_dinvbmu;
+    // PVCDO (opmgpu_set_pvcdo): [n_pvt_regions][5] rows p_ref, B_ref, C_o, mu_ref, C_v of the dead oil of constant compressibility, in the
+    // blob behind everything else.  Not set: NULL in the device-pointer form (the evaluators off the Newton path branch on it), word 0 in
+    // the offset form, where nobody reads it: the kernels that take that form are instantiated for the oil (KM_PVCDO).
+    const double* oil_pvcdo;
 };
 // stone_som: Stone I's residual oil saturation Som = min(SOWCR, SOGCR) of every cell (internal numbering), a device pointer in EVERY form of
 // the tables (it is no table: a per-cell plane that rides here so that each launch site of eval_cell sees it); null unless the model is
@@ -32,7 +36,11 @@ struct DevTables { opmgpu_tables t; TabX x; const double* stone_som; };
 enum { VP_PW = 0, VP_PG = 1, VP_RHO = 2 /* + phase */, VP_U = 5 /* + phase */, VP_RS = 8, VP_RV = 9, VP_COUNT = 10 };
 
 // the saturation-function model a cell-evaluating kernel is instantiated for (eval_cell), chosen on the host: BlackoilDevice::kmodel()
-enum { KM_DEFAULT = 0, KM_STONE = 1, KM_OW = 2 };
+// KM_PVCDO, or-ed to any of the three: the oil is the analytic dead oil of opmgpu_set_pvcdo and not the tabulated one (km_pvcdo; km_model
+// gives the saturation-function model alone).  A template parameter like the model and for the same reason.
+enum { KM_DEFAULT = 0, KM_STONE = 1, KM_OW = 2, KM_PVCDO = 4 };
+constexpr int km_model(int km) { return km & 3; }
+constexpr bool km_pvcdo(int km) { return (km & KM_PVCDO) != 0; }
 
 constexpr int kRedPart = 32;        // d_red: [0, 32) results, per-workgroup partials behind them
 
@@ -45,6 +53,7 @@ public:
     void set_state(const double* p, const double* sat, const double* rs, const double* rv, const int8_t* hc);
     void get_state(double* p, double* sat, double* rs, double* rv, int8_t* hc);
     void fluid_in_place(const int32_t* fipnum, int dims, double* fip_cells, double* values);      // computeFluidInPlace (:2263-2445)
+    void set_pvcdo(const double* pvcdo);                                                          // the analytic dead oil (PVCDO) per PVT region; nullptr = the tabulated oil
     void set_threshold_pressures(const double* thpres);                                            // setThresholdPressures (:421-443); nullptr = none
     void compute_max_dp(const int32_t* eqlnum, int nregions, int n_face_conn, double* dp_conn, double* max_dp);      // computeMaxDp (opm/simulators/thresholdPressures.hpp:46-298)
     void set_swatinit_scaling(const double* sw, const double* pcow, double* sw_out);              // setSwatInitScaling (BlackoilPropsAdFromDeck.cpp:1009-1019)
@@ -119,6 +128,7 @@ public:
 
 private:
     void upload_tables(const opmgpu_tables* t);
+    void upload_blob(const std::vector<double>& blob);
     void perf_props_device();
     void wells_assemble(bool initial);
     // the part of wells_assemble() that reads only the state (perforation properties, updateWellControls): on Newton iterations after the
@@ -174,10 +184,11 @@ private:
     DevTables dto_;                          // pointer fields = WORD OFFSETS into the blob: for the kernels that may stage it in LDS (resolve_tables)
     DevTables dtp_;                          // pointer fields = device pointers into the blob: for every other kernel
     DevArray<double> d_tab;                  // all table arrays in one blob of 8-byte words (staged in LDS by the property kernels)
+    std::vector<double> h_tab;               // the blob as upload_tables formed it (without PVCDO rows): what set_pvcdo appends to
     int tab_words = 0;
     static constexpr int kTabLdsMaxBytes = 24 * 1024;     // 6 workgroups x 24 KiB fit the 160 KiB LDS of a CU: no occupancy lost
     // chooses the kernels' KM instantiations (eval_cell)
-    int kmodel() const { return oil_water() ? KM_OW : (dto_.t.threephase_model != OPMGPU_KRO_DEFAULT ? KM_STONE : KM_DEFAULT); }
+    int kmodel() const { return (oil_water() ? KM_OW : (dto_.t.threephase_model != OPMGPU_KRO_DEFAULT ? KM_STONE : KM_DEFAULT)) | (dtp_.x.oil_pvcdo ? KM_PVCDO : 0); }
     bool oil_water() const { return dto_.t.active_phases == OPMGPU_PHASES_OIL_WATER; }
     int tab_lds_words() const { return tab_words * 8 <= kTabLdsMaxBytes ? tab_words : 0; }
     size_t tab_lds_bytes() const { return size_t(tab_lds_words()) * 8; }

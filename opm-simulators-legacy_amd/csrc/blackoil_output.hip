@@ -74,7 +74,7 @@ __device__ void max_dp_cell(const DevTables& D, int row, const CellPlanes& C, do
     const double p = C.p[row];
     EpsD E;
     eps_load(C.eps, C.eps_u0, C.nbp, row, sreg, E);
-    s[0] = C.sw[row]; s[1] = C.so[row]; s[2] = KM == KM_OW ? 0.0 : C.sg[row];
+    s[0] = C.sw[row]; s[1] = C.so[row]; s[2] = km_model(KM) == KM_OW ? 0.0 : C.sg[row];
     double f, df;
     const int wa = T.swof_ptr[sreg], nw = T.swof_ptr[sreg + 1] - wa;
     sat_curve_s<false>(T.swof_sw + wa, T.swof_pcow + wa, X.swof_dpcow + wa, nw, s[0], E, EC_PCOW, f, df);
@@ -82,8 +82,9 @@ __device__ void max_dp_cell(const DevTables& D, int row, const CellPlanes& C, do
     const double* rhos = T.surface_density + 3 * preg;
     rho[0] = rhos[0] * water_invb_value(T.pvtw + 5 * preg, pp[0]);
     const int oa = T.oil_node_ptr[preg], on = T.oil_node_ptr[preg + 1] - oa;
-    if constexpr (KM == KM_OW) {
-        lin_at(T.oil_psat + oa, T.oil_invb_sat + oa, X.oil_dinvb_sat + oa, pvt_seg(T.oil_psat + oa, on, p), p, f, df);
+    if constexpr (km_model(KM) == KM_OW) {
+        if (X.oil_pvcdo) f = oil_pvcdo_invb_value(X.oil_pvcdo + 5 * preg, p);
+        else lin_at(T.oil_psat + oa, T.oil_invb_sat + oa, X.oil_dinvb_sat + oa, pvt_seg(T.oil_psat + oa, on, p), p, f, df);
         rho[1] = rhos[1] * f; rho[2] = 0.0;
     } else {
         const int ga = T.sgof_ptr[sreg], ng = T.sgof_ptr[sreg + 1] - ga;
@@ -91,7 +92,8 @@ __device__ void max_dp_cell(const DevTables& D, int row, const CellPlanes& C, do
         pp[2] = p + f;
         const double rs = C.rs[row], rv = C.rv[row];
         double b;
-        if (rs >= rs_sat_d(D, preg, p)) lin_at(T.oil_psat + oa, T.oil_invb_sat + oa, X.oil_dinvb_sat + oa, pvt_seg(T.oil_psat + oa, on, p), p, b, df);
+        if (X.oil_pvcdo) b = oil_pvcdo_invb_value(X.oil_pvcdo + 5 * preg, p);
+        else if (rs >= rs_sat_d(D, preg, p)) lin_at(T.oil_psat + oa, T.oil_invb_sat + oa, X.oil_dinvb_sat + oa, pvt_seg(T.oil_psat + oa, on, p), p, b, df);
         else b = pvt2_value(T.oil_rs + oa, on, T.oil_col_ptr + oa, T.oil_col_p, T.oil_col_invb, X.oil_col_dinvb, rs, p);
         rho[1] = rhos[1] * b + rhos[2] * rs * b;
         const int gna = T.gas_node_ptr[preg], gn = T.gas_node_ptr[preg + 1] - gna;
@@ -122,7 +124,7 @@ __global__ __launch_bounds__(kBlock) void k_max_dp(int nconn, int nface, DevTabl
         max_dp_cell<KM>(T, c1, C, p1, r1, s1);
         max_dp_cell<KM>(T, c2, C, p2, r2, s2);
         const double dz = zc[c1] - zc[c2];
-        constexpr int np = KM == KM_OW ? 2 : 3;
+        constexpr int np = km_model(KM) == KM_OW ? 2 : 3;
 #pragma unroll
         for (int ph = 0; ph < np; ++ph) {
             const double rho_avg = (r1[ph] + r2[ph]) / 2;

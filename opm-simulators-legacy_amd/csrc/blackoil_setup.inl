@@ -106,12 +106,9 @@ void BlackoilDevice::upload_tables(const opmgpu_tables* t)
     o.x.gas_drvsat = slopes(t->gas_pg, t->gas_rvsat, t->gas_node_ptr, np); o.x.gas_dinvb_sat = slopes(t->gas_pg, t->gas_invb_sat, t->gas_node_ptr, np);
     o.x.gas_dinvbmu_sat = slopes(t->gas_pg, t->gas_invbmu_sat, t->gas_node_ptr, np);
     o.x.gas_col_dinvb = slopes(t->gas_col_rv, t->gas_col_invb, t->gas_col_ptr, ngn); o.x.gas_col_dinvbmu = slopes(t->gas_col_rv, t->gas_col_invbmu, t->gas_col_ptr, ngn);
-    d_tab.upload(blob, stream);
-    tab_words = int(blob.size());
-    // the device-pointer form for the kernels off the Newton path, which read the blob where it lies
-    dtp_ = dto_;
-    auto rb = [&](auto*& p) { rebase(p, d_tab.p); };
-    for_each_table(dtp_, rb, rb);
+    o.x.oil_pvcdo = nullptr;
+    h_tab = blob;
+    upload_blob(blob);
     // unscaled end points of every saturation region (what opm-material's EclEpsScalingPointsInfo::extractUnscaled reads off the
     // tables): Swl Swcr Swu Sowcr Sgl Sgcr Sgu Sogcr
     h_unscaled.assign(8 * size_t(ns), 0.0);
@@ -134,6 +131,42 @@ void BlackoilDevice::upload_tables(const opmgpu_tables* t)
         m[3] = t->sgof_krg[b + ng - 1]; m[4] = t->sgof_krog[b]; m[5] = t->sgof_pcgo[b + ng - 1];
     }
     OPMGPU_HIP(hipStreamSynchronize(stream));
+}
+
+// the blob onto the device and, from the offset form dto_, the device-pointer form for the kernels off the Newton path, which read the
+// blob where it lies
+void BlackoilDevice::upload_blob(const std::vector<double>& blob)
+{
+    d_tab.upload(blob, stream);
+    tab_words = int(blob.size());
+    dtp_ = dto_;
+    auto rb = [&](auto*& p) { rebase(p, d_tab.p); };
+    for_each_table(dtp_, rb, rb);
+    if (!dto_.x.oil_pvcdo) dtp_.x.oil_pvcdo = nullptr;      // word 0 of the offset form = no PVCDO rows: NULL to the kernels that branch on it
+    OPMGPU_HIP(hipStreamSynchronize(stream));
+}
+
+// The dead oil of constant compressibility (PVCDO; the rule: include/opmgpu.h at opmgpu_set_pvcdo): one row p_ref, B_ref, C_o, mu_ref, C_v
+// per PVT region, appended to the table blob (so a kernel that stages the blob in LDS stages the rows with it); nullptr takes them off
+// again.  The tables are no part of the plan or of the state: a re-plan, save / restore and a change of precision leave them alone.
+void BlackoilDevice::set_pvcdo(const double* pvcdo)
+{
+    const int np = dto_.t.n_pvt_regions;
+    std::vector<double> blob = h_tab;
+    if (pvcdo) {
+        if (dto_.t.has_disgas) throw HipError(OPMGPU_EINVAL, "setPvcdo: the context has dissolved gas (has_disgas); the PVCDO oil is dead");
+        for (int r = 0; r < np; ++r) {
+            const double* o = pvcdo + 5 * size_t(r);
+            for (int k = 0; k < 5; ++k)
+                if (!std::isfinite(o[k])) throw HipError(OPMGPU_EINVAL, "setPvcdo: entry " + std::to_string(k) + " of PVT region " + std::to_string(r) + " is not finite");
+            if (!(o[1] > 0.0)) throw HipError(OPMGPU_EINVAL, "setPvcdo: B_ref of PVT region " + std::to_string(r) + " is not positive");
+            if (!(o[3] > 0.0)) throw HipError(OPMGPU_EINVAL, "setPvcdo: the reference viscosity of PVT region " + std::to_string(r) + " is not positive");
+        }
+        dto_.x.oil_pvcdo = reinterpret_cast<const double*>(blob.size());       // a word offset, never 0: the blob begins with the densities
+        blob.insert(blob.end(), pvcdo, pvcdo + 5 * size_t(np));
+    } else dto_.x.oil_pvcdo = nullptr;
+    OPMGPU_HIP(hipStreamSynchronize(stream));        // no kernel in flight reads the blob that upload may replace
+    upload_blob(blob);
 }
 
 // pattern = stencil U well cliques -> solver plan -> internal numbering of every per-cell array

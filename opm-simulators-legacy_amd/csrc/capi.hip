@@ -847,6 +847,11 @@ int opmgpu_set_threshold_pressures(opmgpu_ctx* c, const double* thpres)
     if (!c || !c->model) return OPMGPU_EINVAL;
     return guarded(c, [&]() { c->model->set_threshold_pressures(thpres); return int(OPMGPU_OK); });
 }
+int opmgpu_set_pvcdo(opmgpu_ctx* c, const double* pvcdo)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { c->model->set_pvcdo(pvcdo); return int(OPMGPU_OK); });
+}
 int opmgpu_compute_max_dp(opmgpu_ctx* c, const int32_t* eqlnum, int nregions, int n_face_conn, double* dp_conn, double* max_dp)
 {
     if (!c || !c->model) return OPMGPU_EINVAL;

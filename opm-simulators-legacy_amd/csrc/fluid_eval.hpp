@@ -11,7 +11,8 @@
 namespace opmgpu {
 
 // the instantiation of a cell-evaluating kernel template <int KM> for this deck's model (inside a BlackoilDevice method)
-#define OPMGPU_BY_MODEL(kernel) (kmodel() == KM_OW ? kernel<KM_OW> : (kmodel() == KM_STONE ? kernel<KM_STONE> : kernel<KM_DEFAULT>))
+#define OPMGPU_BY_MODEL_(kernel, oil) (km_model(kmodel()) == KM_OW ? kernel<KM_OW | oil> : (km_model(kmodel()) == KM_STONE ? kernel<KM_STONE | oil> : kernel<KM_DEFAULT | oil>))
+#define OPMGPU_BY_MODEL(kernel) (km_pvcdo(kmodel()) ? OPMGPU_BY_MODEL_(kernel, KM_PVCDO) : OPMGPU_BY_MODEL_(kernel, 0))
 
 struct V4 { double v, p, w, x; };      // value, d/dP, d/dSw, d/dXvar
 
@@ -143,6 +144,7 @@ __host__ __device__ __forceinline__ void for_each_table(DevTables& D, FD&& fd, F
     fd(X.swof_dkrw); fd(X.swof_dkrow); fd(X.swof_dpcow); fd(X.sgof_dkrg); fd(X.sgof_dkrog); fd(X.sgof_dpcgo);
     fd(X.oil_drs); fd(X.oil_dinvb_sat); fd(X.oil_dinvbmu_sat); fd(X.oil_col_dinvb); fd(X.oil_col_dinvbmu);
     fd(X.gas_drvsat); fd(X.gas_dinvb_sat); fd(X.gas_dinvbmu_sat); fd(X.gas_col_dinvb); fd(X.gas_col_dinvbmu);
+    fd(X.oil_pvcdo);
 }
 // the table word at offset `off` of `base` (pointer fields of the offset form hold the offset itself)
 template <class P>
@@ -289,6 +291,14 @@ __device__ __forceinline__ double water_invb_value(const double* __restrict__ w,
     const double Xc = w[2] * (p - w[0]);
     return (1.0 + Xc * (1.0 + Xc / 2.0)) / w[1];
 }
+// 1 / B_o at pressure p of the dead oil of constant compressibility (PVCDO; o = the region's row p_ref, B_ref, C_o, mu_ref, C_v; the rule is
+// ours and stated in include/opmgpu.h at opmgpu_set_pvcdo), value only.  It DIVIDES by o[1], as water_invb_value does; the Newton
+// evaluators (oil_pvcdo_pair) multiply by the reciprocal.
+__device__ __forceinline__ double oil_pvcdo_invb_value(const double* __restrict__ o, double p)
+{
+    const double Xc = o[2] * (p - o[0]);
+    return (1.0 + Xc * (1.0 + Xc / 2.0)) / o[1];
+}
 // b_w, b_o, b_g of a PVT region at (p, rs, rv), all phases at the SAME pressure; sat_o / sat_g: oil / gas from its saturated curve
 // (ConstantCompressibilityWaterPvt, LiveOilPvt, WetGasPvt: inverseFormationVolumeFactor / saturatedInverseFormationVolumeFactor)
 __device__ __forceinline__ void b_values(const DevTables& D, int preg, double p, double rs, double rv, bool sat_o, bool sat_g, double& bw, double& bo, double& bg)
@@ -297,7 +307,8 @@ __device__ __forceinline__ void b_values(const DevTables& D, int preg, double p,
     bw = water_invb_value(T.pvtw + 5 * preg, p);
     double df;
     const int oa = T.oil_node_ptr[preg], on = T.oil_node_ptr[preg + 1] - oa;
-    if (sat_o) lin_at(T.oil_psat + oa, T.oil_invb_sat + oa, X.oil_dinvb_sat + oa, pvt_seg(T.oil_psat + oa, on, p), p, bo, df);
+    if (X.oil_pvcdo) bo = oil_pvcdo_invb_value(X.oil_pvcdo + 5 * preg, p);
+    else if (sat_o) lin_at(T.oil_psat + oa, T.oil_invb_sat + oa, X.oil_dinvb_sat + oa, pvt_seg(T.oil_psat + oa, on, p), p, bo, df);
     else bo = pvt2_value(T.oil_rs + oa, on, T.oil_col_ptr + oa, T.oil_col_p, T.oil_col_invb, X.oil_col_dinvb, rs, p);
     if (T.active_phases == OPMGPU_PHASES_OIL_WATER) { bg = 1.0; return; }       // the inactive phase's b (no gas table is read)
     const int ga = T.gas_node_ptr[preg], gn = T.gas_node_ptr[preg + 1] - ga;
@@ -381,6 +392,19 @@ __device__ __forceinline__ void oil_sat_pair(const opmgpu_tables& T, const TabX&
     lin_at(T.oil_psat + oa, T.oil_invb_sat + oa, X.oil_dinvb_sat + oa, ip, p, ib, dibp);
     lin_at(T.oil_psat + oa, T.oil_invbmu_sat + oa, X.oil_dinvbmu_sat + oa, ip, p, ibm, dibmp);
 }
+// the same four numbers of the dead oil of constant compressibility (PVCDO, opmgpu_set_pvcdo; o = the region's row): water_pvt's
+// arithmetic with oil's row at the oil pressure, 1 / (b mu) taken directly instead of the viscosity
+__device__ __forceinline__ void oil_pvcdo_pair(const double* __restrict__ o, double p, double& ib, double& dibp, double& ibm, double& dibmp)
+{
+    const double io1 = 1.0 / o[1], iBM = 1.0 / (o[1] * o[3]);
+    const double Xc = o[2] * (p - o[0]);
+    ib = (1.0 + Xc * (1.0 + Xc / 2.0)) * io1;
+    dibp = o[2] * (1.0 + Xc) * io1;
+    const double c = o[2] - o[4];
+    const double Y = c * (p - o[0]);
+    ibm = (1.0 + Y * (1.0 + Y / 2.0)) * iBM;
+    dibmp = c * (1.0 + Y) * iBM;
+}
 
 struct CellEval {
     V4 pw, pg, rs, rv, sw, so, sg;
@@ -395,12 +419,14 @@ struct CellOutput { double mu[3], kr[3], rsSat, rvSat; };
 // KM: the saturation-function model of the deck -- KM_DEFAULT the default three-phase law, KM_STONE Stone I or II (T.threephase_model says
 // which), KM_OW a deck without a gas phase (T.active_phases == OPMGPU_PHASES_OIL_WATER: eval_cell_ow).  A template parameter and not a
 // branch on the fields, chosen on the host for every kernel that evaluates cells: with the branch k_assemble_rows' default instantiation went from 7 to 20 spilled VGPRs.
-template <bool OUTPUT> __device__ void eval_cell_ow(const DevTables& DT, const EpsD& E, int preg, int sreg, double p, double sw_, CellEval& q, CellOutput* out);
+// KM_PVCDO or-ed to it: the oil is the analytic dead oil (oil_pvcdo_pair) instead of the tabulated one -- a template parameter too: as a branch
+// on DT.x.oil_pvcdo it moved the spills and the scratch of ten k_assemble_rows shapes a deck without it runs.
+template <bool OUTPUT, bool PVCDO> __device__ void eval_cell_ow(const DevTables& DT, const EpsD& E, int preg, int sreg, double p, double sw_, CellEval& q, CellOutput* out);
 template <bool OUTPUT = false, int KM = KM_DEFAULT>
 __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int preg, int sreg, double p, double sw_, double sg_, double rs_, double rv_, int hc,
                           int row, CellEval& q, const HystD& H = HystD{ false, 0, 2.0, 2.0, 0.0, 0.0 }, const EpsD* EI = nullptr, CellOutput* out = nullptr)
 {
-    if constexpr (KM == KM_OW) { eval_cell_ow<OUTPUT>(DT, E, preg, sreg, p, sw_, q, out); return; }
+    if constexpr (km_model(KM) == KM_OW) { eval_cell_ow<OUTPUT, km_pvcdo(KM)>(DT, E, preg, sreg, p, sw_, q, out); return; }
     const opmgpu_tables& T = DT.t; const TabX& X = DT.x;
     const bool isSg = hc == OPMGPU_HC_GAS_AND_OIL, isRs = hc == OPMGPU_HC_OIL_ONLY, isRv = hc == OPMGPU_HC_GAS_ONLY;
     const bool freeOil = isSg || isRs, freeGas = isSg || isRv;
@@ -446,7 +472,7 @@ __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int
         krg = vchain(f, df, sg);
     }
     V4 kro;
-    if constexpr (KM == KM_STONE) kro = stone_kro(DT, E, sreg, row, sw_, W, sg, krw, krg);      // (never with hysteresis: refused at creation)
+    if constexpr (km_model(KM) == KM_STONE) kro = stone_kro(DT, E, sreg, row, sw_, W, sg, krw, krg);      // (never with hysteresis: refused at creation)
     else {   // EclDefaultMaterial::krn
         // connate water of the three-phase law: the cell's scaled SWL; a set without horizontal scaling (s0 = u0 = 0, k = 1) has the table's
         const bool hscaled = E.on && (E.k[EC_PCOW] != 1.0 || E.s0[EC_PCOW] != 0.0 || E.u0[EC_PCOW] != 0.0);
@@ -501,7 +527,8 @@ __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int
     // oil PVT (LiveOilPvt; saturated branch when free gas is present or no DISGAS)
     {
         double ib, dibp, dibr = 0.0, ibm, dibmp, dibmr = 0.0;
-        if (freeGas || !T.has_disgas) oil_sat_pair(T, X, oa, ip, p, ib, dibp, ibm, dibmp);
+        if constexpr (km_pvcdo(KM)) oil_pvcdo_pair(X.oil_pvcdo + 5 * preg, p, ib, dibp, ibm, dibmp);
+        else if (freeGas || !T.has_disgas) oil_sat_pair(T, X, oa, ip, p, ib, dibp, ibm, dibmp);
         else {
             const int ir = pvt_seg(T.oil_rs + oa, on, q.rs.v);
             pvt2_pair(T.oil_rs + oa, ir, T.oil_col_ptr + oa, T.oil_col_p, T.oil_col_invb, X.oil_col_dinvb, T.oil_col_invbmu, X.oil_col_dinvbmu,
@@ -562,7 +589,7 @@ __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int
 // krw(Sw) and pcow(Sw) as with three phases, kro = krow(Sw) with the EC_KROW scaling -- no connate-water clamp, no blend --, the dead-oil
 // PVT, So = 1 - Sw.  No gas table is touched.  The inactive gas phase presents b_g = 1, mu_g = 1, mob_g = 0, rho_g = 0, p_g = p_o,
 // Sg = rs = rv = 0 with all derivatives 0, so that what still indexes three phases needs no guard; d/dXvar of everything is 0.
-template <bool OUTPUT>
+template <bool OUTPUT, bool PVCDO>
 __device__ void eval_cell_ow(const DevTables& DT, const EpsD& E, int preg, int sreg, double p, double sw_, CellEval& q, CellOutput* out)
 {
     const opmgpu_tables& T = DT.t; const TabX& X = DT.x;
@@ -596,7 +623,8 @@ __device__ void eval_cell_ow(const DevTables& DT, const EpsD& E, int preg, int s
     {
         const int oa = T.oil_node_ptr[preg], on = T.oil_node_ptr[preg + 1] - oa;
         double ib, dibp, ibm, dibmp;
-        oil_sat_pair(T, X, oa, pvt_seg(T.oil_psat + oa, on, p), p, ib, dibp, ibm, dibmp);
+        if constexpr (PVCDO) oil_pvcdo_pair(X.oil_pvcdo + 5 * preg, p, ib, dibp, ibm, dibmp);
+        else oil_sat_pair(T, X, oa, pvt_seg(T.oil_psat + oa, on, p), p, ib, dibp, ibm, dibmp);
         q.b[1] = mk(ib, dibp, 0, 0);
         const double r = 1.0 / ibm, m = ib * r;
         mu[1] = mk(m, (dibp - m * dibmp) * r, 0, 0);

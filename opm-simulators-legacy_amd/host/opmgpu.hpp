@@ -227,6 +227,14 @@ public:
             throw std::logic_error("Illegal size of threshold_pressures input, must be equal to number of faces + nncs");
         throw_on_status(ctx_, opmgpu_set_threshold_pressures(ctx_, threshold_pressures.empty() ? nullptr : threshold_pressures.data()));
     }
+    /// PVCDO, the dead oil of constant compressibility (opmgpu_set_pvcdo; the rule is stated in opmgpu.h): one row p_ref, B_ref, C_o,
+    /// mu_ref, C_v per PVT region, SI, flattened; an empty vector goes back to the tabulated oil.  std::logic_error for a context with
+    /// dissolved gas, a non-finite entry, B_ref <= 0 or mu_ref <= 0.  The caller gives one row for each PVT region of the tables.
+    void setPvcdo(const std::vector<double>& pvcdo)
+    {
+        if (pvcdo.size() % 5 != 0) throw std::logic_error("setPvcdo: five numbers per PVT region");
+        throw_on_status(ctx_, opmgpu_set_pvcdo(ctx_, pvcdo.empty() ? nullptr : pvcdo.data()));
+    }
     /// computeMaxDp (opm/simulators/thresholdPressures.hpp:46-298) for the resident state: max_dp[a][b] over the 1-based regions `eqlnum`,
     /// scanning the first n_face_conn connections (the grid faces); -1 = no face joins the pair.  dp_conn (optional): per connection.
     std::vector<std::vector<double>> computeMaxDp(const std::vector<int>& eqlnum, int nregions, int n_face_conn, std::vector<double>* dp_conn = nullptr)

@@ -217,6 +217,7 @@ SIGNATURES = {
     "opmgpu_compute_fluid_in_place": (C.c_int, [C.c_void_p, _ip, C.c_int, _dp, _dp]),
     "opmgpu_get_simulator_data": (C.c_int, [C.c_void_p, _dp]),
     "opmgpu_set_threshold_pressures": (C.c_int, [C.c_void_p, _dp]),
+    "opmgpu_set_pvcdo": (C.c_int, [C.c_void_p, _dp]),
     "opmgpu_compute_max_dp": (C.c_int, [C.c_void_p, _ip, C.c_int, C.c_int, _dp, _dp]),
     "opmgpu_set_swatinit_scaling": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
     "opmgpu_get_pcw": (C.c_int, [C.c_void_p, _dp]),

@@ -12,6 +12,9 @@ What `flow_legacy` gets from opm-parser + `DerivedGeology` (opm/autodiff/GeoProp
   GRID      DX DY DZ / DXV DYV DZV, TOPS (+BOX for the top layer) or DEPTHZ (flat) -- or COORD / ZCORN (corner-point, no faults) --, PORO PERMX PERMY PERMZ NTG ACTNUM MINPV, FAULTS + MULTFLT
             MULTX MULTY MULTZ MULTX- MULTY- MULTZ- MULTPV NNC
   PROPS     SWOF SGOF PVTO PVDO PVCDO PVTG PVDG PVTW DENSITY ROCK ROCKTAB VAPPARS SCALECRS (NO and YES) EHYSTR
+            PVCDO: one record per PVT region (TABDIMS; too few is a ValueError).  With Co = Cv = 0 in every record it is a constant
+            two-node dead-oil table; otherwise the tables carry the rows as `FluidTables.pvcdo` (SI) next to that table as a stand-in,
+            and the device evaluates the oil in closed form (opmgpu_set_pvcdo; the rule is stated in include/opmgpu.h).  Not with DISGAS.
             STONE1 STONE2 STONE (= STONE2) STONE1EX: the three-phase oil relative permeability model (none of them: the default model;
             two of them, or one together with SATOPTS HYSTER, is refused)
             SWL SWCR SWU SOWCR SGL SGCR SGU SOGCR  KRW KRO KRG PCW PCG  ISWL ISWCR ISWU ISOWCR ISGL ISGCR ISGU ISOGCR
@@ -168,6 +171,7 @@ class Deck:
         dens = [[r[1], r[0], r[2] if len(r) > 2 and r[2] is not None else 0.0] for r in self.records("DENSITY")[:ntpvt]]
         pvtw = [[r[0], r[1], r[2], r[3], r[4] if len(r) > 4 and r[4] is not None else 0.0] for r in self.records("PVTW")[:ntpvt]]
         disgas, vapoil = self.has("DISGAS"), self.has("VAPOIL")
+        pvcdo = None            # PVCDO rows (deck units) when any of them has a non-zero compressibility or viscosibility
         # oil
         if self.has("PVTO"):
             pvto = []
@@ -181,14 +185,23 @@ class Deck:
             pvto = [[(0.0, [tuple(rec[i:i + 3])]) for i in range(0, len(rec), 3)] for rec in self.records("PVDO")[:ntpvt]]
             disgas = False
         elif self.has("PVCDO"):
-            # constant compressibility dead oil: two nodes far apart reproduce it when Co = Cv = 0 (the reference's tests/fluid.data)
+            # constant compressibility dead oil, one record per PVT region.  Co = Cv = 0 everywhere (the reference's tests/fluid.data): two
+            # nodes far apart reproduce it, a plain table.  Otherwise the tables cannot express it: FluidTables(pvcdo=...) carries the rows
+            # to opmgpu_set_pvcdo and keeps the same two-node table as a stand-in
+            recs = self.records("PVCDO")
+            if len(recs) < ntpvt:
+                raise ValueError("PVCDO holds %d records, expected one per PVT region (%d)" % (len(recs), ntpvt))
             pvto = []
-            for r in self.records("PVCDO")[:ntpvt]:
+            for r in recs[:ntpvt]:
                 pref, bo, co, mu = r[0], r[1], r[2], r[3]
                 cv = r[4] if len(r) > 4 and r[4] is not None else 0.0
-                if co != 0.0 or cv != 0.0:
-                    raise ValueError("PVCDO with non-zero compressibility / viscosibility is not supported")
+                if pvcdo is None and (co != 0.0 or cv != 0.0):
+                    pvcdo = []
                 pvto.append([(0.0, [(pref, bo, mu)]), (0.0, [(pref + 800.0, bo, mu)])])
+            if pvcdo is not None:
+                if disgas:
+                    raise ValueError("PVCDO (a dead oil) in a deck with DISGAS")
+                pvcdo = [[r[0], r[1], r[2], r[3], r[4] if len(r) > 4 and r[4] is not None else 0.0] for r in recs[:ntpvt]]
             disgas = False
         else:
             raise ValueError("no oil PVT keyword (PVTO / PVDO / PVCDO)")
@@ -224,10 +237,12 @@ class Deck:
             r = self.records("VAPPARS")[0]
             vappars = (r[0], r[1])
         model, eta = self.threephase()
+        oil = {} if pvcdo is None else {"pvcdo": pvcdo}        # (a PVCDO deck with Co = Cv = 0 passes nothing: the tables it always made)
         if two_phase:
-            return FluidTables(density_wog=dens, pvtw=pvtw, pvto=pvto, pvtg=None, swof=swof, sgof=None, rock=rock, rocktab=rocktab, phases="wo")
+            return FluidTables(density_wog=dens, pvtw=pvtw, pvto=pvto, pvtg=None, swof=swof, sgof=None, rock=rock, rocktab=rocktab, phases="wo",
+                               **oil)
         return FluidTables(density_wog=dens, pvtw=pvtw, pvto=pvto, pvtg=pvtg, swof=swof, sgof=sgof, rock=rock, disgas=disgas, vapoil=vapoil,
-                           vappars=vappars, rocktab=rocktab, threephase_model=model, stone1_exponent=eta)
+                           vappars=vappars, rocktab=rocktab, threephase_model=model, stone1_exponent=eta, **oil)
 
     def threephase(self):
         """(opmgpu_tables.threephase_model, STONE1EX exponents or None): STONE1 -> Stone I with one exponent per saturation region (STONE1EX,

@@ -28,7 +28,7 @@ class FluidTables:
     """Flat table arrays matching `opmgpu_tables` (include/opmgpu.h)."""
 
     def __init__(self, density_wog, pvtw, pvto, pvtg, swof, sgof, rock, disgas=None, vapoil=None, vappars=(0.0, 0.0), rocktab=None,
-                 threephase_model=0, stone1_exponent=None, phases="wog"):
+                 threephase_model=0, stone1_exponent=None, phases="wog", pvcdo=None):
         """All inputs in deck units (METRIC): lists per region.
 
         pvto: per region, list of (rs, [(p, Bo, muo), ...]) saturated rows with undersaturated
@@ -40,10 +40,28 @@ class FluidTables:
         phases = "wog" (water, oil, gas) or "wo": a deck without a gas phase (opmgpu_tables.active_phases = OPMGPU_PHASES_OIL_WATER) --
         pvtg and sgof are None, pvto is a dead-oil table (PVDO / PVCDO rows), density_wog has two or three columns (a gas density is
         ignored), and there are no gas arrays at all: the struct's gas pointers are NULL.
+        pvcdo = PVCDO rows (p_ref [bar], B_ref, C_o [1/bar], mu_ref [cP], C_v [1/bar]), one per PVT region: the dead oil of constant
+        compressibility and viscosibility (the rule: include/opmgpu.h at opmgpu_set_pvcdo).  The tables cannot express it, so it is no
+        part of struct(): `self.pvcdo` holds the rows in SI for opmgpu_set_pvcdo (GpuBlackoilModel calls it right after creation), and
+        the tabulated oil is a stand-in, a constant two-node table at B_ref, mu_ref (pvto is ignored and may be None).  Not together
+        with disgas=True or with undersaturated pvto branches.
         """
         if phases not in ("wog", "wo"):
             raise ValueError("phases must be 'wog' or 'wo' (oil-gas, gas-water and single-phase decks are not supported): %r" % (phases,))
         self.phases = phases
+        self.pvcdo = None
+        if pvcdo is not None:
+            if disgas:
+                raise ValueError("pvcdo (PVCDO, a dead oil) together with disgas=True")
+            if pvto is not None and any(len(col) > 1 for rows in pvto for _, col in rows):
+                raise ValueError("pvcdo (PVCDO, a dead oil) together with undersaturated pvto branches")
+            o = capi.f64(pvcdo).reshape(-1, 5).copy()
+            if o.shape[0] != len(pvtw):
+                raise ValueError("pvcdo needs one PVCDO row per PVT region (%d), got %d" % (len(pvtw), o.shape[0]))
+            pvto = [[(0.0, [(r[0], r[1], r[3])]), (0.0, [(r[0] + 800.0, r[1], r[3])])] for r in o.tolist()]
+            o[:, 0] *= BAR; o[:, 2] /= BAR; o[:, 3] *= CP; o[:, 4] /= BAR
+            self.pvcdo = o
+            disgas = False
         self.active_phases = capi.PHASES_OIL_WATER if phases == "wo" else capi.PHASES_ALL
         self.n_pvt = len(pvtw)
         self.n_sat = len(swof)

@@ -65,6 +65,8 @@ class HostPvt:
         self.disgas, self.vapoil = bool(t.has_disgas), bool(t.has_vapoil)
         self.rho_w, self.rho_o, self.rho_g = (float(v) for v in t.surface_density[reg])
         self.pvtw = [float(v) for v in t.pvtw[reg]]
+        # PVCDO (FluidTables(pvcdo=...)): the region's row in SI; b_o is then the analytic dead oil, not the stand-in table
+        self.pvcdo = None if getattr(t, "pvcdo", None) is None else [float(v) for v in t.pvcdo[reg]]
         a, b = int(t.oil_node_ptr[reg]), int(t.oil_node_ptr[reg + 1])
         self.o_rs, self.o_psat, self.o_ib = list(t.oil_rs[a:b]), list(t.oil_psat[a:b]), list(t.oil_invb_sat[a:b])
         self.o_cols = [(list(t.oil_col_p[t.oil_col_ptr[k]:t.oil_col_ptr[k + 1]]), list(t.oil_col_invb[t.oil_col_ptr[k]:t.oil_col_ptr[k + 1]]))
@@ -92,6 +94,10 @@ class HostPvt:
         return _lin(self.g_pg, self.g_rv, p) if self.vapoil else 0.0
 
     def b_o(self, p, rs, saturated):
+        if self.pvcdo is not None:          # the rule of include/opmgpu.h at opmgpu_set_pvcdo
+            o = self.pvcdo
+            X = o[2] * (p - o[0])
+            return (1.0 + X * (1.0 + X / 2.0)) / o[1]
         if saturated or not self.disgas:
             return _lin(self.o_psat, self.o_ib, p)
         i = _seg(self.o_rs, rs)

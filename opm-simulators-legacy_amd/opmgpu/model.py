@@ -206,6 +206,8 @@ class GpuBlackoilModel(_CprDiagnostics):
         self.dt = None
         self.use_update_stabilization = True        # BlackoilModelParameters.cpp:98
         self.residual_norms_history, self.current_relaxation = [], 1.0
+        if getattr(tables, "pvcdo", None) is not None:      # the analytic dead oil the tables cannot express (FluidTables(pvcdo=...))
+            self.setPvcdo(tables.pvcdo)
         if wells is not None:
             self.setWells(*wells)
 
@@ -315,6 +317,16 @@ class GpuBlackoilModel(_CprDiagnostics):
         if th is not None and th.shape != (self.grid.nconn,):
             raise ValueError("setThresholdPressures: %d values for %d connections" % (th.size, self.grid.nconn))
         self._chk(self.lib.opmgpu_set_threshold_pressures(self.ctx, capi.dptr(th)))
+
+    def setPvcdo(self, pvcdo):
+        """PVCDO, the dead oil of constant compressibility and viscosibility (opmgpu_set_pvcdo; the rule is stated in include/opmgpu.h):
+        one row (p_ref, B_ref, C_o, mu_ref, C_v) per PVT region in SI, or None to go back to the tabulated oil.  From the call on every
+        evaluator of the oil takes the analytic form; it lasts through setWells / setDeviceWells, saved states and a change of
+        precision.  A context with dissolved gas, a non-finite entry, B_ref <= 0 or mu_ref <= 0 is a ValueError and changes nothing."""
+        o = None if pvcdo is None else capi.f64(pvcdo)
+        if o is not None and o.shape != (self.tables.n_pvt, 5):
+            raise ValueError("setPvcdo: PVCDO needs one row of five numbers per PVT region (%d regions)" % self.tables.n_pvt)
+        self._chk(self.lib.opmgpu_set_pvcdo(self.ctx, capi.dptr(o)))
 
     def computeMaxDp(self, eqlnum, nregions, n_face_conn, conns=False):
         """computeMaxDp (opm/simulators/thresholdPressures.hpp:46-298) for the resident state: max_dp[nregions][nregions], the largest

@@ -49,6 +49,12 @@ class Simulator:
         else:
             self.model = model_factory(self.grid, self.tables, self.params)
             set_state = lambda st: self.model.prepareStep(1.0, st)      # noqa: E731
+            if self.tables.pvcdo is not None and not isinstance(self.model, GpuBlackoilModel):
+                # the tables hold only a constant stand-in for this oil; a model that evaluates them (the CPU oracle behind the host well
+                # model) would compute another fluid
+                if not hasattr(self.model, "setPvcdo"):
+                    raise ValueError("the deck has PVCDO with a compressibility / viscosibility, but the model cannot take the analytic oil (setPvcdo)")
+                self.model.setPvcdo(self.tables.pvcdo)
         if self.deck.swatinit() is not None:
             # FlowMain.hpp:683-690: the capillary pressure of the scaled curve at the initial saturations goes to setSwatInitScaling.  Before
             # computeMaxDp, which must see the scaled curve (the reference's two property objects share one material-law manager); from the
