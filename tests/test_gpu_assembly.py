@@ -5,7 +5,7 @@ import pytest
 
 from opmgpu import capi, decks
 from opmgpu.model import GpuBlackoilModel, NumericalIssue, newton_step
-from util import rel_err
+from util import rel_err, slot_err
 
 pytestmark = pytest.mark.gpu
 
@@ -45,6 +45,7 @@ def test_assembly_parity(gpu_lib, oracle, ordering):
             gr, gc, gv = m.jacobian()
             assert np.array_equal(gr, rowptr) and np.array_equal(gc, col), name
             assert rel_err(gv, v0) < RTOL_JAC, (name, rel_err(gv, v0))
+            assert slot_err(gv, v0) < RTOL_JAC, (name, slot_err(gv, v0))
             assert rel_err(m.residual(), r0) < RTOL_JAC, name                 # initial: accum1 == accum0, flux part only
             # second assembly on a different state with the stored accum0 (Newton iteration > 0)
             st2 = decks.random_state(grid, tab, seed=seed + 10)
@@ -54,6 +55,7 @@ def test_assembly_parity(gpu_lib, oracle, ordering):
             r1, v1, _, binv1 = oracle.assemble(grid, tab, dt, st2, rowptr, col, scale=scale, accum0=acc0)
             _, _, gv1 = m.jacobian()
             assert rel_err(gv1, v1) < RTOL_JAC, (name, rel_err(gv1, v1))
+            assert slot_err(gv1, v1) < RTOL_JAC, (name, slot_err(gv1, v1))
             assert rel_err(m.residual(), r1) < RTOL_JAC, (name, rel_err(m.residual(), r1))
             # convergence scalars
             so, B, CNV, MB, linf, conv = oracle.convergence(grid, prm, dt, r1, binv1)
@@ -244,6 +246,7 @@ def test_dead_oil_dry_gas_tables(gpu_lib, oracle):
     rowptr, col = oracle.pattern(grid)
     r0, v0, _, _ = oracle.assemble(grid, tab, decks.DAY, st, rowptr, col, scale=tuple(prm.matbalscale))
     assert rel_err(m.jacobian()[2], v0) < RTOL_JAC and rel_err(m.residual(), r0) < RTOL_JAC
+    assert slot_err(m.jacobian()[2], v0) < RTOL_JAC, slot_err(m.jacobian()[2], v0)
     m.close()
 
 
@@ -268,6 +271,7 @@ def test_endscale_assembly_and_update_parity(gpu_lib, oracle):
         r_plain, v_plain, _, _ = oracle.assemble(base, tab, 2 * decks.DAY, st, rowptr, col, scale=scale)
         assert rel_err(v_plain, v0) > 1e-3
         assert rel_err(m.jacobian()[2], v0) < RTOL_JAC, rel_err(m.jacobian()[2], v0)
+        assert slot_err(m.jacobian()[2], v0) < RTOL_JAC, slot_err(m.jacobian()[2], v0)
         assert rel_err(m.residual(), r0) < RTOL_JAC
         dx = np.concatenate([rng.standard_normal(nc) * 30 * decks.BAR, rng.standard_normal(nc) * 0.25,
                              rng.standard_normal(nc) * np.where(st.hc == capi.HC_OIL_ONLY, 30.0, np.where(st.hc == capi.HC_GAS_ONLY, 1e-4, 0.25))])
@@ -406,6 +410,7 @@ def test_vappars_rocktab_parity(gpu_lib, oracle):
             oracle.set_sat_oil_max(so_max)
             assert rel_err(v_plain, v0) > 1e-3                        # the keywords matter for this state
             assert rel_err(m.jacobian()[2], v0) < RTOL_JAC, rel_err(m.jacobian()[2], v0)
+            assert slot_err(m.jacobian()[2], v0) < RTOL_JAC, slot_err(m.jacobian()[2], v0)
             assert rel_err(m.residual(), r0) < RTOL_JAC
             dx = np.concatenate([rng.standard_normal(nc) * 30 * decks.BAR, rng.standard_normal(nc) * 0.25,
                                  rng.standard_normal(nc) * np.where(st.hc == capi.HC_OIL_ONLY, 30.0, np.where(st.hc == capi.HC_GAS_ONLY, 1e-4, 0.25))])
@@ -517,6 +522,7 @@ def test_satfunc_options_parity(gpu_lib, oracle, case):
             m.assemble(True)
             r0, v0, _, _ = oracle.assemble(grid, tab, 2 * decks.DAY, st, rowptr, col, scale=scale)
             assert rel_err(m.jacobian()[2], v0) < RTOL_JAC, (case, seed, rel_err(m.jacobian()[2], v0))
+            assert slot_err(m.jacobian()[2], v0) < RTOL_JAC, (case, seed, slot_err(m.jacobian()[2], v0))
             assert rel_err(m.residual(), r0) < RTOL_JAC
             dx = np.concatenate([rng.standard_normal(nc) * 30 * decks.BAR, rng.standard_normal(nc) * 0.25,
                                  rng.standard_normal(nc) * np.where(st.hc == capi.HC_OIL_ONLY, 30.0, np.where(st.hc == capi.HC_GAS_ONLY, 1e-4, 0.25))])
@@ -571,6 +577,7 @@ def test_update_equations_scaling(gpu_lib, oracle, single):
             r, v, _, _ = oracle.assemble(grid, tab, dt, state, rowptr, col, scale=tuple(want), accum0=acc0)
         _, _, gv = m.jacobian()
         assert rel_err(gv, v) < (2e-6 if single else RTOL_JAC)
+        assert slot_err(gv, v) < (2e-6 if single else RTOL_JAC), slot_err(gv, v)
         assert rel_err(m.residual(), r) < RTOL_JAC             # the residual itself is unscaled
     # the solve uses the same factors for the right-hand side: its dx solves the oracle's scaled system
     m.getConvergence()
@@ -693,6 +700,7 @@ def test_table_set_too_large_for_lds(gpu_lib):
             m.close()
         (j1, r1, pvt1, c1, s1), (jR, rR, pvtR, cR, sR) = got
         assert rel_err(jR, j1) < RTOL_JAC and rel_err(rR, r1) < RTOL_JAC, seed
+        assert slot_err(jR, j1) < RTOL_JAC, (seed, slot_err(jR, j1))
         for k in range(5):
             assert rel_err(pvtR[:, k], pvt1[:, k]) < RTOL_JAC, (seed, k)
         assert rel_err(cR, c1) < RTOL_JAC, seed
