@@ -460,6 +460,20 @@ int opmgpu_vfp_evaluate(opmgpu_ctx* ctx, int table, int n, const double* q, cons
 /* nw == 0 removes them.  Multi-GPU: a well lives on ONE rank, and EVERY rank of a run with wells makes this call (nw = 0 where it owns
  * none) -- opmgpu_well_convergence is collective, and the call tells the pressure stage's coarse space that the run has wells. */
 int opmgpu_set_device_wells(opmgpu_ctx* ctx, const opmgpu_wells* wells);
+/* Well efficiency factors (WEFAC): factors[nw] in the order of opmgpu_set_device_wells, each in (0, 1]; NULL = all ones.  The reference
+ * builds one value per perforation from the well's factor (StandardWells_impl.hpp:1405-1434) and subtracts efficiency_factors * cq_s from
+ * the mass balance of the perforated cells (addWellContributionToMassBalanceEq, BlackoilModelBase_impl.hpp:953-975).  The rule: for every
+ * perforation j of well w, R_a[cell_j] -= e_w cq_s[a][j] with every derivative of that term -- the own-cell block -e_w d cq_s / d cell and
+ * the reservoir-row, well-column coupling e_w B_j.  The WELL equations do not see e_w: flux and control equation, D, C, D^-1, wellbore
+ * mixture, cross-flow rules, connection pressures, perfPhaseRates, wellRates, bhp, thp, the pre-solve and opmgpu_well_convergence are
+ * what they are without it.  With every factor 1 the assembly gives bit for bit what it gives without the call.
+ * Call AFTER opmgpu_set_device_wells; a later opmgpu_set_device_wells resets the factors to ones (the well list changed).  The factors are
+ * no part of the saved state: they last through opmgpu_save_state / opmgpu_restore_state, a change of the solve's precision and a
+ * re-plan.  Multi-GPU: rank-local (the factors of this rank's wells), no communication.
+ * OPMGPU_EINVAL with text in opmgpu_last_error(ctx): no device wells are set; a factor is not finite; a factor is outside (0, 1]. */
+int opmgpu_set_well_efficiency(opmgpu_ctx* ctx, const double* factors);
+/* the factors in force (factors[nw]); OPMGPU_EINVAL without device wells */
+int opmgpu_get_well_efficiency(opmgpu_ctx* ctx, double* factors);
 /* WellStateFullyImplicitBlackoil fields: bhp[nw], wellRates qs[nw*3]; perfPress perf_press[nperf] and perfPhaseRates
  * perf_rates[nperf*3] may be NULL (keep).  perf_press feeds the average well-block pressures of computeWellConnectionPressures. */
 int opmgpu_well_state_set(opmgpu_ctx* ctx, const double* bhp, const double* qs, const double* perf_press, const double* perf_rates);

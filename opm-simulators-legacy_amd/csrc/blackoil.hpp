@@ -96,6 +96,8 @@ public:
     struct WellsDev;
     struct VfpDev;
     int set_device_wells(const opmgpu_wells* spec);
+    int set_well_efficiency(const double* factors);         // [nw] in (0, 1] or NULL = ones; throws HipError(OPMGPU_EINVAL) with the reason
+    int get_well_efficiency(double* factors) const;
     int well_state_set(const double* bhp, const double* qs, const double* perf_press, const double* perf_rates);
     int well_state_get(double* bhp, double* qs, double* perf_press, double* perf_rates);
     int well_convergence(double* flux3, double* ctrl);

@@ -646,6 +646,18 @@ int opmgpu_set_device_wells(opmgpu_ctx* c, const opmgpu_wells* wells)
         return st;
     });
 }
+int opmgpu_set_well_efficiency(opmgpu_ctx* c, const double* factors)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    // the next assembly reads the new factors; a matrix loaded or factored before the call is that of the old ones
+    return guarded(c, [&]() { const int st = c->model->set_well_efficiency(factors); c->matrix_loaded = false; return st; });
+}
+int opmgpu_get_well_efficiency(opmgpu_ctx* c, double* factors)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    if (!factors) return fail(c, OPMGPU_EINVAL, "opmgpu_get_well_efficiency: factors is NULL");
+    return guarded(c, [&]() { return c->model->get_well_efficiency(factors); });
+}
 int opmgpu_well_state_set(opmgpu_ctx* c, const double* bhp, const double* qs, const double* perf_press, const double* perf_rates)
 {
     if (!c || !c->model) return OPMGPU_EINVAL;

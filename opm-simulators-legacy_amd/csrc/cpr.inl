@@ -156,6 +156,7 @@ __global__ __launch_bounds__(kBlock) void k_cpr_border(LowRankOp lr, int nbp, co
     __shared__ double sm[4];
     const int k = blockIdx.x;
     const double* g = lr.ctrl_row + 4 * k;
+    const double ew = lr.eff[k];            // the column is a cell-row term: weighed by the well's efficiency factor; the row is the well's own equation
     double acc[1] = { 0.0 };
     for (int j = lr.connpos[k] + threadIdx.x; j < lr.connpos[k + 1]; j += kBlock) {
         const double* Fs = lr.Fsave + 21 * long(j);
@@ -166,7 +167,7 @@ __global__ __launch_bounds__(kBlock) void k_cpr_border(LowRankOp lr, int nbp, co
             cr += g[a] * Fs[3 * a];
             acc[0] += g[a] * Fs[18 + a];
         }
-        out[j] = S(colscale * bc); out[lr.nperf + j] = S(cr);
+        out[j] = S(colscale * (ew * bc)); out[lr.nperf + j] = S(cr);
     }
     block_sum<1>(acc, sm);
     if (threadIdx.x == 0) {

@@ -86,6 +86,9 @@ struct LowRankOp {
     const double* Fsave = nullptr;
     const double* ctrl_row = nullptr;
     double scale[3] = { 1.0, 1.0, 1.0 };
+    // well efficiency factors [nw] (WEFAC): P carries them already (wells.hip, phase E); Fsave holds the UNWEIGHTED derivatives, which the
+    // well equations need, so a reader that builds a CELL-row term from Fsave multiplies by eff itself (k_cpr_border's column)
+    const double* eff = nullptr;
 };
 
 template <class S>

@@ -18,7 +18,8 @@
 //   THP control through VFP tables                   :655-700, :895-960; VFPProd/InjPropertiesLegacy.cpp   (vfp_* of vfp.hpp)
 //   PVT at the average well-block pressure           :218-296                                       (k_well_avg_press + k_perf_pvt)
 //   RESERVOIR_RATE conversion coefficients          RateConverterLegacy.hpp:495-548, :718-768        (k_voidage_coeff, region_state_sums in blackoil_output.hip)
-// Not restated: group controls / guide rates, efficiency factors.
+//   well efficiency factors (WEFAC)                 StandardWells_impl.hpp:1405-1434; BlackoilModelBase_impl.hpp:953-975   (WellArgs::eff, k_well_assemble)
+// Not restated: group controls / guide rates (and with them GEFAC).
 #include "blackoil.hpp"
 #include "vfp.hpp"
 
@@ -94,6 +95,7 @@ struct WellArgs {
     double* Fsave;               // [nperf][9+9+3]: F_i, M_i, fb_i
     double* wellE;               // [nw][4]
     double* Dinv;                // [nw][16]
+    const double* eff;           // [nw] well efficiency factor e_w in (0, 1] (ones by default): weighs what the CELLS see of the well, never the well equations
 };
 
 // average well-block pressure per perforation (computePropertiesForWellConnectionPressures, StandardWells_impl.hpp:228-237):
@@ -293,7 +295,10 @@ __device__ void well_assemble_dev(const WellArgs& A, int w, const int32_t* __res
     const double qs[3] = { A.wstate[4 * w], A.wstate[4 * w + 1], A.wstate[4 * w + 2] };
     const double bhp = A.wstate[4 * w + 3];
     const double compi[3] = { A.comp_frac[3 * w], A.comp_frac[3 * w + 1], A.comp_frac[3 * w + 2] };
-    const double scale[3] = { s0, s1, s2 };
+    // well efficiency factor (addWellContributionToMassBalanceEq subtracts efficiency_factors * cq_s): it weighs the cell rows -- R, the
+    // diagonal blocks, P, rhs_extra -- and nothing of the well equations.  e_w = 1 gives the unweighted bits (1 * x is exact).
+    const double ew = PRE ? 1.0 : A.eff[w];
+    const double escale[3] = { ew * s0, ew * s1, ew * s2 };
     // ---- phase 0: which perforations inject (drawdown < 0), cross-flow rule (:418-452) ----
     if (tid < 2) any_flag[tid] = 0;
     __syncthreads();
@@ -372,13 +377,13 @@ __device__ void well_assemble_dev(const WellArgs& A, int w, const int32_t* __res
             for (int a = 0; a < 3; ++a) Qj[3 * a + v] = alive ? (-f.cq_ps[a].d[v] + cmix[a] * hs) / wbqt : 0.0;
         }
         for (int a = 0; a < 3; ++a) {
-            R[long(a) * A.nbp + row] -= cq_s[a].v;                                   // addWellContributionToMassBalanceEq
+            R[long(a) * A.nbp + row] -= ew * cq_s[a].v;                              // addWellContributionToMassBalanceEq
             A.perf_rates[3 * j + a] = cq_s[a].v;
             acc2[a] += cq_s[a].v;
             acc2[12 + a] += cq_s[a].d[3];
             Fs[18 + a] = cq_s[a].d[3];
             for (int v = 0; v < 3; ++v) {
-                dptr[(3 * a + v) * 64] = MS(double(dptr[(3 * a + v) * 64]) - scale[a] * cq_s[a].d[v]);    // own-cell part of -d cq_s / d cell
+                dptr[(3 * a + v) * 64] = MS(double(dptr[(3 * a + v) * 64]) - escale[a] * cq_s[a].d[v]);   // own-cell part of -e_w d cq_s / d cell
                 Fs[3 * a + v] = cq_s[a].d[v];
                 Fs[9 + 3 * a + v] = cq_s[a].d[4 + v];
                 acc2[3 + 3 * a + v] += cq_s[a].d[4 + v];
@@ -431,7 +436,7 @@ __device__ void well_assemble_dev(const WellArgs& A, int w, const int32_t* __res
     }
     __syncthreads();
     if (PRE) return;
-    // ---- phase E: P_i = -[M_i | B_i D^-1], Q_i = [G_i ; C_i], rhs extra = -(B_i D^-1 E) ----
+    // ---- phase E: P_i = -e_w [M_i | B_i D^-1], Q_i = [G_i ; C_i], rhs extra = -e_w (B_i D^-1 E) ----
     {
         const double* gq = wl + 3; const double* gb = wl + 12; const double* Di = wl + 20; const double* E = wl + 36; const double* Ms = wl + 40;
         for (int j = lo + tid; j < hi; j += kBlock) {
@@ -450,11 +455,11 @@ __device__ void well_assemble_dev(const WellArgs& A, int w, const int32_t* __res
                 for (int k = 0; k < 4; ++k) {
                     double bd = 0.0;
                     for (int c = 0; c < 4; ++c) bd += B[4 * a + c] * Di[4 * c + k];
-                    Pj[7 * a + 3 + k] = -scale[a] * bd;
+                    Pj[7 * a + 3 + k] = -escale[a] * bd;
                     bde += bd * E[k];
                 }
-                for (int c = 0; c < 3; ++c) Pj[7 * a + c] = -scale[a] * M[3 * a + c];
-                rhs_extra[long(a) * A.nbp + row] = -bde;
+                for (int c = 0; c < 3; ++c) Pj[7 * a + c] = -escale[a] * M[3 * a + c];
+                rhs_extra[long(a) * A.nbp + row] = -(ew * bde);
             }
             // C_i rows 0..2 = -(F_i + Ms G_i); row 3 (control equation) = 0.  G_i is already in Q rows 0..2.
             double G[9];
@@ -733,6 +738,8 @@ struct BlackoilDevice::WellsDev {
     DevArray<double> WI, comp_frac, ctrl_target, ctrl_distr, ctrl_alq, depth_ref, z_perf, surf_dens_perf;
     DevArray<double> wstate, thp, cdp, perf_dens, perf_pvt, avgp, qout, perf_rates, perf_press, P, Q, Fsave, wellE, Dinv, t, wdy, wdy_old;
     DevArray<double> bsums, bscratch, snap, presolve_sync, ctrl_row;
+    DevArray<double> eff;           // [nw] well efficiency factors (set_well_efficiency); no part of the well STATE: not saved, not restored
+    std::vector<double> h_eff;
     DevArray<double> saved;         // snapshot for AdaptiveTimeStepping: wstate | thp | cdp | perf_rates | perf_press | perf_dens
     DevArray<int32_t> flags;
     std::vector<int32_t> h_connpos, h_cells, h_ctrl_ptr;
@@ -754,7 +761,7 @@ static WellArgs args_of(BlackoilDevice::WellsDev& W, BlackoilDevice::VfpDev* V, 
     A.V.ntab = V ? V->ntab : 0; A.V.meta = V ? V->meta.p : nullptr; A.V.datum = V ? V->datum.p : nullptr; A.V.blob = V ? V->blob.p : nullptr;
     A.z_perf = W.z_perf.p; A.surf_dens_perf = W.surf_dens_perf.p; A.perf = perf;
     A.wstate = W.wstate.p; A.cdp = W.cdp.p; A.perf_rates = W.perf_rates.p; A.perf_press = W.perf_press.p; A.P = W.P.p; A.Q = W.Q.p;
-    A.Fsave = W.Fsave.p; A.wellE = W.wellE.p; A.Dinv = W.Dinv.p;
+    A.Fsave = W.Fsave.p; A.wellE = W.wellE.p; A.Dinv = W.Dinv.p; A.eff = W.eff.p;
     return A;
 }
 
@@ -890,6 +897,7 @@ int BlackoilDevice::set_device_wells(const opmgpu_wells* s)
     W.thp.alloc(nw); W.thp.zero(stream);
     W.perf_dens.alloc(np); W.perf_dens.zero(stream); W.perf_pvt.alloc(5 * size_t(np)); W.avgp.alloc(np); W.qout.alloc(3 * size_t(np));
     W.ctrl_row.alloc(4 * size_t(nw)); W.ctrl_row.zero(stream);
+    W.h_eff.assign(nw, 1.0); W.eff.upload(W.h_eff, stream);          // a new well list: every factor is 1 again
     W.wdy.alloc(4 * size_t(nw)); W.wdy.zero(stream); W.wdy_old.alloc(4 * size_t(nw)); W.wdy_old.zero(stream);
     W.bsums.alloc(16); W.bscratch.alloc(13 * size_t(kMaxRedBlocks)); W.snap.alloc(5 * size_t(nw) + 4 * size_t(np));
     std::vector<double> zp(np), sd(3 * size_t(np));
@@ -927,9 +935,32 @@ void BlackoilDevice::wells_rebind()
     LowRankOp& L = ls.lowrank;
     L.nw = W.nw; L.nperf = np; L.connpos = W.connpos.p; L.perf_row = W.perf_row.p; L.perf_well = W.perf_well.p; L.perf_of_row = W.perf_of_row.p;
     L.P = W.P.p; L.Q = W.Q.p; L.t = W.t.p;
-    L.Fsave = W.Fsave.p; L.ctrl_row = W.ctrl_row.p;
+    L.Fsave = W.Fsave.p; L.ctrl_row = W.ctrl_row.p; L.eff = W.eff.p;
     for (int a = 0; a < 3; ++a) L.scale[a] = prm.matbalscale[a];
     ls.drop_hierarchies();
+}
+
+// WEFAC: one factor per well in the order of set_device_wells, NULL = all ones.  The array keeps its address, so the kernel arguments and
+// the solver's LowRankOp stay valid; the next assembly reads the new values.
+int BlackoilDevice::set_well_efficiency(const double* factors)
+{
+    if (!wd) throw HipError(OPMGPU_EINVAL, "opmgpu_set_well_efficiency: no device wells are set (opmgpu_set_device_wells comes first)");
+    WellsDev& W = *wd;
+    if (factors)
+        for (int w = 0; w < W.nw; ++w) {
+            if (!std::isfinite(factors[w])) throw HipError(OPMGPU_EINVAL, "opmgpu_set_well_efficiency: the factor of well " + std::to_string(w) + " is not finite");
+            if (!(factors[w] > 0.0 && factors[w] <= 1.0)) throw HipError(OPMGPU_EINVAL, "opmgpu_set_well_efficiency: the factor of well " + std::to_string(w) + " is outside (0, 1]");
+        }
+    if (factors) W.h_eff.assign(factors, factors + W.nw); else W.h_eff.assign(W.nw, 1.0);
+    OPMGPU_HIP(hipMemcpyAsync(W.eff.p, W.h_eff.data(), size_t(W.nw) * sizeof(double), hipMemcpyHostToDevice, stream));
+    OPMGPU_HIP(hipStreamSynchronize(stream));
+    return OPMGPU_OK;
+}
+int BlackoilDevice::get_well_efficiency(double* factors) const
+{
+    if (!wd) throw HipError(OPMGPU_EINVAL, "opmgpu_get_well_efficiency: no device wells are set");
+    std::copy(wd->h_eff.begin(), wd->h_eff.end(), factors);
+    return OPMGPU_OK;
 }
 
 int BlackoilDevice::well_state_set(const double* bhp, const double* qs, const double* perf_press, const double* perf_rates)

@@ -114,6 +114,11 @@ public:
 
     /// wells on the device (StandardWells restated in csrc/wells.hip): topology + controls, then the WellState fields
     void setDeviceWells(const opmgpu_wells& wells) { throw_on_status(ctx_, opmgpu_set_device_wells(ctx_, &wells)); device_wells_ = wells.nw > 0; }
+    /// WEFAC: one efficiency factor in (0, 1] per device well (order of setDeviceWells), empty = all ones.  The perforated cells see e_w times the
+    /// well's rates and their derivatives (StandardWells_impl.hpp:1405-1434, BlackoilModelBase_impl.hpp:953-975); the well equations do not.
+    /// After setDeviceWells, which resets the factors to ones; lasts through saved states, precision changes and re-plans.
+    void setWellEfficiencyFactors(const std::vector<double>& factors) { throw_on_status(ctx_, opmgpu_set_well_efficiency(ctx_, factors.empty() ? nullptr : factors.data())); }
+    std::vector<double> wellEfficiencyFactors(int nw) const { std::vector<double> f(nw > 0 ? nw : 1, 1.0); throw_on_status(ctx_, opmgpu_get_well_efficiency(ctx_, f.data())); f.resize(nw > 0 ? nw : 0); return f; }
     void setWellState(const double* bhp, const double* well_rates, const double* perf_press = nullptr, const double* perf_rates = nullptr) { throw_on_status(ctx_, opmgpu_well_state_set(ctx_, bhp, well_rates, perf_press, perf_rates)); }
     void getWellState(double* bhp, double* well_rates, double* perf_press = nullptr, double* perf_rates = nullptr) { throw_on_status(ctx_, opmgpu_well_state_get(ctx_, bhp, well_rates, perf_press, perf_rates)); }
     /// WellStateFullyImplicitBlackoil::currentControls() / thp(); after an assembly also what solveWellEq did (iterations, converged) per well

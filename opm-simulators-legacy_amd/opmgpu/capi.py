@@ -199,6 +199,8 @@ SIGNATURES = {
     "opmgpu_get_cpr_weights": (C.c_int, [C.c_void_p, _dp]),
     "opmgpu_set_solve_precision": (C.c_int, [C.c_void_p, C.c_int]),
     "opmgpu_set_device_wells": (C.c_int, [C.c_void_p, C.POINTER(WellsSpec)]),
+    "opmgpu_set_well_efficiency": (C.c_int, [C.c_void_p, _dp]),
+    "opmgpu_get_well_efficiency": (C.c_int, [C.c_void_p, _dp]),
     "opmgpu_well_state_set": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp]),
     "opmgpu_well_state_get": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp]),
     "opmgpu_well_convergence": (C.c_int, [C.c_void_p, _dp, _dp]),

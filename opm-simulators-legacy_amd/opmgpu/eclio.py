@@ -262,16 +262,19 @@ class EclOutput:
     def write_summary(self, elapsed_days, wells, well_state, new_report_step=False, fip=None):
         """one ministep: wells = opmgpu.wells.Wells (names, types), well_state = its WellState (bhp [Pa], qs [m3/s], w-o-g, production < 0);
         fip = computeFluidInPlace's row of the whole field (water, oil, gas, dissolved gas, vaporised oil, pore volume, hydrocarbon-pv
-        weighted pressure [Pa]) or None"""
+        weighted pressure [Pa]) or None.  OURS (the reference writes its summary through opm-output, outside its tree): the field rates
+        FOPR FWPR FGPR FWIR FGIR sum e_w times the well's rate, e_w = the well's efficiency factor (WEFAC) -- what the reservoir sees; the
+        W* vectors are the well's own rates while it flows, unweighted."""
         names = list(wells.name)
         if not self._smspec_written:
             self._write_smspec(names)
         kws, wgn = self._vectors
         qs = np.asarray(well_state.qs) * DAY
         prod = np.maximum(-qs, 0.0); inj = np.maximum(qs, 0.0)
+        e = wells.efficiency_factors() if hasattr(wells, "efficiency_factors") else np.ones(len(names))
         row = {("TIME", ":+:+:+:+"): elapsed_days, ("YEARS", ":+:+:+:+"): elapsed_days / 365.25,
-               ("FOPR", ":+:+:+:+"): prod[:, 1].sum(), ("FWPR", ":+:+:+:+"): prod[:, 0].sum(), ("FGPR", ":+:+:+:+"): prod[:, 2].sum(),
-               ("FWIR", ":+:+:+:+"): inj[:, 0].sum(), ("FGIR", ":+:+:+:+"): inj[:, 2].sum()}
+               ("FOPR", ":+:+:+:+"): (e * prod[:, 1]).sum(), ("FWPR", ":+:+:+:+"): (e * prod[:, 0]).sum(), ("FGPR", ":+:+:+:+"): (e * prod[:, 2]).sum(),
+               ("FWIR", ":+:+:+:+"): (e * inj[:, 0]).sum(), ("FGIR", ":+:+:+:+"): (e * inj[:, 2]).sum()}
         if fip is not None:
             f7 = np.asarray(fip, float).reshape(-1)
             row[("FWIP", ":+:+:+:+")], row[("FOIP", ":+:+:+:+")], row[("FGIP", ":+:+:+:+")] = f7[0], f7[1] + f7[4], f7[2] + f7[3]

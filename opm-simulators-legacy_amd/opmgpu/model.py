@@ -328,6 +328,24 @@ class GpuBlackoilModel(_CprDiagnostics):
             raise ValueError("setPvcdo: PVCDO needs one row of five numbers per PVT region (%d regions)" % self.tables.n_pvt)
         self._chk(self.lib.opmgpu_set_pvcdo(self.ctx, capi.dptr(o)))
 
+    def setWellEfficiency(self, factors):
+        """Well efficiency factors (WEFAC; opmgpu_set_well_efficiency, the rule is stated in include/opmgpu.h): one factor in (0, 1] per
+        device well in the order of opmgpu_set_device_wells, or None for all ones.  The cells see e_w times the well's rates and their
+        derivatives; the well equations and the well state do not see it.  Lasts through saved states, a change of precision and a
+        re-plan; a new opmgpu_set_device_wells resets it.  No device wells, a non-finite factor or one outside (0, 1] is a ValueError."""
+        f = None if factors is None else capi.f64(factors).ravel()
+        if f is not None and self.n_device_wells and f.size != self.n_device_wells:
+            raise ValueError("setWellEfficiency: %d factors for %d device wells" % (f.size, self.n_device_wells))
+        self._chk(self.lib.opmgpu_set_well_efficiency(self.ctx, capi.dptr(f)))
+
+    def getWellEfficiency(self):
+        """the factors in force, one per device well"""
+        out = np.zeros(max(self.n_device_wells, 1))
+        self._chk(self.lib.opmgpu_get_well_efficiency(self.ctx, capi.dptr(out)))
+        return out[:self.n_device_wells]
+
+    n_device_wells = 0          # wells of the last opmgpu_set_device_wells (DeviceWellModel records it)
+
     def computeMaxDp(self, eqlnum, nregions, n_face_conn, conns=False):
         """computeMaxDp (opm/simulators/thresholdPressures.hpp:46-298) for the resident state: max_dp[nregions][nregions], the largest
         phase-potential difference over the first n_face_conn connections (the grid faces; NNCs are not scanned) joining each pair of

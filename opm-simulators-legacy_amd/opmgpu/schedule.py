@@ -4,6 +4,8 @@ keywords a standard-well black-oil run needs:
   WELSPECS  name group I J ref-depth preferred-phase            COMPDAT  name I J K1 K2 OPEN|SHUT satnum CF diameter Kh skin D dir
   WCONPROD  name OPEN|SHUT mode ORAT WRAT GRAT LRAT RESV BHP THP VFP ALQ     WCONINJE  name phase OPEN|SHUT mode RATE RESV BHP THP VFP
   WELOPEN   name OPEN|SHUT|STOP [I J K]                            WELTARG  name ORAT|WRAT|GRAT|LRAT|BHP|THP|RATE value
+  WEFAC     name-or-template factor            the well's efficiency factor in (0, 1], in force from its report step on until replaced
+            (item 3, the network flag, is not read); GEFAC is refused: there are no groups
   DATES / TSTEP (report steps), START (RUNSPEC)
   RPTRST    mnemonic list (opmgpu/deck.py:parse_rptrst): REPLACES the list in force (RestartConfig::getRestartKeywords) for the report steps
             that follow it; the SOLUTION section's list holds until then
@@ -45,6 +47,7 @@ class WellSpec:
         self.name, self.i, self.j, self.ref_depth, self.phase = name, i, j, ref_depth, phase
         self.completions = []           # (i, j, k, open, CF or None, diameter, Kh or None, skin)
         self.control = None             # ("PROD", open, mode, limits dict) / ("INJ", phase, open, mode, limits dict)
+        self.efficiency = 1.0           # WEFAC
 
 
 class Schedule:
@@ -127,6 +130,25 @@ class Schedule:
                             c = list(ws.control)
                             c[2 if c[0] == "INJ" else 1] = status == "OPEN"          # STOP (shut above the formation) is treated as SHUT: no crossflow model
                             ws.control = tuple(c)
+            elif name == "WEFAC":            # name-or-template factor: resolved like WELOPEN's names, but a name that matches no well is an error
+                for r in recs:
+                    if not r:
+                        continue
+                    if len(r) < 2 or r[1] is None:
+                        raise ValueError("WEFAC %s: the record has no efficiency factor" % r[0])
+                    try:
+                        e = float(r[1])
+                    except (TypeError, ValueError):
+                        raise ValueError("WEFAC %s: efficiency factor %r is not a number" % (r[0], r[1]))
+                    if not (np.isfinite(e) and 0.0 < e <= 1.0):
+                        raise ValueError("WEFAC %s: efficiency factor %r is outside (0, 1]" % (r[0], r[1]))
+                    matched = [wn for wn in self._match(specs, str(r[0])) if wn in specs]
+                    if not matched:
+                        raise ValueError("WEFAC %s: unknown well (no WELSPECS before it names or matches it)" % r[0])
+                    for wn in matched:
+                        specs[wn].efficiency = e
+            elif name == "GEFAC":
+                raise ValueError("GEFAC: group efficiency factors are not supported (there are no groups; WEFAC sets a well's factor)")
             elif name == "WELTARG":          # name control value: one limit of the current WCONPROD / WCONINJE record changed
                 for r in recs:
                     if not r:
@@ -240,5 +262,5 @@ class Schedule:
             # control mode as the index of the current control: updateWellControls switches to the FIRST broken constraint, so the
             # order decides which one wins when two are broken (and the index goes into the restart file)
             order = list(ctrls.values())
-            out.add_well(name, wtype, ref, cells, wi, comp, order[0], limits=order[1:], current=list(ctrls).index(mode))
+            out.add_well(name, wtype, ref, cells, wi, comp, order[0], limits=order[1:], current=list(ctrls).index(mode), efficiency=ws.efficiency)
         return out

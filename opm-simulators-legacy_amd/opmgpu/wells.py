@@ -19,7 +19,9 @@ terms go back through `addWellTerms` / `addWellRhs`, the perforated cells' incre
   RESERVOIR_RATE controls: the control equation is the weighted rate sum with the control's distribution (:938-955); the distribution
   comes from opmgpu/rateconverter.py (RateConverter::SurfaceToReservoirVoidage + SimulatorBase::computeRESV)
 
-Not restated: group controls / guide rates (WellCollection), efficiency factors.
+  well efficiency factors (WEFAC)                  StandardWells_impl.hpp:1405-1434; BlackoilModelBase_impl.hpp:953-975
+
+Not restated: group controls / guide rates (WellCollection; with them GEFAC).
 """
 import numpy as np
 
@@ -92,13 +94,20 @@ class Wells:
         self.current0 = []
         self.controls = []                                                     # all controls of each well (WellControls), control 0 first
         self.name = []
+        self.efficiency = []                                                   # WEFAC: one factor in (0, 1] per well
 
-    def add_well(self, name, wtype, depth_ref, cells, WI, comp_frac, control, allow_cf=True, limits=(), current=0):
+    def add_well(self, name, wtype, depth_ref, cells, WI, comp_frac, control, allow_cf=True, limits=(), current=0, efficiency=1.0):
         """The well's controls are [control] + limits IN THAT ORDER; `current` is the index of its initial current control in that list
         (default: `control`), the others are inequality constraints that updateWellControls switches to when broken (e.g. a BHP limit
         on a rate-controlled well).  The order matters: updateWellControls switches to the FIRST broken constraint
         (StandardWells_impl.hpp:709-780), and WellsManager keeps a fixed order (ORAT, WRAT, GRAT, LRAT, RESV, BHP, THP) with the current
-        control as an index into it -- opmgpu/schedule.py builds its wells that way."""
+        control as an index into it -- opmgpu/schedule.py builds its wells that way.
+        `efficiency` is the well's efficiency factor e_w in (0, 1] (WEFAC): the perforated cells see e_w times the well's rates
+        (addWellContributionToMassBalanceEq, BlackoilModelBase_impl.hpp:953-975); the well's own equations and state do not see it."""
+        efficiency = float(efficiency)
+        if not (np.isfinite(efficiency) and 0.0 < efficiency <= 1.0):
+            raise ValueError("well %s: efficiency factor %r is outside (0, 1]" % (name, efficiency))
+        self.efficiency.append(efficiency)
         self.name.append(name); self.type.append(wtype); self.depth_ref.append(float(depth_ref))
         self.comp_frac.append(np.asarray(comp_frac, float)); self.allow_cf.append(bool(allow_cf))
         self.cells += [int(c) for c in cells]; self.WI += [float(w) for w in np.broadcast_to(WI, (len(cells),))]
@@ -133,6 +142,14 @@ class Wells:
 
     def arrays(self):
         return np.asarray(self.connpos, np.int32), np.asarray(self.cells, np.int32)
+
+    def efficiency_factors(self):
+        """[nw] efficiency factors (ones for wells that were given none)"""
+        e = np.ones(self.nw)
+        have = np.asarray(getattr(self, "efficiency", ()), float)
+        m = min(have.size, self.nw)
+        e[:m] = have[:m]
+        return e
 
 
 class WellState:
@@ -419,18 +436,20 @@ class StandardWellsHost:
         self._sys = []
         flux_eq = np.zeros((W.nw, 3)); ctrl_eq = np.zeros(W.nw)
         cq_all = np.zeros((nperf, 3))
+        eff = W.efficiency_factors() if hasattr(W, "efficiency_factors") else np.ones(W.nw)
         for w in range(W.nw):
             lo, hi = W.connpos[w], W.connpos[w + 1]
             n = hi - lo
             nv = 3 * n + 4
             I = np.arange(lo, hi)
             cq_s, Ev, Ej = self._well_system(w, pp, ws)
+            ew = eff[w]
             C, D = Ej[:, :3 * n], Ej[:, 3 * n:]
-            # cell rows: R_a[cell_i] -= cq_s[a][i]   (addWellContributionToMassBalanceEq)
+            # cell rows: R_a[cell_i] -= e_w cq_s[a][i]   (addWellContributionToMassBalanceEq); the well rows (Ev, C, D) and the rates do not see e_w
             Jc = np.zeros((3 * n, nv))
             for a in range(3):
-                Jc[a::3] = -cq_s[a].j
-                resid_delta[I, a] = -cq_s[a].v
+                Jc[a::3] = -(ew * cq_s[a].j)
+                resid_delta[I, a] = -(ew * cq_s[a].v)
                 cq_all[I, a] = cq_s[a].v
             Jcc, B = Jc[:, :3 * n], Jc[:, 3 * n:]
             Dinv = np.linalg.inv(D)
@@ -641,6 +660,10 @@ class DeviceWellModel:
         spec.depth_ref, spec.comp_frac, spec.ctrl_type, spec.ctrl_target, spec.ctrl_distr = capi.dptr(k[5]), capi.dptr(k[6]), capi.iptr(k[7]), capi.dptr(k[8]), capi.dptr(k[9])
         spec.ctrl_ptr, spec.ctrl_vfp, spec.ctrl_alq = capi.iptr(k[10]), capi.iptr(k[11]), capi.dptr(k[12])
         backend._chk(backend.lib.opmgpu_set_device_wells(backend.ctx, C.byref(spec)))
+        backend.n_device_wells = nw
+        eff = wells.efficiency_factors() if hasattr(wells, "efficiency_factors") else np.ones(nw)
+        if nw and np.any(eff != 1.0):       # WEFAC (rank-local in decomposed runs: the factors of this rank's wells)
+            backend.setWellEfficiency(eff)
         if tolerance_wells != backend.params.tolerance_wells or tolerance_well_control != backend.params.tolerance_well_control:
             pass        # the pre-solve on the device uses opmgpu_params.tolerance_wells / tolerance_well_control of the context
         self.push_well_state()
