@@ -420,6 +420,58 @@ __global__ __launch_bounds__(kBlock) void k_amg_restrict(int nc, const int32_t* 
     bc[I] = s;
     if (xc) xc[I] = omega * dinv_c[I] * s;      // the coarse level's first pre-smoothing sweep from a zero guess, fused
 }
+// The value `v` of the lane K places ahead in the same row of 16 lanes (DPP row_shl:K, a register move -- no trip through the LDS
+// crossbar); what a lane whose source lies outside the row receives is not used.
+template <int K, class S>
+__device__ __forceinline__ S lane_ahead(S v)
+{
+    static_assert(K >= 1 && K <= 15, "row_shl takes 1..15");
+    int w[sizeof(S) / 4];
+    __builtin_memcpy(w, &v, sizeof(S));
+#pragma unroll
+    for (int k = 0; k < int(sizeof(S) / 4); ++k) w[k] = __builtin_amdgcn_mov_dpp(w[k], 0x100 + K, 0xf, 0xf, false);
+    __builtin_memcpy(&v, w, sizeof(S));
+    return v;
+}
+// s + v_0 + v_1 + .. + v_7, one after the other, with v_k the value of the lane k places ahead: what the first lane of eight computes
+// is the serial sum over its group
+template <class S>
+__device__ __forceinline__ S add_group_of_8(S s, S v)
+{
+    s += v;
+    s += lane_ahead<1>(v); s += lane_ahead<2>(v); s += lane_ahead<3>(v); s += lane_ahead<4>(v);
+    s += lane_ahead<5>(v); s += lane_ahead<6>(v); s += lane_ahead<7>(v);
+    return s;
+}
+// The same restriction with eight adjacent lanes per aggregate: lane u gathers r[arows[q + u]] of a batch (coalesced index loads, eight
+// times the gathers in flight; two batches are fetched together, which covers most aggregates with one round of index loads and one of
+// gathers), then the first lane adds the eight values one after the other in the order of k_amg_restrict -- q0 .. q1 - 1 from 0, the
+// padding of the last batch as zeros -- so bc and the fused first sweep keep their bits.  The eight lanes of an aggregate share q0 and
+// q1, hence every branch: the lanes a move reads from are active.  (kBlock is a multiple of 16: a group never straddles a DPP row.)
+template <class S>
+__global__ __launch_bounds__(kBlock) void k_amg_restrict_lanes(int nc, const int32_t* __restrict__ aptr, const int32_t* __restrict__ arows,
+                                                               const S* __restrict__ r, S* __restrict__ bc, S omega, const S* __restrict__ dinv_c,
+                                                               S* __restrict__ xc, const SolveCtl* __restrict__ ctl)
+{
+    if (ctl && ctl->done) return;
+    const int t = blockIdx.x * kBlock + threadIdx.x;
+    const int I = t >> 3, u = t & 7;
+    if (I >= nc) return;                        // (whole groups of eight)
+    const int q0 = aptr[I], q1 = aptr[I + 1];
+    S s = 0;
+    for (int q = q0; q < q1; q += 16) {
+        const int ia = q + u, ib = q + 8 + u;
+        const int ra = ia < q1 ? arows[ia] : -1;
+        const int rb = ib < q1 ? arows[ib] : -1;
+        const S va = ra >= 0 ? r[ra] : S(0);
+        const S vb = rb >= 0 ? r[rb] : S(0);
+        s = add_group_of_8(s, va);
+        if (q + 8 < q1) s = add_group_of_8(s, vb);
+    }
+    if (u != 0) return;
+    bc[I] = s;
+    if (xc) xc[I] = omega * dinv_c[I] * s;
+}
 template <class S>
 __global__ __launch_bounds__(kBlock) void k_amg_prolong(int n, const int32_t* __restrict__ agg, const S* __restrict__ xc, S* __restrict__ x, S pdamp,
                                                         const SolveCtl* __restrict__ ctl)
@@ -1095,6 +1147,10 @@ void AmgHierarchy<S>::vcycle(const SolveCtl* ctl, bool level0_presmoothed)
         for (int sw = 1; sw < npre; ++sw) { sweep(F, ctl); row_op<0>(F, ctl); }      // further pre-smoothing sweeps, then the residual again
         // the restriction also performs the coarse level's first sweep when that level would launch a separate kernel for it
         presmoothed = fuse && (l + 1 < nl - 1) && C.n > 50000;
+        if (lane_restrict)
+            hipLaunchKernelGGL((k_amg_restrict_lanes<S>), dim3(grid_for(8 * long(C.n))), dim3(kBlock), 0, stream, C.n, F.agg_ptr.p, F.agg_rows.p, F.r.p, C.b.p, om,
+                               presmoothed ? (const S*)C.dinv.p : (const S*)nullptr, presmoothed ? C.x.p : (S*)nullptr, ctl);
+        else
         hipLaunchKernelGGL((k_amg_restrict<S>), dim3(grid_for(C.n)), dim3(kBlock), 0, stream, C.n, F.agg_ptr.p, F.agg_rows.p, F.r.p, C.b.p, om,
                            presmoothed ? (const S*)C.dinv.p : (const S*)nullptr, presmoothed ? C.x.p : (S*)nullptr, ctl);
         mark("down L" + std::to_string(l));
@@ -1161,11 +1217,11 @@ void AmgHierarchy<S>::vcycle_graph(const SolveCtl* ctl, bool level0_presmoothed)
     if (!use_graph || !even || level0_halo || ndist > 0) { vcycle(ctl, level0_presmoothed); return; }          // (the exchange is not capturable)
     join_inverse();          // an event of another stream cannot be waited for inside a capture
     // the captured launches carry the smoother / correction constants as baked-in kernel arguments: they are part of the cache key
-    const double key[6] = { pdamp0, pdamp, omega0(), double(npost), double(npost0), double(npre) };
+    const double key[7] = { pdamp0, pdamp, omega0(), double(npost), double(npost0), double(npre), double(lane_restrict) };
     bool same = graph_exec && graph_ctl == ctl && graph_pre == level0_presmoothed;
-    for (int k = 0; k < 6 && same; ++k) same = graph_key[k] == key[k];
+    for (int k = 0; k < 7 && same; ++k) same = graph_key[k] == key[k];
     if (!same) {
-        for (int k = 0; k < 6; ++k) graph_key[k] = key[k];
+        for (int k = 0; k < 7; ++k) graph_key[k] = key[k];
         if (graph_exec) { (void)hipGraphExecDestroy(graph_exec); graph_exec = nullptr; }
         hipGraph_t g = nullptr;
         OPMGPU_HIP(hipStreamBeginCapture(stream, hipStreamCaptureModeThreadLocal));

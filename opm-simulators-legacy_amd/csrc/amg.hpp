@@ -107,7 +107,7 @@ public:
     void vcycle_graph(const SolveCtl* ctl, bool level0_presmoothed);
     hipGraphExec_t graph_exec = nullptr;
     const SolveCtl* graph_ctl = nullptr;
-    double graph_key[6] = { 0, 0, 0, 0, 0, 0 };
+    double graph_key[7] = { 0, 0, 0, 0, 0, 0, 0 };
     bool graph_pre = false, use_graph = false;
     std::vector<std::unique_ptr<AmgLevel<S>>> levels;
     DevArray<double> dense_inv;      // coarsest: explicit inverse (double), n_c x n_c (border rows included when level 0 is the coarsest)
@@ -140,6 +140,7 @@ public:
     bool npost0_user = false;     // OPMGPU_AMG_NPOST0 given: the solvers do not choose (BiCGStab 2, GMRES 1)
     int coarse_sweeps = 4;        // pairs of Jacobi sweeps standing in for the coarsest solve when it is too big for the dense inverse
     bool fuse = true;             // launch fusions of the V-cycle (A/B: OPMGPU_AMG_FUSE=0)
+    bool lane_restrict = false;   // restriction with eight lanes per aggregate (k_amg_restrict_lanes; same bits): set by LinSolver per solve, part of the graph's key
     bool use_gs = false;          // level 0: Gauss-Seidel by colour instead of damped Jacobi when the row order has two colours (OPMGPU_AMG_GS)
     int gs_n0 = 0;                // rows [0, gs_n0) are the first colour (0 = no two-colour order)
     bool gs_level0() const { return use_gs && gs_n0 > 0 && npre == 1; }

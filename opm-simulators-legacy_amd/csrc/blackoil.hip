@@ -1140,8 +1140,10 @@ template <class S> void BlackoilDevice::store_dx()
 {
     const Plan& P = ls.plan;
     const long n = 3 * long(P.nbp);
-    if (sizeof(S) == 8) OPMGPU_HIP(hipMemcpyAsync(d_dx.p, ls.work<S>().x.p, n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-    else {
+    if (sizeof(S) == 8) {
+        // (the GMRES combination stored the solution here already when it was handed d_dx as its mirror: LinSolver::solution_mirror)
+        if (!ls.mirror_written) OPMGPU_HIP(hipMemcpyAsync(d_dx.p, ls.work<S>().x.p, n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+    } else {
         launch_convert_f2d(n, reinterpret_cast<const float*>(ls.work<S>().x.p), d_dx.p, stream);
     }
     has_dx = true;

@@ -78,7 +78,8 @@ public:
     void perf_dx(double* out);
     // right-hand side of the scaled system into the solver's b vector (precision S)
     template <class S> void build_rhs();
-    template <class S> void store_dx();                 // solver x -> resident dx (double, internal planes)
+    template <class S> void store_dx();                 // solver x -> resident dx (double, internal planes); no copy when the solver wrote it there itself
+    double* dx_device() { return d_dx.p; }              // the resident dx: what a double solve may be handed as LinSolver::solution_mirror
     void dx_to_host(double* dx);                        // resident dx -> host, equation-major caller order
     void update_state(const double* dx_host, double relax);
     void stabilize_update(int relax_type, double omega);

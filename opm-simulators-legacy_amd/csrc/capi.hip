@@ -609,7 +609,13 @@ int opmgpu_solve(opmgpu_ctx* c, int single_precision, double* dx, int* iters, do
             Timed t(c, PH_SOLVE);
             c->model->early_factor_pending = false;          // (no convergence check between the assembly and this solve: the solve starts the factorisation itself)
             if (single_precision) { c->ls->ensure_work<float>(); c->model->build_rhs<float>(); st = solve_loaded<float>(c, true, res); if (st == OPMGPU_OK || st == OPMGPU_ELINSOLVE) c->model->store_dx<float>(); }
-            else { c->ls->ensure_work<double>(); c->model->build_rhs<double>(); st = solve_loaded<double>(c, true, res); if (st == OPMGPU_OK || st == OPMGPU_ELINSOLVE) c->model->store_dx<double>(); }
+            else {
+                struct MirrorScope { LinSolver& ls; ~MirrorScope() { ls.solution_mirror = nullptr; ls.mirror_written = false; } } scope{ *c->ls };      // (also when the solve throws)
+                c->ls->ensure_work<double>(); c->model->build_rhs<double>();
+                c->ls->solution_mirror = c->model->dx_device();          // a GMRES solve stores its solution there too: store_dx then has nothing to copy
+                st = solve_loaded<double>(c, true, res);
+                if (st == OPMGPU_OK || st == OPMGPU_ELINSOLVE) c->model->store_dx<double>();
+            }
         }
         c->cur_single = single_precision ? 1 : 0;
         if (iters) *iters = res.iterations;

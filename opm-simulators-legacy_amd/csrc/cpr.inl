@@ -555,6 +555,8 @@ template <class S> void LinSolver::cpr_apply(const S* d, S* v, double relax, con
     const int g = grid_for(plan.nb);
     const bool coarse = coarse_nsub >= 1;
     const bool emulated = !comm && emulate_ranks > 1;
+    // the sum [x_p; 0; 0] + ILU0^-1 z formed inside the sweeps (linsolver.hpp, cpr_cancel_p): a two-level plan, every relaxation factor 1
+    const bool cancel = cancel_p_now && plan.nlevels == 2 && relax == 1.0 && ell.relax == 1.0 && fill_level == 0 && !point_stage2;
     const bool fused_rsum = coarse && !emulated && g <= kCsRowParts;       // real coarse space: restriction fused into the kernel below
     hipEvent_t kt_a = kt.begin();
     double* const cs_parts = coarse ? cs_buf.p + size_t(2) * coarse_nsub * coarse_nsub + coarse_nsub : nullptr;   // own scratch (the BiCGStab partial arrays are live across an application)
@@ -638,11 +640,11 @@ template <class S> void LinSolver::cpr_apply(const S* d, S* v, double relax, con
     else { if (exchange) halo(comm, w.hx.p, stream); presidual(0); }
     kt.end(KT_CPR_OTHER, kt_a);
     if (point_stage2 && sizeof(S) == 8) point_ilu_apply(reinterpret_cast<const double*>(w.z.p), reinterpret_cast<double*>(v), relax);      // the reference's own stage 2 (pointilu.inl)
-    else ilu_apply<S>(w.z.p, v, relax, ctl);
+    else ilu_apply<S>(w.z.p, v, relax, ctl, cancel ? d : (const S*)nullptr, cancel ? xp : (const S*)nullptr);
     kt_a = kt.begin();
     if (well_woodbury && wb_active && lowrank.nw > 0 && lowrank.P && !comm && wb_buf.p && fill_level == 0)
         hipLaunchKernelGGL((k_wb_apply<S>), dim3(lowrank.nw), dim3(kBlock), 0, stream, lowrank, plan.nbp, (const double*)wb_buf.p,
                            (const double*)(wb_buf.p + size_t(21) * lowrank.nperf), v, ctl);
-    hipLaunchKernelGGL((k_cpr_add_p<S>), dim3(g), dim3(kBlock), 0, stream, plan.nb, xp, v, ctl, S(ell.relax));
+    if (!cancel) hipLaunchKernelGGL((k_cpr_add_p<S>), dim3(g), dim3(kBlock), 0, stream, plan.nb, xp, v, ctl, S(ell.relax));
     kt.end(KT_CPR_OTHER, kt_a);
 }

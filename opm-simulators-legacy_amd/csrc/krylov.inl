@@ -172,8 +172,11 @@ __global__ __launch_bounds__(kBlock) void k_final_check(int j, SolveCtl* __restr
         if (tick_ptr) { __threadfence_system(); *(volatile int*)tick_ptr = tick; }
     }
 }
-__global__ void k_ctl_init(SolveCtl* ctl, SolveCtl* hst, double red)
+// one workgroup.  zbuf (optional): nz doubles cleared in the same launch -- GMRES' Hessenberg block, instead of a fill of its own
+__global__ __launch_bounds__(kBlock) void k_ctl_init(SolveCtl* ctl, SolveCtl* hst, double red, double* __restrict__ zbuf = nullptr, int nz = 0)
 {
+    for (int i = threadIdx.x; i < nz; i += kBlock) zbuf[i] = 0.0;
+    if (threadIdx.x != 0) return;
     hst->done = 0; hst->flag = 0; hst->iters = 0; hst->decided = 0; hst->norm2 = 0.0; hst->norm0_2 = 0.0;
     ctl->rho[0] = 1.0; ctl->rho[1] = 1.0; ctl->alpha = 1.0; ctl->omega = 1.0;
     ctl->norm0_2 = 0.0; ctl->norm2 = 0.0; ctl->thresh2 = 0.0; ctl->done = 0; ctl->flag = 0; ctl->iters = 0; ctl->decided = 0;
@@ -263,6 +266,9 @@ template <class S> SolveResult LinSolver::bicgstab(const opmgpu_params& prm)
     if (cpr) { if (mx) cpr_prepare_mixed(); else cpr_prepare<S>(); }
     if (factor_deferred) { factor_deferred = false; if (mx) factor_async<float>(); else factor_async<S>(); }
     if (cpr) { if (mx) { if (!wf.amg->npost0_user) wf.amg->npost0 = 2; } else if (!w.amg->npost0_user) w.amg->npost0 = 2; }   // post-sweeps on level 0: 2 under BiCGStab, 1 under GMRES (see gmres)
+    solution_mirror = nullptr; mirror_written = false;          // (the mirror is GMRES': this solver's caller copies x)
+    cancel_p_now = false;
+    if (cpr) { if (mx) wf.amg->lane_restrict = lean_conditions(); else w.amg->lane_restrict = lean_conditions(); }      // the V-cycle's restriction: shared with gmres()
     // (with cpr_relax != 1 the pressure part of M^-1 p is scaled, which the closed form does not cover)
     // (mixed precision: the float ILU0 is not the ILU0 of exactly the double matrix -- the closed form would be off by float rounding)
     const bool closed = closed_form_level0 && emulate_ranks <= 1 && !(cpr && ell.relax != 1.0) && !mx && !(cpr && point_stage2) && fill_level == 0;      // (ell.relax = cpr_relax; under CPR prm.ilu_relaxation holds cpr_relax * cpr_stage2_relax: solve_loaded)
@@ -645,13 +651,17 @@ __global__ void k_gm_solve_y(int cnt, int m, GmState g)
         g.y[a] = rhs / g.H[a * m + a];
     }
 }
-template <class S>
-__global__ __launch_bounds__(kBlock) void k_gm_update_x(long n, int cnt, const double* __restrict__ y, const S* __restrict__ kry, S* __restrict__ x)
+// FIRST: the first cycle of a solve from x0 = 0 -- x is not loaded (and was not cleared), the sum is added to the literal 0: the same
+// operations in the same order as on a cleared x.  x2 (optional): every entry is stored there as well (LinSolver::solution_mirror)
+template <class S, bool FIRST = false>
+__global__ __launch_bounds__(kBlock) void k_gm_update_x(long n, int cnt, const double* __restrict__ y, const S* __restrict__ kry, S* __restrict__ x,
+                                                        S* __restrict__ x2 = nullptr)
 {
     constexpr int L = 16 / sizeof(S);              // 16-byte lanes (n is a multiple of 192)
     struct alignas(16) Pack { S v[L]; };
     const long nv = n / L;
     Pack* __restrict__ x4 = reinterpret_cast<Pack*>(x);
+    Pack* __restrict__ m4 = reinterpret_cast<Pack*>(x2);
     for (long q = blockIdx.x * long(kBlock) + threadIdx.x; q < nv; q += long(gridDim.x) * kBlock) {
         Pack acc;
 #pragma unroll
@@ -662,15 +672,22 @@ __global__ __launch_bounds__(kBlock) void k_gm_update_x(long n, int cnt, const d
 #pragma unroll
             for (int u = 0; u < L; ++u) acc.v[u] += ya * k4.v[u];
         }
-        Pack xv = x4[q];
+        Pack xv;
+        if (FIRST) {
+#pragma unroll
+            for (int u = 0; u < L; ++u) xv.v[u] = 0;
+        } else xv = x4[q];
 #pragma unroll
         for (int u = 0; u < L; ++u) xv.v[u] += acc.v[u];
         x4[q] = xv;
+        if (x2) m4[q] = xv;
     }
     for (long i = nv * L + blockIdx.x * long(kBlock) + threadIdx.x; i < n; i += long(gridDim.x) * kBlock) {
         S acc = 0;
         for (int a = cnt - 1; a >= 0; --a) acc += S(y[a]) * kry[long(a) * n + i];
-        x[i] += acc;
+        const S xn = (FIRST ? S(0) : x[i]) + acc;
+        x[i] = xn;
+        if (x2) x2[i] = xn;
     }
 }
 template <class S>
@@ -769,8 +786,19 @@ template <class S> SolveResult LinSolver::gmres(const opmgpu_params& prm)
     static const bool cgs_pyth_env = env_flag("OPMGPU_GMRES_PYTH", true);
     const bool cgs_pyth = cgs_pyth_env && prm.linear_solver_reduction >= 1e-4;
     if (flex) w.kryz.alloc(size_t(m) * n);
+    // The lean start and end of a solve (linsolver.hpp, lean_solve): no clear of x, gmbuf cleared by k_ctl_init, no k_gm_reset_s behind
+    // that clear, the solution stored to the caller's mirror as well.  Not with the flexible form or the verified residual, which keep
+    // the launches they were validated with.
+    const bool lean = lean_conditions() && !flex && !verify;
+    // (double only, like the closed form of the product: float and mixed solves keep the plain sequence, whose rounding the verified
+    // residual's float cases are compared against; cpr_apply adds the plan's and the factors' conditions)
+    cancel_p_now = cpr && cpr_cancel_p && plain_setup() && !flex && !verify && sizeof(S) == 8 && !mx;
+    S* mirror = nullptr;
+    if constexpr (sizeof(S) == 8) { if (lean) mirror = solution_mirror; }
+    solution_mirror = nullptr; mirror_written = false;
+    if (cpr) { if (mx) wf.amg->lane_restrict = lean; else w.amg->lane_restrict = lean; }
     gmbuf.alloc(size_t(m + 1) * m + (m + 1) + 3 * m + 8 + (m + 1));
-    gmbuf.zero(stream);
+    if (!lean) gmbuf.zero(stream);
     GmState g; g.H = gmbuf.p; g.s = g.H + size_t(m + 1) * m; g.cs = g.s + (m + 1); g.sn = g.cs + m; g.y = g.sn + m; g.gam = nullptr;
     // Closed form of the product on the level-0 rows (k_spmv, GM): on the conditions of bicgstab()'s `closed`, and
     //   double only       -- in float the recurrence of gamma drifts from the explicit product by more than the Arnoldi estimate tolerates
@@ -846,11 +874,17 @@ template <class S> SolveResult LinSolver::gmres(const opmgpu_params& prm)
         dot(src, src);
         hipLaunchKernelGGL((k_gm_normalize<S>), dim3(gv), dim3(kBlock), 0, stream, n, -1, first, prm.linear_solver_reduction, dot_arr, dot_np,
                            g.H, g.s, src, V(0), d_ctl, h_ctl_dev, g.gam);
-        hipLaunchKernelGGL(k_gm_reset_s, dim3(1), dim3(1), 0, stream, m, g);
+        // s[1..m] = 0 for the new cycle (k_gm_normalize wrote s[0]).  Lean, first cycle: k_ctl_init has just cleared all of gmbuf, s included
+        if (!(lean && first)) hipLaunchKernelGGL(k_gm_reset_s, dim3(1), dim3(1), 0, stream, m, g);
     };
-    // x0 = 0: defect = b
-    w.x.zero(stream);
-    hipLaunchKernelGGL(k_ctl_init, dim3(1), dim3(1), 0, stream, d_ctl, h_ctl_dev, prm.linear_solver_reduction);
+    // x0 = 0: defect = b.  Lean: x is not cleared, the first cycle's combination writes it (k_gm_update_x<S, true>); the exits that
+    // leave without a combination clear it below
+    bool x_written = !lean;
+    if (!lean) {
+        w.x.zero(stream);
+        hipLaunchKernelGGL(k_ctl_init, dim3(1), dim3(1), 0, stream, d_ctl, h_ctl_dev, prm.linear_solver_reduction);
+    } else
+        hipLaunchKernelGGL(k_ctl_init, dim3(1), dim3(kBlock), 0, stream, d_ctl, h_ctl_dev, prm.linear_solver_reduction, gmbuf.p, int(gmbuf.n));
     if (flex) normalize_start(w.b.p, 1);
     else { precond(w.b.p, w.t.p); normalize_start(w.t.p, 1); }
     // no synchronisation here: the first iteration is enqueued behind the set-up (factorisation, hierarchy, first application); a zero
@@ -955,7 +989,9 @@ template <class S> SolveResult LinSolver::gmres(const opmgpu_params& prm)
         if (h_ctl->done && h_ctl->iters == 0) break;                   // zero defect: x = 0 is the solution, no column was built
         // x += sum_a y_a v_a with R y = s   (i columns were completed)
         hipLaunchKernelGGL(k_gm_solve_y, dim3(1), dim3(1), 0, stream, i, m, g);
-        hipLaunchKernelGGL((k_gm_update_x<S>), dim3(gv), dim3(kBlock), 0, stream, n, i, (const double*)g.y, flex ? (const S*)w.kryz.p : (const S*)w.kry.p, w.x.p);
+        if (!x_written) hipLaunchKernelGGL((k_gm_update_x<S, true>), dim3(gv), dim3(kBlock), 0, stream, n, i, (const double*)g.y, (const S*)w.kry.p, w.x.p, mirror);
+        else hipLaunchKernelGGL((k_gm_update_x<S>), dim3(gv), dim3(kBlock), 0, stream, n, i, (const double*)g.y, flex ? (const S*)w.kryz.p : (const S*)w.kry.p, w.x.p, mirror);
+        x_written = true;
         if (!stop && j <= maxit) {                                     // restart from the true defect
             product(w.x.p, w.v.p, (const SolveCtl*)nullptr);
             hipLaunchKernelGGL((k_gm_defect<S>), dim3(gv), dim3(kBlock), 0, stream, n, (const S*)w.b.p, (const S*)w.v.p, w.r.p);
@@ -964,6 +1000,10 @@ template <class S> SolveResult LinSolver::gmres(const opmgpu_params& prm)
             else { precond(w.r.p, w.t.p); normalize_start(w.t.p, 0); }
         }
     }
+    // lean: no combination ran (zero defect, a breakdown in the first cycle, no iteration allowed) -- x = 0, as the clear would have left it;
+    // the mirror is then not written and the caller copies x as before
+    if (!x_written) w.x.zero(stream);
+    else mirror_written = mirror != nullptr;
     // the status block is current (the last iteration's tick was waited for); what is still in flight (the combination of the basis
     // vectors into x) is ordered before everything the caller enqueues next on this stream.  Without polling: synchronise.
     if (!poll_status || !stop) OPMGPU_HIP(hipStreamSynchronize(stream));

@@ -229,7 +229,7 @@ template <class S>
 __global__ __launch_bounds__(kBlock) void k_ilu_lower(int xm, int lo, int hi, int n0, int nbp, int top, S w, const int32_t* __restrict__ slice_ptr,
                                                       const int32_t* __restrict__ col, const int16_t* __restrict__ nlower,
                                                       const S* __restrict__ lu, const S* __restrict__ d, S* __restrict__ v,
-                                                      const SolveCtl* __restrict__ ctl)
+                                                      const SolveCtl* __restrict__ ctl, const S* __restrict__ xp = nullptr)
 {
     if (ctl && ctl->done) return;
     const int nchunks = (hi - lo + kBlock - 1) / kBlock;
@@ -257,6 +257,7 @@ __global__ __launch_bounds__(kBlock) void k_ilu_lower(int xm, int lo, int hi, in
         const S t1 = b[192] * r0 + b[256] * r1 + b[320] * r2;
         const S t2 = b[384] * r0 + b[448] * r1 + b[512] * r2;
         r0 = t0; r1 = t1; r2 = t2;
+        if (xp) r0 += xp[row];      // CPR, top level of a two-level plan: the row is final, the pressure correction is added here (LinSolver::cpr_cancel_p)
     }
     v[row] = r0; v[nbp + row] = r1; v[2 * nbp + row] = r2;
 }
@@ -527,6 +528,8 @@ LinSolver::LinSolver(hipStream_t s) : stream(s)
     OPMGPU_HIP(hipEventCreateWithFlags(&ev[0], hipEventDisableTiming));
     OPMGPU_HIP(hipEventCreateWithFlags(&ev[1], hipEventDisableTiming));
     closed_form_level0 = env_flag("OPMGPU_CLOSED", closed_form_level0);
+    lean_solve = env_flag("OPMGPU_LEAN_SOLVE", lean_solve);
+    cpr_cancel_p = env_flag("OPMGPU_CPR_CANCEL_P", cpr_cancel_p);
     well_woodbury = env_flag("OPMGPU_WELL_WOODBURY", well_woodbury);
     cpr_speculate = env_flag("OPMGPU_CPR_SPECULATE", cpr_speculate);
     cpr_weight_mode = env_int("OPMGPU_CPR_WEIGHTS", cpr_weight_mode);
@@ -546,6 +549,10 @@ LinSolver::LinSolver(hipStream_t s) : stream(s)
     emulate_ranks = env_int("OPMGPU_EMULATE_RANKS", emulate_ranks);
     emulate_what = env_int("OPMGPU_EMULATE_WHAT", emulate_what);
     coarse_mode = env_int("OPMGPU_COARSE", coarse_mode);
+}
+bool LinSolver::plain_setup() const
+{
+    return !comm && emulate_ranks <= 1 && fill_level == 0 && !point_stage2 && !(well_woodbury && wb_active);
 }
 LinSolver::~LinSolver()
 {
@@ -810,7 +817,10 @@ void LinSolver::join_factor()
     factor_pending = false;
 }
 
-template <class S> void LinSolver::ilu_apply(const S* d, S* v, double relax, const SolveCtl* ctl)
+// d0, xp (CPR with cancel_p_now; cpr_apply has checked the plan and the factors): d = d0 - A [xp; 0; 0] is the second stage's input, d0 the
+// application's.  v = [xp; 0; 0] + (LU)^-1 d without a pass of its own for the sum: the top level's rows add xp as they become final, a
+// level-0 row r has D_r = A_rr and U_rb = A_rb, so its entry of the SUM is D_r^-1 (d0_r - sum_b A_rb v_b) with v_b the final top-level entries
+template <class S> void LinSolver::ilu_apply(const S* d, S* v, double relax, const SolveCtl* ctl, const S* d0, const S* xp)
 {
     join_factor();
     KtScope kts(kt, KT_ILU_APPLY);
@@ -827,13 +837,13 @@ template <class S> void LinSolver::ilu_apply(const S* d, S* v, double relax, con
         const int lo = plan.level_ptr[l], hi = plan.level_ptr[l + 1];
         if (hi == lo) continue;
         hipLaunchKernelGGL((k_ilu_lower<S>), dim3(grid8_for(hi - lo)), dim3(kBlock), 0, stream, xcd_mode(), lo, hi, n0, plan.nbp, int(l == L - 1), S(relax),
-                           dp.slice_ptr.p, dp.col.p, dp.nlower.p, w.LU.p, d, v, ctl);
+                           dp.slice_ptr.p, dp.col.p, dp.nlower.p, w.LU.p, d, v, ctl, xp);
     }
     for (int l = L - 2; l >= 0; --l) {
         const int lo = plan.level_ptr[l], hi = plan.level_ptr[l + 1];
         if (hi == lo) continue;
         hipLaunchKernelGGL((k_ilu_upper<S>), dim3(grid8_for(hi - lo)), dim3(kBlock), 0, stream, xcd_mode(), lo, hi, n0, plan.nbp, S(relax), dp.slice_ptr.p, dp.col.p,
-                           dp.nlower.p, dp.rowlen.p, w.LU.p, d, v, ctl, (const int8_t*)dp.simple.p, ((emulate_what & 1) ? pre_matrix<S>() : matrix<S>()));
+                           dp.nlower.p, dp.rowlen.p, w.LU.p, (l == 0 && d0) ? d0 : d, v, ctl, (const int8_t*)dp.simple.p, ((emulate_what & 1) ? pre_matrix<S>() : matrix<S>()));
     }
 }
 
@@ -1081,7 +1091,7 @@ double LinSolver::time_kernel(int kernel, int reps, int single_precision)
 #define OPMGPU_INST(S)                                                                  \
     template void LinSolver::ensure_work<S>();                                           \
     template int LinSolver::factor<S>(bool);                                                 \
-    template void LinSolver::ilu_apply<S>(const S*, S*, double, const SolveCtl*);        \
+    template void LinSolver::ilu_apply<S>(const S*, S*, double, const SolveCtl*, const S*, const S*);        \
     template void LinSolver::spmv<S>(const S*, S*);                                      \
     template void LinSolver::spmv_at<S>(const S*, S*, const S*, const int32_t*);        \
     template void LinSolver::cpr_prepare<S>();                                           \

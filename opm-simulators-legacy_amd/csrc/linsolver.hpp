@@ -153,7 +153,7 @@ public:
 
     template <class S> int factor(bool wait = true);                                // ILU0 numeric factorisation
     int factor_status() const { return (h_flags[0] & 1) ? OPMGPU_ESINGULAR : OPMGPU_OK; }   // valid after a stream synchronisation
-    template <class S> void ilu_apply(const S* d, S* v, double relax, const SolveCtl* ctl = nullptr);
+    template <class S> void ilu_apply(const S* d, S* v, double relax, const SolveCtl* ctl = nullptr, const S* d0 = nullptr, const S* xp = nullptr);
     template <class S> void spmv(const S* x, S* y);
     template <class S> void spmv_at(const S* x, S* y, const S* val, const int32_t* col);    // the same operator on another copy of the matrix arrays
     // CPR (solver_approach=cpr): build / refresh the pressure AMG for the current matrix; two-stage apply
@@ -314,6 +314,23 @@ public:
     // gamma_i base_i with one device-resident scalar per column (linsolver.hip, k_spmv; the conditions: bicgstab() / gmres()).
     // A/B switch for both: OPMGPU_CLOSED=0, read when the solver is created
     bool closed_form_level0 = true;
+    // Passes and launches a GMRES solve does not need (krylov.inl, gmres()): x is not cleared (the first cycle's
+    // combination starts from the literal 0), the combination also stores to the caller's solution_mirror, the clear of gmbuf rides in
+    // k_ctl_init, no k_gm_reset_s behind that clear, and the V-cycle's restriction runs eight lanes per aggregate.  The same bits as the
+    // plain launches.  A/B switch: OPMGPU_LEAN_SOLVE=0, read when the solver is created
+    bool lean_solve = true;
+    bool plain_setup() const;              // what every item below asks of the set-up: single GPU, no emulated ranks, plain ILU0 second stage, no Woodbury correction
+    bool lean_conditions() const { return lean_solve && plain_setup(); }
+    // Optional second destination of a double GMRES solve's solution (same layout as work<double>().x), set by the caller before the solve
+    // and taken by the first gmres() call behind it; mirror_written: that call stored every entry of x there too
+    double* solution_mirror = nullptr;
+    bool mirror_written = false;
+    // The pressure part cancels on the level-0 rows (cpr_apply, ilu_apply): in a two-level plan with every relaxation
+    // factor 1 a level-0 row's entry of M^-1 d, pressure correction included, is D^-1 (d - sum A_rb (M^-1 d)_b) with d the application's
+    // input -- the top level's forward sweep adds x_p to its rows, the level-0 backward sweep starts from d, k_cpr_add_p is not launched.
+    // Rounds differently from the plain sequence.  Double GMRES solves only.  A/B switch: OPMGPU_CPR_CANCEL_P=0, read when the solver is created
+    bool cpr_cancel_p = true;
+    bool cancel_p_now = false;             // this solve's applications take that path (set by the solvers)
     bool cpr_halo_xp = true;        // multi-GPU CPR: halo-exchange the pressure correction before stage 2 (A/B: OPMGPU_CPR_HALO_XP=0)
     int amg_lag = 1, amg_age = 0;   // A/B: OPMGPU_AMG_LAG
     // refresh policy of the coarse operators of the pressure hierarchy (see cpr_prepare); OPMGPU_AMG_LAG_COARSE
