@@ -410,11 +410,19 @@ int opmgpu_update_state(opmgpu_ctx* ctx, const double* dx, double relax);
  * after opmgpu_set_device_wells, opmgpu_assemble adds the well terms itself, opmgpu_solve uses the coupled operator,
  * opmgpu_update_state also recovers and updates the well unknowns (updateWellState, :611-650), and
  * opmgpu_save_state / restore_state carry the well state along.  Fields mirror opm-core's `Wells` struct.
+ * Shared cells: any number of DIFFERENT wells may perforate one cell (a water and a gas injector of a WAG pair at the same I, J, K, a
+ * producer and its sidetrack, two deviated wells crossing), as in the reference, whose StandardWells works on perforation-to-cell
+ * operators.  One well naming the same cell twice is OPMGPU_EINVAL.  The wells' contributions to such a cell's row -- residual, diagonal
+ * block, right-hand-side term of the eliminated well equations, the coupled operator's P t terms, the pressure stage's border columns
+ * -- are summed in ascending perforation index, the order of well_cells: a fixed order, so every result is the same bits from run to
+ * run.  Refused with shared cells (OPMGPU_EINVAL, text in opmgpu_last_error): a decomposed context (a communicator is attached, whichever
+ * call comes first) and the subdomain coarse space (OPMGPU_COARSE=2, OPMGPU_EMULATE_RANKS > 1); OPMGPU_WELL_WOODBURY=1 is switched off
+ * for such a well list, with one line on stderr.
  * ---------------------------------------------------------------------------------------- */
 typedef struct opmgpu_wells {
     int32_t        nw;
     const int32_t* well_connpos;   /* [nw+1]                                                   */
-    const int32_t* well_cells;     /* [nperf] (a cell may be perforated by one well only)      */
+    const int32_t* well_cells;     /* [nperf] (wells may share a cell; no cell twice in ONE well) */
     const double*  WI;             /* [nperf] well index (connection transmissibility factor)  */
     const int32_t* type;           /* [nw] 0 = INJECTOR, 1 = PRODUCER                          */
     const int32_t* allow_cf;       /* [nw] allow cross flow; NULL = all 1                      */
@@ -472,6 +480,11 @@ int opmgpu_set_device_wells(opmgpu_ctx* ctx, const opmgpu_wells* wells);
  * re-plan.  Multi-GPU: rank-local (the factors of this rank's wells), no communication.
  * OPMGPU_EINVAL with text in opmgpu_last_error(ctx): no device wells are set; a factor is not finite; a factor is outside (0, 1]. */
 int opmgpu_set_well_efficiency(opmgpu_ctx* ctx, const double* factors);
+/* Cells perforated by more than one well (computeWellFlux, StandardWells_impl.hpp:396-560, and addWellContributionToMassBalanceEq,
+ * BlackoilModelBase_impl.hpp:953-975, which superpose any number of perforations on a cell): *shared_rows = number of such cells,
+ * *max_wells_per_cell = the most wells found in one cell; both 0 for a well list without shared cells.  Either pointer may be NULL.
+ * OPMGPU_EINVAL without device wells. */
+int opmgpu_well_shared_cells(opmgpu_ctx* ctx, int32_t* shared_rows, int32_t* max_wells_per_cell);
 /* the factors in force (factors[nw]); OPMGPU_EINVAL without device wells */
 int opmgpu_get_well_efficiency(opmgpu_ctx* ctx, double* factors);
 /* WellStateFullyImplicitBlackoil fields: bhp[nw], wellRates qs[nw*3]; perfPress perf_press[nperf] and perfPhaseRates

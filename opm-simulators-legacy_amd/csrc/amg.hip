@@ -207,7 +207,7 @@ __device__ __forceinline__ S sell_row_dot(const S* __restrict__ v, const int32_t
 template <class S>
 struct Border {
     int nw = 0, n = 0, gcells = 0;
-    const int32_t *connpos = nullptr, *perf_row = nullptr, *perf_of_row = nullptr, *perf_well = nullptr;
+    const int32_t *connpos = nullptr, *perf_row = nullptr, *perf_of_row = nullptr, *perf_well = nullptr, *perf_next = nullptr;
     const S *bcol = nullptr, *crow = nullptr, *dw = nullptr;
 };
 template <class S>
@@ -215,17 +215,20 @@ Border<S> border_of(const AmgLevel<S>& F, int gcells)
 {
     Border<S> B;
     if (F.nw == 0) return B;
-    B.nw = F.nw; B.n = F.n; B.gcells = gcells; B.connpos = F.b_connpos; B.perf_row = F.b_perf_row; B.perf_of_row = F.b_perf_of_row; B.perf_well = F.b_perf_well;
+    B.nw = F.nw; B.n = F.n; B.gcells = gcells; B.connpos = F.b_connpos; B.perf_row = F.b_perf_row; B.perf_of_row = F.b_perf_of_row; B.perf_well = F.b_perf_well; B.perf_next = F.b_perf_next;
     B.bcol = F.val.p + F.nentries; B.crow = B.bcol + F.nperf; B.dw = B.crow + F.nperf;
     return B;
 }
-// cell row: the column entry towards its well's unknown
+// cell row: the column entries towards its wells' unknowns (one per well that perforates the cell, in ascending perforation index)
 template <class S, class XF>
 __device__ __forceinline__ S border_cell(const Border<S>& B, int row, XF xfun)
 {
     if (!B.nw) return S(0);
-    const int j = B.perf_of_row[row];
-    return j >= 0 ? B.bcol[j] * xfun(B.n + B.perf_well[j]) : S(0);
+    int j = B.perf_of_row[row];
+    if (j < 0) return S(0);
+    S acc = B.bcol[j] * xfun(B.n + B.perf_well[j]);
+    for (j = B.perf_next[j]; j >= 0; j = B.perf_next[j]) acc += B.bcol[j] * xfun(B.n + B.perf_well[j]);
+    return acc;
 }
 // well row k by one workgroup: sum_j crow[j] xfun(perf_row[j]) + dw[k] xfun(n + k); result valid in thread 0 (fixed order: deterministic)
 template <class S, class XF>
@@ -869,15 +872,13 @@ void AmgHierarchy<S>::setup(const Plan& P, const int32_t* d_slice_ptr, const int
     // bordered level 0 (amg.hpp): one extra unknown per well; too many wells for the dense coarsest level -> no border
     const int nwb = (border && border->nw > 0 && border->nw <= kDenseMax / 2) ? border->nw : 0;
     const int npb = nwb ? border->nperf : 0;
-    std::vector<int32_t> perf_of(P.nb, -1);
-    for (int j = 0; j < npb; ++j) {
-        // one perforation per cell: the row kernels see ONE border column per cell (perf_of_row), the dense coarsest inverse scatters each
-        if (perf_of[border->perf_row[j]] >= 0) throw HipError(OPMGPU_EINVAL, "CPR well border: a cell is perforated by two wells");
-        perf_of[border->perf_row[j]] = j;
-    }
+    // one border column per (row, well) pair: a row's perforations as a chain in ascending perforation index (first / next, like the
+    // device maps perf_of_row / perf_next); the dense coarsest inverse scatters each pair to its own element
+    std::vector<int32_t> perf_of(P.nb, -1), perf_nx(npb, -1), nborder(P.nb, 0);
+    for (int j = npb - 1; j >= 0; --j) { const int r = border->perf_row[j]; perf_nx[j] = perf_of[r]; perf_of[r] = j; ++nborder[r]; }
     HostCsr A;
     A.n = P.nb + nwb; A.rowptr.assign(A.n + 1, 0);
-    for (int r = 0; r < P.nb; ++r) A.rowptr[r + 1] = A.rowptr[r] + P.rowlen[r] + (perf_of[r] >= 0 ? 1 : 0);
+    for (int r = 0; r < P.nb; ++r) A.rowptr[r + 1] = A.rowptr[r] + P.rowlen[r] + nborder[r];
     for (int k = 0; k < nwb; ++k) A.rowptr[P.nb + k + 1] = A.rowptr[P.nb + k] + (border->connpos[k + 1] - border->connpos[k]) + 1;
     A.col.resize(A.rowptr[A.n]); A.val.resize(A.col.size()); A.dev.resize(A.col.size());
     std::vector<int32_t> diag0(A.n, 0), well_of(npb, 0);
@@ -888,8 +889,8 @@ void AmgHierarchy<S>::setup(const Plan& P, const int32_t* d_slice_ptr, const int
             A.col[s] = P.sell_col[e]; A.val[s] = ap_host[e]; A.dev[s] = e;
             if (A.col[s] == r) diag0[r] = e;
         }
-        if (perf_of[r] >= 0) {          // column entry towards the well's unknown: device id behind the SELL values
-            const int j = perf_of[r], s = A.rowptr[r] + P.rowlen[r];
+        int s = A.rowptr[r] + P.rowlen[r];
+        for (int j = perf_of[r]; j >= 0; j = perf_nx[j], ++s) {          // column entries towards the wells' unknowns: device ids behind the SELL values
             A.col[s] = P.nb + well_of[j]; A.val[s] = border->bcol[j]; A.dev[s] = P.nentries + j;
         }
     }
@@ -903,7 +904,7 @@ void AmgHierarchy<S>::setup(const Plan& P, const int32_t* d_slice_ptr, const int
     std::unique_ptr<AmgLevel<S>> L(new AmgLevel<S>());
     L->n = P.nb; L->nslices = P.nslices; L->nentries = P.nentries; L->slice_ptr = d_slice_ptr; L->col = d_col;
     L->nw = nwb; L->nperf = npb;
-    if (nwb) { L->b_connpos = border->d_connpos; L->b_perf_row = border->d_perf_row; L->b_perf_of_row = border->d_perf_of_row; L->b_perf_well = border->d_perf_well; }
+    if (nwb) { L->b_connpos = border->d_connpos; L->b_perf_row = border->d_perf_row; L->b_perf_of_row = border->d_perf_of_row; L->b_perf_well = border->d_perf_well; L->b_perf_next = border->d_perf_next; }
     L->diag_entry.upload(diag0, stream);
     int npin = nwb;
     const int kMaxDense = kDenseMax;

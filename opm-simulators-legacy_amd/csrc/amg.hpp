@@ -53,7 +53,8 @@ struct AmgLevel {
     int nw = 0, nperf = 0;
     const int32_t* b_connpos = nullptr;         // [nw+1]  (device, owned by the well model)
     const int32_t* b_perf_row = nullptr;        // [nperf]
-    const int32_t* b_perf_of_row = nullptr;     // [>= n] perforation of a row or -1
+    const int32_t* b_perf_of_row = nullptr;     // [>= n] first perforation of a row or -1
+    const int32_t* b_perf_next = nullptr;       // [nperf] next perforation of the same row or -1 (a cell of several wells: one border column each)
     const int32_t* b_perf_well = nullptr;       // [nperf]
     int ntot() const { return n + nw; }
     // Distributed level of a decomposed hierarchy (AmgHierarchy::setup with a communicator).  Level 0: the rows are the
@@ -78,7 +79,7 @@ struct AmgBorderSpec {
     int nw = 0, nperf = 0;
     std::vector<int32_t> connpos, perf_row;     // internal rows
     std::vector<double> bcol, crow, dw;         // representative values (first matrix) for the aggregation strengths
-    const int32_t *d_connpos = nullptr, *d_perf_row = nullptr, *d_perf_of_row = nullptr, *d_perf_well = nullptr;
+    const int32_t *d_connpos = nullptr, *d_perf_row = nullptr, *d_perf_of_row = nullptr, *d_perf_well = nullptr, *d_perf_next = nullptr;
 };
 
 template <class S>

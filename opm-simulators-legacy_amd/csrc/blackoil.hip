@@ -1025,6 +1025,7 @@ double BlackoilDevice::relative_change()
 // multi-GPU: the communicator knows rank-local caller numbering; (re)derive internal rows + global sums
 void BlackoilDevice::attach_comm(CommBase* c, int n_owned)
 {
+    if (shared_well_rows() > 0) throw HipError(OPMGPU_EINVAL, "multi-GPU: a cell is perforated by several wells; a decomposed run (a communicator is attached) does not support that");
     ls.comm = c;
     n_owned_cells = n_owned;
     for (int32_t pc : h_well_cells) if (device_wells && pc >= n_owned) throw HipError(OPMGPU_EINVAL, "multi-GPU: a well perforates a ghost cell; keep every well on one rank");

@@ -99,6 +99,8 @@ public:
     int set_device_wells(const opmgpu_wells* spec);
     int set_well_efficiency(const double* factors);         // [nw] in (0, 1] or NULL = ones; throws HipError(OPMGPU_EINVAL) with the reason
     int get_well_efficiency(double* factors) const;
+    int well_shared_cells(int32_t* shared_rows, int32_t* max_wells_per_cell) const;      // throws HipError(OPMGPU_EINVAL) without device wells
+    int shared_well_rows() const;                           // rows perforated by several wells (0 without device wells)
     int well_state_set(const double* bhp, const double* qs, const double* perf_press, const double* perf_rates);
     int well_state_get(double* bhp, double* qs, double* perf_press, double* perf_rates);
     int well_convergence(double* flux3, double* ctrl);

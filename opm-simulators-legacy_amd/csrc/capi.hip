@@ -362,8 +362,10 @@ template <class S> static int cpr_level_get_t(LinSolver& ls, int level, int32_t*
     std::vector<int32_t> internal(nt), outer(nt);
     for (int i = 0; i < nt; ++i) internal[i] = outer[i] = i;
     if (level == 0) for (int i = 0; i < n; ++i) { internal[i] = ls.plan.pos[i]; outer[ls.plan.pos[i]] = i; }
-    std::vector<int32_t> perf_of(n, -1), well_of(nperf, 0);
-    for (int k = 0; k < nw; ++k) for (int j = connpos[k]; j < connpos[k + 1]; ++j) { perf_of[perf_row[j]] = j; well_of[j] = k; }
+    // a row's perforations as a chain in ascending perforation index: one border column per well of the cell
+    std::vector<int32_t> perf_of(n, -1), perf_nx(nperf, -1), well_of(nperf, 0);
+    for (int k = 0; k < nw; ++k) for (int j = connpos[k]; j < connpos[k + 1]; ++j) well_of[j] = k;
+    for (int j = nperf - 1; j >= 0; --j) { perf_nx[j] = perf_of[perf_row[j]]; perf_of[perf_row[j]] = j; }
     const S* bcol = sv.data() + F.nentries; const S* crow = bcol + nperf; const S* dw = crow + nperf;
     int64_t q = 0;
     if (rowptr) rowptr[0] = 0;
@@ -373,7 +375,7 @@ template <class S> static int cpr_level_get_t(LinSolver& ls, int level, int32_t*
         if (r < n) {
             const int len = level == 0 ? int(ls.plan.rowlen[r]) : F.h_rowlen[r];
             for (int k = 0; k < len; ++k) { const long e = long(sp[r >> 6] + k) * 64 + (r & 63); put(sc[e], double(sv[e])); }
-            if (nw && perf_of[r] >= 0) put(n + well_of[perf_of[r]], double(bcol[perf_of[r]]));
+            if (nw) for (int j = perf_of[r]; j >= 0; j = perf_nx[j]) put(n + well_of[j], double(bcol[j]));
         } else {
             const int k = r - n;
             for (int j = connpos[k]; j < connpos[k + 1]; ++j) put(perf_row[j], double(crow[j]));
@@ -648,7 +650,7 @@ int opmgpu_set_device_wells(opmgpu_ctx* c, const opmgpu_wells* wells)
                 if (wells->well_cells[j] >= c->model->n_owned_cells) return fail(c, OPMGPU_EINVAL, "multi-GPU: a well perforates a ghost cell; keep every well on one rank");
         c->ls->run_has_wells = true; c->ls->cs_for = nullptr;       // the coarse space of the pressure stage keeps one unknown per rank then
         const int st = c->model->set_device_wells(wells);
-        if (st != OPMGPU_OK) return fail(c, st, "invalid well specification (missing array, cell out of range or perforated twice)");
+        if (st != OPMGPU_OK) return fail(c, st, "invalid well specification (missing array or cell out of range)");
         return st;
     });
 }
@@ -657,6 +659,11 @@ int opmgpu_set_well_efficiency(opmgpu_ctx* c, const double* factors)
     if (!c || !c->model) return OPMGPU_EINVAL;
     // the next assembly reads the new factors; a matrix loaded or factored before the call is that of the old ones
     return guarded(c, [&]() { const int st = c->model->set_well_efficiency(factors); c->matrix_loaded = false; return st; });
+}
+int opmgpu_well_shared_cells(opmgpu_ctx* c, int32_t* shared_rows, int32_t* max_wells_per_cell)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { return c->model->well_shared_cells(shared_rows, max_wells_per_cell); });
 }
 int opmgpu_get_well_efficiency(opmgpu_ctx* c, double* factors)
 {
@@ -1175,6 +1182,9 @@ static int comm_init_common(opmgpu_ctx* c, int rank, int nranks, const uint8_t* 
     if (!c || !c->model || (!id && !transport) || nranks < 1 || rank < 0 || rank >= nranks || n_owned <= 0 || n_owned > c->model->nc || n_neigh < 0) return OPMGPU_EINVAL;
     if (n_neigh > 0 && (!neigh_rank || !send_ptr || !send_cells || !recv_ptr || !recv_cells)) return OPMGPU_EINVAL;
     return guarded(c, [&]() {
+        // the decomposed code sums a perforated row's well terms from one workgroup per well: refused before anything is attached
+        if (c->model->shared_well_rows() > 0)
+            return fail(c, OPMGPU_EINVAL, "multi-GPU: a cell is perforated by several wells; a decomposed run (a communicator is attached) does not support that");
         std::unique_ptr<RcclComm> cm(new RcclComm());
         static const int32_t zero2[2] = { 0, 0 };
         const int st = cm->init(rank, nranks, id, transport, n_owned, c->model->nc, n_neigh, neigh_rank, n_neigh ? send_ptr : zero2, send_cells,

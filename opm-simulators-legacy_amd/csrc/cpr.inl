@@ -485,7 +485,7 @@ template <class S> void LinSolver::cpr_prepare()
             bt.download(hb.data(), bt.n, stream);
             OPMGPU_HIP(hipStreamSynchronize(stream));
             bs.bcol.assign(hb.begin(), hb.begin() + bs.nperf); bs.crow.assign(hb.begin() + bs.nperf, hb.begin() + 2 * bs.nperf); bs.dw.assign(hb.begin() + 2 * bs.nperf, hb.end());
-            bs.d_connpos = lowrank.connpos; bs.d_perf_row = lowrank.perf_row; bs.d_perf_of_row = lowrank.perf_of_row; bs.d_perf_well = lowrank.perf_well;
+            bs.d_connpos = lowrank.connpos; bs.d_perf_row = lowrank.perf_row; bs.d_perf_of_row = lowrank.perf_of_row; bs.d_perf_well = lowrank.perf_well; bs.d_perf_next = lowrank.perf_next;
         }
         w.amg->dcomm = dist_hierarchy() ? comm : nullptr;
         w.amg->setup(plan, dp.slice_ptr.p, dp.col.p, hd, bs.nw > 0 ? &bs : nullptr);

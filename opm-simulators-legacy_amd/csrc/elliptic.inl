@@ -78,7 +78,7 @@ __global__ __launch_bounds__(kBlock) void k_ell_border_diag(int n, int nw, S w, 
     if (k < nw) v[n + k] = w * dinv[n + k] * d[n + k];
 }
 
-struct EllBorder { int nw, gcells; const int32_t *connpos, *perf_row, *perf_of_row, *perf_well; };
+struct EllBorder { int nw, gcells; const int32_t *connpos, *perf_row, *perf_of_row, *perf_well, *perf_next; };
 
 // y = A_p x on the (bordered) level 0: `gcells` workgroups for the cell rows + one workgroup per well row
 template <class S>
@@ -100,7 +100,7 @@ __global__ __launch_bounds__(kBlock) void k_ell_spmv(int n, const int32_t* __res
     const int base = slice_ptr[row >> 6], width = slice_ptr[(row >> 6) + 1] - base, lane = row & 63;
     S acc = 0;
     for (int k = 0; k < width; ++k) { const long e = long(base + k) * 64 + lane; acc += val[e] * x[col[e]]; }
-    if (B.nw) { const int j = B.perf_of_row[row]; if (j >= 0) acc += bcol[j] * x[n + B.perf_well[j]]; }
+    if (B.nw) for (int j = B.perf_of_row[row]; j >= 0; j = B.perf_next[j]) acc += bcol[j] * x[n + B.perf_well[j]];     // one border column per well of the cell
     y[row] = acc;
 }
 
@@ -213,7 +213,7 @@ template <class S> void LinSolver::elliptic_solve()
     S* const v = p + stride; S* const t = v + stride; S* const y = t + stride;
     ell_parts.ensure(size_t(2) * kMaxPart + 8);
     double* const parts = ell_parts.p; double* const red = parts + size_t(2) * kMaxPart;
-    EllBorder B = { nw, gcells, L0.b_connpos, L0.b_perf_row, L0.b_perf_of_row, L0.b_perf_well };
+    EllBorder B = { nw, gcells, L0.b_connpos, L0.b_perf_row, L0.b_perf_of_row, L0.b_perf_well, L0.b_perf_next };
     const S* const bcol = L0.val.p + L0.nentries; const S* const crow = bcol + L0.nperf; const S* const dw = crow + L0.nperf;
     auto spmv = [&](const S* in, S* out) {
         hipLaunchKernelGGL((k_ell_spmv<S>), dim3(gcells + nw), dim3(kBlock), 0, stream, n, L0.slice_ptr, L0.col, (const S*)L0.val.p, in, out, B, bcol, crow, dw);

@@ -81,14 +81,33 @@ __device__ __forceinline__ void reduce_partials(const double* const (&arr)[NV], 
 template <class S>
 __device__ __forceinline__ void lowrank_add(const LowRankOp& lr, int row, S& y0, S& y1, S& y2)
 {
+    // a row of several wells: one term per perforation, in ascending perforation index
     const int pf = lr.perf_of_row[row];
     if (pf < 0) return;
-    const double* __restrict__ P = lr.P + 21 * long(pf);
-    const double* __restrict__ t = lr.t + 7 * lr.perf_well[pf];
-    double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+    {
+        const double* __restrict__ P = lr.P + 21 * long(pf);
+        const double* __restrict__ t = lr.t + 7 * lr.perf_well[pf];
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+        // the 28 operands in two batches (same sums, same order): all at once they are the kernel's register peak -- 56 VGPRs for a handful of
+        // rows -- and cost every row a wave of occupancy
 #pragma unroll
-    for (int k = 0; k < 7; ++k) { a0 += P[k] * t[k]; a1 += P[7 + k] * t[k]; a2 += P[14 + k] * t[k]; }
-    y0 += S(a0); y1 += S(a1); y2 += S(a2);
+        for (int k = 0; k < 4; ++k) { a0 += P[k] * t[k]; a1 += P[7 + k] * t[k]; a2 += P[14 + k] * t[k]; }
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int k = 4; k < 7; ++k) { a0 += P[k] * t[k]; a1 += P[7 + k] * t[k]; a2 += P[14 + k] * t[k]; }
+        y0 += S(a0); y1 += S(a1); y2 += S(a2);
+    }
+    // the further perforations of a row of several wells (a handful of rows per deck), same sums in the same order; rolled, so that the rows
+    // of one perforation or none keep the kernel's registers
+#pragma nounroll
+    for (int nx = lr.perf_next[pf]; nx >= 0; nx = lr.perf_next[nx]) {
+        const double* __restrict__ P = lr.P + 21 * long(nx);
+        const double* __restrict__ t = lr.t + 7 * lr.perf_well[nx];
+        double a0 = 0.0, a1 = 0.0, a2 = 0.0;
+#pragma nounroll
+        for (int k = 0; k < 7; ++k) { a0 += P[k] * t[k]; a1 += P[7 + k] * t[k]; a2 += P[14 + k] * t[k]; }
+        y0 += S(a0); y1 += S(a1); y2 += S(a2);
+    }
 }
 // t_w = Q_w x: one workgroup per well, fixed reduction order
 template <class S>

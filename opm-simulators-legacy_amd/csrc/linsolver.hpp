@@ -76,7 +76,8 @@ struct LowRankOp {
     const int32_t* connpos = nullptr;      // [nw+1]
     const int32_t* perf_row = nullptr;     // [nperf] internal row of every perforation
     const int32_t* perf_well = nullptr;    // [nperf]
-    const int32_t* perf_of_row = nullptr;  // [nbp] perforation of a row or -1
+    const int32_t* perf_of_row = nullptr;  // [nbp] FIRST (lowest-index) perforation of a row or -1
+    const int32_t* perf_next = nullptr;    // [nperf] next perforation of the same row (a cell of several wells) or -1
     const double* P = nullptr;             // [nperf][3][7], rows already matbal-scaled
     const double* Q = nullptr;             // [nperf][7][3]
     double* t = nullptr;                   // [nw][7] scratch
@@ -308,6 +309,7 @@ public:
     // (k_wb_apply).  Under GMRES only (BiCGStab's closed-form rows assume x = M^-1 p with the plain ILU0).  OPMGPU_WELL_WOODBURY=1.
     DevArray<double> wb_buf;       // [nperf][3][7] Y | [nw][49] inverses
     bool well_woodbury = false, wb_active = false;
+    bool wb_suspended = false;     // the correction was asked for and is off while wells share a cell (wells_rebind)
     double wb_relax = 0.9;         // the ILU0's relaxation factor (omega above), set by the caller before the factorisation
     // k_spmv shortcut on level-0 rows, which have no lower entries (half of all rows with the 2-colour ordering): no matrix traffic there.
     // BiCGStab: (A M^-1 p)_i from p and the second stage's input; left-preconditioned GMRES in double with relaxation 1: (A v_i)_i =

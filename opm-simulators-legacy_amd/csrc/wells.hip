@@ -25,7 +25,9 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstring>
+#include <string>
 
 namespace opmgpu {
 
@@ -96,6 +98,12 @@ struct WellArgs {
     double* wellE;               // [nw][4]
     double* Dinv;                // [nw][16]
     const double* eff;           // [nw] well efficiency factor e_w in (0, 1] (ones by default): weighs what the CELLS see of the well, never the well equations
+    // rows perforated by several wells: perf_of_row[row] = the row's FIRST (lowest-index) perforation or -1, perf_next[j] = the next
+    // perforation of the same row or -1.  A perforation of such a row leaves the row's R, diagonal block and rhs_extra to k_well_shared_rows,
+    // which sums the wells' terms in ascending perforation index; bde[nperf][3] = its B_i D^-1 E (unweighted) for that kernel.
+    // perf_shared[j] != 0: perforation j shares its row (one load next to perf_row[j], nothing that waits for the row).
+    const int32_t *perf_of_row, *perf_next, *perf_well, *perf_shared;
+    double* bde;
 };
 
 // average well-block pressure per perforation (computePropertiesForWellConnectionPressures, StandardWells_impl.hpp:228-237):
@@ -359,6 +367,7 @@ __device__ void well_assemble_dev(const WellArgs& A, int w, const int32_t* __res
         Du<7> cq_s[3];
         for (int a = 0; a < 3; ++a) cq_s[a] = f.cq_ps[a] + cm[a] * cqt_is;                                          // :553-560
         const int row = A.perf_row[j];
+        const bool shared = !PRE && A.perf_shared[j] != 0;
         if (PRE) {
             for (int a = 0; a < 3; ++a) {
                 A.perf_rates[3 * j + a] = cq_s[a].v;                                 // updatePerfPhaseRatesAndPressures (:1059)
@@ -377,13 +386,13 @@ __device__ void well_assemble_dev(const WellArgs& A, int w, const int32_t* __res
             for (int a = 0; a < 3; ++a) Qj[3 * a + v] = alive ? (-f.cq_ps[a].d[v] + cmix[a] * hs) / wbqt : 0.0;
         }
         for (int a = 0; a < 3; ++a) {
-            R[long(a) * A.nbp + row] -= ew * cq_s[a].v;                              // addWellContributionToMassBalanceEq
+            if (!shared) R[long(a) * A.nbp + row] -= ew * cq_s[a].v;                 // addWellContributionToMassBalanceEq
             A.perf_rates[3 * j + a] = cq_s[a].v;
             acc2[a] += cq_s[a].v;
             acc2[12 + a] += cq_s[a].d[3];
             Fs[18 + a] = cq_s[a].d[3];
             for (int v = 0; v < 3; ++v) {
-                dptr[(3 * a + v) * 64] = MS(double(dptr[(3 * a + v) * 64]) - escale[a] * cq_s[a].d[v]);   // own-cell part of -e_w d cq_s / d cell
+                if (!shared) dptr[(3 * a + v) * 64] = MS(double(dptr[(3 * a + v) * 64]) - escale[a] * cq_s[a].d[v]);   // own-cell part of -e_w d cq_s / d cell
                 Fs[3 * a + v] = cq_s[a].d[v];
                 Fs[9 + 3 * a + v] = cq_s[a].d[4 + v];
                 acc2[3 + 3 * a + v] += cq_s[a].d[4 + v];
@@ -450,6 +459,7 @@ __device__ void well_assemble_dev(const WellArgs& A, int w, const int32_t* __res
                 B[4 * a + 3] = -(fb[a] + s);
             }
             const int row = A.perf_row[j];
+            const bool shared = A.perf_shared[j] != 0;
             for (int a = 0; a < 3; ++a) {
                 double bde = 0.0;
                 for (int k = 0; k < 4; ++k) {
@@ -459,7 +469,7 @@ __device__ void well_assemble_dev(const WellArgs& A, int w, const int32_t* __res
                     bde += bd * E[k];
                 }
                 for (int c = 0; c < 3; ++c) Pj[7 * a + c] = -escale[a] * M[3 * a + c];
-                rhs_extra[long(a) * A.nbp + row] = -(ew * bde);
+                if (shared) A.bde[3 * long(j) + a] = bde; else rhs_extra[long(a) * A.nbp + row] = -(ew * bde);
             }
             // C_i rows 0..2 = -(F_i + Ms G_i); row 3 (control equation) = 0.  G_i is already in Q rows 0..2.
             double G[9];
@@ -482,6 +492,33 @@ __global__ __launch_bounds__(kBlock) void k_well_assemble(WellArgs A, const int3
 {
     if (PRE && flags[WF_DONE]) return;
     well_assemble_dev<MS, PRE>(A, blockIdx.x, slice_ptr, nlower, s0, s1, s2, R, Amat, rhs_extra, flags, A.wellE + 4 * blockIdx.x, false);
+}
+
+// Rows perforated by several wells, one thread per such row: what k_well_assemble<MS, false> writes itself for a row with one perforation,
+// applied for the row's perforations in ascending perforation index from the per-perforation data the wells' workgroups left (perf_rates =
+// cq_s, Fsave = F, bde = B D^-1 E).  One thread owns the row, so the order -- that of np.add.at on the restatements' side -- is fixed and
+// the result the same bits in every run; no atomics.
+template <class MS>
+__global__ __launch_bounds__(64) void k_well_shared_rows(int nshared, const int32_t* __restrict__ shared_rows, WellArgs A, const int32_t* __restrict__ slice_ptr,
+                                                         const int16_t* __restrict__ nlower, double s0, double s1, double s2, double* __restrict__ R,
+                                                         MS* __restrict__ Amat, double* __restrict__ rhs_extra)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= nshared) return;
+    const int row = shared_rows[i];
+    MS* dptr = Amat + long(slice_ptr[row >> 6] + nlower[row]) * 576 + (row & 63);
+    double rx[3] = { 0.0, 0.0, 0.0 };
+    for (int j = A.perf_of_row[row]; j >= 0; j = A.perf_next[j]) {
+        const double ew = A.eff[A.perf_well[j]];
+        const double escale[3] = { ew * s0, ew * s1, ew * s2 };
+        const double* F = A.Fsave + 21 * long(j);
+        for (int a = 0; a < 3; ++a) {
+            R[long(a) * A.nbp + row] -= ew * A.perf_rates[3 * long(j) + a];
+            for (int v = 0; v < 3; ++v) dptr[(3 * a + v) * 64] = MS(double(dptr[(3 * a + v) * 64]) - escale[a] * F[3 * a + v]);
+            rx[a] += -(ew * A.bde[3 * long(j) + a]);
+        }
+    }
+    for (int a = 0; a < 3; ++a) rhs_extra[long(a) * A.nbp + row] = rx[a];
 }
 
 // ---- the explicit well pre-solve (solveWellEq, BlackoilModelBase_impl.hpp:1018-1133) -----------------------------------------------
@@ -740,6 +777,10 @@ struct BlackoilDevice::WellsDev {
     DevArray<double> bsums, bscratch, snap, presolve_sync, ctrl_row;
     DevArray<double> eff;           // [nw] well efficiency factors (set_well_efficiency); no part of the well STATE: not saved, not restored
     std::vector<double> h_eff;
+    // rows perforated by several wells (WellArgs): the chain, the rows' list (internal rows, ascending) and every perforated row ONCE
+    DevArray<int32_t> perf_next, perf_shared, shared_rows, perf_rows_once;
+    DevArray<double> bde;
+    int nshared = 0, max_wells_per_cell = 0, nrows_once = 0;
     DevArray<double> saved;         // snapshot for AdaptiveTimeStepping: wstate | thp | cdp | perf_rates | perf_press | perf_dens
     DevArray<int32_t> flags;
     std::vector<int32_t> h_connpos, h_cells, h_ctrl_ptr;
@@ -762,6 +803,7 @@ static WellArgs args_of(BlackoilDevice::WellsDev& W, BlackoilDevice::VfpDev* V, 
     A.z_perf = W.z_perf.p; A.surf_dens_perf = W.surf_dens_perf.p; A.perf = perf;
     A.wstate = W.wstate.p; A.cdp = W.cdp.p; A.perf_rates = W.perf_rates.p; A.perf_press = W.perf_press.p; A.P = W.P.p; A.Q = W.Q.p;
     A.Fsave = W.Fsave.p; A.wellE = W.wellE.p; A.Dinv = W.Dinv.p; A.eff = W.eff.p;
+    A.perf_of_row = W.perf_of_row.p; A.perf_next = W.perf_next.p; A.perf_well = W.perf_well.p; A.perf_shared = W.perf_shared.p; A.bde = W.bde.p;
     return A;
 }
 
@@ -837,11 +879,23 @@ int BlackoilDevice::set_device_wells(const opmgpu_wells* s)
     if (!s->well_connpos || !s->well_cells || !s->WI || !s->type || !s->depth_ref || !s->comp_frac || !s->ctrl_type || !s->ctrl_target) return OPMGPU_EINVAL;
     const int nw = s->nw, np = s->well_connpos[nw];
     if (s->ctrl_ptr && s->ctrl_ptr[0] != 0) return OPMGPU_EINVAL;
-    std::vector<int8_t> seen(nc, 0);
-    for (int j = 0; j < np; ++j) {
-        const int c = s->well_cells[j];
-        if (c < 0 || c >= nc || seen[c]) return OPMGPU_EINVAL;         // a cell perforated twice is not supported
-        seen[c] = 1;
+    // any number of DIFFERENT wells may perforate a cell; one well naming a cell twice is refused (WellsManager never produces it: a
+    // repeated COMPDAT entry replaces the earlier one)
+    std::vector<int32_t> last_well(nc, -1), per_cell(nc, 0);
+    int nshared_cells = 0, max_per_cell = 0;
+    for (int w = 0; w < nw; ++w)
+        for (int j = s->well_connpos[w]; j < s->well_connpos[w + 1]; ++j) {
+            const int c = s->well_cells[j];
+            if (c < 0 || c >= nc) return OPMGPU_EINVAL;
+            if (last_well[c] == w) throw HipError(OPMGPU_EINVAL, "opmgpu_set_device_wells: well " + std::to_string(w) + " names cell " + std::to_string(c) + " twice (several wells may share a cell, one well may not repeat it)");
+            last_well[c] = w;
+            if (++per_cell[c] == 2) ++nshared_cells;
+            if (per_cell[c] >= 2) max_per_cell = std::max(max_per_cell, int(per_cell[c]));
+        }
+    if (nshared_cells > 0) {
+        // what sums a shared row's terms from one workgroup per well stays out of reach: the decomposed code and the subdomain coarse space
+        if (ls.comm) throw HipError(OPMGPU_EINVAL, "opmgpu_set_device_wells: a cell is perforated by several wells; a decomposed run (a communicator is attached) does not support that");
+        if (ls.coarse_mode == 2 || ls.emulate_ranks > 1) throw HipError(OPMGPU_EINVAL, "opmgpu_set_device_wells: a cell is perforated by several wells; the subdomain coarse space (OPMGPU_COARSE=2, OPMGPU_EMULATE_RANKS > 1) does not support that");
     }
     if (oil_water()) {
         // no gas phase: with the inactive phase's b_g = 1, mob_g = 0, rho_g = 0 the well kernels work as they are -- the gas well equation
@@ -856,7 +910,7 @@ int BlackoilDevice::set_device_wells(const opmgpu_wells* s)
     wells_free();
     wd = new WellsDev();
     WellsDev& W = *wd;
-    W.nw = nw;
+    W.nw = nw; W.nshared = nshared_cells; W.max_wells_per_cell = max_per_cell;
     W.h_connpos.assign(s->well_connpos, s->well_connpos + nw + 1);
     W.h_cells.assign(s->well_cells, s->well_cells + np);
     device_wells = true;
@@ -913,6 +967,7 @@ int BlackoilDevice::set_device_wells(const opmgpu_wells* s)
     W.cdp.alloc(np); W.cdp.zero(stream); W.perf_rates.alloc(3 * size_t(np)); W.perf_rates.zero(stream); W.perf_press.alloc(np); W.perf_press.zero(stream);
     W.P.alloc(21 * size_t(np)); W.Q.alloc(21 * size_t(np)); W.Fsave.alloc(21 * size_t(np)); W.wellE.alloc(4 * size_t(nw)); W.Dinv.alloc(16 * size_t(nw));
     W.P.zero(stream); W.Q.zero(stream); W.wellE.zero(stream); W.Dinv.zero(stream);
+    W.bde.alloc(3 * size_t(np)); W.bde.zero(stream);
     W.t.alloc(7 * size_t(nw)); W.t.zero(stream);
     W.flags.alloc(WF_COUNT); W.flags.zero(stream);
     OPMGPU_HIP(hipHostMalloc(reinterpret_cast<void**>(&W.h_pinned), (4 * size_t(nw) + 8) * sizeof(double)));
@@ -928,12 +983,27 @@ void BlackoilDevice::wells_rebind()
     WellsDev& W = *wd;
     const Plan& P = ls.plan;
     const int np = int(W.h_cells.size());
-    std::vector<int32_t> pr(np), por(P.nbp, -1);
-    for (int j = 0; j < np; ++j) { pr[j] = P.pos[W.h_cells[j]]; por[pr[j]] = j; }
-    W.perf_row.upload(pr, stream); W.perf_of_row.upload(por, stream);
+    // por[row] = the FIRST perforation of the row, pnext[j] = the next one of the same row: chains in ascending perforation index
+    std::vector<int32_t> pr(np), por(P.nbp, -1), pnext(std::max(np, 1), -1), shared, once;
+    for (int j = np - 1; j >= 0; --j) { pr[j] = P.pos[W.h_cells[j]]; pnext[j] = por[pr[j]]; por[pr[j]] = j; }
+    for (int j = 0; j < np; ++j) if (por[pr[j]] == j) { once.push_back(pr[j]); if (pnext[j] >= 0) shared.push_back(pr[j]); }
+    std::vector<int32_t> pshared(std::max(np, 1), 0);
+    for (int j = 0; j < np; ++j) pshared[j] = (pnext[j] >= 0 || por[pr[j]] != j) ? 1 : 0;
+    W.perf_shared.upload(pshared, stream);
+    std::sort(shared.begin(), shared.end());
+    W.nshared = int(shared.size()); W.nrows_once = int(once.size());
+    if (shared.empty()) shared.push_back(0);
+    W.perf_row.upload(pr, stream); W.perf_of_row.upload(por, stream); W.perf_next.upload(pnext, stream);
+    W.shared_rows.upload(shared, stream); W.perf_rows_once.upload(once, stream);
+    // the opt-in Woodbury correction of stage 2 updates a perforated row from one workgroup per well: off while wells share a cell
+    if (W.nshared > 0 && ls.well_woodbury) {
+        static bool said = false;
+        if (!said) { said = true; std::fprintf(stderr, "[opmgpu] OPMGPU_WELL_WOODBURY=1 is switched off for this well list: a cell is perforated by several wells\n"); }
+        ls.well_woodbury = false; ls.wb_suspended = true;
+    } else if (W.nshared == 0 && ls.wb_suspended) { ls.well_woodbury = true; ls.wb_suspended = false; }
     d_rhs_extra.alloc(3 * size_t(P.nbp));
     LowRankOp& L = ls.lowrank;
-    L.nw = W.nw; L.nperf = np; L.connpos = W.connpos.p; L.perf_row = W.perf_row.p; L.perf_well = W.perf_well.p; L.perf_of_row = W.perf_of_row.p;
+    L.nw = W.nw; L.nperf = np; L.connpos = W.connpos.p; L.perf_row = W.perf_row.p; L.perf_well = W.perf_well.p; L.perf_of_row = W.perf_of_row.p; L.perf_next = W.perf_next.p;
     L.P = W.P.p; L.Q = W.Q.p; L.t = W.t.p;
     L.Fsave = W.Fsave.p; L.ctrl_row = W.ctrl_row.p; L.eff = W.eff.p;
     for (int a = 0; a < 3; ++a) L.scale[a] = prm.matbalscale[a];
@@ -956,6 +1026,15 @@ int BlackoilDevice::set_well_efficiency(const double* factors)
     OPMGPU_HIP(hipStreamSynchronize(stream));
     return OPMGPU_OK;
 }
+// rows perforated by more than one well, and the largest number of wells in one cell (both 0 without shared cells)
+int BlackoilDevice::well_shared_cells(int32_t* shared_rows, int32_t* max_wells_per_cell) const
+{
+    if (!wd) throw HipError(OPMGPU_EINVAL, "opmgpu_well_shared_cells: no device wells are set");
+    if (shared_rows) *shared_rows = wd->nshared;
+    if (max_wells_per_cell) *max_wells_per_cell = wd->max_wells_per_cell;
+    return OPMGPU_OK;
+}
+int BlackoilDevice::shared_well_rows() const { return wd ? wd->nshared : 0; }
 int BlackoilDevice::get_well_efficiency(double* factors) const
 {
     if (!wd) throw HipError(OPMGPU_EINVAL, "opmgpu_get_well_efficiency: no device wells are set");
@@ -1092,7 +1171,17 @@ void BlackoilDevice::wells_assemble(bool initial)
     else
         hipLaunchKernelGGL((k_well_assemble<double, false>), dim3(W.nw), dim3(kBlock), 0, stream, A, ls.dp.slice_ptr.p, ls.dp.nlower.p, sc[0], sc[1], sc[2], d_R.p,
                            ls.matrix_d(), d_rhs_extra.p, W.flags.p);
-    if (ls.matrix_is_float) ls.cpr_reweigh_rows<float>(W.perf_row.p, int(W.h_cells.size())); else ls.cpr_reweigh_rows<double>(W.perf_row.p, int(W.h_cells.size()));
+    if (W.nshared > 0) {          // rows of several wells: their terms in ascending perforation index, behind the wells' workgroups
+        const int gsh = (W.nshared + 63) / 64;
+        if (ls.matrix_is_float)
+            hipLaunchKernelGGL((k_well_shared_rows<float>), dim3(gsh), dim3(64), 0, stream, W.nshared, (const int32_t*)W.shared_rows.p, A, ls.dp.slice_ptr.p, ls.dp.nlower.p,
+                               sc[0], sc[1], sc[2], d_R.p, ls.matrix_f(), d_rhs_extra.p);
+        else
+            hipLaunchKernelGGL((k_well_shared_rows<double>), dim3(gsh), dim3(64), 0, stream, W.nshared, (const int32_t*)W.shared_rows.p, A, ls.dp.slice_ptr.p, ls.dp.nlower.p,
+                               sc[0], sc[1], sc[2], d_R.p, ls.matrix_d(), d_rhs_extra.p);
+    }
+    // every perforated row once (a row of several wells appears once)
+    if (ls.matrix_is_float) ls.cpr_reweigh_rows<float>(W.perf_rows_once.p, W.nrows_once); else ls.cpr_reweigh_rows<double>(W.perf_rows_once.p, W.nrows_once);
     has_rhs_extra = true;
     W.dy_valid = false;
 }

@@ -118,6 +118,8 @@ public:
     /// well's rates and their derivatives (StandardWells_impl.hpp:1405-1434, BlackoilModelBase_impl.hpp:953-975); the well equations do not.
     /// After setDeviceWells, which resets the factors to ones; lasts through saved states, precision changes and re-plans.
     void setWellEfficiencyFactors(const std::vector<double>& factors) { throw_on_status(ctx_, opmgpu_set_well_efficiency(ctx_, factors.empty() ? nullptr : factors.data())); }
+    // {cells perforated by more than one well, most wells in one cell}; {0, 0} without shared cells (opmgpu_well_shared_cells)
+    std::pair<int, int> wellSharedCells() const { int32_t rows = 0, most = 0; throw_on_status(ctx_, opmgpu_well_shared_cells(ctx_, &rows, &most)); return { int(rows), int(most) }; }
     std::vector<double> wellEfficiencyFactors(int nw) const { std::vector<double> f(nw > 0 ? nw : 1, 1.0); throw_on_status(ctx_, opmgpu_get_well_efficiency(ctx_, f.data())); f.resize(nw > 0 ? nw : 0); return f; }
     void setWellState(const double* bhp, const double* well_rates, const double* perf_press = nullptr, const double* perf_rates = nullptr) { throw_on_status(ctx_, opmgpu_well_state_set(ctx_, bhp, well_rates, perf_press, perf_rates)); }
     void getWellState(double* bhp, double* well_rates, double* perf_press = nullptr, double* perf_rates = nullptr) { throw_on_status(ctx_, opmgpu_well_state_get(ctx_, bhp, well_rates, perf_press, perf_rates)); }

@@ -344,6 +344,14 @@ class GpuBlackoilModel(_CprDiagnostics):
         self._chk(self.lib.opmgpu_get_well_efficiency(self.ctx, capi.dptr(out)))
         return out[:self.n_device_wells]
 
+    def wellSharedCells(self):
+        """(shared_rows, max_wells_per_cell) of the device wells (opmgpu_well_shared_cells): the number of cells perforated by more than one
+        well and the most wells found in one cell; (0, 0) for a well list without shared cells.  ValueError without device wells."""
+        import ctypes as C
+        rows, most = C.c_int32(0), C.c_int32(0)
+        self._chk(self.lib.opmgpu_well_shared_cells(self.ctx, C.byref(rows), C.byref(most)))
+        return rows.value, most.value
+
     n_device_wells = 0          # wells of the last opmgpu_set_device_wells (DeviceWellModel records it)
 
     def computeMaxDp(self, eqlnum, nregions, n_face_conn, conns=False):

@@ -668,6 +668,10 @@ class DeviceWellModel:
             pass        # the pre-solve on the device uses opmgpu_params.tolerance_wells / tolerance_well_control of the context
         self.push_well_state()
 
+    def shared_cells(self):
+        """(cells perforated by more than one well, most wells in one cell) as the device counts them; (0, 0) without wells"""
+        return self.m.wellSharedCells() if self.w.nw else (0, 0)
+
     def push_well_state(self):
         from . import capi
         m, ws = self.m, self.ws
