@@ -297,6 +297,9 @@ int opmgpu_cpr_correction_factors(opmgpu_ctx* ctx, double* into_level0, double* 
  *     level's explicit inverse, row-major n x n, when it has one (n <= 96).  Any output pointer may be NULL.
  *   opmgpu_cpr_vcycle_apply: x = one V-cycle from a zero start on the level-0 vector b (n[0] entries, numbered like level 0).
  *   opmgpu_cpr_apply: v3 = the whole two-stage preconditioner as a solve applies it (d3 / v3 block-interleaved like opmgpu_ilu0_apply).
+ *     It takes the path of the context's last solve: behind a double GMRES solve on that path's conditions the pressure correction is
+ *     added inside the ILU0 sweeps (OPMGPU_CPR_CANCEL_P) and the top level's stage-2 residual goes through the ILU0 factor
+ *     (OPMGPU_CPR_FACTOR_P); behind any other solve it is the plain sequence.
  *   opmgpu_cpr_elliptic_ilu_apply: x = cpr_relax (L U)^-1 b with the point ILU0 of A_p that preconditions the inner elliptic solve
  *     (cpr_use_amg = 0, cpr_max_ell_iter > 0); border rows by their own diagonal.  b / x numbered like level 0. */
 int opmgpu_cpr_levels(opmgpu_ctx* ctx, int32_t* nlevels, int32_t* n, int64_t* nnz, int32_t* nw);

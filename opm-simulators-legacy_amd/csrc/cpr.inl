@@ -202,6 +202,37 @@ __global__ __launch_bounds__(kBlock) void k_cpr_presidual(int xm, int nb, int nb
     }
     z[row] = z0; z[nbp + row] = z1; z[2 * long(nbp) + row] = z2;
 }
+// The same on the level-0 rows alone, WITHOUT the row's own diagonal term: s_r = d_r - sum_{k != r} A_rk[:,0] x_p,k, written where z_r is
+// (LinSolver::cpr_factor_p: the top level's forward sweep reads it through its L blocks and forms its own rows' part itself; nothing is
+// launched for, or written to, the top rows).  Single GPU only: no owner mask, no halo phases.
+template <class S>
+__global__ __launch_bounds__(kBlock) void k_cpr_presidual_l0(int xm, int n0, int nbp, const int32_t* __restrict__ slice_ptr, const int32_t* __restrict__ col,
+                                                             const int16_t* __restrict__ nlower, const S* __restrict__ val, const S* __restrict__ d,
+                                                             const S* __restrict__ xp, S* __restrict__ z, const SolveCtl* __restrict__ ctl)
+{
+    if (ctl && ctl->done) return;
+    const int nchunks = (n0 + kBlock - 1) / kBlock;
+    const int ch = xcd_first(nchunks, xm);
+    if (ch >= xcd_end(nchunks, xm)) return;
+    const int row = ch * kBlock + threadIdx.x;
+    if (row >= n0) return;
+    // (the last slice of the level may hold top rows too: its width is theirs as well, the slots past this row's own entries are padding, value 0)
+    const int base = slice_ptr[row >> 6], width = slice_ptr[(row >> 6) + 1] - base, lane = row & 63, nl = nlower[row];
+    const S* __restrict__ v = val + vidx(base, lane);
+    const int32_t* __restrict__ c = col + long(base) * 64 + lane;
+    S z0 = d[row], z1 = d[nbp + row], z2 = d[2 * long(nbp) + row];
+    for (int k = 0; k < nl; ++k) {               // (a level-0 row has no lower entries: nl = 0, the diagonal is its first slot)
+        const S x0 = xp[c[k * 64]];
+        const S* __restrict__ b = v + k * 576;
+        z0 -= b[0] * x0; z1 -= b[192] * x0; z2 -= b[384] * x0;
+    }
+    for (int k = nl + 1; k < width; ++k) {
+        const S x0 = xp[c[k * 64]];
+        const S* __restrict__ b = v + k * 576;
+        z0 -= b[0] * x0; z1 -= b[192] * x0; z2 -= b[384] * x0;
+    }
+    z[row] = z0; z[nbp + row] = z1; z[2 * long(nbp) + row] = z2;
+}
 template <class S>
 __global__ __launch_bounds__(kBlock) void k_cpr_add_p(int nb, const S* __restrict__ xp, S* __restrict__ v, const SolveCtl* __restrict__ ctl, S c)
 {
@@ -557,6 +588,19 @@ template <class S> void LinSolver::cpr_apply(const S* d, S* v, double relax, con
     const bool emulated = !comm && emulate_ranks > 1;
     // the sum [x_p; 0; 0] + ILU0^-1 z formed inside the sweeps (linsolver.hpp, cpr_cancel_p): a two-level plan, every relaxation factor 1
     const bool cancel = cancel_p_now && plan.nlevels == 2 && relax == 1.0 && ell.relax == 1.0 && fill_level == 0 && !point_stage2;
+    // the top level's part of the stage-2 residual through the ILU0 factor (linsolver.hpp, cpr_factor_p).  Everything `cancel` asks, each for
+    // a reason of this path's own:
+    //   cancel_p_now      -- the level-0 rows' backward sweep starts from d, so z on those rows is the forward sweep's input and nothing else,
+    //                        and s can stand where it stood; set by a double GMRES solve that is neither mixed, flexible nor verified, on
+    //                        plain_setup(): one GPU and no emulated ranks (the ILU0 is of exactly the matrix the residual multiplies, and
+    //                        no owner mask or halo phase reaches the residual), no Woodbury correction
+    //   two levels        -- every lower entry of a top row lies on level 0, where the forward sweep is the identity: the row reads s itself
+    //   relaxation 1      -- s_r enters the sum unscaled; with w != 1 the sweep's input is w z
+    //   fill_level 0, no point stage 2 -- D_r = A_rr on level 0 and L_ir = A_ir A_rr^-1: the factor of the matrix's own pattern
+    // Perforated rows need no exception: what the device wells add to A itself lies in the diagonal blocks of their cells, which the ILU0
+    // factors and the sweep's diagonal term reads like any other; the rest of the wells is the low-rank operator (LowRankOp, applied inside
+    // k_spmv), which neither k_cpr_presidual nor the factor ever saw, with the switch on or off.
+    const bool factor_p = cancel && cpr_factor_p;
     const bool fused_rsum = coarse && !emulated && g <= kCsRowParts;       // real coarse space: restriction fused into the kernel below
     hipEvent_t kt_a = kt.begin();
     double* const cs_parts = coarse ? cs_buf.p + size_t(2) * coarse_nsub * coarse_nsub + coarse_nsub : nullptr;   // own scratch (the BiCGStab partial arrays are live across an application)
@@ -633,6 +677,12 @@ template <class S> void LinSolver::cpr_apply(const S* d, S* v, double relax, con
     const int8_t* own = comm ? comm->owner_mask() : (const int8_t*)nullptr;
     const bool overlap = exchange && halo_overlap && halo_stream && light_ok_for == comm && light_ok.n == size_t(plan.nbp);
     auto presidual = [&](int phase) {
+        if (factor_p) {          // (plain_setup(): no exchange, phase 0, no owner mask)
+            const int n0 = plan.level_ptr[1];
+            if (n0 > 0) hipLaunchKernelGGL((k_cpr_presidual_l0<S>), dim3(grid8_for(n0)), dim3(kBlock), 0, stream, xcd_mode(), n0, plan.nbp, dp.slice_ptr.p, dp.col.p,
+                                           dp.nlower.p, amat, d, xp, w.z.p, ctl);
+            return;
+        }
         hipLaunchKernelGGL((k_cpr_presidual<S>), dim3(grid8_for(plan.nb)), dim3(kBlock), 0, stream, xcd_mode(), plan.nb, plan.nbp, dp.slice_ptr.p, dp.col.p, amat, d, xp, w.z.p, own, ctl,
                            phase, phase ? (const int8_t*)light_ok.p : (const int8_t*)nullptr);
     };
@@ -640,7 +690,7 @@ template <class S> void LinSolver::cpr_apply(const S* d, S* v, double relax, con
     else { if (exchange) halo(comm, w.hx.p, stream); presidual(0); }
     kt.end(KT_CPR_OTHER, kt_a);
     if (point_stage2 && sizeof(S) == 8) point_ilu_apply(reinterpret_cast<const double*>(w.z.p), reinterpret_cast<double*>(v), relax);      // the reference's own stage 2 (pointilu.inl)
-    else ilu_apply<S>(w.z.p, v, relax, ctl, cancel ? d : (const S*)nullptr, cancel ? xp : (const S*)nullptr);
+    else ilu_apply<S>(w.z.p, v, relax, ctl, cancel ? d : (const S*)nullptr, cancel ? xp : (const S*)nullptr, factor_p ? amat : (const S*)nullptr);
     kt_a = kt.begin();
     if (well_woodbury && wb_active && lowrank.nw > 0 && lowrank.P && !comm && wb_buf.p && fill_level == 0)
         hipLaunchKernelGGL((k_wb_apply<S>), dim3(lowrank.nw), dim3(kBlock), 0, stream, lowrank, plan.nbp, (const double*)wb_buf.p,

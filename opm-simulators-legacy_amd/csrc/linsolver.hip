@@ -244,11 +244,16 @@ __global__ __launch_bounds__(kBlock) void k_spmv(int xm, int nb, int nbp, const 
 // rows (their forward sweep is the identity, so it is never launched) and y_j = v_j otherwise.  For the
 // top level the pivot inverse is applied at once (no upper entries there).
 // ParallelOverlappingILU0::apply, lower part; the relaxation factor w is folded in (the sweeps are linear).
-template <class S>
+// FP (LinSolver::cpr_factor_p; the top level of a two-level plan, w = 1, xp given): the row forms its own right-hand side.  d is the CPR
+// application's input, A the unfactorised matrix, s holds on the level-0 rows their stage-2 residual without its diagonal term
+// (k_cpr_presidual_l0).  The row starts from d_i - A_ii[:,0] x_p,i and reads s_r where the plain form reads w d_r: L_ir = A_ir A_rr^-1
+// carries A_ir[:,0] x_p,r, the part of the row's residual that was left out of s_r, into the sum.
+template <class S, bool FP = false>
 __global__ __launch_bounds__(kBlock) void k_ilu_lower(int xm, int lo, int hi, int n0, int nbp, int top, S w, const int32_t* __restrict__ slice_ptr,
                                                       const int32_t* __restrict__ col, const int16_t* __restrict__ nlower,
                                                       const S* __restrict__ lu, const S* __restrict__ d, S* __restrict__ v,
-                                                      const SolveCtl* __restrict__ ctl, const S* __restrict__ xp = nullptr)
+                                                      const SolveCtl* __restrict__ ctl, const S* __restrict__ xp = nullptr,
+                                                      const S* __restrict__ A = nullptr, const S* __restrict__ s = nullptr)
 {
     if (ctl && ctl->done) return;
     const int nchunks = (hi - lo + kBlock - 1) / kBlock;
@@ -259,11 +264,17 @@ __global__ __launch_bounds__(kBlock) void k_ilu_lower(int xm, int lo, int hi, in
     const int base = slice_ptr[row >> 6], lane = row & 63, nl = nlower[row];
     const S* __restrict__ m = lu + vidx(base, lane);
     const int32_t* __restrict__ c = col + long(base) * 64 + lane;
-    S r0 = w * d[row], r1 = w * d[nbp + row], r2 = w * d[2 * nbp + row];
+    S r0, r1, r2;
+    if constexpr (FP) {
+        const S* __restrict__ a = A + vidx(base, lane) + nl * 576;       // A's own diagonal block: its pressure column
+        const S xi = xp[row];
+        r0 = d[row] - a[0] * xi; r1 = d[nbp + row] - a[192] * xi; r2 = d[2 * nbp + row] - a[384] * xi;
+    } else { r0 = w * d[row]; r1 = w * d[nbp + row]; r2 = w * d[2 * nbp + row]; }
     for (int k = 0; k < nl; ++k) {
         const int cc = c[k * 64];
         S x0, x1, x2;
-        if (cc < n0) { x0 = w * d[cc]; x1 = w * d[nbp + cc]; x2 = w * d[2 * nbp + cc]; }
+        if constexpr (FP) { x0 = s[cc]; x1 = s[nbp + cc]; x2 = s[2 * nbp + cc]; }          // (every lower entry lies on level 0)
+        else if (cc < n0) { x0 = w * d[cc]; x1 = w * d[nbp + cc]; x2 = w * d[2 * nbp + cc]; }
         else { x0 = v[cc]; x1 = v[nbp + cc]; x2 = v[2 * nbp + cc]; }
         const S* __restrict__ b = m + k * 576;
         r0 -= b[0] * x0 + b[64] * x1 + b[128] * x2;
@@ -549,6 +560,7 @@ LinSolver::LinSolver(hipStream_t s) : stream(s)
     closed_form_level0 = env_flag("OPMGPU_CLOSED", closed_form_level0);
     lean_solve = env_flag("OPMGPU_LEAN_SOLVE", lean_solve);
     cpr_cancel_p = env_flag("OPMGPU_CPR_CANCEL_P", cpr_cancel_p);
+    cpr_factor_p = env_flag("OPMGPU_CPR_FACTOR_P", cpr_factor_p);
     well_woodbury = env_flag("OPMGPU_WELL_WOODBURY", well_woodbury);
     cpr_speculate = env_flag("OPMGPU_CPR_SPECULATE", cpr_speculate);
     cpr_weight_mode = env_int("OPMGPU_CPR_WEIGHTS", cpr_weight_mode);
@@ -838,8 +850,10 @@ void LinSolver::join_factor()
 
 // d0, xp (CPR with cancel_p_now; cpr_apply has checked the plan and the factors): d = d0 - A [xp; 0; 0] is the second stage's input, d0 the
 // application's.  v = [xp; 0; 0] + (LU)^-1 d without a pass of its own for the sum: the top level's rows add xp as they become final, a
-// level-0 row r has D_r = A_rr and U_rb = A_rb, so its entry of the SUM is D_r^-1 (d0_r - sum_b A_rb v_b) with v_b the final top-level entries
-template <class S> void LinSolver::ilu_apply(const S* d, S* v, double relax, const SolveCtl* ctl, const S* d0, const S* xp)
+// level-0 row r has D_r = A_rr and U_rb = A_rb, so its entry of the SUM is D_r^-1 (d0_r - sum_b A_rb v_b) with v_b the final top-level entries.
+// a_fp (cpr_factor_p, with d0 and xp; a two-level plan): the unfactorised matrix.  d then holds, on the level-0 rows only, the residual
+// without its diagonal term; the top level's sweep forms its rows' right-hand side from d0, xp and a_fp (k_ilu_lower, FP)
+template <class S> void LinSolver::ilu_apply(const S* d, S* v, double relax, const SolveCtl* ctl, const S* d0, const S* xp, const S* a_fp)
 {
     join_factor();
     KtScope kts(kt, KT_ILU_APPLY);
@@ -855,8 +869,12 @@ template <class S> void LinSolver::ilu_apply(const S* d, S* v, double relax, con
     for (int l = 1; l < L; ++l) {
         const int lo = plan.level_ptr[l], hi = plan.level_ptr[l + 1];
         if (hi == lo) continue;
-        hipLaunchKernelGGL((k_ilu_lower<S>), dim3(grid8_for(hi - lo)), dim3(kBlock), 0, stream, xcd_mode(), lo, hi, n0, plan.nbp, int(l == L - 1), S(relax),
-                           dp.slice_ptr.p, dp.col.p, dp.nlower.p, w.LU.p, d, v, ctl, xp);
+        if (a_fp && d0 && xp && L == 2)
+            hipLaunchKernelGGL((k_ilu_lower<S, true>), dim3(grid8_for(hi - lo)), dim3(kBlock), 0, stream, xcd_mode(), lo, hi, n0, plan.nbp, 1, S(relax),
+                               dp.slice_ptr.p, dp.col.p, dp.nlower.p, w.LU.p, d0, v, ctl, xp, a_fp, d);
+        else
+            hipLaunchKernelGGL((k_ilu_lower<S>), dim3(grid8_for(hi - lo)), dim3(kBlock), 0, stream, xcd_mode(), lo, hi, n0, plan.nbp, int(l == L - 1), S(relax),
+                               dp.slice_ptr.p, dp.col.p, dp.nlower.p, w.LU.p, d, v, ctl, xp);
     }
     for (int l = L - 2; l >= 0; --l) {
         const int lo = plan.level_ptr[l], hi = plan.level_ptr[l + 1];
@@ -1110,7 +1128,7 @@ double LinSolver::time_kernel(int kernel, int reps, int single_precision)
 #define OPMGPU_INST(S)                                                                  \
     template void LinSolver::ensure_work<S>();                                           \
     template int LinSolver::factor<S>(bool);                                                 \
-    template void LinSolver::ilu_apply<S>(const S*, S*, double, const SolveCtl*, const S*, const S*);        \
+    template void LinSolver::ilu_apply<S>(const S*, S*, double, const SolveCtl*, const S*, const S*, const S*);        \
     template void LinSolver::spmv<S>(const S*, S*);                                      \
     template void LinSolver::spmv_at<S>(const S*, S*, const S*, const int32_t*);        \
     template void LinSolver::cpr_prepare<S>();                                           \

@@ -154,7 +154,7 @@ public:
 
     template <class S> int factor(bool wait = true);                                // ILU0 numeric factorisation
     int factor_status() const { return (h_flags[0] & 1) ? OPMGPU_ESINGULAR : OPMGPU_OK; }   // valid after a stream synchronisation
-    template <class S> void ilu_apply(const S* d, S* v, double relax, const SolveCtl* ctl = nullptr, const S* d0 = nullptr, const S* xp = nullptr);
+    template <class S> void ilu_apply(const S* d, S* v, double relax, const SolveCtl* ctl = nullptr, const S* d0 = nullptr, const S* xp = nullptr, const S* a_fp = nullptr);
     template <class S> void spmv(const S* x, S* y);
     template <class S> void spmv_at(const S* x, S* y, const S* val, const int32_t* col);    // the same operator on another copy of the matrix arrays
     // CPR (solver_approach=cpr): build / refresh the pressure AMG for the current matrix; two-stage apply
@@ -333,6 +333,13 @@ public:
     // Rounds differently from the plain sequence.  Double GMRES solves only.  A/B switch: OPMGPU_CPR_CANCEL_P=0, read when the solver is created
     bool cpr_cancel_p = true;
     bool cancel_p_now = false;             // this solve's applications take that path (set by the solvers)
+    // The top level's part of the stage-2 residual travels through the ILU0 factor (cpr_apply, ilu_apply): a top row i of
+    // a two-level plan has lower entries to level-0 rows only and L_ir = A_ir A_rr^-1, so its forward sweep
+    // y_i = z_i - sum_r L_ir z_r, z = d - A [x_p; 0; 0], is (d_i - A_ii[:,0] x_p,i) - sum_r L_ir s_r with s_r the level-0 row's residual
+    // without its own diagonal term.  k_cpr_presidual_l0 forms s on the level-0 rows alone, the sweep its own rows' part; z on the top
+    // rows is never formed.  On the cancellation's conditions, and with it on.  Rounds differently again.  A/B switch: OPMGPU_CPR_FACTOR_P=0,
+    // read when the solver is created
+    bool cpr_factor_p = true;
     bool cpr_halo_xp = true;        // multi-GPU CPR: halo-exchange the pressure correction before stage 2 (A/B: OPMGPU_CPR_HALO_XP=0)
     int amg_lag = 1, amg_age = 0;   // A/B: OPMGPU_AMG_LAG
     // refresh policy of the coarse operators of the pressure hierarchy (see cpr_prepare); OPMGPU_AMG_LAG_COARSE
