@@ -111,78 +111,15 @@ struct Timed {
     ~Timed() { if (e1) { (void)hipEventRecord(e1, c->stream); return; } (void)hipEventRecord(c->evp[ph][1], c->stream); c->ev_pending[ph] = true; }
 };
 
-static inline int fill_level_of(const opmgpu_params& prm) { return prm.use_cpr ? prm.cpr_ilu_n : prm.ilu_fillin_level; }
+// the precision dispatch of this file: f(float()) for a single-precision matrix / solve, f(double()) otherwise
+template <class F> auto by_precision(bool single, F&& f) { if (single) return f(float()); return f(double()); }
 
-template <class S> int solve_loaded(opmgpu_ctx* c, bool matrix_changed, SolveResult& res)
-{
-    LinSolver& ls = *c->ls;
-    // under CPR the second stage's ILU0 takes the CPR preconditioner's own relaxation (cpr_relax, NewtonIterationBlackoilCPR.hpp:59), not
-    // the interleaved solver's ilu_relaxation: the solvers below read ONE relaxation field
-    opmgpu_params prm = c->prm;
-    if (prm.use_cpr) {
-        if (prm.cpr_ilu_n > 0 && prm.cpr_reference_transform == 2) return fail(c, OPMGPU_EINVAL, "cpr_ilu_n > 0 with cpr_reference_transform = 2: the point ILU of the scalar system is an ILU0");
-        if (!(prm.cpr_relax > 0.0) || !(prm.cpr_solver_tol > 0.0) || prm.cpr_max_ell_iter < 0) return fail(c, OPMGPU_EINVAL, "cpr_relax / cpr_solver_tol must be positive, cpr_max_ell_iter >= 0");
-        if (!(prm.cpr_stage2_relax > 0.0)) return fail(c, OPMGPU_EINVAL, "cpr_stage2_relax must be positive");
-        prm.ilu_relaxation = prm.cpr_relax * prm.cpr_stage2_relax;
-        // the elliptic part (elliptic.inl): cpr_max_ell_iter = 0 is this library's one-V-cycle stage, which needs the AMG
-        if (prm.cpr_max_ell_iter == 0 && !prm.cpr_use_amg) return fail(c, OPMGPU_EINVAL, "cpr_max_ell_iter = 0 (one application, no inner Krylov method) needs cpr_use_amg = 1");
-        ls.ell.inner = prm.cpr_max_ell_iter > 0; ls.ell.use_amg = prm.cpr_use_amg != 0; ls.ell.bicgstab = prm.cpr_use_bicgstab != 0;
-        ls.ell.tol = prm.cpr_solver_tol; ls.ell.maxit = prm.cpr_max_ell_iter; ls.ell.relax = prm.cpr_relax;
-    }
-    ls.wb_relax = prm.ilu_relaxation;
-    // block ILU(n) instead of the ILU0 (fillilu.inl): cpr_ilu_n under CPR, the interleaved solver's ilu_fillin_level otherwise
-    const int fill = fill_level_of(prm);
-    if (fill < 0 || fill > 8) return fail(c, OPMGPU_EINVAL, "cpr_ilu_n / ilu_fillin_level must be in 0..8");
-    if (fill != ls.fill_level) { ls.join_factor(); ls.factor_early = 0; ls.fill_level = fill; }        // (an early factorisation of the other kind is void)
-    if (prm.use_cpr) ls.correction_policy_choose();
-    // mixed precision (preconditioner_single): a double solve with its preconditioner in the float work set; not with the in-place transform
-    const bool mixed = prm.preconditioner_single && sizeof(S) == 8 && !(prm.use_cpr && prm.cpr_reference_transform) && ls.emulate_ranks <= 1;
-    ls.mixed = mixed;
-    ls.prepare<S>(matrix_changed);
-    if (mixed) ls.mixed_prepare(matrix_changed);
-    // the reference's CPR formulation (whole-system L transform, 200-bar pressure row, ||L r|| stopping) as an option; once per matrix
-    if (prm.use_cpr && prm.cpr_reference_transform) ls.cpr_reference_transform<S>();
-    else { ls.border_weights = nullptr; ls.border_colscale = 1.0; }
-    // cpr_reference_transform = 2: the reference's own second stage, a point ILU0 of the transformed system as a scalar equation-major matrix
-    ls.point_stage2 = prm.use_cpr && prm.cpr_reference_transform == 2;
-    if (ls.point_stage2) {
-        if (sizeof(S) != 8) return fail(c, OPMGPU_EINVAL, "cpr_reference_transform = 2 (point ILU0 of the scalar system) is double only, like the reference's CPR plug-in");
-        if (ls.comm || ls.emulate_ranks > 1) return fail(c, OPMGPU_EINVAL, "cpr_reference_transform = 2 is a single-GPU comparison mode");
-        if (ls.pilu.stale) { ls.point_ilu_factor(); ls.pilu.stale = false; }
-    }
-    // next to the pressure stage's set-up (cpr_prepare, inside the solver); not in the emulated-decomposition diagnostics, whose cut copy of
-    // the matrix is built lazily by whichever of the two asks first
-    static const bool after_rows = env_flag("OPMGPU_FACTOR_AFTER_ROWS", true);      // measured +0.5 %
-    const bool early = ls.factor_early == (mixed ? 4 : int(sizeof(S))) && matrix_changed && !prm.cpr_reference_transform;      // the model started it behind the assembly (LinSolver::factor_early)
-    ls.factor_early = 0;
-    if (ls.point_stage2) { /* the point ILU0 above is the second stage: no block factorisation */ }
-    else if (early) { /* running on the factor stream already; the first ILU0 sweep joins it */ }
-    else if (ls.factor_overlap && prm.use_cpr && ls.emulate_ranks <= 1) { if (after_rows) ls.factor_deferred = true; else if (mixed) ls.factor_async<float>(); else ls.factor_async<S>(); }
-    else if (mixed) (void)ls.factor<float>(false);
-    else (void)ls.factor<S>(false);      // status read below: the solver's own final synchronisation covers it
-    res = prm.newton_use_gmres ? ls.gmres<S>(prm) : ls.bicgstab<S>(prm);
-    if (prm.use_cpr) ls.correction_policy_report(res.iterations, res.status == OPMGPU_OK);
-    if (res.status != OPMGPU_OK && prm.use_cpr && ls.corr_policy.active && ls.corr_policy.cur > 0 && ls.factor_status() == OPMGPU_OK) {
-        // the solve ran with a scaled coarse-grid correction: once more with the plain Galerkin correction (factor 1.0, the safe end of the policy's
-        // ladder) before anything is reported -- a failed linear solve costs the caller a chopped time step.  The rest of the step stays on it;
-        // the failure counts against the factor at once and bans it and every larger one for a while (LinSolver::CorrectionPolicy)
-        ls.corr_policy.fail_at_current(res.iterations);
-        if (mixed) ls.work<float>().amg->pdamp0 = ls.work<float>().amg->pdamp = ls.corr_policy.arm[0];
-        else ls.work<S>().amg->pdamp0 = ls.work<S>().amg->pdamp = ls.corr_policy.arm[0];
-        res = prm.newton_use_gmres ? ls.gmres<S>(prm) : ls.bicgstab<S>(prm);
-        ls.correction_policy_report(res.iterations, res.status == OPMGPU_OK);
-    }
-    if (res.status != OPMGPU_OK && prm.use_cpr && !ls.refreshed && ls.factor_status() == OPMGPU_OK) {
-        // the solve ran on lagged coarse operators of the pressure hierarchy (LinSolver::cpr_prepare): once more on fresh ones
-        ls.force_refresh = true; ls.lag_block = 8;
-        res = prm.newton_use_gmres ? ls.gmres<S>(prm) : ls.bicgstab<S>(prm);
-    }
-    if (!ls.point_stage2 && ls.factor_status() != OPMGPU_OK) { c->factored = false; return fail(c, OPMGPU_ESINGULAR, "singular diagonal block in ILU0"); }
-    c->factored = true;
-    if (res.status == OPMGPU_ELINSOLVE) c->err = "Convergence failure for linear solver.";
-    if (res.status == OPMGPU_EBREAKDOWN) c->err = ls.breakdown_note.empty() ? std::string("breakdown in the Krylov method") : ls.breakdown_note;
-    return res.status;
-}
+// what the status of LinSolver::solve means for the context: a refused call (OPMGPU_EINVAL) leaves `factored` untouched, a singular diagonal
+// block clears it, every other return sets it
+int solved(opmgpu_ctx* c, int st) { if (st != OPMGPU_EINVAL) c->factored = st != OPMGPU_ESINGULAR; return st; }
+
+// the CPR diagnostics read the hierarchy of the last CPR solve in the precision it ran in
+bool cpr_float(opmgpu_ctx* c) { return c->cur_single == 1 || c->ls->now.mixed; }
 
 } // namespace
 
@@ -296,262 +233,56 @@ int opmgpu_cpr_elliptic_stats(opmgpu_ctx* c, int64_t* solves, int64_t* iteration
 int opmgpu_cpr_correction_factors(opmgpu_ctx* c, double* into_level0, double* below)
 {
     if (!c || !c->ls) return OPMGPU_EINVAL;
-    LinSolver& ls = *c->ls;
-    const bool f = c->cur_single == 1 || ls.mixed;
-    if (f ? !(ls.work<float>().amg && ls.work<float>().amg->ready()) : !(ls.work<double>().amg && ls.work<double>().amg->ready())) return OPMGPU_EINVAL;
-    if (into_level0) *into_level0 = f ? ls.work<float>().amg->pdamp0 : ls.work<double>().amg->pdamp0;
-    if (below) *below = f ? ls.work<float>().amg->pdamp : ls.work<double>().amg->pdamp;
-    return OPMGPU_OK;
+    return by_precision(cpr_float(c), [&](auto tag) {
+        auto* H = c->ls->cpr_hierarchy<decltype(tag)>();
+        if (!H) return int(OPMGPU_EINVAL);
+        if (into_level0) *into_level0 = H->pdamp0;
+        if (below) *below = H->pdamp;
+        return int(OPMGPU_OK);
+    });
 }
 
-} // extern "C"
-
-// ---------------------------------------------------------------- diagnostics of the CPR pressure hierarchy (tests/test_gpu_cpr_stages.py)
-// They read the hierarchy of the last CPR solve in the precision it ran in and leave the solver's state as they found it: the x / x2 roles
-// of every level and level 0's right-hand side are restored, the correction factors and `factors_kept` are not touched.
-template <class S> static AmgHierarchy<S>* cpr_hierarchy(LinSolver& ls)
-{
-    SolverWork<S>& w = ls.work<S>();
-    return (w.amg && w.amg->ready()) ? w.amg.get() : nullptr;
-}
-static bool cpr_float(opmgpu_ctx* c) { return c->cur_single == 1 || c->ls->mixed; }
-
-template <class S> static int cpr_levels_t(LinSolver& ls, int32_t* nlevels, int32_t* n, int64_t* nnz, int32_t* nw)
-{
-    AmgHierarchy<S>* H = cpr_hierarchy<S>(ls);
-    if (!H) return OPMGPU_EINVAL;
-    const int nl = int(H->levels.size());
-    const int cap = *nlevels;
-    *nlevels = nl;
-    if (nw) *nw = H->levels[0]->nw;
-    for (int l = 0; l < nl && l < cap; ++l) {
-        const AmgLevel<S>& F = *H->levels[l];
-        int64_t cnt = 2 * int64_t(F.nperf) + F.nw;
-        if (l == 0) for (int r = 0; r < F.n; ++r) cnt += ls.plan.rowlen[r];
-        else for (int r = 0; r < F.n; ++r) cnt += F.h_rowlen[r];
-        if (n) n[l] = F.ntot();
-        if (nnz) nnz[l] = cnt;
-    }
-    return OPMGPU_OK;
-}
-
-template <class S> static int cpr_level_get_t(LinSolver& ls, int level, int32_t* rowptr, int32_t* col, double* val, int32_t* agg, double* dense_inv)
-{
-    AmgHierarchy<S>* H = cpr_hierarchy<S>(ls);
-    if (!H || level < 0 || level >= int(H->levels.size())) return OPMGPU_EINVAL;
-    const hipStream_t st = ls.stream;
-    H->join_inverse();
-    const AmgLevel<S>& F = *H->levels[level];
-    const int n = F.n, nw = F.nw, nt = F.ntot(), nperf = F.nperf;
-    std::vector<int32_t> sp(F.nslices + 1), sc(F.nentries), connpos(nw + 1, 0), perf_row(nperf);
-    std::vector<S> sv(F.nentries + 2 * size_t(nperf) + nw);
-    OPMGPU_HIP(hipMemcpyAsync(sp.data(), F.slice_ptr, sp.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    OPMGPU_HIP(hipMemcpyAsync(sc.data(), F.col, sc.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    F.val.download(sv.data(), sv.size(), st);
-    if (nw) {
-        OPMGPU_HIP(hipMemcpyAsync(connpos.data(), F.b_connpos, connpos.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-        OPMGPU_HIP(hipMemcpyAsync(perf_row.data(), F.b_perf_row, perf_row.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    }
-    const bool last = level + 1 == int(H->levels.size());
-    std::vector<int32_t> ag;
-    if (!last) { ag.resize(nt); F.agg.download(ag.data(), nt, st); }
-    std::vector<double> inv;
-    if (last && H->n_coarsest <= 96) { inv.resize(size_t(nt) * nt); H->dense_inv.download(inv.data(), inv.size(), st); }
-    OPMGPU_HIP(hipStreamSynchronize(st));
-    // numbering of the output: level 0 in caller order (cells), then the wells; coarse levels their own
-    std::vector<int32_t> internal(nt), outer(nt);
-    for (int i = 0; i < nt; ++i) internal[i] = outer[i] = i;
-    if (level == 0) for (int i = 0; i < n; ++i) { internal[i] = ls.plan.pos[i]; outer[ls.plan.pos[i]] = i; }
-    // a row's perforations as a chain in ascending perforation index: one border column per well of the cell
-    std::vector<int32_t> perf_of(n, -1), perf_nx(nperf, -1), well_of(nperf, 0);
-    for (int k = 0; k < nw; ++k) for (int j = connpos[k]; j < connpos[k + 1]; ++j) well_of[j] = k;
-    for (int j = nperf - 1; j >= 0; --j) { perf_nx[j] = perf_of[perf_row[j]]; perf_of[perf_row[j]] = j; }
-    const S* bcol = sv.data() + F.nentries; const S* crow = bcol + nperf; const S* dw = crow + nperf;
-    int64_t q = 0;
-    if (rowptr) rowptr[0] = 0;
-    auto put = [&](int c, double v) { if (col) col[q] = c < nt ? outer[c] : c; if (val) val[q] = v; ++q; };
-    for (int o = 0; o < nt; ++o) {
-        const int r = internal[o];
-        if (r < n) {
-            const int len = level == 0 ? int(ls.plan.rowlen[r]) : F.h_rowlen[r];
-            for (int k = 0; k < len; ++k) { const long e = long(sp[r >> 6] + k) * 64 + (r & 63); put(sc[e], double(sv[e])); }
-            if (nw) for (int j = perf_of[r]; j >= 0; j = perf_nx[j]) put(n + well_of[j], double(bcol[j]));
-        } else {
-            const int k = r - n;
-            for (int j = connpos[k]; j < connpos[k + 1]; ++j) put(perf_row[j], double(crow[j]));
-            put(r, double(dw[k]));
-        }
-        if (rowptr) rowptr[o + 1] = int32_t(q);
-    }
-    if (agg && !last) for (int o = 0; o < nt; ++o) agg[o] = ag[internal[o]];
-    if (dense_inv && !inv.empty())          // the device keeps it transposed (k_dense_apply): inv[j * n + i] = Ainv(i, j)
-        for (int i = 0; i < nt; ++i) for (int j = 0; j < nt; ++j) dense_inv[size_t(outer[i]) * nt + outer[j]] = inv[size_t(j) * nt + i];
-    return OPMGPU_OK;
-}
-
-// the x / x2 buffers of every level (a cycle swaps them; the solver's captured cycle relies on their roles)
-template <class S> static std::vector<std::pair<S*, S*>> cpr_roles(AmgHierarchy<S>& H)
-{
-    std::vector<std::pair<S*, S*>> r;
-    for (auto& L : H.levels) r.emplace_back(L->x.p, L->x2.p);
-    return r;
-}
-template <class S> static void cpr_restore_roles(AmgHierarchy<S>& H, const std::vector<std::pair<S*, S*>>& r)
-{
-    for (size_t l = 0; l < r.size(); ++l) { H.levels[l]->x.p = r[l].first; H.levels[l]->x2.p = r[l].second; }
-}
-
-template <class S> static int cpr_vcycle_apply_t(LinSolver& ls, const double* b, double* x)
-{
-    AmgHierarchy<S>* H = cpr_hierarchy<S>(ls);
-    if (!H) return OPMGPU_EINVAL;
-    AmgLevel<S>& L0 = *H->levels[0];
-    const int n = L0.n, nt = L0.ntot();
-    const hipStream_t st = ls.stream;
-    std::vector<S> hb(nt), hx(nt);
-    // a distributed hierarchy (collective call): the rank's owned cells, then its wells; the ghost rows follow their owners inside the cycle
-    const int nown = H->ndist > 0 ? int(std::count(L0.h_owned.begin(), L0.h_owned.end(), int8_t(1))) : n;
-    for (int i = 0; i < nown; ++i) hb[ls.plan.pos[i]] = S(b[i]);
-    for (int k = n; k < nt; ++k) hb[k] = S(b[nown + k - n]);
-    DevArray<S> keep; keep.alloc(nt);
-    OPMGPU_HIP(hipMemcpyAsync(keep.p, L0.b.p, nt * sizeof(S), hipMemcpyDeviceToDevice, st));
-    const auto roles = cpr_roles(*H);
-    L0.b.upload(hb.data(), nt, st);
-    H->vcycle_graph(nullptr, false);
-    OPMGPU_HIP(hipMemcpyAsync(hx.data(), L0.x.p, nt * sizeof(S), hipMemcpyDeviceToHost, st));
-    cpr_restore_roles(*H, roles);
-    OPMGPU_HIP(hipMemcpyAsync(L0.b.p, keep.p, nt * sizeof(S), hipMemcpyDeviceToDevice, st));
-    OPMGPU_HIP(hipStreamSynchronize(st));
-    for (int i = 0; i < nown; ++i) x[i] = double(hx[ls.plan.pos[i]]);
-    for (int k = n; k < nt; ++k) x[nown + k - n] = double(hx[k]);
-    return OPMGPU_OK;
-}
-
-// A distributed hierarchy in global numbering (tests/test_gpu_dist_hierarchy.py).  Rows of a distributed level: this rank's owned ones (level 0:
-// owned cells in caller order, ids in caller-local numbering with the wells at n_local + k, as opmgpu_cpr_level_get); coarse levels: global
-// ids.  agg_gid: the global id of every row's aggregate (-1 on the coarsest level).  A tail level comes back whole.
-template <class S> static int cpr_dist_level_get_t(LinSolver& ls, int level, int64_t* counts, int64_t* row_gid, int32_t* rowptr, int64_t* col_gid,
-                                                   double* val, int64_t* agg_gid)
-{
-    AmgHierarchy<S>* H = cpr_hierarchy<S>(ls);
-    if (!H || level < 0 || level >= int(H->levels.size())) return OPMGPU_EINVAL;
-    int32_t nl = int32_t(H->levels.size());
-    std::vector<int32_t> n(nl); std::vector<int64_t> nnz(nl);
-    int st = cpr_levels_t<S>(ls, &nl, n.data(), nnz.data(), nullptr);
-    if (st != OPMGPU_OK) return st;
-    const int nt = n[level];
-    std::vector<int32_t> rp(nt + 1), cl(nnz[level]), ag(nt, -1);
-    std::vector<double> vl(nnz[level]);
-    st = cpr_level_get_t<S>(ls, level, rp.data(), cl.data(), vl.data(), ag.data(), nullptr);
-    if (st != OPMGPU_OK) return st;
-    const AmgLevel<S>& F = *H->levels[level];
-    const bool last = level + 1 == nl;
-    auto agg_g = [&](int o) -> int64_t {
-        if (last) return -1;
-        const AmgLevel<S>& C = *H->levels[level + 1];
-        return C.dist ? C.h_gid[ag[o]] : int64_t(ag[o]);
-    };
-    std::vector<int> rows;
-    int64_t cnt = 0;
-    const int nown0 = level == 0 && F.dist ? int(std::count(F.h_owned.begin(), F.h_owned.end(), int8_t(1))) : 0;
-    for (int o = 0; o < nt; ++o) {
-        if (level == 0 && F.dist && o >= nown0 && o < F.n) continue;          // a ghost cell
-        rows.push_back(o); cnt += rp[o + 1] - rp[o];
-    }
-    if (counts) { counts[0] = int64_t(rows.size()); counts[1] = cnt; }
-    int64_t q = 0;
-    if (rowptr) rowptr[0] = 0;
-    for (size_t k = 0; k < rows.size(); ++k) {
-        const int o = rows[k];
-        if (row_gid) row_gid[k] = (F.dist && level > 0) ? F.h_gid[o] : int64_t(o);
-        if (agg_gid) agg_gid[k] = agg_g(o);
-        for (int e = rp[o]; e < rp[o + 1]; ++e, ++q) {
-            if (col_gid) col_gid[q] = (F.dist && level > 0) ? F.h_gid[cl[e]] : int64_t(cl[e]);
-            if (val) val[q] = vl[e];
-        }
-        if (rowptr) rowptr[k + 1] = int32_t(q);
-    }
-    return OPMGPU_OK;
-}
-
-template <class S> static int cpr_apply_t(LinSolver& ls, const double* d3, double* v3, double relax)
-{
-    AmgHierarchy<S>* H = cpr_hierarchy<S>(ls);
-    if (!H) return OPMGPU_EINVAL;
-    SolverWork<S>& w = ls.work<S>();
-    const auto roles = cpr_roles(*H);
-    ls.vec_from_host<S>(d3, VEC_BLOCK_INTERLEAVED, w.p.p);
-    ls.cpr_apply<S>(w.p.p, w.y.p, relax, nullptr);
-    ls.vec_to_host<S>(w.y.p, VEC_BLOCK_INTERLEAVED, v3);
-    cpr_restore_roles(*H, roles);
-    return OPMGPU_OK;
-}
-
-template <class S> static int cpr_elliptic_ilu_apply_t(LinSolver& ls, const double* b, double* x)
-{
-    AmgHierarchy<S>* H = cpr_hierarchy<S>(ls);
-    SolverWork<S>& w = ls.work<S>();
-    if (!H || !w.plu.p || !ls.ell.inner || ls.ell.use_amg) return OPMGPU_EINVAL;
-    const AmgLevel<S>& L0 = *H->levels[0];
-    const int n = L0.n, nt = L0.ntot();
-    const hipStream_t st = ls.stream;
-    std::vector<S> hb(nt), hx(nt);
-    for (int i = 0; i < n; ++i) hb[ls.plan.pos[i]] = S(b[i]);
-    for (int k = n; k < nt; ++k) hb[k] = S(b[k]);
-    DevArray<S> db, dx; db.alloc(nt); dx.alloc(nt);
-    db.upload(hb.data(), nt, st);
-    dx.zero(st);
-    ls.elliptic_ilu_apply<S>(db.p, dx.p);
-    dx.download(hx.data(), nt, st);
-    OPMGPU_HIP(hipStreamSynchronize(st));
-    for (int i = 0; i < n; ++i) x[i] = double(hx[ls.plan.pos[i]]);
-    for (int k = n; k < nt; ++k) x[k] = double(hx[k]);
-    return OPMGPU_OK;
-}
-
-extern "C" {
-
+// diagnostics of the CPR pressure hierarchy (LinSolver, cpr_inspect.inl)
 int opmgpu_cpr_elliptic_ilu_apply(opmgpu_ctx* c, const double* b, double* x)
 {
     if (!c || !c->ls || !b || !x) return OPMGPU_EINVAL;
-    return guarded(c, [&]() { return cpr_float(c) ? cpr_elliptic_ilu_apply_t<float>(*c->ls, b, x) : cpr_elliptic_ilu_apply_t<double>(*c->ls, b, x); });
+    return guarded(c, [&]() { return by_precision(cpr_float(c), [&](auto tag) { return c->ls->cpr_elliptic_ilu_apply_host<decltype(tag)>(b, x); }); });
 }
 int opmgpu_cpr_levels(opmgpu_ctx* c, int32_t* nlevels, int32_t* n, int64_t* nnz, int32_t* nw)
 {
     if (!c || !c->ls || !nlevels) return OPMGPU_EINVAL;
-    return guarded(c, [&]() { return cpr_float(c) ? cpr_levels_t<float>(*c->ls, nlevels, n, nnz, nw) : cpr_levels_t<double>(*c->ls, nlevels, n, nnz, nw); });
+    return guarded(c, [&]() { return by_precision(cpr_float(c), [&](auto tag) { return c->ls->cpr_levels<decltype(tag)>(nlevels, n, nnz, nw); }); });
 }
 int opmgpu_cpr_level_get(opmgpu_ctx* c, int level, int32_t* rowptr, int32_t* col, double* val, int32_t* agg, double* dense_inv)
 {
     if (!c || !c->ls) return OPMGPU_EINVAL;
-    return guarded(c, [&]() { return cpr_float(c) ? cpr_level_get_t<float>(*c->ls, level, rowptr, col, val, agg, dense_inv)
-                                                  : cpr_level_get_t<double>(*c->ls, level, rowptr, col, val, agg, dense_inv); });
+    return guarded(c, [&]() { return by_precision(cpr_float(c), [&](auto tag) { return c->ls->cpr_level_get<decltype(tag)>(level, rowptr, col, val, agg, dense_inv); }); });
 }
 int opmgpu_cpr_dist_levels(opmgpu_ctx* c, int32_t* nlevels, int32_t* ndist)
 {
     if (!c || !c->ls || !nlevels || !ndist) return OPMGPU_EINVAL;
-    return guarded(c, [&]() {
-        auto get = [&](auto* H) { if (!H) return int(OPMGPU_EINVAL); *nlevels = int32_t(H->levels.size()); *ndist = H->ndist; return int(OPMGPU_OK); };
-        return cpr_float(c) ? get(cpr_hierarchy<float>(*c->ls)) : get(cpr_hierarchy<double>(*c->ls));
-    });
+    return guarded(c, [&]() { return by_precision(cpr_float(c), [&](auto tag) {
+        auto* H = c->ls->cpr_hierarchy<decltype(tag)>();
+        if (H) { *nlevels = int32_t(H->levels.size()); *ndist = H->ndist; }
+        return int(H ? OPMGPU_OK : OPMGPU_EINVAL);
+    }); });
 }
 int opmgpu_cpr_dist_level_get(opmgpu_ctx* c, int level, int64_t* counts, int64_t* row_gid, int32_t* rowptr, int64_t* col_gid, double* val, int64_t* agg_gid)
 {
     if (!c || !c->ls) return OPMGPU_EINVAL;
-    return guarded(c, [&]() { return cpr_float(c) ? cpr_dist_level_get_t<float>(*c->ls, level, counts, row_gid, rowptr, col_gid, val, agg_gid)
-                                                  : cpr_dist_level_get_t<double>(*c->ls, level, counts, row_gid, rowptr, col_gid, val, agg_gid); });
+    return guarded(c, [&]() { return by_precision(cpr_float(c), [&](auto tag) { return c->ls->cpr_dist_level_get<decltype(tag)>(level, counts, row_gid, rowptr, col_gid, val, agg_gid); }); });
 }
 int opmgpu_cpr_vcycle_apply(opmgpu_ctx* c, const double* b, double* x)
 {
     if (!c || !c->ls || !b || !x) return OPMGPU_EINVAL;
-    return guarded(c, [&]() { return cpr_float(c) ? cpr_vcycle_apply_t<float>(*c->ls, b, x) : cpr_vcycle_apply_t<double>(*c->ls, b, x); });
+    return guarded(c, [&]() { return by_precision(cpr_float(c), [&](auto tag) { return c->ls->cpr_vcycle_apply_host<decltype(tag)>(b, x); }); });
 }
 int opmgpu_cpr_apply(opmgpu_ctx* c, const double* d3, double* v3)
 {
     if (!c || !c->ls || !d3 || !v3) return OPMGPU_EINVAL;
     if (!c->factored) return fail(c, OPMGPU_EINVAL, "no factored CPR solve yet");
-    const double relax = c->prm.cpr_relax * c->prm.cpr_stage2_relax;          // what solve_loaded hands the solvers under CPR
-    return guarded(c, [&]() { return cpr_float(c) ? cpr_apply_t<float>(*c->ls, d3, v3, relax) : cpr_apply_t<double>(*c->ls, d3, v3, relax); });
+    const double relax = cpr_stage2_relaxation(c->prm);          // what solve() hands the solvers under CPR
+    return guarded(c, [&]() { return by_precision(cpr_float(c), [&](auto tag) { return c->ls->cpr_apply_host<decltype(tag)>(d3, v3, relax); }); });
 }
 
 int opmgpu_get_matbalscale(opmgpu_ctx* c, double* scale3)
@@ -609,15 +340,15 @@ int opmgpu_solve(opmgpu_ctx* c, int single_precision, double* dx, int* iters, do
         int st;
         {
             Timed t(c, PH_SOLVE);
-            c->model->early_factor_pending = false;          // (no convergence check between the assembly and this solve: the solve starts the factorisation itself)
-            if (single_precision) { c->ls->ensure_work<float>(); c->model->build_rhs<float>(); st = solve_loaded<float>(c, true, res); if (st == OPMGPU_OK || st == OPMGPU_ELINSOLVE) c->model->store_dx<float>(); }
-            else {
-                struct MirrorScope { LinSolver& ls; ~MirrorScope() { ls.solution_mirror = nullptr; ls.mirror_written = false; } } scope{ *c->ls };      // (also when the solve throws)
-                c->ls->ensure_work<double>(); c->model->build_rhs<double>();
-                c->ls->solution_mirror = c->model->dx_device();          // a GMRES solve stores its solution there too: store_dx then has nothing to copy
-                st = solve_loaded<double>(c, true, res);
-                if (st == OPMGPU_OK || st == OPMGPU_ELINSOLVE) c->model->store_dx<double>();
-            }
+            struct MirrorScope { LinSolver& ls; ~MirrorScope() { ls.solution_mirror = nullptr; ls.mirror_written = false; } } scope{ *c->ls };      // (also when the solve throws)
+            st = by_precision(single_precision != 0, [&](auto tag) {
+                using S = decltype(tag);
+                c->ls->ensure_work<S>(); c->model->build_rhs<S>();
+                if (sizeof(S) == 8) c->ls->solution_mirror = c->model->dx_device();          // a GMRES solve stores its solution there too: store_dx then has nothing to copy
+                const int s = solved(c, c->ls->solve<S>(c->prm, true, res, c->err));
+                if (s == OPMGPU_OK || s == OPMGPU_ELINSOLVE) c->model->store_dx<S>();
+                return s;
+            });
         }
         c->cur_single = single_precision ? 1 : 0;
         if (iters) *iters = res.iterations;
@@ -980,7 +711,7 @@ int opmgpu_load_bsr(opmgpu_ctx* c, int nb, const int32_t* rowptr, const int32_t*
         const int st = c->ls->set_pattern(nb, rowptr, col, c->prm.ilu_ordering);
         if (st != OPMGPU_OK) return fail(c, st, "invalid BSR pattern");
         c->ls->load_host_bsr(val9);
-        if (single_precision) c->ls->prepare<float>(true); else c->ls->prepare<double>(true);
+        by_precision(single_precision != 0, [&](auto tag) { c->ls->prepare<decltype(tag)>(true); });
         c->cur_single = single_precision ? 1 : 0;
         c->matrix_loaded = true; c->factored = false; c->ls->ref_transformed = false;
         return int(OPMGPU_OK);
@@ -993,21 +724,20 @@ int opmgpu_solve_bsr(opmgpu_ctx* c, int nb, const int32_t* rowptr, const int32_t
     if (!c || !rhs3 || !x3) return OPMGPU_EINVAL;
     const int st0 = opmgpu_load_bsr(c, nb, rowptr, col, val9, single_precision);
     if (st0 != OPMGPU_OK) return st0;
-    return guarded(c, [&]() {
+    return guarded(c, [&]() { return by_precision(single_precision != 0, [&](auto tag) {
+        using S = decltype(tag);
+        LinSolver& ls = *c->ls;
         SolveResult res; int st;
         {
             Timed t(c, PH_SOLVE);
-            if (single_precision) { c->ls->vec_from_host<float>(rhs3, VEC_BLOCK_INTERLEAVED, c->ls->work<float>().b.p); st = solve_loaded<float>(c, false, res); }
-            else { c->ls->vec_from_host<double>(rhs3, VEC_BLOCK_INTERLEAVED, c->ls->work<double>().b.p); st = solve_loaded<double>(c, false, res); }
+            ls.vec_from_host<S>(rhs3, VEC_BLOCK_INTERLEAVED, ls.work<S>().b.p);
+            st = solved(c, ls.solve<S>(c->prm, false, res, c->err));
         }
         if (iters) *iters = res.iterations;
         if (reduction) *reduction = res.reduction;
-        if (st == OPMGPU_OK || st == OPMGPU_ELINSOLVE) {
-            if (single_precision) c->ls->vec_to_host<float>(c->ls->work<float>().x.p, VEC_BLOCK_INTERLEAVED, x3);
-            else c->ls->vec_to_host<double>(c->ls->work<double>().x.p, VEC_BLOCK_INTERLEAVED, x3);
-        }
+        if (st == OPMGPU_OK || st == OPMGPU_ELINSOLVE) ls.vec_to_host<S>(ls.work<S>().x.p, VEC_BLOCK_INTERLEAVED, x3);
         return st;
-    });
+    }); });
 }
 
 // make sure the matrix exists in the precision the kernel-level entry points will use
@@ -1024,8 +754,7 @@ int opmgpu_spmv(opmgpu_ctx* c, const double* x3, double* y3)
     return guarded(c, [&]() {
         const int st = ensure_prepared(c); if (st) return st;
         LinSolver& ls = *c->ls;
-        if (c->cur_single) { auto& w = ls.work<float>(); ls.vec_from_host<float>(x3, VEC_BLOCK_INTERLEAVED, w.p.p); ls.spmv<float>(w.p.p, w.v.p); ls.vec_to_host<float>(w.v.p, VEC_BLOCK_INTERLEAVED, y3); }
-        else { auto& w = ls.work<double>(); ls.vec_from_host<double>(x3, VEC_BLOCK_INTERLEAVED, w.p.p); ls.spmv<double>(w.p.p, w.v.p); ls.vec_to_host<double>(w.v.p, VEC_BLOCK_INTERLEAVED, y3); }
+        by_precision(c->cur_single != 0, [&](auto tag) { using S = decltype(tag); auto& w = ls.work<S>(); ls.vec_from_host<S>(x3, VEC_BLOCK_INTERLEAVED, w.p.p); ls.spmv<S>(w.p.p, w.v.p); ls.vec_to_host<S>(w.v.p, VEC_BLOCK_INTERLEAVED, y3); });
         return int(OPMGPU_OK);
     });
 }
@@ -1036,9 +765,9 @@ int opmgpu_ilu0_factor(opmgpu_ctx* c)
     return guarded(c, [&]() {
         const int st = ensure_prepared(c); if (st) return st;
         const int fill = fill_level_of(c->prm);
-        if (fill < 0 || fill > 8) return fail(c, OPMGPU_EINVAL, "cpr_ilu_n / ilu_fillin_level must be in 0..8");
+        if (fill < 0) return fail(c, OPMGPU_EINVAL, kFillLevelRange);
         c->ls->fill_level = fill;
-        const int s2 = c->cur_single ? c->ls->factor<float>() : c->ls->factor<double>();
+        const int s2 = by_precision(c->cur_single != 0, [&](auto tag) { return c->ls->factor<decltype(tag)>(); });
         c->factored = (s2 == OPMGPU_OK);
         return s2 == OPMGPU_OK ? int(OPMGPU_OK) : fail(c, s2, "singular diagonal block in ILU0");
     });
@@ -1050,8 +779,7 @@ int opmgpu_ilu0_apply(opmgpu_ctx* c, const double* d3, double* v3)
     if (!c->factored) return fail(c, OPMGPU_EINVAL, "call opmgpu_ilu0_factor first");
     return guarded(c, [&]() {
         LinSolver& ls = *c->ls;
-        if (c->cur_single) { auto& w = ls.work<float>(); ls.vec_from_host<float>(d3, VEC_BLOCK_INTERLEAVED, w.p.p); ls.ilu_apply<float>(w.p.p, w.y.p, c->prm.ilu_relaxation, nullptr); ls.vec_to_host<float>(w.y.p, VEC_BLOCK_INTERLEAVED, v3); }
-        else { auto& w = ls.work<double>(); ls.vec_from_host<double>(d3, VEC_BLOCK_INTERLEAVED, w.p.p); ls.ilu_apply<double>(w.p.p, w.y.p, c->prm.ilu_relaxation, nullptr); ls.vec_to_host<double>(w.y.p, VEC_BLOCK_INTERLEAVED, v3); }
+        by_precision(c->cur_single != 0, [&](auto tag) { using S = decltype(tag); auto& w = ls.work<S>(); ls.vec_from_host<S>(d3, VEC_BLOCK_INTERLEAVED, w.p.p); ls.ilu_apply<S>(w.p.p, w.y.p, c->prm.ilu_relaxation, nullptr); ls.vec_to_host<S>(w.y.p, VEC_BLOCK_INTERLEAVED, v3); });
         return int(OPMGPU_OK);
     });
 }
@@ -1075,7 +803,7 @@ int opmgpu_ilu0_get(opmgpu_ctx* c, double* val9)
     if (!c || !val9) return OPMGPU_EINVAL;
     if (!c->factored) return fail(c, OPMGPU_EINVAL, "call opmgpu_ilu0_factor first");
     if (c->ls->fill_level > 0) return fail(c, OPMGPU_EINVAL, "opmgpu_ilu0_get returns the ILU0 factors on the matrix's pattern: not with cpr_ilu_n / ilu_fillin_level > 0");
-    return guarded(c, [&]() { if (c->cur_single) c->ls->get_lu_bsr<float>(val9); else c->ls->get_lu_bsr<double>(val9); return OPMGPU_OK; });
+    return guarded(c, [&]() { by_precision(c->cur_single != 0, [&](auto tag) { c->ls->get_lu_bsr<decltype(tag)>(val9); }); return OPMGPU_OK; });
 }
 
 int opmgpu_get_ordering(opmgpu_ctx* c, int32_t* position, int32_t* level, int32_t* nlevels)
@@ -1090,12 +818,12 @@ int opmgpu_get_ordering(opmgpu_ctx* c, int32_t* position, int32_t* level, int32_
 int opmgpu_get_cpr_weights(opmgpu_ctx* c, double* w)
 {
     if (!c || !w || !c->ls->has_pattern()) return OPMGPU_EINVAL;
-    return guarded(c, [&]() {
-        LinSolver& ls = *c->ls;
-        if (c->cur_single == 1) { if (!ls.work<float>().cprw.p) return fail(c, OPMGPU_EINVAL, "no CPR solve yet"); ls.vec_to_host<float>(ls.work<float>().cprw.p, VEC_EQUATION_MAJOR, w); }
-        else { if (!ls.work<double>().cprw.p) return fail(c, OPMGPU_EINVAL, "no CPR solve yet"); ls.vec_to_host<double>(ls.work<double>().cprw.p, VEC_EQUATION_MAJOR, w); }
+    return guarded(c, [&]() { return by_precision(c->cur_single == 1, [&](auto tag) {
+        const auto& cprw = c->ls->work<decltype(tag)>().cprw;
+        if (!cprw.p) return fail(c, OPMGPU_EINVAL, "no CPR solve yet");
+        c->ls->vec_to_host<decltype(tag)>(cprw.p, VEC_EQUATION_MAJOR, w);
         return int(OPMGPU_OK);
-    });
+    }); });
 }
 
 int opmgpu_get_residual(opmgpu_ctx* c, double* r)
@@ -1132,7 +860,7 @@ int opmgpu_time_kernel(opmgpu_ctx* c, int kernel, int reps, double* ms_per_launc
             return int(OPMGPU_OK);
         }
         const int st = ensure_prepared(c); if (st) return st;
-        if (c->cur_single) c->ls->ensure_work<float>(); else c->ls->ensure_work<double>();
+        by_precision(c->cur_single != 0, [&](auto tag) { c->ls->ensure_work<decltype(tag)>(); });
         if ((kernel == OPMGPU_K_ILU_APPLY) && !c->factored) return fail(c, OPMGPU_EINVAL, "call opmgpu_ilu0_factor first");
         *ms_per_launch = c->ls->time_kernel(kernel, reps, c->cur_single);
         return int(OPMGPU_OK);

@@ -397,7 +397,7 @@ template <class S> void LinSolver::cpr_reference_transform()
         // coarse space); the bordered well column is formed from the ORIGINAL weights and carries the pressure row's scaling
         hipLaunchKernelGGL((k_unit_weights<S>), dim3(grid_for(plan.nbp)), dim3(kBlock), 0, stream, plan.nbp, w.cprw.p);
         weights_from_assembly = true;
-        border_weights = w.cprw_orig.p; border_colscale = pscale;
+        now.border_weights = w.cprw_orig.p; now.border_colscale = pscale;
         ref_transformed = true;
         pre_stale = true;
         pilu.stale = true;
@@ -469,7 +469,7 @@ template <class S> void LinSolver::cpr_prepare()
         //    this time step and the next 8 (bicgstab's epilogue sets lag_block);
         //  * only for the loose reductions of Newton solves (>= 1e-4): at 1e-11 a lagged hierarchy stagnated on a grid with isolated
         //    cells (several near-null modes; tests/test_gpu_fullsize.py, Norne-like); and a lagged solve that fails is repeated once
-        //    on fresh operators before the failure is reported (solve_loaded in capi.hip).
+        //    on fresh operators before the failure is reported (solve(), solve.inl).
         // OPMGPU_AMG_LAG_COARSE: 0 = refresh for every matrix, 1 = this policy (default), k > 1 = every k-th matrix, no guards.
         bool refresh;
         if (coarse_lag == 0) refresh = true;
@@ -482,11 +482,11 @@ template <class S> void LinSolver::cpr_prepare()
         new_step_hint = false;
         refreshed = refresh;
         if (w.amg->border_nw() > 0)
-            hipLaunchKernelGGL((k_cpr_border<S>), dim3(lowrank.nw), dim3(kBlock), 0, stream, lowrank, plan.nbp, border_weights ? (const S*)border_weights : (const S*)w.cprw.p, w.amg->levels[0]->val.p + w.amg->levels[0]->nentries, border_colscale);
+            hipLaunchKernelGGL((k_cpr_border<S>), dim3(lowrank.nw), dim3(kBlock), 0, stream, lowrank, plan.nbp, now.border_weights ? (const S*)now.border_weights : (const S*)w.cprw.p, w.amg->levels[0]->val.p + w.amg->levels[0]->nentries, now.border_colscale);
         // The factorisation (HBM-bound, 140 us, on its own stream) is needed by the first ILU0 sweep only, i.e. behind the hierarchy set-up
         // AND the first V-cycle.  It starts when the level 0 -> 1 Galerkin sums are done -- the one bandwidth-heavy kernel of the chain,
         // which it would slow from 60 to 100 us -- and runs next to the small levels' sums and the first cycle (latency-bound launches).
-        w.amg->galerkin(refresh && !(ell.inner && !ell.use_amg), [&] { if (factor_deferred) { factor_deferred = false; factor_async<S>(); } });
+        w.amg->galerkin(refresh && !(ell.inner && !ell.use_amg), [&] { if (now.factor_deferred) { now.factor_deferred = false; factor_async<S>(); } });
         if (ell.inner && !ell.use_amg) elliptic_factor<S>();
         if (coarse_nsub >= 1) coarse_setup<S>(true);
         return;
@@ -511,7 +511,7 @@ template <class S> void LinSolver::cpr_prepare()
             OPMGPU_HIP(hipMemcpyAsync(bs.connpos.data(), lowrank.connpos, (bs.nw + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
             OPMGPU_HIP(hipMemcpyAsync(bs.perf_row.data(), lowrank.perf_row, bs.nperf * sizeof(int32_t), hipMemcpyDeviceToHost, stream));
             DevArray<S> bt; bt.alloc(2 * size_t(bs.nperf) + bs.nw);
-            hipLaunchKernelGGL((k_cpr_border<S>), dim3(lowrank.nw), dim3(kBlock), 0, stream, lowrank, plan.nbp, border_weights ? (const S*)border_weights : (const S*)w.cprw.p, bt.p, border_colscale);
+            hipLaunchKernelGGL((k_cpr_border<S>), dim3(lowrank.nw), dim3(kBlock), 0, stream, lowrank, plan.nbp, now.border_weights ? (const S*)now.border_weights : (const S*)w.cprw.p, bt.p, now.border_colscale);
             std::vector<S> hb(bt.n);
             bt.download(hb.data(), bt.n, stream);
             OPMGPU_HIP(hipStreamSynchronize(stream));
@@ -524,7 +524,7 @@ template <class S> void LinSolver::cpr_prepare()
     hipLaunchKernelGGL((k_extract_pressure<S>), dim3(grid_for(plan.nbp)), dim3(kBlock), 0, stream, plan.nb, plan.nbp, dp.slice_ptr.p, (const S*)w.cprw.p, ((emulate_what & 2) ? pre_matrix<S>() : matrix<S>()),
                        w.amg->levels[0]->val.p);
     if (w.amg->border_nw() > 0)
-        hipLaunchKernelGGL((k_cpr_border<S>), dim3(lowrank.nw), dim3(kBlock), 0, stream, lowrank, plan.nbp, border_weights ? (const S*)border_weights : (const S*)w.cprw.p, w.amg->levels[0]->val.p + w.amg->levels[0]->nentries, border_colscale);
+        hipLaunchKernelGGL((k_cpr_border<S>), dim3(lowrank.nw), dim3(kBlock), 0, stream, lowrank, plan.nbp, now.border_weights ? (const S*)now.border_weights : (const S*)w.cprw.p, w.amg->levels[0]->val.p + w.amg->levels[0]->nentries, now.border_colscale);
     w.amg->galerkin();
     if (ell.inner && !ell.use_amg) elliptic_factor<S>();
     new_step_hint = false; refreshed = true;
@@ -587,7 +587,7 @@ template <class S> void LinSolver::cpr_apply(const S* d, S* v, double relax, con
     const bool coarse = coarse_nsub >= 1;
     const bool emulated = !comm && emulate_ranks > 1;
     // the sum [x_p; 0; 0] + ILU0^-1 z formed inside the sweeps (linsolver.hpp, cpr_cancel_p): a two-level plan, every relaxation factor 1
-    const bool cancel = cancel_p_now && plan.nlevels == 2 && relax == 1.0 && ell.relax == 1.0 && fill_level == 0 && !point_stage2;
+    const bool cancel = cancel_p_now && plan.nlevels == 2 && relax == 1.0 && ell.relax == 1.0 && fill_level == 0 && !now.point_stage2;
     // the top level's part of the stage-2 residual through the ILU0 factor (linsolver.hpp, cpr_factor_p).  Everything `cancel` asks, each for
     // a reason of this path's own:
     //   cancel_p_now      -- the level-0 rows' backward sweep starts from d, so z on those rows is the forward sweep's input and nothing else,
@@ -689,7 +689,7 @@ template <class S> void LinSolver::cpr_apply(const S* d, S* v, double relax, con
     if (overlap) halo_overlapped(*this, w.hx.p, presidual);
     else { if (exchange) halo(comm, w.hx.p, stream); presidual(0); }
     kt.end(KT_CPR_OTHER, kt_a);
-    if (point_stage2 && sizeof(S) == 8) point_ilu_apply(reinterpret_cast<const double*>(w.z.p), reinterpret_cast<double*>(v), relax);      // the reference's own stage 2 (pointilu.inl)
+    if (now.point_stage2 && sizeof(S) == 8) point_ilu_apply(reinterpret_cast<const double*>(w.z.p), reinterpret_cast<double*>(v), relax);      // the reference's own stage 2 (pointilu.inl)
     else ilu_apply<S>(w.z.p, v, relax, ctl, cancel ? d : (const S*)nullptr, cancel ? xp : (const S*)nullptr, factor_p ? amat : (const S*)nullptr);
     kt_a = kt.begin();
     if (well_woodbury && wb_active && lowrank.nw > 0 && lowrank.P && !comm && wb_buf.p && fill_level == 0)

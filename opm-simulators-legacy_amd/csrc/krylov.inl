@@ -262,16 +262,16 @@ template <class S> SolveResult LinSolver::bicgstab(const opmgpu_params& prm)
     // neighbours is a ghost whose entry of M^-1 p is overwritten by the halo exchange (multi-GPU: light_ok masks those rows out)
     const bool cpr = prm.use_cpr != 0;                   // multi-GPU: rank-local (additive Schwarz) AMG + block-Jacobi ILU0
     lag_allowed = prm.linear_solver_reduction >= 1e-4;
-    const bool mx = mixed && sizeof(S) == 8;
+    const bool mx = now.mixed && sizeof(S) == 8;
     if (cpr) { if (mx) cpr_prepare_mixed(); else cpr_prepare<S>(); }
-    if (factor_deferred) { factor_deferred = false; if (mx) factor_async<float>(); else factor_async<S>(); }
+    if (now.factor_deferred) { now.factor_deferred = false; if (mx) factor_async<float>(); else factor_async<S>(); }
     if (cpr) { if (mx) { if (!wf.amg->npost0_user) wf.amg->npost0 = 2; } else if (!w.amg->npost0_user) w.amg->npost0 = 2; }   // post-sweeps on level 0: 2 under BiCGStab, 1 under GMRES (see gmres)
     solution_mirror = nullptr; mirror_written = false;          // (the mirror is GMRES': this solver's caller copies x)
     cancel_p_now = false;
     if (cpr) { if (mx) wf.amg->lane_restrict = lean_conditions(); else w.amg->lane_restrict = lean_conditions(); }      // the V-cycle's restriction: shared with gmres()
     // (with cpr_relax != 1 the pressure part of M^-1 p is scaled, which the closed form does not cover)
     // (mixed precision: the float ILU0 is not the ILU0 of exactly the double matrix -- the closed form would be off by float rounding)
-    const bool closed = closed_form_level0 && emulate_ranks <= 1 && !(cpr && ell.relax != 1.0) && !mx && !(cpr && point_stage2) && fill_level == 0;      // (ell.relax = cpr_relax; under CPR prm.ilu_relaxation holds cpr_relax * cpr_stage2_relax: solve_loaded)
+    const bool closed = closed_form_level0 && emulate_ranks <= 1 && !(cpr && ell.relax != 1.0) && !mx && !(cpr && now.point_stage2) && fill_level == 0;      // (ell.relax = cpr_relax; under CPR prm.ilu_relaxation holds cpr_relax * cpr_stage2_relax: solve())
     const int8_t* lightmask = nullptr;
     const bool overlap = comm && halo_overlap;
     if (comm && (closed || overlap)) {
@@ -752,9 +752,9 @@ template <class S> SolveResult LinSolver::gmres(const opmgpu_params& prm)
     // the GMRES option keeps the pressure hierarchy fresh for every matrix (it is the reference's robustness fallback; the lag policy of the
     // BiCGStab path, cpr_prepare, was measured under it without a gain on the 5-spot deck)
     lag_allowed = false;
-    const bool mx = mixed && sizeof(S) == 8;
+    const bool mx = now.mixed && sizeof(S) == 8;
     if (cpr) { if (mx) cpr_prepare_mixed(); else cpr_prepare<S>(); }
-    if (factor_deferred) { factor_deferred = false; if (mx) factor_async<float>(); else factor_async<S>(); }
+    if (now.factor_deferred) { now.factor_deferred = false; if (mx) factor_async<float>(); else factor_async<S>(); }
     // one post-smoothing sweep on level 0 instead of two: measured over nine decks with wells +1..+5 % under GMRES (the same iteration
     // counts within 0.1, a cheaper cycle), -7..0 % under BiCGStab on the well-free decks (profiles/r02_amg_sweep_gmres.log)
     if (cpr) { if (mx) { if (!wf.amg->npost0_user) wf.amg->npost0 = 1; } else if (!w.amg->npost0_user) w.amg->npost0 = 1; }
@@ -814,7 +814,7 @@ template <class S> SolveResult LinSolver::gmres(const opmgpu_params& prm)
     //   no row transform  -- cpr_reference_transform is the comparison mode against the reference's formulation (L A x = L b, optionally its point
     //                        ILU0): it keeps the explicit product, the closed form was not validated on the transformed system.
     // The perforated level-0 rows keep the full product (gm_light).
-    const bool gm_closed = closed_form_level0 && emulate_ranks <= 1 && !(cpr && ell.relax != 1.0) && !mx && !(cpr && point_stage2) && fill_level == 0      // bicgstab()'s `closed`
+    const bool gm_closed = closed_form_level0 && emulate_ranks <= 1 && !(cpr && ell.relax != 1.0) && !mx && !(cpr && now.point_stage2) && fill_level == 0      // bicgstab()'s `closed`
                            && sizeof(S) == 8 && !flex && !verify && !comm && prm.ilu_relaxation == 1.0 && !(well_woodbury && wb_active) && prm.cpr_reference_transform == 0;
     const int8_t* gm_mask = nullptr;
     if (gm_closed) {

@@ -19,6 +19,7 @@
 #include <cstring>
 #include <map>
 #include <memory>
+#include <type_traits>
 
 namespace opmgpu {
 
@@ -358,8 +359,8 @@ __global__ __launch_bounds__(kBlock) void k_ilu_factor(int lo, int hi, const int
                                                        const int32_t* __restrict__ trip_t, const S* __restrict__ A, const int16_t* __restrict__ rowlen,
                                                        S* __restrict__ lu, int32_t* __restrict__ flags, const int8_t* __restrict__ simple_row, int copy_upper)
 {
-    // grid-stride over the level's rows: the launch may be capped to a fraction of the device (LinSolver::factor_grid_cap) so that a
-    // factorisation running on its side stream leaves compute units and HBM queue slots to the latency-bound kernels of the main stream
+    // grid-stride over the level's rows (factor() launches one thread per row; a launch capped to a fraction of the device, for a
+    // factorisation on its side stream, changed nothing: DESIGN section 11)
   for (int row = lo + blockIdx.x * kBlock + threadIdx.x; row < hi; row += gridDim.x * kBlock) {
     const int base = slice_ptr[row >> 6], lane = row & 63, nl = nlower[row];
     const int len = rowlen[row];
@@ -570,8 +571,7 @@ LinSolver::LinSolver(hipStream_t s) : stream(s)
     cpr_halo_xp = env_flag("OPMGPU_CPR_HALO_XP", cpr_halo_xp);
     halo_overlap = env_flag("OPMGPU_HALO_OVERLAP", halo_overlap);
     factor_overlap = env_flag("OPMGPU_FACTOR_OVERLAP", factor_overlap);
-    if (const char* e = std::getenv("OPMGPU_FACTOR_EARLY")) { factor_early_on = std::atoi(e) != 0; if (factor_early_on) factor_early_mode = std::atoi(e) == 2 ? 2 : 1; }
-    factor_grid_cap = env_int("OPMGPU_FACTOR_GRID", factor_grid_cap);
+    factor_early_on = env_flag("OPMGPU_FACTOR_EARLY", factor_early_on);
     cs_recur = env_flag("OPMGPU_CS_RECUR", cs_recur);
     if (const char* e = std::getenv("OPMGPU_CPR_L0_HALO")) { cpr_l0_halo = std::atoi(e) != 0; cpr_l0_halo_down = std::atoi(e) != 2; }
     corr_policy.on = env_flag("OPMGPU_AMG_ADAPT", corr_policy.on);
@@ -583,7 +583,7 @@ LinSolver::LinSolver(hipStream_t s) : stream(s)
 }
 bool LinSolver::plain_setup() const
 {
-    return !comm && emulate_ranks <= 1 && fill_level == 0 && !point_stage2 && !(well_woodbury && wb_active);
+    return !comm && emulate_ranks <= 1 && fill_level == 0 && !now.point_stage2 && !(well_woodbury && wb_active);
 }
 LinSolver::~LinSolver()
 {
@@ -801,9 +801,7 @@ template <class S> int LinSolver::factor(bool wait)
     for (int l = 0; l < plan.nlevels; ++l) {
         const int lo = plan.level_ptr[l], hi = plan.level_ptr[l + 1];
         if (hi == lo) continue;
-        const int gfull = grid_for(hi - lo);
-        const int gcap = (factor_throttled && factor_grid_cap > 0) ? std::min(gfull, factor_grid_cap) : gfull;
-        hipLaunchKernelGGL((k_ilu_factor<S>), dim3(gcap), dim3(kBlock), 0, stream, lo, hi, dp.slice_ptr.p, dp.col.p,
+        hipLaunchKernelGGL((k_ilu_factor<S>), dim3(grid_for(hi - lo)), dim3(kBlock), 0, stream, lo, hi, dp.slice_ptr.p, dp.col.p,
                            dp.nlower.p, dp.trip_ptr.p, dp.trip_l.p, dp.trip_u.p, dp.trip_t.p, ((emulate_what & 1) ? pre_matrix<S>() : matrix<S>()), dp.rowlen.p, w.LU.p, flags.p,
                            (const int8_t*)dp.simple.p, int(lu_copy_upper));
     }
@@ -834,9 +832,7 @@ template <class S> void LinSolver::factor_async()
     OPMGPU_HIP(hipStreamWaitEvent(factor_stream, ev_factor[0], 0));
     {
         StreamSwapGuard g(stream, factor_stream, kt.on);  // (event brackets belong to the main stream); restored also if factor() throws
-        factor_throttled = true;
-        try { (void)factor<S>(false); } catch (...) { factor_throttled = false; throw; }
-        factor_throttled = false;
+        (void)factor<S>(false);
     }
     OPMGPU_HIP(hipEventRecord(ev_factor[1], factor_stream));
     factor_pending = true;
@@ -996,7 +992,7 @@ void LinSolver::cpr_prepare_mixed()
 }
 template <class S> void LinSolver::precond_apply(const S* d, S* out, double relax, const SolveCtl* ctl, bool cpr, const double* cr_given)
 {
-    if (!mixed || sizeof(S) == 4) {
+    if (!now.mixed || sizeof(S) == 4) {
         if (cpr) cpr_apply<S>(d, out, relax, ctl, cr_given); else ilu_apply<S>(d, out, relax, ctl);
         return;
     }
@@ -1008,6 +1004,8 @@ template <class S> void LinSolver::precond_apply(const S* d, S* out, double rela
 }
 
 #include "krylov.inl"
+#include "solve.inl"
+#include "cpr_inspect.inl"
 
 template <class S> void LinSolver::vec_in(const double* dsrc, int layout, S* d)
 {
@@ -1124,29 +1122,25 @@ double LinSolver::time_kernel(int kernel, int reps, int single_precision)
     return single_precision ? time_kernel_t<float>(*this, kernel, reps, 0.9) : time_kernel_t<double>(*this, kernel, reps, 0.9);
 }
 
-// explicit instantiations
+// explicit instantiations: what other translation units call; bicgstab and gmres (solve() calls them) stay named symbols of the library
 #define OPMGPU_INST(S)                                                                  \
     template void LinSolver::ensure_work<S>();                                           \
     template int LinSolver::factor<S>(bool);                                                 \
     template void LinSolver::ilu_apply<S>(const S*, S*, double, const SolveCtl*, const S*, const S*, const S*);        \
     template void LinSolver::spmv<S>(const S*, S*);                                      \
-    template void LinSolver::spmv_at<S>(const S*, S*, const S*, const int32_t*);        \
-    template void LinSolver::cpr_prepare<S>();                                           \
-    template void LinSolver::elliptic_ilu_apply<S>(const S*, S*);                         \
-    template void LinSolver::cpr_reference_transform<S>();                               \
     template void LinSolver::cpr_reweigh_rows<S>(const int32_t*, int);                   \
-    template const S* LinSolver::pre_matrix<S>();                                        \
-    template void LinSolver::coarse_setup<S>(bool);                                      \
-    template void LinSolver::coarse_begin<S>();                                          \
-    template void LinSolver::cpr_apply<S>(const S*, S*, double, const SolveCtl*, const double*);        \
-    template void LinSolver::factor_async<S>();                                          \
-    template void LinSolver::precond_apply<S>(const S*, S*, double, const SolveCtl*, bool, const double*); \
     template SolveResult LinSolver::bicgstab<S>(const opmgpu_params&);                   \
     template SolveResult LinSolver::gmres<S>(const opmgpu_params&);                      \
+    template int LinSolver::solve<S>(const opmgpu_params&, bool, SolveResult&, std::string&);      \
+    template AmgHierarchy<S>* LinSolver::cpr_hierarchy<S>();                             \
+    template int LinSolver::cpr_levels<S>(int32_t*, int32_t*, int64_t*, int32_t*);       \
+    template int LinSolver::cpr_level_get<S>(int, int32_t*, int32_t*, double*, int32_t*, double*);        \
+    template int LinSolver::cpr_dist_level_get<S>(int, int64_t*, int64_t*, int32_t*, int64_t*, double*, int64_t*);        \
+    template int LinSolver::cpr_vcycle_apply_host<S>(const double*, double*);            \
+    template int LinSolver::cpr_apply_host<S>(const double*, double*, double);           \
+    template int LinSolver::cpr_elliptic_ilu_apply_host<S>(const double*, double*);      \
     template void LinSolver::vec_from_host<S>(const double*, int, S*);                   \
     template void LinSolver::vec_to_host<S>(const S*, int, double*);                     \
-    template void LinSolver::vec_in<S>(const double*, int, S*);                          \
-    template void LinSolver::vec_out<S>(const S*, int, double*);                         \
     template void LinSolver::get_lu_bsr<S>(double*);
 OPMGPU_INST(float)
 OPMGPU_INST(double)

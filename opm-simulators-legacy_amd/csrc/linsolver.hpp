@@ -110,7 +110,18 @@ struct SolverWork {
     bool allocated = false;
 };
 
+// called between the library's own objects only and naming a type of the C ABI: kept out of the shared library's dynamic symbols
+#define OPMGPU_LOCAL __attribute__((visibility("hidden")))
+
 struct SolveResult { int status = 0; int iterations = 0; double reduction = 0.0; bool converged = false; };
+
+// Two readings of opmgpu_params that the solve's driver, the early factorisation and the diagnostic entry points share.
+// Under CPR the second stage's ILU0 takes the CPR preconditioner's own relaxation (cpr_relax, NewtonIterationBlackoilCPR.hpp:59) times
+// cpr_stage2_relax, not the interleaved solver's ilu_relaxation
+inline double cpr_stage2_relaxation(const opmgpu_params& prm) { return prm.cpr_relax * prm.cpr_stage2_relax; }
+// block ILU(n) instead of the ILU0 (fillilu.inl): cpr_ilu_n under CPR, the interleaved solver's ilu_fillin_level otherwise; -1 = outside 0..8
+inline int fill_level_of(const opmgpu_params& prm) { const int n = prm.use_cpr ? prm.cpr_ilu_n : prm.ilu_fillin_level; return n < 0 || n > 8 ? -1 : n; }
+constexpr const char* kFillLevelRange = "cpr_ilu_n / ilu_fillin_level must be in 0..8";
 
 class LinSolver {
 public:
@@ -163,7 +174,7 @@ public:
     void drop_hierarchies();            // the wells changed: the bordered pressure hierarchy is rebuilt from the next matrix
     // The elliptic part the way the reference's CPR plug-in documents it (NewtonIterationBlackoilCPR.hpp:59-63; elliptic.inl): an inner
     // BiCGStab / CG on A_p, preconditioned by a point ILU0 of A_p (cpr_use_amg = 0) or by the AMG cycle.  inner = false (cpr_max_ell_iter
-    // = 0): one application of the AMG cycle, no inner method.  Set from opmgpu_params before every solve (capi.hip, solve_loaded).
+    // = 0): one application of the AMG cycle, no inner method.  Set from opmgpu_params by every solve().
     struct EllipticCfg { bool inner = false, use_amg = true, bicgstab = true; double tol = 1e-2; int maxit = 25; double relax = 1.0; } ell;
     long ell_solves = 0, ell_iterations = 0;     // inner solves / inner iterations since the context was created (opmgpu_cpr_elliptic_stats)
     DevArray<double> ell_parts;
@@ -171,6 +182,14 @@ public:
     template <class S> void elliptic_solve();
     template <class S> void elliptic_ilu_apply(const S* d, S* out);   // out = relax (LU)^-1 d: the point ILU0 of A_p (border rows: their diagonal)
     template <class S> void cpr_apply(const S* d, S* v, double relax, const SolveCtl* ctl, const double* cr_given = nullptr);
+    // Diagnostics of the pressure hierarchy (cpr_inspect.inl; the opmgpu_cpr_* entry points): host arrays in caller numbering, OPMGPU_* status
+    template <class S> AmgHierarchy<S>* cpr_hierarchy();      // the hierarchy of the last CPR solve in precision S, or nullptr
+    template <class S> int cpr_levels(int32_t* nlevels, int32_t* n, int64_t* nnz, int32_t* nw);
+    template <class S> int cpr_level_get(int level, int32_t* rowptr, int32_t* col, double* val, int32_t* agg, double* dense_inv);
+    template <class S> int cpr_dist_level_get(int level, int64_t* counts, int64_t* row_gid, int32_t* rowptr, int64_t* col_gid, double* val, int64_t* agg_gid);
+    template <class S> int cpr_vcycle_apply_host(const double* b, double* x);
+    template <class S> int cpr_apply_host(const double* d3, double* v3, double relax);
+    template <class S> int cpr_elliptic_ilu_apply_host(const double* b, double* x);
     // opmgpu_params.cpr_reference_transform: the reference's CPR formulation (NewtonIterationUtilities.cpp:253-287 formEllipticSystem,
     // NewtonIterationBlackoilCPR.cpp:117-131): the WHOLE system is row-transformed by the per-cell matrix L -- first row = the sum of the
     // dominant equations (the pressure equation), scaled by 200 bar; second / third row = the water / gas equation, or the oil equation
@@ -179,8 +198,6 @@ public:
     // select the transformed pressure row.  The solution x is that of the untransformed system.
     template <class S> void cpr_reference_transform();
     bool ref_transformed = false;      // the resident matrix is L A (reset by whoever writes a new matrix)
-    const void* border_weights = nullptr;   // weights of the bordered pressure column when cprw are the transformed system's unit weights
-    double border_colscale = 1.0;
     // The scaling of the coarse-grid corrections, chosen per TIME STEP by what it does to the iteration counts (DESIGN sections 4b, 11): two
     // settings; a whole time step runs under one of them and is scored by its linear iterations per Newton iteration (one solve's count
     // follows the Newton iteration's index more than the setting -- round 3's first, per-solve form of this policy was misled by that);
@@ -232,25 +249,35 @@ public:
         bool built = false;
         int for_level = -1, for_ordering = -1, for_plan_id = -1, nnzb_filled = 0;
     } fill;
-    int fill_level = 0;
+    int fill_level = 0;                // the kind of the resident factors (what ilu_apply / get_lu_bsr read): set by solve(), and by opmgpu_ilu0_factor before its factor<S>()
     void fill_setup();
     template <class S> int fill_factor(bool wait);
     template <class S> void fill_apply(const S* d, S* v, double relax, const SolveCtl* ctl);
     std::string breakdown_note;        // what the last OPMGPU_EBREAKDOWN was (for the error text)
     int plan_id = 0;                   // counts re-plans (set_pattern)
-    bool point_stage2 = false;         // set per solve (capi.hip)
     void point_ilu_setup();
     void point_ilu_factor();
     void point_ilu_apply(const double* d, double* v, double relax);
     // opmgpu_params.preconditioner_single: a double solve whose preconditioner lives in the FLOAT work set (wf: float matrix copy, float ILU0
-    // factors, float pressure hierarchy); the Krylov method converts the vector it hands over and the one it gets back.  Set per solve.
-    bool mixed = false;
+    // factors, float pressure hierarchy); the Krylov method converts the vector it hands over and the one it gets back (now.mixed).
     bool float_copy_valid = false;       // wf.A holds the current matrix (written by mixed_prepare; reset by whoever writes a new matrix)
     void mixed_prepare(bool matrix_changed);
     void cpr_prepare_mixed();
     template <class S> void precond_apply(const S* d, S* out, double relax, const SolveCtl* ctl, bool cpr, const double* cr_given = nullptr);
     template <class S> SolveResult bicgstab(const opmgpu_params& prm);
     template <class S> SolveResult gmres(const opmgpu_params& prm);      // newton_use_gmres: restarted, left-preconditioned
+    // The driver of a linear solve (solve.inl): the loaded matrix, right-hand side in work<S>().b, solution in work<S>().x.  It checks prm,
+    // configures this solve (`now`, ell, fill_level, wb_relax), factorises unless factor_ahead() has, runs the Krylov method and its retries.
+    // Returns the status; OPMGPU_EINVAL = refused (its text in err, nothing solved), otherwise res is the last solver run's and err its text, if any
+    template <class S> OPMGPU_LOCAL int solve(const opmgpu_params& prm, bool matrix_changed, SolveResult& res, std::string& err);
+    // This solve: what solve() derives from prm and the loaded matrix for the solvers, cpr_prepare() and cpr_apply() to read.  Nobody outside
+    // the solver writes it.
+    struct ThisSolve {
+        bool mixed = false;                    // preconditioner_single in effect: the preconditioner of this double solve is the float work set's
+        bool point_stage2 = false;             // cpr_reference_transform = 2: the point ILU0 is the second stage
+        const void* border_weights = nullptr; double border_colscale = 1.0;      // weights (and scale) of the bordered pressure column when cprw are the transformed system's unit weights
+        bool factor_deferred = false;          // factor_async() is started by cpr_prepare() behind its pass over the matrix
+    } now;
 
     // host <-> device vector staging (caller numbering <-> internal, component-major planes)
     template <class S> void vec_from_host(const double* h, int layout, S* d);
@@ -310,7 +337,7 @@ public:
     DevArray<double> wb_buf;       // [nperf][3][7] Y | [nw][49] inverses
     bool well_woodbury = false, wb_active = false;
     bool wb_suspended = false;     // the correction was asked for and is off while wells share a cell (wells_rebind)
-    double wb_relax = 0.9;         // the ILU0's relaxation factor (omega above), set by the caller before the factorisation
+    double wb_relax = 0.9;         // the ILU0's relaxation factor (omega above), set by solve() / factor_ahead() before the factorisation
     // k_spmv shortcut on level-0 rows, which have no lower entries (half of all rows with the 2-colour ordering): no matrix traffic there.
     // BiCGStab: (A M^-1 p)_i from p and the second stage's input; left-preconditioned GMRES in double with relaxation 1: (A v_i)_i =
     // gamma_i base_i with one device-resident scalar per column (linsolver.hip, k_spmv; the conditions: bicgstab() / gmres()).
@@ -365,18 +392,14 @@ public:
     // The ILU0 factorisation of a freshly ASSEMBLED matrix starts at the end of the assembly (behind the wells' diagonal contributions), on its
     // own stream: it then runs next to getConvergence, the host's decision and the first pass of the pressure stage's set-up instead of next
     // to the small levels' Galerkin sums, which it slowed from ~25 to ~200 us (profiles/r04_e trace).  A call that turns out converged has
-    // factorised for nothing (device time only; such a call is 0.5 ms against 2.8).  factor_early: set by the model when it has started the
-    // factorisation for the current matrix; solve_loaded then does not start another.  A/B: OPMGPU_FACTOR_EARLY=0
+    // factorised for nothing (device time only; such a call is 0.5 ms against 2.8).  factor_ahead() is the model's call at the end of its
+    // assembly: it decides whether this matrix qualifies and in which precision the solve will want the factors, runs `matrix_final` (what
+    // the model still owes the matrix copy the factorisation reads) and starts it; solve() then does not start another.
+    // A/B: OPMGPU_FACTOR_EARLY=0
     bool factor_early_on = true;
-    int factor_early_mode = 1;     // OPMGPU_FACTOR_EARLY: 1 = behind the assembly, 2 = behind the convergence check's kernels (runs while the host reads them back)
-    int factor_early = 0;          // 0 = not started; 4 / 8 = started for the float / double matrix
-    // A factorisation on its side stream has slack (it is needed by the first ILU0 sweep, ~0.6 ms later): capped to `factor_grid_cap` workgroups
-    // it runs longer but leaves the latency-bound kernels of the main stream their compute units and memory-queue slots.  0 = uncapped.
-    // A/B: OPMGPU_FACTOR_GRID
-    int factor_grid_cap = 0;
-    bool factor_throttled = false;
+    enum Ahead { AHEAD_NONE, AHEAD_FLOAT, AHEAD_DOUBLE } ahead = AHEAD_NONE;      // the factors factor_ahead() started for the current matrix
+    OPMGPU_LOCAL void factor_ahead(const opmgpu_params& prm, bool host_wells, const std::function<void()>& matrix_final);
     DevArray<double> cgs_parts;          // decomposed GMRES, classical Gram-Schmidt: (restart + 1) partial arrays + their all-reduced sums
-    bool factor_deferred = false;        // factor_async() is started by cpr_prepare() behind its pass over the matrix
     hipStream_t factor_stream = nullptr;
     hipEvent_t ev_factor[2] = { nullptr, nullptr };
     template <class S> void factor_async();

@@ -1,5 +1,6 @@
 """GPU parity: SELL-64 SpMV, level-scheduled block-ILU0 and BiCGStab vs the CPU oracle, through the C ABI."""
 import os
+import re
 
 import numpy as np
 import pytest
@@ -125,6 +126,26 @@ def test_solver_error_contract(gpu_lib, oracle):
     with pytest.raises(ValueError):                                      # pattern without a diagonal
         s.computeNewtonIncrement(np.array([0, 1, 2], np.int32), np.array([1, 0], np.int32), np.ones((2, 9)), np.ones(6), False)
     s.close()
+    # the refusals of the solve's driver (LinSolver::solve): a ValueError with the library's text, and the context is not marked factored
+    refusals = [(dict(use_cpr=1, cpr_ilu_n=1, cpr_reference_transform=2), False, "the point ILU of the scalar system is an ILU0"),
+                (dict(use_cpr=1, cpr_relax=0.0), False, "cpr_relax / cpr_solver_tol must be positive"),
+                (dict(use_cpr=1, cpr_stage2_relax=0.0), False, "cpr_stage2_relax must be positive"),
+                (dict(use_cpr=1, cpr_use_amg=0, cpr_max_ell_iter=0), False, "needs cpr_use_amg = 1"),
+                (dict(ilu_fillin_level=9), False, "must be in 0..8"),
+                (dict(use_cpr=1, cpr_ilu_n=-1), False, "must be in 0..8"),
+                (dict(use_cpr=1, cpr_use_amg=1, cpr_reference_transform=2), True, "double only")]
+    x = np.zeros(3 * grid.nc)
+    for kw, single, text in refusals:
+        s = GpuNewtonIteration(capi.default_params(**kw))
+        with pytest.raises(ValueError, match=re.escape(text)):
+            s.computeNewtonIncrement(rowptr, col, val, b, single)
+        assert s.lib.opmgpu_ilu0_apply(s.ctx, capi.dptr(b), capi.dptr(x)) == capi.EINVAL, kw
+        s.close()
+        # (a refusal, not a broken library: the same matrix with valid parameters in a fresh context; the oracle's ILU0 + BiCGStab needs 456 iterations)
+        s = GpuNewtonIteration(capi.default_params(linear_solver_maxiter=2000))
+        xs = s.computeNewtonIncrement(rowptr, col, val, b, False)
+        assert s.reduction < 1e-2 and np.linalg.norm(bsr_to_scipy(rowptr, col, val) @ xs - b) < 1.5e-2 * np.linalg.norm(b), (kw, s.iterations(), s.reduction)
+        s.close()
 
 
 def test_pattern_cache_and_replan(gpu_lib, oracle):
