@@ -87,7 +87,8 @@ typedef struct opmgpu_grid {
      * pressure hysteresis; EclHysteresisTwoPhaseLaw, reached from SaturationPropsFromDeck.cpp:74-204 / updateSatHyst :206-222).
      * imbnum: 0-based saturation region of every cell's IMBIBITION curves (IMBNUM), NULL = no hysteresis.  ieps: scaled end points
      * of the imbibition curves (ISWL ISWCR ISWU ISOWCR ISGL ISGCR ISGU ISOGCR), all eight or all NULL (= the drainage ones, eps[]).
-     * The history (minimum wetting saturation seen by each two-phase system) lives on the device: opmgpu_update_hysteresis. */
+     * The history (minimum wetting saturation seen by each two-phase system) lives on the device: opmgpu_update_hysteresis.
+     * EHYSTR item 2 = 2, Killough's model for the same two phases, is chosen after creation: opmgpu_set_hysteresis_model. */
     const int32_t* imbnum;
     const double*  ieps[8];
 } opmgpu_grid;
@@ -668,6 +669,49 @@ int opmgpu_get_sat_oil_max(opmgpu_ctx* ctx, double* so_max);
 int opmgpu_update_hysteresis(opmgpu_ctx* ctx);
 int opmgpu_set_hysteresis(opmgpu_ctx* ctx, const double* krn_sw_mdc_ow, const double* krn_sw_mdc_go);
 int opmgpu_get_hysteresis(opmgpu_ctx* ctx, double* krn_sw_mdc_ow, double* krn_sw_mdc_go, double* delta_ow, double* delta_go);
+/* (Under OPMGPU_HYST_KILLOUGH, below, the two delta planes hold the offsets of the affine form the device evaluates the scanning curves
+ * in, with Carlson's signs: the imbibition krow is read at  m_ow Sw_ow + delta_ow,  the imbibition krg at  m_go Sg - delta_go;  that is
+ * delta_ow = 1 - Sncri_ow - m_ow (1 - Sncrt_ow),  delta_go = m_go Sncrt_go - Sncri_go.) */
+
+/* The model of the non-wetting phases' scanning curves (EHYSTR item 2): OPMGPU_HYST_CARLSON, the default and what every context has
+ * until this call, or OPMGPU_HYST_KILLOUGH with killough_a = EHYSTR item 4 (0.1 in a deck that defaults it).  opm-material's Killough
+ * model is not part of the reference tree, so the rule is OURS:
+ *
+ *   Two two-phase systems per cell, as for Carlson.  Sn is the non-wetting saturation, mdc the system's history plane.
+ *     gas-oil:    Sn = Sg.  krnd = the cell's drainage krg (SATNUM table through eps[] / eps_v[]), krni = its imbibition krg (IMBNUM
+ *                 table through ieps[]).  Shy = 1 - krn_sw_mdc_go.
+ *     oil-water:  Sn = 1 - Sw_ow with Sw_ow = Sg + max(Sw, Swco), the abscissa of krow in the three-phase law.  krnd(S) = the cell's
+ *                 drainage krow at 1 - S, krni likewise from the imbibition curve.  Shy = 1 - krn_sw_mdc_ow.
+ *   The history planes, their update (once per report step, opmgpu_update_hysteresis) and the switch between the drainage and the
+ *   scanning curve (scanning where 1 - Sn > mdc) are Carlson's.  Wetting phases stay on their drainage curves; capillary pressure
+ *   carries no hysteresis.
+ *
+ *   Per cell and system:  Sncrd = the largest Sn at which the scaled drainage curve is still zero (the end of the table's run of zeros,
+ *   mapped through the cell's scaling),  Sncri = the same of the imbibition table through the imbibition scaling,  Snmax = the largest
+ *   non-wetting saturation of the scaled drainage curve (gas: the last Sg node; oil: 1 - the first Sw node),  a = killough_a.
+ *   With a history (mdc < 2) and Shy clamped to at most Snmax:
+ *     kd = krnd(Shy),  ki = krni(Snmax),  D = Shy - Sncrd
+ *     C     = 1 / (Sncri - Sncrd) - 1 / (Snmax - Sncrd)
+ *     Sncrt = Sncrd + D / (1 + a (Snmax - Shy) + C D)                           (Land / Killough trapped saturation)
+ *     m     = (Snmax - Sncri) / (Shy - Sncrt),   R = kd / ki
+ *     krn(Sn) = R krni(Sncri + m (Sn - Sncrt)),   d krn / d Sn = R m krni'(.)    on the scanning side
+ *   Guards, exact and without tolerances:  kd <= 0, ki <= 0 or Snmax <= Sncri  ->  R = m = 0 (the scanning side is zero, which is
+ *   the drainage curve there);  Sncri <= Sncrd, or a drainage curve without a mobile range (Snmax <= Sncrd)  ->  Sncrt = Sncrd.
+ *   The manual's form divides by krnd(Snmax); this one divides by krni(Snmax), so the curve is continuous at the turning point whatever
+ *   the tables are, and equals the manual's where the two curves meet at Snmax, as decks make them.  Shy = Snmax gives the imbibition
+ *   curve itself.  Without a history (mdc = 2) m = R = 1, Sncrt = 0 and the offsets are 0.
+ *
+ * The call recomputes the derived planes of a resident history and makes a loaded matrix stale (assemble again).  The model is no part
+ * of the saved state, of the tables or of the plan: it lasts through opmgpu_save_state / opmgpu_restore_state, a change of the solve's
+ * precision, opmgpu_set_wells / opmgpu_set_device_wells and a re-plan.  Multi-GPU: rank-local, no communication.
+ * OPMGPU_EINVAL with text in opmgpu_last_error(ctx), nothing changed: a context without hysteresis (opmgpu_grid.imbnum == NULL); a model
+ * that is neither of the two; a killough_a that is not finite or is negative. */
+#define OPMGPU_HYST_CARLSON  0
+#define OPMGPU_HYST_KILLOUGH 2
+int opmgpu_set_hysteresis_model(opmgpu_ctx* ctx, int model, double killough_a);
+/* The scanning-curve parameters in force, [nc] each in the caller's order, any pointer may be NULL: Sncrt, m and R of the oil-water and
+ * of the gas-oil system.  Under OPMGPU_HYST_CARLSON m = R = 1 and Sncrt = 0 (not computed).  OPMGPU_EINVAL without hysteresis. */
+int opmgpu_get_hysteresis_scanning(opmgpu_ctx* ctx, double* sncrt_ow, double* m_ow, double* r_ow, double* sncrt_go, double* m_go, double* r_go);
 
 /* NonlinearSolver::stabilizeNonlinearUpdate (NonlinearSolver_impl.hpp:260-301) on the resident
  * increment: dx_old <- dx, then DAMPEN: dx *= omega, SOR: dx = omega*dx + (1-omega)*dx_old(previous).

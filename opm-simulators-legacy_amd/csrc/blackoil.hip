@@ -47,7 +47,7 @@ __global__ __launch_bounds__(kBlock) void k_cell_values(int nb, int nbp, DevTabl
         EpsD E, EI;
         HystD H;
         eps_load(eps, eps_u0, nbp, row, satnum[row], E);
-        hyst_load(hy.imbnum, hy.hist, nbp, row, H);
+        hyst_load<KM>(hy.imbnum, hy.hist, nbp, row, H);
         if (H.on) eps_load(hy.ieps, hy.iureg, nbp, row, H.ireg, EI);
         eval_cell<false, KM>(D, E, (D.t.vap1 > 0.0 || D.t.vap2 > 0.0) ? somax[row] : 0.0, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], row, q, H, &EI);
         // (no gas phase: the five water / oil planes only -- nobody reads the other five --, and 1 / b_g = 1 per cell)
@@ -115,7 +115,7 @@ __global__ __launch_bounds__(kBlock, asm_rows_waves(LDS, DUAL, KM)) void k_assem
         EpsD E, EI;
         HystD H;
         eps_load(eps, eps_u0, nbp, row, satnum[row], E);
-        hyst_load(hy.imbnum, hy.hist, nbp, row, H);
+        hyst_load<KM>(hy.imbnum, hy.hist, nbp, row, H);
         if (H.on) eps_load(hy.ieps, hy.iureg, nbp, row, H.ireg, EI);
         eval_cell<false, KM>(DT, E, (DT.t.vap1 > 0.0 || DT.t.vap2 > 0.0) ? somax[row] : 0.0, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], row, q, H, &EI);
     }
@@ -669,12 +669,38 @@ __device__ double table_inverse(const double* __restrict__ x, const double* __re
     for (int i = 0; i + 1 < n; ++i) if (y[i] > yv && yv >= y[i + 1]) return x[i] + (yv - y[i]) / (y[i + 1] - y[i]) * (x[i + 1] - x[i]);
     return x[n - 1];
 }
+// the end of the run of zero ordinates at the low (low = true) or the high end of a table: the abscissa of the run's innermost node; the
+// end node itself where the curve is not zero there
+__device__ double table_zero_end(const double* __restrict__ x, const double* __restrict__ y, int n, bool low)
+{
+    if (low) { int i = 0; while (i + 1 < n && y[i + 1] <= 0.0) ++i; return x[i]; }
+    int i = n - 1;
+    while (i > 0 && y[i - 1] <= 0.0) --i;
+    return x[i];
+}
+// Killough's scanning curve of one two-phase system in the non-wetting saturation Sn (the rule is stated in include/opmgpu.h at
+// opmgpu_set_hysteresis_model): trapped saturation, slope and ratio from the turning point shy, the critical saturations of the cell's
+// drainage and imbibition curves, the drainage curve's largest saturation and the cell's two curves themselves
+template <class KD, class KI>
+__device__ void killough_scan(double shy, double sncrd, double sncri, double snmax, double a, KD&& krnd, KI&& krni, double& sncrt, double& m, double& R)
+{
+    shy = fmin(shy, snmax);
+    const double kd = krnd(shy), ki = krni(snmax), D = shy - sncrd;
+    sncrt = sncrd;
+    if (sncri > sncrd && snmax > sncrd) {
+        const double C = 1.0 / (sncri - sncrd) - 1.0 / (snmax - sncrd);
+        sncrt = sncrd + D / (1.0 + a * (snmax - shy) + C * D);
+    }
+    m = 0.0; R = 0.0;
+    if (kd > 0.0 && ki > 0.0 && snmax > sncri) { m = (snmax - sncri) / (shy - sncrt); R = kd / ki; }
+}
 // EclDefaultMaterial::updateHysteresis ("inconsistent" form: krnSw = 1 - So / 1 - Sg) + EclHysteresisTwoPhaseLawParams::update +
-// updateDynamicParams_ (Carlson shift: delta = Sw_imb(krn_drain(mdc)) - mdc), one thread per cell
+// updateDynamicParams_ (Carlson shift: delta = Sw_imb(krn_drain(mdc)) - mdc), one thread per cell.  model == OPMGPU_HYST_KILLOUGH: the
+// parameters of Killough's scanning curves instead, in the affine form the evaluator takes (HystD); Carlson fills m = R = 1.
 __global__ __launch_bounds__(kBlock) void k_hyst_update(int nb, int nbp, DevTables D, const int32_t* __restrict__ satnum, const int32_t* __restrict__ imbnum,
                                                         const double* __restrict__ so, const double* __restrict__ sg, const double* __restrict__ eps,
                                                         const double* __restrict__ ieps, const double* __restrict__ ureg, const double* __restrict__ iureg,
-                                                        double* __restrict__ hist, int force)
+                                                        double* __restrict__ hist, int force, int model, double kill_a)
 {
     const int c = blockIdx.x * kBlock + threadIdx.x;
     if (c >= nb) return;
@@ -692,6 +718,37 @@ __global__ __launch_bounds__(kBlock) void k_hyst_update(int nb, int nbp, DevTabl
     eps_load(eps, ureg, nbp, c, sreg, E);
     eps_load(ieps, iureg, nbp, c, ireg, EI);
     double dow = 0.0, dgo = 0.0, f, df;
+    double m_ow = 1.0, m_go = 1.0, r_ow = 1.0, r_go = 1.0, t_ow = 0.0, t_go = 0.0;
+    const long np = nbp;
+    if (model == OPMGPU_HYST_KILLOUGH) {
+        const TabX& X = D.x;
+        if (mow < 2.0) {        // oil against water: Sn = 1 - Sw_ow, the curves are krow at 1 - Sn
+            const int wa = T.swof_ptr[sreg], wi = T.swof_ptr[ireg], nw = T.swof_ptr[sreg + 1] - wa, ni = T.swof_ptr[ireg + 1] - wi;
+            const double* xd = T.swof_sw + wa; const double* xi = T.swof_sw + wi;
+            const double sncrd = 1.0 - eps_unmap(E, EC_KROW, table_zero_end(xd, T.swof_krow + wa, nw, false));
+            const double sncri = 1.0 - eps_unmap(EI, EC_KROW, table_zero_end(xi, T.swof_krow + wi, ni, false));
+            const double snmax = 1.0 - eps_unmap(E, EC_KROW, xd[0]);
+            auto kd = [&](double S) { double g, dg; sat_curve_s<false>(xd, T.swof_krow + wa, X.swof_dkrow + wa, nw, 1.0 - S, E, EC_KROW, g, dg); return g; };
+            auto ki = [&](double S) { double g, dg; sat_curve_s<false>(xi, T.swof_krow + wi, X.swof_dkrow + wi, ni, 1.0 - S, EI, EC_KROW, g, dg); return g; };
+            killough_scan(1.0 - mow, sncrd, sncri, snmax, kill_a, kd, ki, t_ow, m_ow, r_ow);
+            dow = 1.0 - sncri - m_ow * (1.0 - t_ow);            // Sw_imb = 1 - (Sncri + m (1 - Sw_ow - Sncrt)) = d_ow + m Sw_ow
+        }
+        if (mgo < 2.0) {        // gas against oil: Sn = Sg
+            const int ga = T.sgof_ptr[sreg], gi = T.sgof_ptr[ireg], ng = T.sgof_ptr[sreg + 1] - ga, ni = T.sgof_ptr[ireg + 1] - gi;
+            const double* xd = T.sgof_sg + ga; const double* xi = T.sgof_sg + gi;
+            const double sncrd = eps_unmap(E, EC_KRG, table_zero_end(xd, T.sgof_krg + ga, ng, true));
+            const double sncri = eps_unmap(EI, EC_KRG, table_zero_end(xi, T.sgof_krg + gi, ni, true));
+            const double snmax = eps_unmap(E, EC_KRG, xd[ng - 1]);
+            auto kd = [&](double S) { double g, dg; sat_curve_s<true>(xd, T.sgof_krg + ga, X.sgof_dkrg + ga, ng, S, E, EC_KRG, g, dg); return g; };
+            auto ki = [&](double S) { double g, dg; sat_curve_s<true>(xi, T.sgof_krg + gi, X.sgof_dkrg + gi, ni, S, EI, EC_KRG, g, dg); return g; };
+            killough_scan(1.0 - mgo, sncrd, sncri, snmax, kill_a, kd, ki, t_go, m_go, r_go);
+            dgo = m_go * t_go - sncri;                          // Sg_imb = Sncri + m (Sg - Sncrt) = m Sg - d_go
+        }
+        hist[c] = mow; hist[np + c] = mgo; hist[HP_D_OW * np + c] = dow; hist[HP_D_GO * np + c] = dgo;
+        hist[HP_M_OW * np + c] = m_ow; hist[HP_M_GO * np + c] = m_go; hist[HP_R_OW * np + c] = r_ow; hist[HP_R_GO * np + c] = r_go;
+        hist[HP_SNCRT_OW * np + c] = t_ow; hist[HP_SNCRT_GO * np + c] = t_go;
+        return;
+    }
     if (mow < 2.0) {
         const int wa = T.swof_ptr[sreg], wi = T.swof_ptr[ireg];
         sat_curve_s<false>(T.swof_sw + wa, T.swof_krow + wa, D.x.swof_dkrow + wa, T.swof_ptr[sreg + 1] - wa, mow, E, EC_KROW, f, df);
@@ -706,27 +763,71 @@ __global__ __launch_bounds__(kBlock) void k_hyst_update(int nb, int nbp, DevTabl
         if (ku > 0.0) dgo = sgm - eps_unmap(EI, EC_KRG, table_inverse(T.sgof_sg + gi, T.sgof_krg + gi, T.sgof_ptr[ireg + 1] - gi, ku, true));
     }
     hist[c] = mow; hist[nbp + c] = mgo; hist[2 * long(nbp) + c] = dow; hist[3 * long(nbp) + c] = dgo;
+    if (force) {        // Carlson's m = R = 1, Sncrt = 0 are what the planes start with (hist_planes): only a change of model rewrites them
+        hist[HP_M_OW * np + c] = m_ow; hist[HP_M_GO * np + c] = m_go; hist[HP_R_OW * np + c] = r_ow; hist[HP_R_GO * np + c] = r_go;
+        hist[HP_SNCRT_OW * np + c] = t_ow; hist[HP_SNCRT_GO * np + c] = t_go;
+    }
+}
+// the HP_COUNT planes of a plan without a history: mdc = 2, zero shifts, m = R = 1 (Carlson's affine form), Sncrt = 0 -- padding rows included
+std::vector<double> BlackoilDevice::hist_planes() const
+{
+    const size_t nbp = ls.plan.nbp;
+    std::vector<double> hp(size_t(HP_COUNT) * nbp, 0.0);
+    for (size_t r = 0; r < nbp; ++r) {
+        hp[r] = 2.0; hp[nbp + r] = 2.0;
+        for (int k = HP_M_OW; k <= HP_R_GO; ++k) hp[size_t(k) * nbp + r] = 1.0;
+    }
+    return hp;
+}
+void BlackoilDevice::launch_hyst_update(int force)
+{
+    hipLaunchKernelGGL(k_hyst_update, dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, ls.plan.nbp, dtp_, d_satnum.p, d_imbnum.p, d_so.p, d_sg.p,
+                       (const double*)d_eps.p, (const double*)d_ieps.p, (const double*)d_eps_u0.p, (const double*)d_ieps_u0.p, d_hist.p, force, hyst_model, killough_a);
 }
 
 int BlackoilDevice::update_hysteresis()
 {
     if (!use_hyst) return OPMGPU_OK;
     if (!has_state) return OPMGPU_EINVAL;
-    hipLaunchKernelGGL(k_hyst_update, dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, ls.plan.nbp, dtp_, d_satnum.p, d_imbnum.p, d_so.p, d_sg.p,
-                       (const double*)d_eps.p, (const double*)d_ieps.p, (const double*)d_eps_u0.p, (const double*)d_ieps_u0.p, d_hist.p, 0);
+    launch_hyst_update(0);
     return OPMGPU_OK;
 }
 int BlackoilDevice::set_hysteresis(const double* mdc_ow, const double* mdc_go)
 {
     if (!use_hyst || !mdc_ow || !mdc_go) return OPMGPU_EINVAL;
     const Plan& P = ls.plan;
-    std::vector<double> hp(4 * size_t(P.nbp), 0.0);
-    for (int r = 0; r < P.nbp; ++r) { hp[r] = r < nc ? mdc_ow[P.nat[r]] : 2.0; hp[size_t(P.nbp) + r] = r < nc ? mdc_go[P.nat[r]] : 2.0; }
+    std::vector<double> hp = hist_planes();
+    for (int r = 0; r < nc; ++r) { hp[r] = mdc_ow[P.nat[r]]; hp[size_t(P.nbp) + r] = mdc_go[P.nat[r]]; }
     d_hist.upload(hp, stream);
-    // the shifts follow from the history
-    hipLaunchKernelGGL(k_hyst_update, dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, P.nbp, dtp_, d_satnum.p, d_imbnum.p, d_so.p, d_sg.p,
-                       (const double*)d_eps.p, (const double*)d_ieps.p, (const double*)d_eps_u0.p, (const double*)d_ieps_u0.p, d_hist.p, 1);
+    // the shifts (the scanning parameters) follow from the history
+    launch_hyst_update(1);
     OPMGPU_HIP(hipStreamSynchronize(stream));
+    return OPMGPU_OK;
+}
+// The scanning-curve model of the hysteresis (opmgpu_set_hysteresis_model).  With a resident history its derived planes are recomputed
+// from the two history planes (the force path of k_hyst_update, as set_hysteresis does).
+int BlackoilDevice::set_hysteresis_model(int model, double a)
+{
+    if (!use_hyst) throw HipError(OPMGPU_EINVAL, "opmgpu_set_hysteresis_model: the context has no hysteresis (opmgpu_grid.imbnum is NULL)");
+    if (model != OPMGPU_HYST_CARLSON && model != OPMGPU_HYST_KILLOUGH)
+        throw HipError(OPMGPU_EINVAL, "opmgpu_set_hysteresis_model: model " + std::to_string(model) + " is neither OPMGPU_HYST_CARLSON (0) nor OPMGPU_HYST_KILLOUGH (2)");
+    if (!std::isfinite(a)) throw HipError(OPMGPU_EINVAL, "opmgpu_set_hysteresis_model: killough_a is not finite");
+    if (a < 0.0) throw HipError(OPMGPU_EINVAL, "opmgpu_set_hysteresis_model: killough_a is negative");
+    hyst_model = model; killough_a = a;
+    launch_hyst_update(1);
+    OPMGPU_HIP(hipStreamSynchronize(stream));
+    return OPMGPU_OK;
+}
+int BlackoilDevice::get_hysteresis_scanning(double* sncrt_ow, double* m_ow, double* r_ow, double* sncrt_go, double* m_go, double* r_go)
+{
+    if (!use_hyst) throw HipError(OPMGPU_EINVAL, "opmgpu_get_hysteresis_scanning: the context has no hysteresis (opmgpu_grid.imbnum is NULL)");
+    const Plan& P = ls.plan;
+    std::vector<double> hp(size_t(HP_COUNT) * P.nbp);
+    d_hist.download(hp.data(), hp.size(), stream);
+    OPMGPU_HIP(hipStreamSynchronize(stream));
+    double* out[6] = { sncrt_ow, m_ow, r_ow, sncrt_go, m_go, r_go };
+    const int plane[6] = { HP_SNCRT_OW, HP_M_OW, HP_R_OW, HP_SNCRT_GO, HP_M_GO, HP_R_GO };
+    for (int k = 0; k < 6; ++k) if (out[k]) for (int r = 0; r < nc; ++r) out[k][P.nat[r]] = hp[size_t(plane[k]) * P.nbp + r];
     return OPMGPU_OK;
 }
 int BlackoilDevice::get_hysteresis(double* mdc_ow, double* mdc_go, double* d_ow, double* d_go)
@@ -791,7 +892,8 @@ template <class F> static auto kernel_by_shape(bool lds, int km, F&& pick)
             return km_pvcdo(km) ? pick(L, std::integral_constant<int, decltype(K)::value | KM_PVCDO>{}) : pick(L, K);
         };
         return km_model(km) == KM_OW ? by_oil(std::integral_constant<int, KM_OW>{})
-             : km_model(km) == KM_STONE ? by_oil(std::integral_constant<int, KM_STONE>{}) : by_oil(std::integral_constant<int, KM_DEFAULT>{});
+             : km_model(km) == KM_STONE ? by_oil(std::integral_constant<int, KM_STONE>{})
+             : km_model(km) == KM_KILLOUGH ? by_oil(std::integral_constant<int, KM_KILLOUGH>{}) : by_oil(std::integral_constant<int, KM_DEFAULT>{});
     };
     return lds ? by_model(std::true_type{}) : by_model(std::false_type{});
 }

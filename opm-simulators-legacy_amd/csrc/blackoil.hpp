@@ -38,7 +38,9 @@ enum { VP_PW = 0, VP_PG = 1, VP_RHO = 2 /* + phase */, VP_U = 5 /* + phase */, V
 // the saturation-function model a cell-evaluating kernel is instantiated for (eval_cell), chosen on the host: BlackoilDevice::kmodel()
 // KM_PVCDO, or-ed to any of the three: the oil is the analytic dead oil of opmgpu_set_pvcdo and not the tabulated one (km_pvcdo; km_model
 // gives the saturation-function model alone).  A template parameter like the model and for the same reason.
-enum { KM_DEFAULT = 0, KM_STONE = 1, KM_OW = 2, KM_PVCDO = 4 };
+// KM_KILLOUGH: the default three-phase law whose non-wetting scanning curves are Killough's (opmgpu_set_hysteresis_model) -- a model of its
+// own and not a branch, so that the kernels of every other context are the ones they were: only it loads the m / R planes of the history.
+enum { KM_DEFAULT = 0, KM_STONE = 1, KM_OW = 2, KM_KILLOUGH = 3, KM_PVCDO = 4 };
 constexpr int km_model(int km) { return km & 3; }
 constexpr bool km_pvcdo(int km) { return (km & KM_PVCDO) != 0; }
 
@@ -90,6 +92,8 @@ public:
     int update_hysteresis();
     int set_hysteresis(const double* mdc_ow, const double* mdc_go);
     int get_hysteresis(double* mdc_ow, double* mdc_go, double* d_ow, double* d_go);
+    int set_hysteresis_model(int model, double killough_a);     // throws HipError(OPMGPU_EINVAL) with the reason
+    int get_hysteresis_scanning(double* sncrt_ow, double* m_ow, double* r_ow, double* sncrt_go, double* m_go, double* r_go);
     void get_residual(double* r);
     // wells on the device (wells.hip)
     struct WellsDev;
@@ -172,7 +176,11 @@ private:
     bool has_endpoints = false, scalecrs = false, use_hyst = false, has_iendpoints = false;
     std::vector<double> h_eps[8], h_unscaled, h_eps_v[5], h_ieps[8];
     std::vector<int32_t> h_imbnum;
-    DevArray<double> d_eps, d_eps_u0, d_somax, d_saved, d_ieps, d_ieps_u0, d_hist;     // d_hist: [mdc_ow | mdc_go | d_ow | d_go] planes
+    DevArray<double> d_eps, d_eps_u0, d_somax, d_saved, d_ieps, d_ieps_u0, d_hist;     // d_hist: the HP_COUNT planes of the history (fluid_eval.hpp)
+    int hyst_model = OPMGPU_HYST_CARLSON;    // opmgpu_set_hysteresis_model: no part of the state, of the plan or of the tables
+    double killough_a = 0.1;
+    void launch_hyst_update(int force);
+    std::vector<double> hist_planes() const;
     DevArray<int32_t> d_imbnum;
     DevArray<double> d_stone_som;            // DevTables::stone_som
     HystArgs hyst_args() const;
@@ -191,7 +199,7 @@ private:
     int tab_words = 0;
     static constexpr int kTabLdsMaxBytes = 24 * 1024;     // 6 workgroups x 24 KiB fit the 160 KiB LDS of a CU: no occupancy lost
     // chooses the kernels' KM instantiations (eval_cell)
-    int kmodel() const { return (oil_water() ? KM_OW : (dto_.t.threephase_model != OPMGPU_KRO_DEFAULT ? KM_STONE : KM_DEFAULT)) | (dtp_.x.oil_pvcdo ? KM_PVCDO : 0); }
+    int kmodel() const { return (oil_water() ? KM_OW : (dto_.t.threephase_model != OPMGPU_KRO_DEFAULT ? KM_STONE : (use_hyst && hyst_model == OPMGPU_HYST_KILLOUGH ? KM_KILLOUGH : KM_DEFAULT))) | (dtp_.x.oil_pvcdo ? KM_PVCDO : 0); }
     bool oil_water() const { return dto_.t.active_phases == OPMGPU_PHASES_OIL_WATER; }
     int tab_lds_words() const { return tab_words * 8 <= kTabLdsMaxBytes ? tab_words : 0; }
     size_t tab_lds_bytes() const { return size_t(tab_lds_words()) * 8; }

@@ -179,6 +179,10 @@ void BlackoilDevice::rebuild_structure()
     // keep the state across a re-plan (wells change between report steps)
     std::vector<double> sp, ssat, srs, srv; std::vector<int8_t> shc;
     std::vector<double> smax;
+    // (the hysteresis history likewise, read in the OLD numbering: after set_pattern the plan is the new one)
+    std::vector<double> hist;
+    if (use_hyst && d_hist.p && has_state) { hist.resize(4 * size_t(nc)); get_hysteresis(hist.data(), hist.data() + nc, hist.data() + 2 * size_t(nc), hist.data() + 3 * size_t(nc)); }
+    const bool hyst_carried = !hist.empty();
     if (d_somax.p) { smax.resize(nc); get_sat_oil_max(smax.data()); }
     if (has_state) { sp.resize(nc); ssat.resize(3 * size_t(nc)); srs.resize(nc); srv.resize(nc); shc.resize(nc); get_state(sp.data(), ssat.data(), srs.data(), srv.data(), shc.data()); }
     const int st2 = ls.set_pattern(nc, rowptr.data(), col.data(), prm.ilu_ordering);
@@ -220,10 +224,7 @@ void BlackoilDevice::rebuild_structure()
             std::vector<int32_t> im(nbp, 0);
             for (int r = 0; r < nc; ++r) im[r] = h_imbnum[P.nat[r]];
             d_imbnum.upload(im, stream);
-            std::vector<double> hist;
-            if (d_hist.p && has_state) { hist.resize(4 * size_t(nc)); get_hysteresis(hist.data(), hist.data() + nc, hist.data() + 2 * size_t(nc), hist.data() + 3 * size_t(nc)); }
-            std::vector<double> hp(4 * size_t(nbp), 0.0);
-            for (int r = 0; r < nbp; ++r) { hp[r] = 2.0; hp[size_t(nbp) + r] = 2.0; }       // no history
+            std::vector<double> hp = hist_planes();             // no history
             if (!hist.empty())
                 for (int r = 0; r < nc; ++r) for (int k = 0; k < 4; ++k) hp[size_t(k) * nbp + r] = hist[size_t(k) * nc + P.nat[r]];
             d_hist.upload(hp, stream);
@@ -262,6 +263,8 @@ void BlackoilDevice::rebuild_structure()
     if (!smax.empty()) set_sat_oil_max(smax.data());
     wells_rebind();
     if (has_state) set_state(sp.data(), ssat.data(), srs.data(), srv.data(), shc.data());
+    // Killough: the scanning parameters follow from the two history planes in the new numbering (the force path of k_hyst_update)
+    if (hyst_carried && hyst_model == OPMGPU_HYST_KILLOUGH) { launch_hyst_update(1); OPMGPU_HIP(hipStreamSynchronize(stream)); }
 }
 
 // per region: unscaled fixed points of every curve (u0 | u1).  A set of curves WITHOUT scaled end points keeps the saturation exactly

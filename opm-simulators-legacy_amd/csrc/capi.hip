@@ -692,6 +692,17 @@ int opmgpu_get_hysteresis(opmgpu_ctx* c, double* mdc_ow, double* mdc_go, double*
     if (!c || !c->model) return OPMGPU_EINVAL;
     return guarded(c, [&]() { return c->model->get_hysteresis(mdc_ow, mdc_go, d_ow, d_go); });
 }
+int opmgpu_set_hysteresis_model(opmgpu_ctx* c, int model, double killough_a)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    // the next assembly evaluates the new scanning curves; a matrix loaded or factored before the call is that of the old ones
+    return guarded(c, [&]() { const int st = c->model->set_hysteresis_model(model, killough_a); c->matrix_loaded = false; return st; });
+}
+int opmgpu_get_hysteresis_scanning(opmgpu_ctx* c, double* sncrt_ow, double* m_ow, double* r_ow, double* sncrt_go, double* m_go, double* r_go)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { return c->model->get_hysteresis_scanning(sncrt_ow, m_ow, r_ow, sncrt_go, m_go, r_go); });
+}
 
 int opmgpu_stabilize_update(opmgpu_ctx* c, int relax_type, double omega)
 {

@@ -11,7 +11,7 @@
 namespace opmgpu {
 
 // the instantiation of a cell-evaluating kernel template <int KM> for this deck's model (inside a BlackoilDevice method)
-#define OPMGPU_BY_MODEL_(kernel, oil) (km_model(kmodel()) == KM_OW ? kernel<KM_OW | oil> : (km_model(kmodel()) == KM_STONE ? kernel<KM_STONE | oil> : kernel<KM_DEFAULT | oil>))
+#define OPMGPU_BY_MODEL_(kernel, oil) (km_model(kmodel()) == KM_OW ? kernel<KM_OW | oil> : (km_model(kmodel()) == KM_STONE ? kernel<KM_STONE | oil> : (km_model(kmodel()) == KM_KILLOUGH ? kernel<KM_KILLOUGH | oil> : kernel<KM_DEFAULT | oil>)))
 #define OPMGPU_BY_MODEL(kernel) (km_pvcdo(kmodel()) ? OPMGPU_BY_MODEL_(kernel, KM_PVCDO) : OPMGPU_BY_MODEL_(kernel, 0))
 
 struct V4 { double v, p, w, x; };      // value, d/dP, d/dSw, d/dXvar
@@ -79,7 +79,12 @@ __device__ __forceinline__ double eps_unmap(const EpsD& e, int c, double su)    
 }
 // Relative-permeability hysteresis of a cell (EclHysteresisTwoPhaseLaw, Carlson for the non-wetting phases, KR only): the history
 // planes hold the smallest wetting saturation each two-phase system has seen (2.0 = none) and the shift of the imbibition curve.
-struct HystD { bool on; int ireg; double mdc_ow, mdc_go, d_ow, d_go; };
+// Killough's model (KM_KILLOUGH; the rule is stated in include/opmgpu.h at opmgpu_set_hysteresis_model) takes the scanning curve in ONE
+// affine form, krn = R krn_imb(A0 + m S) over the abscissa S the Carlson branch shifts (Sw_ow resp. Sg): the shift planes then hold A0
+// with Carlson's signs (+d_ow, -d_go) and the m / R planes are loaded by that model's kernels alone.  The trapped saturations Sncrt are
+// kept for the caller (opmgpu_get_hysteresis_scanning); no evaluator reads them.
+enum { HP_MDC_OW = 0, HP_MDC_GO, HP_D_OW, HP_D_GO, HP_M_OW, HP_M_GO, HP_R_OW, HP_R_GO, HP_SNCRT_OW, HP_SNCRT_GO, HP_COUNT };
+struct HystD { bool on; int ireg; double mdc_ow, mdc_go, d_ow, d_go, m_ow, m_go, r_ow, r_go; };
 struct HystArgs { const int32_t* imbnum; const double* hist; const double* ieps; const double* iureg; };      // kernel argument: imbnum == nullptr = no hysteresis
 // The resident state as a cell evaluator reads it: the region numbers, the state planes, the end-point scaling (eps == nullptr: none), the
 // VAPPARS history and the hysteresis arguments, all in internal numbering with stride nbp.  Passed to kernels by value;
@@ -92,12 +97,16 @@ struct CellPlanes {
     long nbp;
     HystArgs hy;
 };
+template <int KM = KM_DEFAULT>
 __device__ __forceinline__ void hyst_load(const int32_t* __restrict__ imbnum, const double* __restrict__ hist, long nbp, int row, HystD& h)
 {
     h.on = imbnum != nullptr;
     if (!h.on) return;
     h.ireg = imbnum[row];
     h.mdc_ow = hist[row]; h.mdc_go = hist[nbp + row]; h.d_ow = hist[2 * nbp + row]; h.d_go = hist[3 * nbp + row];
+    if constexpr (km_model(KM) == KM_KILLOUGH) {
+        h.m_ow = hist[HP_M_OW * nbp + row]; h.m_go = hist[HP_M_GO * nbp + row]; h.r_ow = hist[HP_R_OW * nbp + row]; h.r_go = hist[HP_R_GO * nbp + row];
+    }
 }
 
 // VAPPARS (applyVap, BlackoilPropsAdFromDeck.cpp:1052-1078): factor (so/soMax)^vap and its so-derivative
@@ -424,7 +433,7 @@ struct CellOutput { double mu[3], kr[3], rsSat, rvSat; };
 template <bool OUTPUT, bool PVCDO> __device__ void eval_cell_ow(const DevTables& DT, const EpsD& E, int preg, int sreg, double p, double sw_, CellEval& q, CellOutput* out);
 template <bool OUTPUT = false, int KM = KM_DEFAULT>
 __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int preg, int sreg, double p, double sw_, double sg_, double rs_, double rv_, int hc,
-                          int row, CellEval& q, const HystD& H = HystD{ false, 0, 2.0, 2.0, 0.0, 0.0 }, const EpsD* EI = nullptr, CellOutput* out = nullptr)
+                          int row, CellEval& q, const HystD& H = HystD{ false, 0, 2.0, 2.0, 0.0, 0.0, 1.0, 1.0, 1.0, 1.0 }, const EpsD* EI = nullptr, CellOutput* out = nullptr)
 {
     if constexpr (km_model(KM) == KM_OW) { eval_cell_ow<OUTPUT, km_pvcdo(KM)>(DT, E, preg, sreg, p, sw_, q, out); return; }
     const opmgpu_tables& T = DT.t; const TabX& X = DT.x;
@@ -468,7 +477,10 @@ __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int
     }
     if (gas_imb) {
         const int gi = T.sgof_ptr[H.ireg];
-        sat_curve_s<true>(T.sgof_sg + gi, T.sgof_krg + gi, X.sgof_dkrg + gi, T.sgof_ptr[H.ireg + 1] - gi, sg.v - H.d_go, *EI, EC_KRG, f, df);
+        if constexpr (km_model(KM) == KM_KILLOUGH) {      // Killough's scanning curve R krg_imb(A0 + m Sg), A0 = -d_go
+            sat_curve_s<true>(T.sgof_sg + gi, T.sgof_krg + gi, X.sgof_dkrg + gi, T.sgof_ptr[H.ireg + 1] - gi, fma(H.m_go, sg.v, -H.d_go), *EI, EC_KRG, f, df);
+            f *= H.r_go; df *= H.r_go * H.m_go;
+        } else sat_curve_s<true>(T.sgof_sg + gi, T.sgof_krg + gi, X.sgof_dkrg + gi, T.sgof_ptr[H.ireg + 1] - gi, sg.v - H.d_go, *EI, EC_KRG, f, df);
         krg = vchain(f, df, sg);
     }
     V4 kro;
@@ -481,7 +493,10 @@ __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int
         const V4 swow = vadd(sg, swp);
         if (H.on && swow.v > H.mdc_ow) {         // oil against water on its (shifted) imbibition curve
             const int wi = T.swof_ptr[H.ireg];
-            sat_curve_s<false>(T.swof_sw + wi, T.swof_krow + wi, X.swof_dkrow + wi, T.swof_ptr[H.ireg + 1] - wi, swow.v + H.d_ow, *EI, EC_KROW, f, df);
+            if constexpr (km_model(KM) == KM_KILLOUGH) {  // Killough's scanning curve R krow_imb(A0 + m Sw_ow), A0 = d_ow
+                sat_curve_s<false>(T.swof_sw + wi, T.swof_krow + wi, X.swof_dkrow + wi, T.swof_ptr[H.ireg + 1] - wi, fma(H.m_ow, swow.v, H.d_ow), *EI, EC_KROW, f, df);
+                f *= H.r_ow; df *= H.r_ow * H.m_ow;
+            } else sat_curve_s<false>(T.swof_sw + wi, T.swof_krow + wi, X.swof_dkrow + wi, T.swof_ptr[H.ireg + 1] - wi, swow.v + H.d_ow, *EI, EC_KROW, f, df);
         } else sat_curve_s<false>(xsw, T.swof_krow + wa, X.swof_dkrow + wa, nw, swow.v, E, EC_KROW, f, df);
         const V4 kow = vchain(f, df, swow);
         const V4 sgeq = mk(swow.v - swco, swow.p, swow.w, swow.x);
@@ -666,7 +681,7 @@ __device__ __forceinline__ void eval_row(const DevTables& DT, int row, const Cel
     EpsD E, EI;
     HystD H;
     eps_load(C.eps, C.eps_u0, C.nbp, row, C.satnum[row], E);
-    hyst_load(C.hy.imbnum, C.hy.hist, C.nbp, row, H);
+    hyst_load<KM>(C.hy.imbnum, C.hy.hist, C.nbp, row, H);
     if (H.on) eps_load(C.hy.ieps, C.hy.iureg, C.nbp, row, H.ireg, EI);
     eval_cell<OUTPUT, KM>(DT, E, C.somax[row], C.pvtnum[row], C.satnum[row], C.p[row], C.sw[row], C.sg[row], C.rs[row], C.rv[row], C.hc[row], row, q, H, &EI, out);
 }

@@ -136,6 +136,13 @@ public:
     /// once per report step, where SimulatorBase::run calls props.updateSatOilMax / updateSatHyst (SimulatorBase_impl.hpp:190-192)
     void updateSatOilMax() { throw_on_status(ctx_, opmgpu_update_sat_oil_max(ctx_)); }
     void updateSatHyst() { throw_on_status(ctx_, opmgpu_update_hysteresis(ctx_)); }
+    /// EHYSTR item 2 / item 4: OPMGPU_HYST_CARLSON (the default) or OPMGPU_HYST_KILLOUGH with Killough's curvature parameter (opmgpu.h)
+    void setHysteresisModel(int model, double killough_a = 0.1) { throw_on_status(ctx_, opmgpu_set_hysteresis_model(ctx_, model, killough_a)); }
+    /// Sncrt, m, R of the oil-water and of the gas-oil scanning curves ([nc] each, any pointer may be null)
+    void getHysteresisScanning(double* sncrt_ow, double* m_ow, double* r_ow, double* sncrt_go, double* m_go, double* r_go)
+    {
+        throw_on_status(ctx_, opmgpu_get_hysteresis_scanning(ctx_, sncrt_ow, m_ow, r_ow, sncrt_go, m_go, r_go));
+    }
     /// BlackoilModelBase::nonlinearIteration + the NonlinearSolver's update stabilisation in ONE library call (opmgpu_nonlinear_iteration):
     /// the same sequence NonlinearSolverGpu::step issues call by call, without the host round trips between the phases.
     /// Returns true when the iteration found the step converged; throws like the single calls do.

@@ -16,6 +16,7 @@ HC_GAS_ONLY, HC_GAS_AND_OIL, HC_OIL_ONLY = 0, 1, 2
 RELAX_DAMPEN, RELAX_SOR = 0, 1
 ORDER_NATURAL, ORDER_MULTICOLOR = 0, 1
 KRO_DEFAULT, KRO_STONE1, KRO_STONE2 = 0, 1, 2          # opmgpu_tables.threephase_model
+HYST_CARLSON, HYST_KILLOUGH = 0, 2                     # opmgpu_set_hysteresis_model (EHYSTR item 2's own numbers)
 PHASES_ALL, PHASES_OIL_WATER = 0, 1                    # opmgpu_tables.active_phases
 K_SPMV, K_ILU_APPLY, K_ILU_FACTOR, K_ASSEMBLE, K_DOT, K_AXPY, K_PROPS, K_STREAM_COPY, K_CPR_APPLY, K_VCYCLE, K_CPR_SETUP, K_SPMV_COLD = range(12)
 KT_NAMES = ["cell_props", "flux", "wells", "convergence", "ilu0_factor", "cpr_setup", "spmv_fused_dot1", "spmv_fused_dot2", "ilu0_apply", "amg_vcycle",
@@ -196,6 +197,8 @@ SIGNATURES = {
     "opmgpu_update_hysteresis": (C.c_int, [C.c_void_p]),
     "opmgpu_set_hysteresis": (C.c_int, [C.c_void_p, _dp, _dp]),
     "opmgpu_get_hysteresis": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp]),
+    "opmgpu_set_hysteresis_model": (C.c_int, [C.c_void_p, C.c_int, C.c_double]),
+    "opmgpu_get_hysteresis_scanning": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp, _dp, _dp]),
     "opmgpu_get_cpr_weights": (C.c_int, [C.c_void_p, _dp]),
     "opmgpu_set_solve_precision": (C.c_int, [C.c_void_p, C.c_int]),
     "opmgpu_set_device_wells": (C.c_int, [C.c_void_p, C.POINTER(WellsSpec)]),

@@ -20,8 +20,9 @@ What `flow_legacy` gets from opm-parser + `DerivedGeology` (opm/autodiff/GeoProp
             SWL SWCR SWU SOWCR SGL SGCR SGU SOGCR  KRW KRO KRG PCW PCG  ISWL ISWCR ISWU ISOWCR ISGL ISGCR ISGU ISOGCR
             SWATINIT (an imposed initial water saturation per cell; read like SWL, `swatinit()`; EQUIL then rescales each cell's PCW,
             opmgpu/equil.py; needs EQUIL and a water phase)
-            (SATOPTS HYSTER in RUNSPEC switches the hysteresis on; EHYSTR item 2 = 0 and item 5 = KR -- Carlson, relative permeabilities
-            only -- is the model the device implements)
+            (SATOPTS HYSTER in RUNSPEC switches the hysteresis on; EHYSTR item 2 = 0 -- Carlson -- or 2 -- Killough, with item 4 its
+            curvature parameter -- and item 5 = KR, relative permeabilities only, are the models the device implements:
+            `hysteresis_model()`; items 1 and 3 are read past, the wetting-phase models 1, 3, 4 are refused)
   REGIONS   PVTNUM SATNUM IMBNUM FIPNUM (fluid-in-place regions of computeFluidInPlace; 1-based in the deck and in `fipnum()`)
             EQLNUM (equilibration regions: EQUIL's, and the regions THPRES puts barriers between; 1-based in `eqlnum()`)
   SOLUTION  PRESSURE SWAT SGAS RS RV (explicit initial state; EQUIL is outside the hot path)
@@ -687,16 +688,32 @@ class Deck:
         return out
 
     def hysteresis(self):
-        """SATOPTS HYSTER with the EHYSTR model the device implements (item 2 = 0: Carlson / drainage for the wetting phase, item 5 = KR)"""
+        """SATOPTS HYSTER with an EHYSTR model the device implements: item 2 = 0 (Carlson) or 2 (Killough) for the non-wetting phases,
+        drainage curves for the wetting phases, item 5 = KR (relative permeabilities only).  Which of the two: hysteresis_model()."""
         if not self.has("SATOPTS") or not any(str(x).upper().startswith("HYST") for r in self.records("SATOPTS") for x in r):
             return False
+        self.hysteresis_model()          # (refuses what the device does not implement)
+        return True
+
+    def hysteresis_model(self):
+        """(model, a) of EHYSTR: item 2 as capi.HYST_CARLSON (0, also without the keyword) or capi.HYST_KILLOUGH (2), and item 4, Killough's
+        curvature parameter (default 0.1; Carlson does not use it).  Items 1 and 3 (capillary-pressure curvature, the wetting-phase
+        modification) are read past.  ValueError naming EHYSTR for item 2 in 1, 3, 4 (the wetting-phase models), any other model number,
+        and item 5 other than KR."""
+        model, a = capi.HYST_CARLSON, 0.1
         if self.has("EHYSTR"):
             r = self.records("EHYSTR")[0]
             model = int(r[1]) if len(r) > 1 and r[1] is not None else 0
+            if len(r) > 3 and r[3] is not None:
+                a = float(r[3])
             what = str(r[4]).upper() if len(r) > 4 and r[4] is not None else "BOTH"
-            if model != 0 or what != "KR":
-                raise ValueError("EHYSTR: only item 2 = 0 (Carlson) with item 5 = KR is supported")
-        return True
+            if model in (1, 3, 4):
+                raise ValueError("EHYSTR: item 2 = %d (hysteresis of the wetting phase) is not supported; 0 (Carlson) and 2 (Killough) are" % model)
+            if model not in (capi.HYST_CARLSON, capi.HYST_KILLOUGH):
+                raise ValueError("EHYSTR: item 2 = %d is not a model; 0 (Carlson) and 2 (Killough) are supported" % model)
+            if what != "KR":
+                raise ValueError("EHYSTR: item 5 = %s is not supported, only KR (no capillary-pressure hysteresis)" % what)
+        return model, a
 
     def endpoints(self, prefix="", regions="SATNUM"):
         """ENDSCALE: per-cell scaled end points; the ones the deck does not give default to the cell's table values

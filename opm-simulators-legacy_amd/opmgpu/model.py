@@ -428,6 +428,17 @@ class GpuBlackoilModel(_CprDiagnostics):
     def setHysteresis(self, mdc_ow, mdc_go):
         self._chk(self.lib.opmgpu_set_hysteresis(self.ctx, capi.dptr(capi.f64(mdc_ow)), capi.dptr(capi.f64(mdc_go))))
 
+    def setHysteresisModel(self, model, killough_a=0.1):
+        """EHYSTR item 2 / item 4 (opmgpu_set_hysteresis_model, the rule is stated in include/opmgpu.h): capi.HYST_CARLSON, the default
+        of every context, or capi.HYST_KILLOUGH with Killough's curvature parameter.  ValueError with the library's text when refused."""
+        self._chk(self.lib.opmgpu_set_hysteresis_model(self.ctx, int(model), float(killough_a)))
+
+    def getHysteresisScanning(self):
+        """(Sncrt_ow, m_ow, R_ow, Sncrt_go, m_go, R_go) of the scanning curves in force, caller cell order"""
+        out = [np.zeros(self.nc) for _ in range(6)]
+        self._chk(self.lib.opmgpu_get_hysteresis_scanning(self.ctx, *[capi.dptr(a) for a in out]))
+        return out
+
     def setSolvePrecision(self, single_precision=None):
         """residual_.singlePrecision = dt < maxSinglePrecisionTimeStep (:284), told to the device BEFORE the assembly so that
         the Jacobian is written in the solve's precision."""

@@ -62,7 +62,11 @@ class LocalDomain:
                              thpres=None if grid.thpres is None else grid.thpres[keep],
                              pvtnum=None if grid.pvtnum is None else grid.pvtnum[self.global_of_local],
                              satnum=None if grid.satnum is None else grid.satnum[self.global_of_local],
-                             eps=None if grid.eps is None else {k: grid.eps[i][self.global_of_local] for i, k in enumerate(GridData.EPS_NAMES)})
+                             eps=None if grid.eps is None else {k: grid.eps[i][self.global_of_local] for i, k in enumerate(GridData.EPS_NAMES)},
+                             scalecrs=grid.scalecrs,
+                             eps_v=None if grid.eps_v is None else {k: v[self.global_of_local] for k, v in grid.eps_v.items()},
+                             imbnum=None if grid.imbnum is None else grid.imbnum[self.global_of_local],
+                             ieps=None if grid.ieps is None else {k: grid.ieps[i][self.global_of_local] for i, k in enumerate(GridData.EPS_NAMES)})
         if hasattr(grid, "n_face_conn"):          # (host-only, Deck.grid()): the kept connections keep their order, grid faces before NNCs
             self.grid.n_face_conn = int(np.count_nonzero(self.conn_index < grid.n_face_conn))
         # halo lists

@@ -55,6 +55,14 @@ class Simulator:
                 if not hasattr(self.model, "setPvcdo"):
                     raise ValueError("the deck has PVCDO with a compressibility / viscosibility, but the model cannot take the analytic oil (setPvcdo)")
                 self.model.setPvcdo(self.tables.pvcdo)
+        if self.deck.hysteresis():
+            hmodel, killough_a = self.deck.hysteresis_model()
+            if hmodel == capi.HYST_KILLOUGH:
+                # the scanning curves are the device's own rule (opmgpu_set_hysteresis_model); a model without the setter (the CPU oracle
+                # behind the host well model) would run Carlson's
+                if not hasattr(self.model, "setHysteresisModel"):
+                    raise ValueError("EHYSTR item 2 = 2 (Killough): the model cannot take the hysteresis model (setHysteresisModel)")
+                self.model.setHysteresisModel(hmodel, killough_a)
         if self.deck.swatinit() is not None:
             # FlowMain.hpp:683-690: the capillary pressure of the scaled curve at the initial saturations goes to setSwatInitScaling.  Before
             # computeMaxDp, which must see the scaled curve (the reference's two property objects share one material-law manager); from the
