@@ -484,6 +484,38 @@ int opmgpu_set_device_wells(opmgpu_ctx* ctx, const opmgpu_wells* wells);
  * re-plan.  Multi-GPU: rank-local (the factors of this rank's wells), no communication.
  * OPMGPU_EINVAL with text in opmgpu_last_error(ctx): no device wells are set; a factor is not finite; a factor is outside (0, 1]. */
 int opmgpu_set_well_efficiency(opmgpu_ctx* ctx, const double* factors);
+/* Group rate control (GCONPROD, GCONINJE) shared by guide rates.  The reference calls the group logic from its Newton loop
+ * (setupGroupControl at the first assembly of a time step, updateWellTargets behind updateWellControls at every assembly and inside the
+ * well pre-solve: BlackoilModelBase_impl.hpp:779-792, :1090-1093) but WellCollection / WellsGroup themselves are opm-core's and not part
+ * of the reference tree.  The sharing rule below is therefore OURS: stated here, pinned by a numpy restatement
+ * (tests/group_reference.py), and unpinned against opm-core.
+ * A controlled group g has a sign s_g (-1 production, +1 injection), a target T_g >= 0 (surface volume rate, SI), phase weights d_g[3]
+ * in water, oil, gas order (ORAT {0,1,0}, WRAT {1,0,0}, GRAT {0,0,1}, LRAT {1,1,0}; an injection group: the unit vector of its phase) and
+ * member wells M_g, each with a guide rate gamma_w > 0.  A well belongs to at most one controlled group.  Every member carries one GROUP
+ * SLOT: a SURFACE_RATE control with distr d_g that is the LAST control of the well (so updateWellControls, which switches to the first
+ * broken constraint, gives it the lowest priority); s_w is its index within the well.  With r_w = e_w (d_g . qs_w) (e_w: the well's
+ * efficiency factor), I = {w in M_g : current[w] != s_w} (individual control) and C = M_g \ I (group control), the slot targets are a pure
+ * function of (current, qs, gamma, e, T):
+ *     w in C:  Gamma   = sum_{v in C} gamma_v,             rem   = max(0, T_g - s_g sum_{v in I} r_v),           target_w = s_g (gamma_w / Gamma)   rem   / e_w
+ *     w in I:  Gamma_w = gamma_w + sum_{v in C} gamma_v,   rem_w = max(0, T_g - s_g sum_{v in I, v != w} r_v),   target_w = s_g (gamma_w / Gamma_w) rem_w / e_w
+ * (for a well in I: what it would get if it joined).  The rule is stateless: a well that left group control has a defined way back.
+ * Nothing else of a well's controls changes.  The device re-shares (k_group_targets) before and after updateWellControls at every
+ * assembly, behind the control update of every iteration of the well pre-solve, which takes its unfused path while groups are set, and
+ * behind the restore of the well state after a pre-solve that did not converge.
+ * Sums run per group in a fixed order without floating-point atomics: the same input gives the same bits in every run.
+ * opmgpu_set_well_groups: members of group g = group_wells[group_ptr[g] .. group_ptr[g+1]) (well indices of opmgpu_set_device_wells),
+ * guide[] in the same positions, sign[ngroups], target[ngroups], distr[ngroups*3].  Call AFTER opmgpu_set_device_wells; ngroups == 0
+ * removes the groups and puts the slots' targets back to what the caller gave them.  A later opmgpu_set_device_wells removes the groups
+ * (the well list changed); they are no part of the saved state and last through opmgpu_save_state / opmgpu_restore_state, a change of
+ * the solve's precision and a re-plan.  With no groups set nothing is launched and every path gives the bits it gave before.
+ * OPMGPU_EINVAL with text in opmgpu_last_error(ctx), and the groups in force stay: no device wells are set; a communicator is attached
+ * (a group's wells may sit on several ranks: out of scope); a well is in two groups; a member's last control is not a SURFACE_RATE slot
+ * with the group's distr; a guide rate is not finite or not positive; a target is not finite or negative.
+ * opmgpu_get_well_group_targets: runs the rule on the well state and current controls as they stand and returns slot_target[nw] (NaN for
+ * a well in no group) and group_rate[ngroups] = sum_{w in M_g} r_w (signed as the wells' rates are); either pointer may be NULL. */
+int opmgpu_set_well_groups(opmgpu_ctx* ctx, int ngroups, const int32_t* group_ptr, const int32_t* group_wells, const double* sign,
+                           const double* target, const double* distr, const double* guide);
+int opmgpu_get_well_group_targets(opmgpu_ctx* ctx, double* slot_target, double* group_rate);
 /* Cells perforated by more than one well (computeWellFlux, StandardWells_impl.hpp:396-560, and addWellContributionToMassBalanceEq,
  * BlackoilModelBase_impl.hpp:953-975, which superpose any number of perforations on a cell): *shared_rows = number of such cells,
  * *max_wells_per_cell = the most wells found in one cell; both 0 for a well list without shared cells.  Either pointer may be NULL.

@@ -101,6 +101,11 @@ public:
     int set_device_wells(const opmgpu_wells* spec);
     int set_well_efficiency(const double* factors);         // [nw] in (0, 1] or NULL = ones; throws HipError(OPMGPU_EINVAL) with the reason
     int get_well_efficiency(double* factors) const;
+    // controlled groups (the rule: opmgpu_set_well_groups in include/opmgpu.h); both throw HipError(OPMGPU_EINVAL) with the reason
+    int set_well_groups(int ngroups, const int32_t* group_ptr, const int32_t* group_wells, const double* sign, const double* target,
+                        const double* distr, const double* guide);
+    int get_well_group_targets(double* slot_target, double* group_rate);
+    int well_group_count() const;
     int well_shared_cells(int32_t* shared_rows, int32_t* max_wells_per_cell) const;      // throws HipError(OPMGPU_EINVAL) without device wells
     int shared_well_rows() const;                           // rows perforated by several wells (0 without device wells)
     int well_state_set(const double* bhp, const double* qs, const double* perf_press, const double* perf_rates);

@@ -391,6 +391,18 @@ int opmgpu_set_well_efficiency(opmgpu_ctx* c, const double* factors)
     // the next assembly reads the new factors; a matrix loaded or factored before the call is that of the old ones
     return guarded(c, [&]() { const int st = c->model->set_well_efficiency(factors); c->matrix_loaded = false; return st; });
 }
+int opmgpu_set_well_groups(opmgpu_ctx* c, int ngroups, const int32_t* group_ptr, const int32_t* group_wells, const double* sign, const double* target,
+                           const double* distr, const double* guide)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    // the next assembly takes the well equations' targets from the groups: a matrix loaded or factored before the call is the old one's
+    return guarded(c, [&]() { const int st = c->model->set_well_groups(ngroups, group_ptr, group_wells, sign, target, distr, guide); c->matrix_loaded = false; return st; });
+}
+int opmgpu_get_well_group_targets(opmgpu_ctx* c, double* slot_target, double* group_rate)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { return c->model->get_well_group_targets(slot_target, group_rate); });
+}
 int opmgpu_well_shared_cells(opmgpu_ctx* c, int32_t* shared_rows, int32_t* max_wells_per_cell)
 {
     if (!c || !c->model) return OPMGPU_EINVAL;
@@ -924,6 +936,9 @@ static int comm_init_common(opmgpu_ctx* c, int rank, int nranks, const uint8_t* 
         // the decomposed code sums a perforated row's well terms from one workgroup per well: refused before anything is attached
         if (c->model->shared_well_rows() > 0)
             return fail(c, OPMGPU_EINVAL, "multi-GPU: a cell is perforated by several wells; a decomposed run (a communicator is attached) does not support that");
+        // a group's wells may sit on several ranks and the re-share is rank-local: refused here too, so that the context stays single-domain
+        if (c->model->well_group_count() > 0)
+            return fail(c, OPMGPU_EINVAL, "multi-GPU: controlled well groups are set; group control in a decomposed run (a communicator is attached) is not supported");
         std::unique_ptr<RcclComm> cm(new RcclComm());
         static const int32_t zero2[2] = { 0, 0 };
         const int st = cm->init(rank, nranks, id, transport, n_owned, c->model->nc, n_neigh, neigh_rank, n_neigh ? send_ptr : zero2, send_cells,

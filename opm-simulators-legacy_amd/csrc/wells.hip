@@ -19,7 +19,10 @@
 //   PVT at the average well-block pressure           :218-296                                       (k_well_avg_press + k_perf_pvt)
 //   RESERVOIR_RATE conversion coefficients          RateConverterLegacy.hpp:495-548, :718-768        (k_voidage_coeff, region_state_sums in blackoil_output.hip)
 //   well efficiency factors (WEFAC)                 StandardWells_impl.hpp:1405-1434; BlackoilModelBase_impl.hpp:953-975   (WellArgs::eff, k_well_assemble)
-// Not restated: group controls / guide rates (and with them GEFAC).
+//   group rate control shared by guide rates        BlackoilModelBase_impl.hpp:779-792, :1090-1093 call it; WellCollection / WellsGroup are
+//                                                   opm-core and not in the reference tree: the sharing rule is OURS, stated at
+//                                                   opmgpu_set_well_groups in include/opmgpu.h   (k_group_targets, group_targets_dev)
+// Not restated: GEFAC, group modes other than a surface rate, nested targets.
 #include "blackoil.hpp"
 #include "vfp.hpp"
 
@@ -77,7 +80,8 @@ __device__ void perf_flux(const double* __restrict__ pp, double bhp_v, double cd
 struct WellArgs {
     int nbp;
     const int32_t *connpos, *perf_row, *type, *allow_cf, *ctrl_type;
-    const double *WI, *comp_frac, *ctrl_target, *ctrl_distr, *depth_ref, *z_perf, *surf_dens_perf;
+    const double *WI, *comp_frac, *ctrl_distr, *depth_ref, *z_perf, *surf_dens_perf;
+    double* ctrl_target;         // [nctrl]; written by group_targets_dev alone (the group slots), read by everything else
     const int32_t *ctrl_ptr, *ctrl_vfp, *thp_ctrl;       // controls of well w: [ctrl_ptr[w], ctrl_ptr[w+1]); VFP table INDEX per control (-1); first THP control of the well (-1)
     const double* ctrl_alq;
     int32_t* current;            // [nw] currentControls(): index relative to ctrl_ptr[w]
@@ -104,6 +108,12 @@ struct WellArgs {
     // perf_shared[j] != 0: perforation j shares its row (one load next to perf_row[j], nothing that waits for the row).
     const int32_t *perf_of_row, *perf_next, *perf_well, *perf_shared;
     double* bde;
+    // controlled groups (opmgpu_set_well_groups; ngroups == 0: none, nothing below is read): members of group g =
+    // group_wells[group_ptr[g] .. group_ptr[g + 1]), guide rates in the same positions; group_rate[g] = the members' weighted rate sum
+    int ngroups;
+    const int32_t *group_ptr, *group_wells;
+    const double *group_sign, *group_target, *group_distr, *group_guide;
+    double* group_rate;
 };
 
 // average well-block pressure per perforation (computePropertiesForWellConnectionPressures, StandardWells_impl.hpp:228-237):
@@ -254,6 +264,48 @@ __device__ void well_apply_increment(const WellArgs& A, int w, const double dy[4
         A.thp[w] = vfp_thp(A.V, t, q, ws[3] + vfp_dp(A, w, t), A.ctrl_alq[tc]);
     }
 }
+
+// ---- group rate control: the slot targets of one controlled group (the rule: opmgpu_set_well_groups, include/opmgpu.h) ----------
+// Called by ALL kBlock threads of a workgroup.  The three sums of the group -- guide rates of the wells on their slot, weighted rates of
+// the wells under individual control, weighted rates of all members -- are taken per thread over a fixed stride and then through
+// block_sum's fixed tree: no atomics, the same bits in every run, any group size.  What the calling workgroup wrote to wstate / current
+// before must be behind a __syncthreads(); the function ends with one, so the targets are visible to the workgroup on return.
+__device__ void group_targets_dev(const WellArgs& A, int g)
+{
+    __shared__ double gsm[12];
+    __shared__ double gtot[3];
+    const int tid = threadIdx.x;
+    const int lo = A.group_ptr[g], hi = A.group_ptr[g + 1];
+    const double sg = A.group_sign[g], T = A.group_target[g];
+    const double d0 = A.group_distr[3 * g], d1 = A.group_distr[3 * g + 1], d2 = A.group_distr[3 * g + 2];
+    double acc[3] = { 0.0, 0.0, 0.0 };          // Gamma = sum of gamma over C; sum of r over I; sum of r over all members
+    for (int i = lo + tid; i < hi; i += kBlock) {
+        const int w = A.group_wells[i];
+        const double* ws = A.wstate + 4 * w;
+        const double r = A.eff[w] * (d0 * ws[0] + d1 * ws[1] + d2 * ws[2]);
+        if (A.current[w] != A.ctrl_ptr[w + 1] - A.ctrl_ptr[w] - 1) acc[1] += r; else acc[0] += A.group_guide[i];
+        acc[2] += r;
+    }
+    block_sum<3>(acc, gsm);
+    if (tid == 0) { gtot[0] = acc[0]; gtot[1] = acc[1]; gtot[2] = acc[2]; A.group_rate[g] = acc[2]; }
+    __syncthreads();
+    const double Gamma = gtot[0], RI = gtot[1];
+    for (int i = lo + tid; i < hi; i += kBlock) {
+        const int w = A.group_wells[i];
+        const double* ws = A.wstate + 4 * w;
+        const double e = A.eff[w], gam = A.group_guide[i];
+        const int slot = A.ctrl_ptr[w + 1] - 1;
+        double share, rem;
+        if (A.current[w] != slot - A.ctrl_ptr[w]) {     // under individual control: what the well would get if it joined
+            const double r = e * (d0 * ws[0] + d1 * ws[1] + d2 * ws[2]);
+            share = gam / (gam + Gamma); rem = T - sg * (RI - r);
+        } else { share = gam / Gamma; rem = T - sg * RI; }
+        A.ctrl_target[slot] = sg * share * fmax(0.0, rem) / e;
+    }
+    __syncthreads();
+}
+// one workgroup per controlled group
+__global__ __launch_bounds__(kBlock) void k_group_targets(WellArgs A) { group_targets_dev(A, blockIdx.x); }
 
 // flags[]: 0 = error bits (WE_*), 1 = pre-solve done, 2 = pre-solve converged, 3 = pre-solve iterations
 enum { WF_ERR = 0, WF_DONE, WF_CONV, WF_ITS, WF_COUNT };
@@ -679,6 +731,7 @@ __global__ __launch_bounds__(kBlock) void k_well_presolve_serial(int nw, int np,
         for (int w = tid; w < nw; w += kBlock) presolve_newton_step(A, w, Ebuf + 4 * size_t(w), S.dbhp_max_rel, flags);
         __threadfence();
         __syncthreads();
+        for (int g = 0; g < A.ngroups; ++g) group_targets_dev(A, g);          // updateWellTargets (:1090-1093); ends with a barrier
         if (it >= S.max_it) { if (tid == 0) presolve_finish(flags, 0, it); return; }
     }
 }
@@ -703,6 +756,10 @@ __global__ __launch_bounds__(kBlock) void k_well_presolve_step(int nw, WellArgs 
     const int verdict = presolve_verdict(nw, A.wellE, S, LoadPlain());
     if (verdict != 0) { if (tid == 0) presolve_finish(flags, verdict, flags[WF_ITS]); return; }
     for (int w = tid; w < nw; w += kBlock) presolve_newton_step(A, w, A.wellE + 4 * size_t(w), S.dbhp_max_rel, flags);
+    if (A.ngroups > 0) {          // updateWellTargets behind updateWellControls (BlackoilModelBase_impl.hpp:1090-1093)
+        __syncthreads();
+        for (int g = 0; g < A.ngroups; ++g) group_targets_dev(A, g);
+    }
     if (tid == 0) { const int it = flags[WF_ITS] + 1; if (it >= S.max_it) presolve_finish(flags, 0, it); else flags[WF_ITS] = it; }
 }
 
@@ -777,6 +834,13 @@ struct BlackoilDevice::WellsDev {
     DevArray<double> bsums, bscratch, snap, presolve_sync, ctrl_row;
     DevArray<double> eff;           // [nw] well efficiency factors (set_well_efficiency); no part of the well STATE: not saved, not restored
     std::vector<double> h_eff;
+    // controlled groups (set_well_groups): no part of the well STATE either; indexed by well and control, never by row, so a re-plan
+    // leaves them alone.  group_rate[ngroups] is written by every k_group_targets launch.
+    int ngroups = 0;
+    DevArray<int32_t> group_ptr, group_wells;
+    DevArray<double> group_sign, group_target, group_distr, group_guide, group_rate;
+    std::vector<int32_t> h_group_of;        // [nw] group of the well or -1
+    std::vector<double> h_ctrl_target;      // [nctrl] the targets as the caller gave them: what a removal of the groups puts back into the slots
     // rows perforated by several wells (WellArgs): the chain, the rows' list (internal rows, ascending) and every perforated row ONCE
     DevArray<int32_t> perf_next, perf_shared, shared_rows, perf_rows_once;
     DevArray<double> bde;
@@ -804,6 +868,8 @@ static WellArgs args_of(BlackoilDevice::WellsDev& W, BlackoilDevice::VfpDev* V, 
     A.wstate = W.wstate.p; A.cdp = W.cdp.p; A.perf_rates = W.perf_rates.p; A.perf_press = W.perf_press.p; A.P = W.P.p; A.Q = W.Q.p;
     A.Fsave = W.Fsave.p; A.wellE = W.wellE.p; A.Dinv = W.Dinv.p; A.eff = W.eff.p;
     A.perf_of_row = W.perf_of_row.p; A.perf_next = W.perf_next.p; A.perf_well = W.perf_well.p; A.perf_shared = W.perf_shared.p; A.bde = W.bde.p;
+    A.ngroups = W.ngroups; A.group_ptr = W.group_ptr.p; A.group_wells = W.group_wells.p; A.group_sign = W.group_sign.p; A.group_target = W.group_target.p;
+    A.group_distr = W.group_distr.p; A.group_guide = W.group_guide.p; A.group_rate = W.group_rate.p;
     return A;
 }
 
@@ -952,6 +1018,7 @@ int BlackoilDevice::set_device_wells(const opmgpu_wells* s)
     W.perf_dens.alloc(np); W.perf_dens.zero(stream); W.perf_pvt.alloc(5 * size_t(np)); W.avgp.alloc(np); W.qout.alloc(3 * size_t(np));
     W.ctrl_row.alloc(4 * size_t(nw)); W.ctrl_row.zero(stream);
     W.h_eff.assign(nw, 1.0); W.eff.upload(W.h_eff, stream);          // a new well list: every factor is 1 again
+    W.h_group_of.assign(nw, -1); W.h_ctrl_target.assign(s->ctrl_target, s->ctrl_target + nct);      // ... and no controlled groups
     W.wdy.alloc(4 * size_t(nw)); W.wdy.zero(stream); W.wdy_old.alloc(4 * size_t(nw)); W.wdy_old.zero(stream);
     W.bsums.alloc(16); W.bscratch.alloc(13 * size_t(kMaxRedBlocks)); W.snap.alloc(5 * size_t(nw) + 4 * size_t(np));
     std::vector<double> zp(np), sd(3 * size_t(np));
@@ -1026,6 +1093,79 @@ int BlackoilDevice::set_well_efficiency(const double* factors)
     OPMGPU_HIP(hipStreamSynchronize(stream));
     return OPMGPU_OK;
 }
+// Controlled groups (the rule: include/opmgpu.h).  Everything is checked against the host copies of the well list before anything is
+// uploaded, so a refused call leaves the groups in force as they were.  ngroups == 0 removes them.
+int BlackoilDevice::set_well_groups(int ngroups, const int32_t* group_ptr, const int32_t* group_wells, const double* sign, const double* target,
+                                    const double* distr, const double* guide)
+{
+    const std::string who = "opmgpu_set_well_groups: ";
+    if (!wd) throw HipError(OPMGPU_EINVAL, who + "no device wells are set (opmgpu_set_device_wells comes first)");
+    if (ls.comm) throw HipError(OPMGPU_EINVAL, who + "a communicator is attached; group control in a decomposed run is not supported (a group's wells may sit on several ranks)");
+    WellsDev& W = *wd;
+    if (ngroups < 0) throw HipError(OPMGPU_EINVAL, who + "ngroups is negative");
+    if (ngroups == 0) {
+        if (W.ngroups > 0) { W.ctrl_target.upload(W.h_ctrl_target, stream); OPMGPU_HIP(hipStreamSynchronize(stream)); }      // the slots' targets as they were given
+        W.ngroups = 0; W.h_group_of.assign(W.nw, -1);
+        return OPMGPU_OK;
+    }
+    if (!group_ptr || !group_wells || !sign || !target || !distr || !guide) throw HipError(OPMGPU_EINVAL, who + "an array is NULL");
+    if (group_ptr[0] != 0) throw HipError(OPMGPU_EINVAL, who + "group_ptr does not start at 0");
+    // the controls as they were given: the slot's type and distr are checked against them
+    std::vector<int32_t> h_type(W.nctrl);
+    std::vector<double> h_distr(3 * size_t(W.nctrl));
+    W.ctrl_type.download(h_type.data(), h_type.size(), stream); W.ctrl_distr.download(h_distr.data(), h_distr.size(), stream);
+    OPMGPU_HIP(hipStreamSynchronize(stream));
+    std::vector<int32_t> group_of(W.nw, -1);
+    for (int g = 0; g < ngroups; ++g) {
+        const std::string gs = "group " + std::to_string(g);
+        if (group_ptr[g + 1] < group_ptr[g]) throw HipError(OPMGPU_EINVAL, who + "group_ptr decreases at " + gs);
+        if (sign[g] != 1.0 && sign[g] != -1.0) throw HipError(OPMGPU_EINVAL, who + "the sign of " + gs + " is neither -1 (production) nor +1 (injection)");
+        if (!std::isfinite(target[g])) throw HipError(OPMGPU_EINVAL, who + "the target of " + gs + " is not finite");
+        if (target[g] < 0.0) throw HipError(OPMGPU_EINVAL, who + "the target of " + gs + " is negative");
+        for (int a = 0; a < 3; ++a) if (!std::isfinite(distr[3 * g + a])) throw HipError(OPMGPU_EINVAL, who + "a phase weight of " + gs + " is not finite");
+        for (int i = group_ptr[g]; i < group_ptr[g + 1]; ++i) {
+            const int w = group_wells[i];
+            if (w < 0 || w >= W.nw) throw HipError(OPMGPU_EINVAL, who + gs + " names well " + std::to_string(w) + ", which does not exist");
+            const std::string wsn = "well " + std::to_string(w);
+            if (group_of[w] >= 0) throw HipError(OPMGPU_EINVAL, who + wsn + " is in two groups (" + std::to_string(group_of[w]) + " and " + std::to_string(g) + ")");
+            group_of[w] = g;
+            if (!std::isfinite(guide[i])) throw HipError(OPMGPU_EINVAL, who + "the guide rate of " + wsn + " is not finite");
+            if (!(guide[i] > 0.0)) throw HipError(OPMGPU_EINVAL, who + "the guide rate of " + wsn + " is not positive");
+            const int c = W.h_ctrl_ptr[w + 1] - 1;
+            bool same = h_type[c] == OPMGPU_CTRL_SURFACE_RATE;
+            for (int a = 0; a < 3; ++a) same = same && h_distr[3 * size_t(c) + a] == distr[3 * g + a];
+            if (!same) throw HipError(OPMGPU_EINVAL, who + "the last control of " + wsn + " is not a SURFACE_RATE slot with the distr of " + gs);
+        }
+    }
+    const size_t nm = size_t(group_ptr[ngroups]);
+    if (W.ngroups > 0) W.ctrl_target.upload(W.h_ctrl_target, stream);      // wells that were members and are no longer: their slots' targets as they were given
+    W.group_ptr.upload(group_ptr, size_t(ngroups) + 1, stream); W.group_wells.upload(group_wells, nm, stream);
+    W.group_sign.upload(sign, size_t(ngroups), stream); W.group_target.upload(target, size_t(ngroups), stream);
+    W.group_distr.upload(distr, 3 * size_t(ngroups), stream); W.group_guide.upload(guide, nm, stream);
+    W.group_rate.ensure(size_t(ngroups)); W.group_rate.zero(stream);
+    OPMGPU_HIP(hipStreamSynchronize(stream));          // the caller's arrays may go
+    W.ngroups = ngroups; W.h_group_of = group_of;
+    return OPMGPU_OK;
+}
+// the slot targets the rule gives for the well state and current controls as they stand (the kernel runs here too, so the call needs no
+// assembly before it): slot_target[nw], NaN for a well in no group; group_rate[ngroups]
+int BlackoilDevice::get_well_group_targets(double* slot_target, double* group_rate)
+{
+    if (!wd) throw HipError(OPMGPU_EINVAL, "opmgpu_get_well_group_targets: no device wells are set");
+    WellsDev& W = *wd;
+    std::vector<double> tg(W.nctrl);
+    if (W.ngroups > 0) {
+        hipLaunchKernelGGL(k_group_targets, dim3(W.ngroups), dim3(kBlock), 0, stream, args_of(W, vfp, ls.plan.nbp, d_perf.p, gravity));
+        OPMGPU_HIP(hipGetLastError());
+        W.ctrl_target.download(tg.data(), tg.size(), stream);
+        if (group_rate) W.group_rate.download(group_rate, size_t(W.ngroups), stream);
+        OPMGPU_HIP(hipStreamSynchronize(stream));
+    }
+    if (slot_target)
+        for (int w = 0; w < W.nw; ++w) slot_target[w] = (W.ngroups > 0 && W.h_group_of[w] >= 0) ? tg[W.h_ctrl_ptr[w + 1] - 1] : std::nan("");
+    return OPMGPU_OK;
+}
+int BlackoilDevice::well_group_count() const { return wd ? wd->ngroups : 0; }
 // rows perforated by more than one well, and the largest number of wells in one cell (both 0 without shared cells)
 int BlackoilDevice::well_shared_cells(int32_t* shared_rows, int32_t* max_wells_per_cell) const
 {
@@ -1086,7 +1226,11 @@ void BlackoilDevice::wells_prologue()
     perf_props_device();
     WellArgs A = args_of(W, vfp, ls.plan.nbp, d_perf.p, gravity);
     if (W.vfp_active) wells_connection_pressures(nullptr);        // VFP: densities for the hydrostatic correction, every assembly (:771-776)
+    // group targets before the control update (applyGroupControls of setupGroupControl, :779-783: the rule is stateless, so every assembly
+    // may do what the reference does at the first) and after it (updateWellTargets, :791)
+    if (W.ngroups > 0) hipLaunchKernelGGL(k_group_targets, dim3(W.ngroups), dim3(kBlock), 0, stream, A);
     hipLaunchKernelGGL(k_well_controls, dim3((W.nw + 63) / 64), dim3(64), 0, stream, W.nw, A, W.flags.p);        // updateWellControls (:785)
+    if (W.ngroups > 0) hipLaunchKernelGGL(k_group_targets, dim3(W.ngroups), dim3(kBlock), 0, stream, A);
 }
 // Newton iterations after the first of a time step: the prologue needs the state only, the reservoir assembly (0.36 ms) does not touch what
 // it writes (d_perf, the wells' control state) -- so it runs beside it on its own stream instead of 35 us behind it.  Not on the first
@@ -1141,7 +1285,11 @@ void BlackoilDevice::wells_assemble(bool initial)
             // fallback that takes over when the fused kernel's barrier gives up.  Read per call: once per time step.
             const char* fenv = std::getenv("OPMGPU_WELL_PRESOLVE_FUSED");
             const int fmode = fenv ? std::atoi(fenv) : 1;
-            if (fmode != 0 && W.nw <= std::min(kFusedWells, fused_presolve_capacity())) {
+            // With controlled groups every iteration's group targets need ALL wells' new rates and controls: the fused kernel has no
+            // grid-wide meeting point behind its Newton step, so groups take the unfused pair below, whose one-workgroup step kernel
+            // re-shares the targets behind its control update (the serial fallback, fmode 2, does the same and stays reachable).
+            const bool fused_ok = W.ngroups == 0 || fmode == 2;
+            if (fmode != 0 && fused_ok && W.nw <= std::min(kFusedWells, fused_presolve_capacity())) {
                 // one launch: one workgroup per well, counter barrier per iteration -- all nw workgroups fit the device together
                 // (fused_presolve_capacity: the kernel's occupancy x compute units, with a margin)
                 W.presolve_sync.alloc(4 + 8 * size_t(W.nw)); W.presolve_sync.zero(stream);
@@ -1162,6 +1310,9 @@ void BlackoilDevice::wells_assemble(bool initial)
             // converged: connection pressures from the new well state (:1122); otherwise the well state is restored (:1124-1126)
             wells_connection_pressures(W.flags.p + WF_CONV);
             hipLaunchKernelGGL(k_well_snapshot, dim3(gs), dim3(kBlock), 0, stream, W.nw, np, A, W.snap.p, W.isnap.p, 1, (const int32_t*)W.flags.p);
+            // a pre-solve that did not converge has put wstate and current back: the slot targets follow the state they are a function of
+            // (after a converged one the launch recomputes the bits that are there)
+            if (W.ngroups > 0) hipLaunchKernelGGL(k_group_targets, dim3(W.ngroups), dim3(kBlock), 0, stream, A);
         }
     }
     d_rhs_extra.zero(stream);
@@ -1339,7 +1490,7 @@ int BlackoilDevice::well_controls_set_targets(const double* target, const double
 {
     if (!wd) return OPMGPU_EINVAL;
     WellsDev& W = *wd;
-    if (target) W.ctrl_target.upload(target, size_t(W.nctrl), stream);
+    if (target) { W.ctrl_target.upload(target, size_t(W.nctrl), stream); W.h_ctrl_target.assign(target, target + W.nctrl); }
     if (distr) W.ctrl_distr.upload(distr, 3 * size_t(W.nctrl), stream);
     OPMGPU_HIP(hipStreamSynchronize(stream));
     return OPMGPU_OK;

@@ -118,6 +118,24 @@ public:
     /// well's rates and their derivatives (StandardWells_impl.hpp:1405-1434, BlackoilModelBase_impl.hpp:953-975); the well equations do not.
     /// After setDeviceWells, which resets the factors to ones; lasts through saved states, precision changes and re-plans.
     void setWellEfficiencyFactors(const std::vector<double>& factors) { throw_on_status(ctx_, opmgpu_set_well_efficiency(ctx_, factors.empty() ? nullptr : factors.data())); }
+    /// Group rate control shared by guide rates (opmgpu_set_well_groups; the sharing rule is stated in include/opmgpu.h): members of group g are
+    /// group_wells[group_ptr[g] .. group_ptr[g+1]) with their guide rates in the same positions; sign -1 production / +1 injection, target in SI,
+    /// distr[3 g ..] the phase weights.  Every member's last control is the group slot.  An empty group_ptr removes the groups.  After
+    /// setDeviceWells, which removes them; lasts through saved states, precision changes and re-plans.
+    void setWellGroups(const std::vector<int32_t>& group_ptr, const std::vector<int32_t>& group_wells, const std::vector<double>& sign,
+                       const std::vector<double>& target, const std::vector<double>& distr, const std::vector<double>& guide)
+    {
+        const int ng = group_ptr.empty() ? 0 : int(group_ptr.size()) - 1;
+        throw_on_status(ctx_, opmgpu_set_well_groups(ctx_, ng, group_ptr.data(), group_wells.data(), sign.data(), target.data(), distr.data(), guide.data()));
+    }
+    /// {slot targets [nw] (NaN for a well in no group), group rates [ngroups]} the rule gives for the well state as it stands
+    std::pair<std::vector<double>, std::vector<double>> wellGroupTargets(int nw, int ngroups) const
+    {
+        std::vector<double> t(nw > 0 ? nw : 1, 0.0), r(ngroups > 0 ? ngroups : 1, 0.0);
+        throw_on_status(ctx_, opmgpu_get_well_group_targets(ctx_, t.data(), r.data()));
+        t.resize(nw > 0 ? nw : 0); r.resize(ngroups > 0 ? ngroups : 0);
+        return { t, r };
+    }
     // {cells perforated by more than one well, most wells in one cell}; {0, 0} without shared cells (opmgpu_well_shared_cells)
     std::pair<int, int> wellSharedCells() const { int32_t rows = 0, most = 0; throw_on_status(ctx_, opmgpu_well_shared_cells(ctx_, &rows, &most)); return { int(rows), int(most) }; }
     std::vector<double> wellEfficiencyFactors(int nw) const { std::vector<double> f(nw > 0 ? nw : 1, 1.0); throw_on_status(ctx_, opmgpu_get_well_efficiency(ctx_, f.data())); f.resize(nw > 0 ? nw : 0); return f; }

@@ -204,6 +204,8 @@ SIGNATURES = {
     "opmgpu_set_device_wells": (C.c_int, [C.c_void_p, C.POINTER(WellsSpec)]),
     "opmgpu_set_well_efficiency": (C.c_int, [C.c_void_p, _dp]),
     "opmgpu_get_well_efficiency": (C.c_int, [C.c_void_p, _dp]),
+    "opmgpu_set_well_groups": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, _dp, _dp, _dp, _dp]),
+    "opmgpu_get_well_group_targets": (C.c_int, [C.c_void_p, _dp, _dp]),
     "opmgpu_well_shared_cells": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "opmgpu_well_state_set": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp]),
     "opmgpu_well_state_get": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp]),

@@ -344,6 +344,37 @@ class GpuBlackoilModel(_CprDiagnostics):
         self._chk(self.lib.opmgpu_get_well_efficiency(self.ctx, capi.dptr(out)))
         return out[:self.n_device_wells]
 
+    def setWellGroups(self, groups):
+        """Controlled groups of the device wells (opmgpu_set_well_groups; the sharing rule is stated in include/opmgpu.h).  `groups`: a
+        sequence of objects with sign (-1 production, +1 injection), target, distr[3], wells (indices of opmgpu_set_device_wells) and
+        guide (one positive guide rate per member) -- opmgpu.wells.WellGroup -- or None / empty to remove the groups.  Every member's last
+        control must be the group slot.  Lasts through saved states, a change of precision and a re-plan; a new opmgpu_set_device_wells
+        removes the groups.  Every refusal of the C entry is a ValueError with its text."""
+        groups = list(groups or ())
+        if not groups:
+            self._chk(self.lib.opmgpu_set_well_groups(self.ctx, 0, None, None, None, None, None, None))
+            self.n_well_groups = 0
+            return
+        ptr = np.concatenate([[0], np.cumsum([len(g.wells) for g in groups])])
+        members = np.concatenate([np.asarray(g.wells, np.int64) for g in groups]) if ptr[-1] else np.zeros(0, np.int64)
+        guide = np.concatenate([np.asarray(g.guide, float) for g in groups]) if ptr[-1] else np.zeros(0)
+        if guide.size != members.size:
+            raise ValueError("setWellGroups: %d guide rates for %d member wells" % (guide.size, members.size))
+        keep = [capi.i32(ptr), capi.i32(members if members.size else [0]), capi.f64([g.sign for g in groups]), capi.f64([g.target for g in groups]),
+                capi.f64(np.asarray([g.distr for g in groups], float).reshape(-1, 3)), capi.f64(guide if guide.size else [1.0])]
+        self._chk(self.lib.opmgpu_set_well_groups(self.ctx, len(groups), capi.iptr(keep[0]), capi.iptr(keep[1]), capi.dptr(keep[2]), capi.dptr(keep[3]),
+                                                  capi.dptr(keep[4]), capi.dptr(keep[5])))
+        self.n_well_groups = len(groups)
+
+    def wellGroupTargets(self):
+        """(slot_target[nw], group_rate[ngroups]) of opmgpu_get_well_group_targets: the rule applied on the device to the well state and
+        current controls as they stand; NaN for a well in no group."""
+        tg, rate = np.zeros(max(self.n_device_wells, 1)), np.zeros(max(self.n_well_groups, 1))
+        self._chk(self.lib.opmgpu_get_well_group_targets(self.ctx, capi.dptr(tg), capi.dptr(rate)))
+        return tg[:self.n_device_wells], rate[:self.n_well_groups]
+
+    n_well_groups = 0           # groups of the last setWellGroups
+
     def wellSharedCells(self):
         """(shared_rows, max_wells_per_cell) of the device wells (opmgpu_well_shared_cells): the number of cells perforated by more than one
         well and the most wells found in one cell; (0, 0) for a well list without shared cells.  ValueError without device wells."""

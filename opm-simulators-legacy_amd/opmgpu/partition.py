@@ -91,6 +91,11 @@ class LocalDomain:
         """The wells of this rank in rank-local cell numbering: a well belongs to the rank that owns ALL of its perforated
         cells (ValueError if a well straddles ranks: choose a partition that keeps wells intact)."""
         from .wells import Wells
+        if getattr(wells, "groups", None):
+            # a group's wells may sit on several ranks and the re-share is rank-local: dropping the groups here would let the field
+            # over-produce without a word (opmgpu_set_well_groups refuses a context with a communicator for the same reason)
+            raise ValueError("the well list has controlled groups (%s): group control in a decomposed run is not supported"
+                             % ", ".join(g.name for g in wells.groups))
         g2l = -np.ones(part.size, dtype=np.int64)
         g2l[self.global_of_local] = np.arange(self.global_of_local.size)
         out = Wells()

@@ -5,7 +5,13 @@ keywords a standard-well black-oil run needs:
   WCONPROD  name OPEN|SHUT mode ORAT WRAT GRAT LRAT RESV BHP THP VFP ALQ     WCONINJE  name phase OPEN|SHUT mode RATE RESV BHP THP VFP
   WELOPEN   name OPEN|SHUT|STOP [I J K]                            WELTARG  name ORAT|WRAT|GRAT|LRAT|BHP|THP|RATE value
   WEFAC     name-or-template factor            the well's efficiency factor in (0, 1], in force from its report step on until replaced
-            (item 3, the network flag, is not read); GEFAC is refused: there are no groups
+            (item 3, the network flag, is not read); GEFAC is refused: groups have no efficiency factor here
+  GRUPTREE  child parent                          the group tree; a group WELSPECS or GCONPROD / GCONINJE names without a parent hangs under FIELD
+  GCONPROD  group mode ORAT WRAT GRAT LRAT exceed-action ...     mode ORAT | WRAT | GRAT | LRAT with its target, or NONE | FLD (no target of
+            its own); exceed action RATE or defaulted
+  GCONINJE  group phase mode rate ...             phase WATER | GAS, mode RATE with its target, or NONE | FLD
+  WGRUPCON  well YES|NO guide-rate                NO: the well is no member of a controlled group (it runs on its own limits and its rate is
+            not counted against the group's target); guide rate defaulted or <= 0: taken from the well potentials (items 4, 5 are not read)
   DATES / TSTEP (report steps), START (RUNSPEC)
   RPTRST    mnemonic list (opmgpu/deck.py:parse_rptrst): REPLACES the list in force (RestartConfig::getRestartKeywords) for the report steps
             that follow it; the SOLUTION section's list holds until then
@@ -15,7 +21,13 @@ the deck gives, the deck's control mode is the initial current control, the othe
 updateWellControls switches to (StandardWells_impl.hpp:709-800).  Producer rate targets are negative (flow into the wellbore).
 A defaulted connection factor is Peaceman's for a vertical well in a block-centred cell (WellsManager::createWellsFromSpecs ->
 computeWellIndices, opm-core, external: restated from the published formula).  METRIC units.
-Not read: groups (GCONPROD ...), WCONHIST, multi-segment wells, horizontal completions (dir X / Y).  A RESV target becomes a
+Group rate control: a well's CONTROLLING GROUP is its nearest ancestor (its own group first) with an active target of the well's kind
+-- a production target controls producers, an injection target the injectors of its phase.  Every member gets the group slot as its last
+control and starts on it when its deck mode is GRUP (Wells.add_group; the sharing rule is stated in include/opmgpu.h).  Refused with a
+ValueError naming keyword and item: RESV / CRAT / PRBL (GCONPROD), RESV / REIN / VREP (GCONINJE), a rate limit of GCONPROD other than the
+mode's own target, an exceed action other than RATE, two ancestors with an active target for one well, GRUP on a well without a
+controlling group, a gas group in a deck without GAS, GEFAC.
+Not read: WCONHIST, multi-segment wells, horizontal completions (dir X / Y).  A RESV target becomes a
 RESERVOIR_RATE control with distr {1, 1, 1}; opmgpu/rateconverter.py's computeRESV gives it the conversion coefficients once per report
 step (SimulatorBase_impl.hpp:196, :476-553).
 A deck without a gas phase (RUNSPEC: OIL WATER; Deck.phases() == "wo"): a GRAT target (WCONPROD item 6, WELTARG GRAT), a GAS injector and a
@@ -43,8 +55,9 @@ def _date(rec):
 
 
 class WellSpec:
-    def __init__(self, name, i, j, ref_depth, phase):
-        self.name, self.i, self.j, self.ref_depth, self.phase = name, i, j, ref_depth, phase
+    def __init__(self, name, i, j, ref_depth, phase, group="FIELD"):
+        self.name, self.i, self.j, self.ref_depth, self.phase, self.group = name, i, j, ref_depth, phase, group
+        self.group_available, self.guide_rate = True, None      # WGRUPCON: available for group control; guide rate (None: from the potentials)
         self.completions = []           # (i, j, k, open, CF or None, diameter, Kh or None, skin)
         self.control = None             # ("PROD", open, mode, limits dict) / ("INJ", phase, open, mode, limits dict)
         self.efficiency = 1.0           # WEFAC
@@ -61,6 +74,7 @@ class Schedule:
         self.two_phase = deck.phases() == "wo"
         self.steps = []                 # [(length in s, {name: WellSpec snapshot})]
         self.rptrst = []                # per report step: {RPTRST mnemonic: int} in force for the restart file written at its end
+        self.groups = []                # per report step: {"parent": {group: parent}, "prod": {group: (mode, target)}, "inje": {(group, phase): target}}
         self._build()
 
     def _build(self):
@@ -69,6 +83,7 @@ class Schedule:
         order = []
         now = self.start
         rptrst = self.deck.rptrst()
+        groups = {"parent": {}, "prod": {}, "inje": {}}
         for name, recs in self.deck.schedule:
             if name == "RPTRST":
                 rptrst = parse_rptrst(recs[0] if recs else [])
@@ -80,7 +95,7 @@ class Schedule:
                     wn = str(r[0])
                     if wn not in specs:
                         order.append(wn)
-                    specs[wn] = WellSpec(wn, int(r[2]) - 1, int(r[3]) - 1, _get(r, 4), str(_get(r, 5, "OIL")).upper())
+                    specs[wn] = WellSpec(wn, int(r[2]) - 1, int(r[3]) - 1, _get(r, 4), str(_get(r, 5, "OIL")).upper(), str(_get(r, 1, "FIELD")).upper())
             elif name == "COMPDAT":
                 for r in recs:
                     if not r:
@@ -148,7 +163,33 @@ class Schedule:
                     for wn in matched:
                         specs[wn].efficiency = e
             elif name == "GEFAC":
-                raise ValueError("GEFAC: group efficiency factors are not supported (there are no groups; WEFAC sets a well's factor)")
+                raise ValueError("GEFAC: group efficiency factors are not supported (WEFAC sets a well's factor)")
+            elif name == "GRUPTREE":
+                for r in recs:
+                    if r:
+                        groups["parent"][str(r[0]).upper()] = str(_get(r, 1, "FIELD")).upper()
+            elif name == "GCONPROD":
+                for r in recs:
+                    if r:
+                        self._gconprod(groups, r)
+            elif name == "GCONINJE":
+                for r in recs:
+                    if r:
+                        self._gconinje(groups, r)
+            elif name == "WGRUPCON":
+                for r in recs:
+                    if not r:
+                        continue
+                    avail = str(_get(r, 1, "YES")).upper()
+                    if avail not in ("YES", "NO", "Y", "N"):
+                        raise ValueError("WGRUPCON %s: item 2 (available for group control) is %r, not YES or NO" % (r[0], avail))
+                    gr = _get(r, 2)
+                    matched = [wn for wn in self._match(specs, str(r[0])) if wn in specs]
+                    if not matched:
+                        raise ValueError("WGRUPCON %s: unknown well (no WELSPECS before it names or matches it)" % r[0])
+                    for wn in matched:
+                        specs[wn].group_available = avail.startswith("Y")
+                        specs[wn].guide_rate = float(gr) if gr is not None and float(gr) > 0.0 else None
             elif name == "WELTARG":          # name control value: one limit of the current WCONPROD / WCONINJE record changed
                 for r in recs:
                     if not r:
@@ -174,13 +215,95 @@ class Schedule:
                     d = _date(r)
                     self.steps.append(((d - now).days * DAY, copy.deepcopy({n: specs[n] for n in order})))
                     self.rptrst.append(dict(rptrst))
+                    self.groups.append(copy.deepcopy(groups))
                     now = d
             elif name == "TSTEP":
                 for r in recs:
                     for dt in r:
                         self.steps.append((float(dt) * DAY, copy.deepcopy({n: specs[n] for n in order})))
                         self.rptrst.append(dict(rptrst))
+                        self.groups.append(copy.deepcopy(groups))
                         now = now + datetime.timedelta(days=float(dt))
+
+    PROD_DISTR = {"ORAT": (0.0, 1.0, 0.0), "WRAT": (1.0, 0.0, 0.0), "GRAT": (0.0, 0.0, 1.0), "LRAT": (1.0, 1.0, 0.0)}
+    INJE_DISTR = {"WATER": (1.0, 0.0, 0.0), "GAS": (0.0, 0.0, 1.0)}
+
+    def _gconprod(self, groups, r):
+        """GCONPROD: 1 group, 2 mode, 3-6 ORAT WRAT GRAT LRAT, 7 exceed action, (8-13 not read), 14 RESV"""
+        g, mode = str(r[0]).upper(), str(_get(r, 1, "NONE")).upper()
+        if mode in ("RESV", "CRAT", "PRBL"):
+            raise ValueError("GCONPROD %s: item 2, control mode %s, is not supported (ORAT, WRAT, GRAT, LRAT, NONE or FLD)" % (g, mode))
+        if mode not in ("ORAT", "WRAT", "GRAT", "LRAT", "NONE", "FLD"):
+            raise ValueError("GCONPROD %s: item 2, control mode %r, is unknown" % (g, mode))
+        items = {"ORAT": 2, "WRAT": 3, "GRAT": 4, "LRAT": 5, "RESV": 13}
+        for key, i in items.items():
+            if key != mode and _get(r, i) is not None:
+                raise ValueError("GCONPROD %s: item %d, a %s limit next to control mode %s, is not supported (only the mode's own target)" % (g, i + 1, key, mode))
+        action = str(_get(r, 6, "RATE")).upper()
+        if action != "RATE":
+            raise ValueError("GCONPROD %s: item 7, exceed action %s, is not supported (RATE or defaulted)" % (g, action))
+        if mode in ("NONE", "FLD"):
+            groups["prod"].pop(g, None)
+            return
+        if self.two_phase and mode == "GRAT":
+            raise ValueError("GCONPROD %s: item 2, GRAT, in a deck without GAS (RUNSPEC: OIL WATER)" % g)
+        target = _get(r, items[mode])
+        if target is None or not np.isfinite(float(target)) or float(target) < 0.0:
+            raise ValueError("GCONPROD %s: item %d, the %s target, is missing or negative" % (g, items[mode] + 1, mode))
+        groups["prod"][g] = (mode, float(target))
+        groups["parent"].setdefault(g, "FIELD")
+
+    def _gconinje(self, groups, r):
+        """GCONINJE: 1 group, 2 phase, 3 mode, 4 surface rate target"""
+        g, phase, mode = str(r[0]).upper(), str(_get(r, 1, "")).upper(), str(_get(r, 2, "NONE")).upper()
+        phase = "WATER" if phase == "WAT" else phase
+        if mode in ("RESV", "REIN", "VREP"):
+            raise ValueError("GCONINJE %s: item 3, control mode %s, is not supported (RATE, NONE or FLD)" % (g, mode))
+        if mode not in ("RATE", "NONE", "FLD"):
+            raise ValueError("GCONINJE %s: item 3, control mode %r, is unknown" % (g, mode))
+        if phase not in ("WATER", "GAS"):
+            raise ValueError("GCONINJE %s: item 2, phase %r, is not supported (WATER or GAS)" % (g, phase))
+        if self.two_phase and phase == "GAS":
+            raise ValueError("GCONINJE %s: item 2, GAS, in a deck without GAS (RUNSPEC: OIL WATER)" % g)
+        if mode in ("NONE", "FLD"):
+            groups["inje"].pop((g, phase), None)
+            return
+        target = _get(r, 3)
+        if target is None or not np.isfinite(float(target)) or float(target) < 0.0:
+            raise ValueError("GCONINJE %s: item 4, the RATE target, is missing or negative" % g)
+        groups["inje"][(g, phase)] = float(target)
+        groups["parent"].setdefault(g, "FIELD")
+
+    def group_tree(self, step):
+        """{group: parent} of report step `step`: GRUPTREE, and FIELD as the parent of every other group a well or a target names"""
+        G = self.groups[step]
+        tree = dict(G["parent"])
+        for ws in self.steps[step][1].values():
+            tree.setdefault(ws.group, "FIELD")
+        for g in list(tree.values()):
+            if g != "FIELD":
+                tree.setdefault(g, "FIELD")
+        tree.pop("FIELD", None)
+        return tree
+
+    def controlling_group(self, step, group, kind):
+        """the nearest ancestor of `group` (itself first) with an active target of `kind` ("PROD", or the injection phase "WATER" / "GAS"):
+        (name, sign, target in SI, distr) or None.  Two such ancestors: ValueError."""
+        G, tree = self.groups[step], self.group_tree(step)
+        found, g, seen = [], group, set()
+        while g is not None and g not in seen:
+            seen.add(g)
+            if kind == "PROD" and g in G["prod"]:
+                mode, t = G["prod"][g]
+                found.append((g, -1.0, t / DAY, self.PROD_DISTR[mode]))
+            elif kind != "PROD" and (g, kind) in G["inje"]:
+                found.append((g, 1.0, G["inje"][(g, kind)] / DAY, self.INJE_DISTR[kind]))
+            g = tree.get(g) if g != "FIELD" else None
+        if len(found) > 1:
+            kw = "GCONPROD" if kind == "PROD" else "GCONINJE"
+            raise ValueError("%s: groups %s and %s, one above the other, both have an active target (item %d); nested targets are not supported"
+                             % (kw, found[0][0], found[1][0], 2 if kind == "PROD" else 3))
+        return found[0] if found else None
 
     @staticmethod
     def _refuse_gas(keyword, well, mode="", **items):
@@ -208,6 +331,7 @@ class Schedule:
         """The `Wells` of report step `step` (open wells with open completions in active cells only; order of WELSPECS)."""
         out = W.Wells()
         act = np.asarray(self.grid.active_index)
+        members = {}                    # controlling group -> [(well index, guide rate or NaN, starts on GRUP)], in the wells' order
         for name, ws in self.steps[step][1].items():
             if ws.control is None:
                 continue
@@ -237,8 +361,7 @@ class Schedule:
                     ctrls["BHP"] = (W.BHP, lim["BHP"] * BAR)
                 if lim["THP"] is not None and lim["VFP"] > 0:
                     ctrls["THP"] = (W.THP, lim["THP"] * BAR, None, lim["VFP"], 0.0)
-                if mode == "GRUP":
-                    raise ValueError("WCONINJE %s: control mode %s is not supported" % (name, mode))
+                kind = "WATER" if phase == "WAT" else phase
                 wtype = W.INJECTOR
             else:
                 _, _, mode, lim = ws.control
@@ -253,14 +376,29 @@ class Schedule:
                     ctrls["BHP"] = (W.BHP, lim["BHP"] * BAR)
                 if lim["THP"] is not None and lim["VFP"] > 0:
                     ctrls["THP"] = (W.THP, lim["THP"] * BAR, None, lim["VFP"], lim["ALQ"] or 0.0)
-                if mode in ("GRUP", "CRAT"):
+                if mode == "CRAT":
                     raise ValueError("WCONPROD %s: control mode %s is not supported" % (name, mode))
+                kind = "PROD"
                 wtype = W.PRODUCER
-            if mode not in ctrls:
+            keyword = "WCONINJE" if is_inj else "WCONPROD"
+            ctl = self.controlling_group(step, ws.group, kind) if ws.group_available and kind in ("PROD", "WATER", "GAS") else None
+            if mode == "GRUP":
+                if ctl is None:
+                    raise ValueError("%s %s: item %d, control mode GRUP, but the well has no controlling group (no ancestor of group %s has an "
+                                     "active target for it%s)" % (keyword, name, 4 if is_inj else 3, ws.group, "" if ws.group_available else "; WGRUPCON makes it unavailable"))
+                if not ctrls:
+                    raise ValueError("%s %s: control mode GRUP needs at least one limit of the well's own (a BHP limit)" % (keyword, name))
+            elif mode not in ctrls:
                 raise ValueError("well %s: control mode %r has no target in the deck" % (name, mode))
+            if ctl is not None:
+                members.setdefault(ctl, []).append((out.nw, float("nan") if ws.guide_rate is None else ws.guide_rate, mode == "GRUP"))
             # WellsManager's fixed order (ORAT, WRAT, GRAT, LRAT, [RESV], BHP, THP; injectors RATE, [RESV], BHP, THP) with the deck's
             # control mode as the index of the current control: updateWellControls switches to the FIRST broken constraint, so the
             # order decides which one wins when two are broken (and the index goes into the restart file)
             order = list(ctrls.values())
-            out.add_well(name, wtype, ref, cells, wi, comp, order[0], limits=order[1:], current=list(ctrls).index(mode), efficiency=ws.efficiency)
+            out.add_well(name, wtype, ref, cells, wi, comp, order[0], limits=order[1:], current=0 if mode == "GRUP" else list(ctrls).index(mode),
+                         efficiency=ws.efficiency)
+        # the controlled groups in the order of their first member: the slot behind every member's own controls, GRUP wells on it
+        for (gname, sign, target, distr), mem in members.items():
+            out.add_group(gname, sign, target, distr, [m[0] for m in mem], [m[1] for m in mem], on_group=[m[0] for m in mem if m[2]])
         return out

@@ -176,6 +176,8 @@ class Simulator:
                 model = self.well_model_factory(gm, wl, ws)
             else:
                 model = W.DeviceWellModel(gm, wl, ws, vfp_tables=self.vfp_tables)
+            if wl.nw > 0 and getattr(wl, "groups", None):
+                self._install_groups(model, wl)
             host_ws = ws if (wl.nw > 0 and not hasattr(model, "pull_well_state")) else None        # a host well model keeps the well state here
             rep = self.ats.step(t, dt, _Solver(), model, event=event, well_state=host_ws)
             t += dt
@@ -203,6 +205,18 @@ class Simulator:
                     self.out.write_summary(t / DAY, wl, ws, new_report_step=True, fip=fip)
             prev_ws, prev_names = (ws.copy(), list(wl.name)) if wl.nw > 0 else (None, None)
         return self.reports
+
+    def _install_groups(self, model, wl):
+        """Group control of the report step.  Guide rates the deck leaves to the potentials (WGRUPCON defaulted, or no WGRUPCON) come from
+        computeWellPotentials, called once per report step and only then (BlackoilModelBase_impl.hpp:2576-2619 does so when the deck has
+        group controls): |d_g . potential| with a tiny positive floor.  The device well model then takes the groups behind its wells
+        (opmgpu_set_well_groups); the host well model reads them from the well list."""
+        if hasattr(model, "install_groups"):
+            model.install_groups(lambda: model.computeWellPotentials(self.grid.z, self.tables.surface_density[0], self.vfp_tables))
+        elif hasattr(model, "computeWellPotentials"):
+            W.resolve_guide_rates(wl.groups, lambda: model.computeWellPotentials(from_well_state=True))
+        elif any(np.isnan(g) for grp in wl.groups for g in grp.guide):
+            raise ValueError("the deck leaves a guide rate to the well potentials, but the well model cannot compute them (computeWellPotentials)")
 
     def close(self):
         if hasattr(self.model, "close"):

@@ -21,7 +21,11 @@ terms go back through `addWellTerms` / `addWellRhs`, the perforated cells' incre
 
   well efficiency factors (WEFAC)                  StandardWells_impl.hpp:1405-1434; BlackoilModelBase_impl.hpp:953-975
 
-Not restated: group controls / guide rates (WellCollection; with them GEFAC).
+  group rate control shared by guide rates: called where the reference calls WellCollection (BlackoilModelBase_impl.hpp:779-792,
+  :1090-1093); WellCollection / WellsGroup are opm-core's and not in the reference tree, so the sharing rule is OURS -- stated in
+  include/opmgpu.h (opmgpu_set_well_groups), restated in tests/group_reference.py   (Wells.add_group, StandardWellsHost.update_group_targets)
+
+Not restated: GEFAC, group modes other than a surface rate, nested group targets.
 """
 import numpy as np
 
@@ -84,6 +88,40 @@ class AD:
         return AD(np.repeat(self.v, n), np.repeat(self.j, n, axis=0))
 
 
+GUIDE_RATE_FLOOR = 1e-30        # a guide rate taken from a zero potential: tiny and positive, so that the shares stay defined
+
+
+class WellGroup:
+    """One controlled group: sign (-1 production, +1 injection), target T >= 0 (SI surface rate), distr[3] phase weights (w, o, g), the
+    member wells (indices) and one guide rate per member -- NaN = take it from the well potentials (resolve_guide_rates)."""
+
+    def __init__(self, name, sign, target, distr, wells, guide):
+        self.name, self.sign, self.target = name, float(sign), float(target)
+        self.distr = np.asarray(distr, float).reshape(3)
+        self.wells = [int(w) for w in wells]
+        self.guide = [float(g) for g in guide]
+        if self.sign not in (-1.0, 1.0):
+            raise ValueError("group %s: sign %r is neither -1 (production) nor +1 (injection)" % (name, sign))
+        if not (np.isfinite(self.target) and self.target >= 0.0):
+            raise ValueError("group %s: target %r is not a finite rate >= 0" % (name, target))
+        if len(self.guide) != len(self.wells):
+            raise ValueError("group %s: %d guide rates for %d wells" % (name, len(self.guide), len(self.wells)))
+        for g in self.guide:
+            if not np.isnan(g) and not (np.isfinite(g) and g > 0.0):
+                raise ValueError("group %s: guide rate %r is not positive" % (name, g))
+
+
+def resolve_guide_rates(groups, potentials):
+    """guide rates that were left to the potentials (NaN): |d_g . potential_w| with a tiny positive floor.  potentials: [nw, 3] of
+    computeWellPotentials, or a callable that returns them (called only if some guide rate is NaN).  In place; returns groups."""
+    if not any(np.isnan(g) for grp in groups for g in grp.guide):
+        return groups
+    pot = np.asarray(potentials() if callable(potentials) else potentials, float)
+    for grp in groups:
+        grp.guide = [max(abs(float(np.dot(grp.distr, pot[w]))), GUIDE_RATE_FLOOR) if np.isnan(g) else g for w, g in zip(grp.wells, grp.guide)]
+    return groups
+
+
 class Wells:
     """The parts of opm-core's `Wells` struct the model reads."""
 
@@ -95,6 +133,7 @@ class Wells:
         self.controls = []                                                     # all controls of each well (WellControls), control 0 first
         self.name = []
         self.efficiency = []                                                   # WEFAC: one factor in (0, 1] per well
+        self.groups = []                                                       # controlled groups (WellGroup), see add_group
 
     def add_well(self, name, wtype, depth_ref, cells, WI, comp_frac, control, allow_cf=True, limits=(), current=0, efficiency=1.0):
         """The well's controls are [control] + limits IN THAT ORDER; `current` is the index of its initial current control in that list
@@ -120,6 +159,30 @@ class Wells:
         self.ctrl_distr.append(np.asarray(cur[2], float))
         self.controls.append(ctrls)
         self.current0.append(int(current))
+        return self
+
+    def add_group(self, name, sign, target, distr, wells, guide=None, on_group=()):
+        """A controlled group over the wells `wells` (indices or names; every one added before): appends the GROUP SLOT -- a SURFACE_RATE
+        control with the group's distr -- as the LAST control of each member (lowest priority for updateWellControls) and records the
+        group.  guide: one guide rate per member, None / NaN = from the well potentials.  on_group: the members that START on their slot
+        (deck mode GRUP); the others start on their own mode with the slot as a constraint.  The slots' targets are written by
+        update_group_targets / the device kernel; until then they hold the whole group target with the group's sign."""
+        idx = [self.name.index(w) if isinstance(w, str) else int(w) for w in wells]
+        on = {self.name.index(w) if isinstance(w, str) else int(w) for w in on_group}
+        taken = {w for g in self.groups for w in g.wells}
+        for w in idx:
+            if w in taken:
+                raise ValueError("well %s is in two controlled groups" % self.name[w])
+            if self.type[w] != (PRODUCER if sign < 0 else INJECTOR):
+                raise ValueError("well %s: a %s group does not control it" % (self.name[w], "production" if sign < 0 else "injection"))
+        grp = WellGroup(name, sign, target, distr, idx, [float("nan")] * len(idx) if guide is None else guide)
+        for w in idx:
+            self.controls[w] = self.controls[w] + [_ctrl((SURFACE_RATE, grp.sign * grp.target, grp.distr))]
+            if w in on:
+                cur = self.controls[w][-1]
+                self.current0[w] = len(self.controls[w]) - 1
+                self.ctrl_type[w], self.ctrl_target[w], self.ctrl_distr[w] = cur[0], float(cur[1]), np.asarray(cur[2], float)
+        self.groups.append(grp)
         return self
 
     def control_arrays(self):
@@ -332,6 +395,34 @@ class StandardWellsHost:
                     break
         return switched
 
+    # ---- group rate control (the rule: include/opmgpu.h, opmgpu_set_well_groups) ----------------------------------------------
+    def update_group_targets(self, ws):
+        """the slot targets of every controlled group from (current, qs, guide, e, T): a pure function of the well state.  Called where
+        the reference calls WellCollection: before updateWellControls (applyGroupControls of setupGroupControl) and behind it
+        (updateWellTargets) at every assembly, and behind the control update of every pre-solve iteration.  Returns {well: target}."""
+        W = self.w
+        out = {}
+        groups = getattr(W, "groups", ())
+        if not groups:
+            return out
+        eff = W.efficiency_factors()
+        for g in groups:
+            slot = {w: len(W.controls[w]) - 1 for w in g.wells}
+            r = {w: eff[w] * float(np.dot(g.distr, ws.qs[w])) for w in g.wells}
+            indiv = [w for w in g.wells if int(ws.current[w]) != slot[w]]
+            gam = dict(zip(g.wells, g.guide))
+            Gamma = sum(gam[w] for w in g.wells if w not in indiv)
+            RI = sum(r[w] for w in indiv)
+            for w in g.wells:
+                if w in indiv:
+                    share, rem = gam[w] / (gam[w] + Gamma), g.target - g.sign * (RI - r[w])
+                else:
+                    share, rem = gam[w] / Gamma, g.target - g.sign * RI
+                out[w] = g.sign * share * max(0.0, rem) / eff[w]
+                c = W.controls[w][-1]
+                W.controls[w][-1] = (c[0], out[w]) + tuple(c[2:])
+        return out
+
     # ---- well equations ----------------------------------------------------------------------------------------------------
     def _well_system(self, w, pp, ws, const_cells=False):
         """computeWellFlux + addWellFluxEq + addWellControlEq of one well as dense AD: returns (cq_s[3] AD over [3n cell vars | qs(3) | bhp], E values (4), E Jacobian (4 x nv))"""
@@ -495,6 +586,7 @@ class StandardWellsHost:
                 Ev, D = systems[w]
                 self._apply_well_increment(w, np.linalg.solve(D, Ev), ws)
             self.update_well_controls(ws)
+            self.update_group_targets(ws)                     # updateWellTargets (:1090-1093)
             if it >= max_it:
                 break
         self.well_iterations = it
@@ -502,6 +594,7 @@ class StandardWellsHost:
             self.compute_connection_pressures(pp, ws, pvt_at)
         else:
             ws.assign(ws0)
+            self.update_group_targets(ws)                     # the slot targets follow the state they are a function of
         return converged, it
 
     def converged(self, B_avg):
@@ -568,7 +661,9 @@ class WellCoupledModel:
         m, wh, ws = self.m, self.wh, self.ws
         if wh.vfp_active:       # VFP tables need the connection densities for the hydrostatic correction (:771-776)
             wh.compute_connection_pressures(m.perfProps(self.nperf).reshape(self.nperf, 9, 4), ws, self._pvt_at())
+        wh.update_group_targets(ws)                                   # applyGroupControls (setupGroupControl, :779-783)
         wh.update_well_controls(ws)                                   # :785
+        wh.update_group_targets(ws)                                   # updateWellTargets (:791)
         m.assemble(initial)
         pp = m.perfProps(self.nperf).reshape(self.nperf, 9, 4)
         if initial:
@@ -579,10 +674,20 @@ class WellCoupledModel:
         m.addWellTerms(resid_delta, rc, blocks)
         m.addWellRhs(rhs_delta)
 
-    def computeWellPotentials(self):
-        """well potentials from the resident state (StandardWells::computeWellPotentials): [nw, 3]"""
+    def computeWellPotentials(self, from_well_state=False):
+        """well potentials from the resident state (StandardWells::computeWellPotentials): [nw, 3].  from_well_state: the connection
+        pressure differences are the well state's own, perfPress - bhp (StandardWells_impl.hpp:664-673) -- what the device well model's
+        computeWellPotentials uses, and what is there before the first assembly of a run has computed any."""
         pp = self.m.perfProps(self.nperf).reshape(self.nperf, 9, 4)
-        return self.wh.compute_well_potentials(pp, self.ws)
+        if not from_well_state:
+            return self.wh.compute_well_potentials(pp, self.ws)
+        W = self.wh.w
+        perf_well = np.repeat(np.arange(W.nw), np.diff(np.asarray(W.connpos)))
+        cdp, self.wh.cdp = self.wh.cdp, np.asarray(self.ws.perf_press) - np.asarray(self.ws.bhp)[perf_well]
+        try:
+            return self.wh.compute_well_potentials(pp, self.ws)
+        finally:
+            self.wh.cdp = cdp
 
     def nonlinearIteration(self, iteration, single_precision=None, nonlinear_solver=None):
         """BlackoilModelBase::nonlinearIteration (BlackoilModelBase_impl.hpp:239-326)"""
@@ -664,9 +769,32 @@ class DeviceWellModel:
         eff = wells.efficiency_factors() if hasattr(wells, "efficiency_factors") else np.ones(nw)
         if nw and np.any(eff != 1.0):       # WEFAC (rank-local in decomposed runs: the factors of this rank's wells)
             backend.setWellEfficiency(eff)
+        backend.n_well_groups = 0           # a new well list has no groups
         if tolerance_wells != backend.params.tolerance_wells or tolerance_well_control != backend.params.tolerance_well_control:
             pass        # the pre-solve on the device uses opmgpu_params.tolerance_wells / tolerance_well_control of the context
         self.push_well_state()
+        self.install_groups()               # groups with given guide rates; those left to the potentials wait for install_groups(potentials)
+
+    def install_groups(self, potentials=None):
+        """the well list's controlled groups -> the device (opmgpu_set_well_groups), behind the wells.  Guide rates left to the potentials
+        (NaN) need `potentials` ([nw, 3] or a callable, computeWellPotentials); without it such groups wait for a later call
+        (opmgpu.simulator makes it once per report step, when the state is resident)."""
+        groups = list(getattr(self.w, "groups", ()) or ())
+        self.groups_pending = False
+        if not groups or self.w.nw == 0:
+            return False
+        if any(np.isnan(g) for grp in groups for g in grp.guide):
+            if potentials is None:
+                self.groups_pending = True          # prepareStep / nonlinearIteration refuse to run until the groups are on the device
+                return False
+            resolve_guide_rates(groups, potentials)
+        self.m.setWellGroups(groups)
+        return True
+
+    def _require_groups(self):
+        if getattr(self, "groups_pending", False):
+            raise ValueError("the well list has controlled groups whose guide rates are left to the well potentials and they are not installed: "
+                             "call install_groups(potentials) first (without it every member's slot would hold the whole group target)")
 
     def shared_cells(self):
         """(cells perforated by more than one well, most wells in one cell) as the device counts them; (0, 0) without wells"""
@@ -698,6 +826,7 @@ class DeviceWellModel:
         return ws
 
     def prepareStep(self, dt, state=None):
+        self._require_groups()
         self.m.prepareStep(dt, state)
 
     def saveState(self):
@@ -732,6 +861,7 @@ class DeviceWellModel:
 
     def nonlinearIteration(self, iteration, single_precision=None, nonlinear_solver=None):
         m, ns = self.m, nonlinear_solver
+        self._require_groups()
         if getattr(m, "fused_iteration", False) and ns is not None and (self.tol_wells, self.tol_ctrl) == (m.params.tolerance_wells, m.params.tolerance_well_control):
             converged, lin = m._fused_iteration(iteration, single_precision, ns)          # the library checks the wells' convergence itself
             self.linear_iterations, self.current_relaxation = lin, m.current_relaxation
