@@ -694,6 +694,52 @@ int opmgpu_set_sat_oil_max(opmgpu_ctx* ctx, const double* so_max);
 int opmgpu_update_sat_oil_max(opmgpu_ctx* ctx);
 int opmgpu_get_sat_oil_max(opmgpu_ctx* ctx, double* so_max);
 
+/* DRSDT / DRVDT: limits on how fast the dissolved-gas ratio Rs and the vaporised-oil ratio Rv of a cell may RISE within a time step.
+ * The reference has neither keyword (VAPPARS is its only brake), so THE RULE IS OURS; it is stated here, restated independently under
+ * tests/ and pinned to no other simulator.
+ *
+ * Per context: a rate a_s >= 0 [1/s] for Rs with the flag free_only, and a rate a_v >= 0 [1/s] for Rv; each may be off.  With a limit on,
+ * the context carries two per-cell planes rs_cap[nc], rv_cap[nc]; +inf means no cap.
+ *
+ * Begin of a time step of length dt (opmgpu_begin_dissolution_step, after any state upload and again whenever a failed sub-step has
+ * restored the saved state and a shorter dt is tried): the host forms d_s = a_s * dt and d_v = a_v * dt once, in float64; one kernel
+ * writes per cell rs_cap[c] = rs[c] + d_s and rv_cap[c] = rv[c] + d_v from the RESIDENT state (one addition, one rounding, no FMA: a
+ * float64 restatement matches bit for bit).  With free_only, cells whose resident sg[c] == 0 get rs_cap = +inf (DRSDT's option FREE: the
+ * limit acts only where free gas is present); DRVDT has no option.  A rate that is off writes +inf everywhere.
+ *
+ * Evaluator (every kernel that evaluates a cell: assembly, perforation properties, fluid in place, the output record; three-phase models
+ * only).  After the VAPPARS factor, capped_s = rs_cap[c] < RsSat (strict: a tie is not capped).  When capped, the effective saturated
+ * ratio is the CONSTANT rs_cap[c], all derivatives zero; otherwise it is RsSat as before.  rs of the cell is the primary variable in an
+ * OIL_ONLY cell, else the effective saturated ratio.  The oil PVT takes its saturated branch iff !has_disgas || (free gas && !capped_s),
+ * otherwise the undersaturated table at (rs, p): a capped cell with free gas holds undersaturated oil at (p, rs_cap), whose derivatives
+ * with respect to the third variable vanish through the chain rule.  Rv is symmetric: capped_v = rv_cap[c] < RvSat, the gas PVT is
+ * saturated iff !has_vapoil || (free oil && !capped_v), otherwise the table at (p_g, rv).  opmgpu_simulator_data reports the effective
+ * values as RSSAT / RVSAT; PBUB / PDEW are unchanged.
+ *
+ * State update (opmgpu_update_state): the two saturated Rs values the phase switching compares against (at the old and at the new
+ * pressure) each become min(value, rs_cap[c]), the two of Rv min(value, rv_cap[c]).  Nothing else in the switching logic changes.
+ * That logic frees gas from an OIL_ONLY cell only when its new rs passes the saturated ratio by the factor 1 + sqrt(DBL_EPSILON) AND its
+ * old rs was within that factor of it, so by itself it lets rs stand above the cap for an iteration (and within the factor for good).
+ * Therefore a cell that the decision -- taken with the unlimited new value, as before -- leaves OIL_ONLY gets rs = min(new rs,
+ * rs_cap[c]), and one it leaves GAS_ONLY rv = min(new rv, rv_cap[c]): after every update every cell has rs <= rs_cap, rv <= rv_cap.  The
+ * next assembly evaluates the limited state, so a converged step is converged for it; where the cap does not bind nothing changes.
+ *
+ * Unchanged: the well-bore mixture of opmgpu_perf_pvt (average well-block pressures; the plain curves), opmgpu_compute_max_dp, the
+ * voidage coefficients, the bubble- / dew-point inversion.
+ *
+ * set_dissolution_limits: a negative rate means off; both off removes the planes, and every kernel is again the one a context that
+ * never had limits runs.  OPMGPU_EINVAL (with text, the previous limits stay in force) for: a context without a gas phase; a PVCDO context
+ * (and opmgpu_set_pvcdo refuses a context with limits); drsdt on without has_disgas; drvdt on without has_vapoil; a non-finite rate; a
+ * context with a communicator attached (opmgpu_comm_init* in turn refuses a context with limits: ghost cells' step-start Rs is not
+ * exchanged).  begin_dissolution_step: OPMGPU_EINVAL for dt <= 0 or not finite, without limits, or before a state has been set.
+ * get / set_dissolution_caps: the planes in the caller's cell order (restart; tests); either pointer may be NULL; get without limits
+ * gives +inf, set without limits or with a NaN is OPMGPU_EINVAL.  Limits and caps last through opmgpu_set_wells / opmgpu_set_device_wells (a re-plan),
+ * opmgpu_save_state / opmgpu_restore_state (which do not touch the caps) and a change of the solve precision. */
+int opmgpu_set_dissolution_limits(opmgpu_ctx* ctx, double drsdt /* [1/s], < 0 = off */, int drsdt_free_only, double drvdt /* [1/s], < 0 = off */);
+int opmgpu_begin_dissolution_step(opmgpu_ctx* ctx, double dt);
+int opmgpu_get_dissolution_caps(opmgpu_ctx* ctx, double* rs_cap /* [nc] or NULL */, double* rv_cap /* [nc] or NULL */);
+int opmgpu_set_dissolution_caps(opmgpu_ctx* ctx, const double* rs_cap /* [nc] or NULL */, const double* rv_cap /* [nc] or NULL */);
+
 /* Hysteresis history (EclHysteresisTwoPhaseLawParams::update, called once per report step by SimulatorBase_impl.hpp:190-191 ->
  * BlackoilPropsAdFromDeck::updateSatHyst): update = take the resident state's saturations into the history (krnSwMdc of both two-phase
  * systems = running minimum of 1 - So resp. 1 - Sg, the reference's "inconsistent" update) and recompute the Carlson shifts.

@@ -49,7 +49,8 @@ __global__ __launch_bounds__(kBlock) void k_cell_values(int nb, int nbp, DevTabl
         eps_load(eps, eps_u0, nbp, row, satnum[row], E);
         hyst_load<KM>(hy.imbnum, hy.hist, nbp, row, H);
         if (H.on) eps_load(hy.ieps, hy.iureg, nbp, row, H.ireg, EI);
-        eval_cell<false, KM>(D, E, (D.t.vap1 > 0.0 || D.t.vap2 > 0.0) ? somax[row] : 0.0, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], row, q, H, &EI);
+        eval_cell<false, KM>(D, E, (D.t.vap1 > 0.0 || D.t.vap2 > 0.0) ? somax[row] : 0.0, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], row, q, H, &EI, nullptr,
+                             rs_cap_of<KM>(somax, nbp, row), rv_cap_of<KM>(somax, nbp, row));
         // (no gas phase: the five water / oil planes only -- nobody reads the other five --, and 1 / b_g = 1 per cell)
         constexpr int NP = km_model(KM) == KM_OW ? 2 : 3;
         vals[long(VP_PW) * nbp + row] = q.pw.v; if constexpr (NP == 3) vals[long(VP_PG) * nbp + row] = q.pg.v;
@@ -81,7 +82,7 @@ __global__ __launch_bounds__(kBlock) void k_cell_values(int nb, int nbp, DevTabl
 // Shapes: MS the Jacobian's precision, LDS the tables staged in LDS (the blob fits), DUAL a float copy of a double Jacobian written in the
 // same pass, KM the model.  Compiled for 3 waves per SIMD in the default model's plain LDS shape and for 2 everywhere else
 // (asm_rows_waves; the two concluded experiments behind that are quoted at assemble_kernels).
-constexpr int asm_rows_waves(bool lds, bool dual, int km) { return km == KM_DEFAULT && lds && !dual ? 3 : 2; }
+constexpr int asm_rows_waves(bool lds, bool dual, int km) { return km == KM_DEFAULT && lds && !dual ? 3 : 2; }      // (the KM_DRDT shapes were never tuned: 2)
 template <class MS, bool LDS, bool DUAL, int KM>
 __global__ __launch_bounds__(kBlock, asm_rows_waves(LDS, DUAL, KM)) void k_assemble_rows(int xm, int nb, int nbp, DevTables DT, const int32_t* __restrict__ pvtnum, const int32_t* __restrict__ satnum,
                                                           const double* __restrict__ pv, const double* __restrict__ p, const double* __restrict__ sw,
@@ -117,7 +118,8 @@ __global__ __launch_bounds__(kBlock, asm_rows_waves(LDS, DUAL, KM)) void k_assem
         eps_load(eps, eps_u0, nbp, row, satnum[row], E);
         hyst_load<KM>(hy.imbnum, hy.hist, nbp, row, H);
         if (H.on) eps_load(hy.ieps, hy.iureg, nbp, row, H.ireg, EI);
-        eval_cell<false, KM>(DT, E, (DT.t.vap1 > 0.0 || DT.t.vap2 > 0.0) ? somax[row] : 0.0, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], row, q, H, &EI);
+        eval_cell<false, KM>(DT, E, (DT.t.vap1 > 0.0 || DT.t.vap2 > 0.0) ? somax[row] : 0.0, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], row, q, H, &EI, nullptr,
+                             rs_cap_of<KM>(somax, nbp, row), rv_cap_of<KM>(somax, nbp, row));
     }
     // NP == 2, a deck without a gas phase (KM_OW): only water and oil flow.  Neither the own nor the neighbour's p_g, gas density, gas
     // b * mobility, rs and rv planes are loaded (5 of the 10 dependent loads per connection), the gas equation is the identity row and
@@ -398,8 +400,11 @@ __global__ __launch_bounds__(kBlock) void k_conv_gather(int phase, int nv, int n
     }
 }
 
-// updateState (BlackoilModelBase_impl.hpp:1147-1389), one thread per cell
-template <bool LDS>
+// updateState (BlackoilModelBase_impl.hpp:1147-1389), one thread per cell.  DRDT (dissolution limits, opmgpu_set_dissolution_limits): each of
+// the four saturated ratios the switching logic compares against is the smaller of its present value and the cell's cap, which rides
+// behind so_max (rs_cap_of / rv_cap_of), and a cell the decision leaves OIL_ONLY (GAS_ONLY) takes min(new rs, rs_cap) (min(new rv, rv_cap)):
+// the decision itself is taken with the unlimited value.  Nothing else changes.
+template <bool LDS, bool DRDT>
 __global__ __launch_bounds__(kBlock) void k_update_state(int nb, int nbp, DevTables D, const int32_t* __restrict__ pvtnum,
                                                          const int32_t* __restrict__ satnum, const double* __restrict__ dx, double relax,
                                                          double dp_max_rel, double ds_max, double dr_max_rel,
@@ -447,11 +452,15 @@ __global__ __launch_bounds__(kBlock) void k_update_state(int nb, int nbp, DevTab
         double v0, v1;
         vap_factor(T.vap2, so_old, somax[c], v0, df);
         vap_factor(T.vap2, o_, somax[c], v1, df);
-        const double rsSat0 = v0 * rs_sat_d(D, preg, p_old), rsSat = v1 * rs_sat_d(D, preg, pn);
+        double rsSat0 = v0 * rs_sat_d(D, preg, p_old), rsSat = v1 * rs_sat_d(D, preg, pn);
+        if constexpr (DRDT) { const double cap = rs_cap_of<KM_DRDT>(somax, nbp, c); rsSat0 = fmin(rsSat0, cap); rsSat = fmin(rsSat, cap); }
         const bool hasGas = (g_ > 0 && !isRs);
         const bool gasVaporized = ((rsn > rsSat * (1 + eps) && isRs) && (rs_old > rsSat0 * (1 - eps)));
         if (watOnly || hasGas || gasVaporized) { rsn = rsSat; if (watOnly) { o_ = 0; g_ = 0; rsn = 0; } }
-        else hn = OPMGPU_HC_OIL_ONLY;
+        else {
+            hn = OPMGPU_HC_OIL_ONLY;
+            if constexpr (DRDT) rsn = fmin(rsn, rs_cap_of<KM_DRDT>(somax, nbp, c));
+        }
     }
     if (T.has_vapoil) {
         const int ga = T.sgof_ptr[sreg], ng = T.sgof_ptr[sreg + 1] - ga;
@@ -462,11 +471,15 @@ __global__ __launch_bounds__(kBlock) void k_update_state(int nb, int nbp, DevTab
         double v0, v1;
         vap_factor(T.vap1, so_old, somax[c], v0, df);
         vap_factor(T.vap1, o_, somax[c], v1, df);
-        const double rvSat0 = v0 * rv_sat_d(D, preg, pg_old), rvSat = v1 * rv_sat_d(D, preg, pg_new);
+        double rvSat0 = v0 * rv_sat_d(D, preg, pg_old), rvSat = v1 * rv_sat_d(D, preg, pg_new);
+        if constexpr (DRDT) { const double cap = rv_cap_of<KM_DRDT>(somax, nbp, c); rvSat0 = fmin(rvSat0, cap); rvSat = fmin(rvSat, cap); }
         const bool hasOil = (o_ > 0 && !isRv);
         const bool oilCondensed = ((rvn > rvSat * (1 + eps) && isRv) && (rv_old > rvSat0 * (1 - eps)));
         if (watOnly || hasOil || oilCondensed) { rvn = rvSat; if (watOnly) { o_ = 0; g_ = 0; rvn = 0; } }
-        else hn = OPMGPU_HC_GAS_ONLY;
+        else {
+            hn = OPMGPU_HC_GAS_ONLY;
+            if constexpr (DRDT) rvn = fmin(rvn, rv_cap_of<KM_DRDT>(somax, nbp, c));
+        }
     }
     p[c] = pn; sw[c] = w_; so[c] = o_; sg[c] = g_;
     if (T.has_disgas) rs[c] = rsn;
@@ -888,6 +901,10 @@ void BlackoilDevice::get_state(double* p, double* sat, double* rs, double* rv, i
 template <class F> static auto kernel_by_shape(bool lds, int km, F&& pick)
 {
     auto by_model = [&](auto L) {
+        // dissolution limits (KM_DRDT): the three three-phase models with the tabulated oil, nothing else (set_dissolution_limits refuses the rest)
+        if (km_drdt(km))
+            return km_model(km) == KM_STONE ? pick(L, std::integral_constant<int, KM_STONE | KM_DRDT>{})
+                 : km_model(km) == KM_KILLOUGH ? pick(L, std::integral_constant<int, KM_KILLOUGH | KM_DRDT>{}) : pick(L, std::integral_constant<int, KM_DEFAULT | KM_DRDT>{});
         auto by_oil = [&](auto K) {       // the tabulated oil, or the analytic one of opmgpu_set_pvcdo
             return km_pvcdo(km) ? pick(L, std::integral_constant<int, decltype(K)::value | KM_PVCDO>{}) : pick(L, K);
         };
@@ -1254,7 +1271,8 @@ void BlackoilDevice::update_state(const double* dx_host, double relax)
     if (dx_host) { ls.vec_from_host<double>(dx_host, VEC_EQUATION_MAJOR, d_dx.p); OPMGPU_HIP(hipStreamSynchronize(stream)); has_dx = true; }   // caller's buffer: done with it on return
     KtScope kts(ls.kt, KT_UPDATE_STATE);
     if (device_wells) wells_update(relax, dx_host != nullptr);          // updateWellState from the recovered (and possibly relaxed) well increment
-    auto kern = tab_lds_words() > 0 ? k_update_state<true> : k_update_state<false>;
+    auto kern = drdt_on() ? (tab_lds_words() > 0 ? k_update_state<true, true> : k_update_state<false, true>)
+                          : (tab_lds_words() > 0 ? k_update_state<true, false> : k_update_state<false, false>);
     hipLaunchKernelGGL(kern, dim3(grid_for(nc)), dim3(kBlock), tab_lds_bytes(), stream, nc, P.nbp, dto_, d_pvtnum.p, d_satnum.p, d_dx.p, relax,
                        prm.dp_max_rel, prm.ds_max, prm.dr_max_rel, d_p.p, d_sw.p, d_so.p, d_sg.p, d_rs.p, d_rv.p, d_hc.p, eps_planes(), d_eps_u0.p, d_somax.p,
                        (const double*)d_tab.p, tab_lds_words());
@@ -1285,6 +1303,88 @@ void BlackoilDevice::get_sat_oil_max(double* v)
     OPMGPU_HIP(hipMemcpyAsync(h.data(), d_somax.p, size_t(P.nbp) * sizeof(double), hipMemcpyDeviceToHost, stream));
     OPMGPU_HIP(hipStreamSynchronize(stream));
     for (int r = 0; r < nc; ++r) v[P.nat[r]] = h[r];
+}
+
+// ---- DRSDT / DRVDT: the dissolution limits (the rule is stated in include/opmgpu.h at opmgpu_set_dissolution_limits) -----------------------
+// The caps of a time step from the resident state, one thread per cell: rs_cap = rs + d_s (+inf where free_only and the cell holds no
+// free gas, or the rate is off), rv_cap = rv + d_v.  d_s = a_s dt and d_v = a_v dt are formed once on the host; the sum is ONE rounding
+// (an addition alone: nothing to contract into an FMA), so a float64 restatement on the host matches bit for bit.
+__global__ __launch_bounds__(kBlock) void k_dissolution_caps(int nb, const double* __restrict__ rs, const double* __restrict__ rv, const double* __restrict__ sg,
+                                                            int on_s, int free_only, double d_s, int on_v, double d_v,
+                                                            double* __restrict__ rs_cap, double* __restrict__ rv_cap)
+{
+    const int c = blockIdx.x * kBlock + threadIdx.x;
+    if (c >= nb) return;
+    const double inf = __builtin_inf();
+    rs_cap[c] = (on_s && !(free_only && sg[c] == 0.0)) ? rs[c] + d_s : inf;
+    rv_cap[c] = on_v ? rv[c] + d_v : inf;
+}
+// d_somax with (so_max | rs_cap | rv_cap) or without the planes of the caps, so_max kept; new caps are +inf (padding rows included)
+void BlackoilDevice::resize_somax(bool with_caps)
+{
+    const size_t nbp = size_t(ls.plan.nbp);
+    if (d_somax.n == (with_caps ? 3 : 1) * nbp) return;
+    OPMGPU_HIP(hipStreamSynchronize(stream));        // no kernel in flight reads the array that is replaced
+    std::vector<double> h(3 * nbp, std::numeric_limits<double>::infinity());
+    d_somax.download(h.data(), nbp, stream);
+    OPMGPU_HIP(hipStreamSynchronize(stream));
+    d_somax.alloc((with_caps ? 3 : 1) * nbp);
+    d_somax.upload(h.data(), d_somax.n, stream);
+    OPMGPU_HIP(hipStreamSynchronize(stream));
+}
+void BlackoilDevice::set_dissolution_limits(double a_s, int free_only, double a_v)
+{
+    const char* who = "opmgpu_set_dissolution_limits: ";
+    if (std::isnan(a_s) || std::isinf(a_s)) throw HipError(OPMGPU_EINVAL, std::string(who) + "drsdt is not finite");
+    if (std::isnan(a_v) || std::isinf(a_v)) throw HipError(OPMGPU_EINVAL, std::string(who) + "drvdt is not finite");
+    const bool on_s = a_s >= 0.0, on_v = a_v >= 0.0;
+    if (on_s || on_v) {
+        if (oil_water()) throw HipError(OPMGPU_EINVAL, std::string(who) + "the context has no gas phase (OPMGPU_PHASES_OIL_WATER)");
+        if (dtp_.x.oil_pvcdo) throw HipError(OPMGPU_EINVAL, std::string(who) + "the context has the analytic dead oil (opmgpu_set_pvcdo); dissolution limits are not supported with it");
+        if (on_s && !dto_.t.has_disgas) throw HipError(OPMGPU_EINVAL, std::string(who) + "drsdt needs dissolved gas (has_disgas)");
+        if (on_v && !dto_.t.has_vapoil) throw HipError(OPMGPU_EINVAL, std::string(who) + "drvdt needs vaporised oil (has_vapoil)");
+        if (ls.comm) throw HipError(OPMGPU_EINVAL, std::string(who) + "a communicator is attached; a decomposed run does not support dissolution limits");
+    }
+    drsdt = on_s ? a_s : -1.0; drsdt_free_only = on_s && free_only != 0; drvdt = on_v ? a_v : -1.0;
+    resize_somax(drdt_on());
+}
+void BlackoilDevice::begin_dissolution_step(double dt)
+{
+    const char* who = "opmgpu_begin_dissolution_step: ";
+    if (!drdt_on()) throw HipError(OPMGPU_EINVAL, std::string(who) + "no dissolution limit is set (opmgpu_set_dissolution_limits)");
+    if (!(dt > 0.0) || std::isinf(dt)) throw HipError(OPMGPU_EINVAL, std::string(who) + "dt is not positive and finite");
+    if (!has_state) throw HipError(OPMGPU_EINVAL, std::string(who) + "no state is resident (opmgpu_set_state)");
+    const size_t nbp = size_t(ls.plan.nbp);
+    const double d_s = drsdt >= 0.0 ? drsdt * dt : 0.0, d_v = drvdt >= 0.0 ? drvdt * dt : 0.0;
+    hipLaunchKernelGGL(k_dissolution_caps, dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, (const double*)d_rs.p, (const double*)d_rv.p, (const double*)d_sg.p,
+                       int(drsdt >= 0.0), int(drsdt_free_only), d_s, int(drvdt >= 0.0), d_v, d_somax.p + nbp, d_somax.p + 2 * nbp);
+}
+// the caps in the caller's cell order (restart, tests); either pointer may be null.  Without limits there are no caps: +inf, and nothing to set
+void BlackoilDevice::get_dissolution_caps(double* rs_cap, double* rv_cap)
+{
+    const Plan& P = ls.plan;
+    const size_t nbp = size_t(P.nbp);
+    std::vector<double> h(2 * nbp, std::numeric_limits<double>::infinity());
+    if (drdt_on()) { OPMGPU_HIP(hipMemcpyAsync(h.data(), d_somax.p + nbp, 2 * nbp * sizeof(double), hipMemcpyDeviceToHost, stream)); OPMGPU_HIP(hipStreamSynchronize(stream)); }
+    for (int r = 0; r < nc; ++r) { if (rs_cap) rs_cap[P.nat[r]] = h[r]; if (rv_cap) rv_cap[P.nat[r]] = h[nbp + r]; }
+}
+void BlackoilDevice::set_dissolution_caps(const double* rs_cap, const double* rv_cap)
+{
+    if (!drdt_on()) throw HipError(OPMGPU_EINVAL, "opmgpu_set_dissolution_caps: no dissolution limit is set (opmgpu_set_dissolution_limits)");
+    const Plan& P = ls.plan;
+    const size_t nbp = size_t(P.nbp);
+    const double* src[2] = { rs_cap, rv_cap };
+    for (int k = 0; k < 2; ++k) {
+        if (!src[k]) continue;
+        for (int c = 0; c < nc; ++c) if (std::isnan(src[k][c])) throw HipError(OPMGPU_EINVAL, "opmgpu_set_dissolution_caps: a cap is NaN");
+    }
+    std::vector<double> h(nbp, std::numeric_limits<double>::infinity());
+    for (int k = 0; k < 2; ++k) {
+        if (!src[k]) continue;
+        for (int r = 0; r < nc; ++r) h[r] = src[k][P.nat[r]];
+        OPMGPU_HIP(hipMemcpyAsync(d_somax.p + (1 + k) * nbp, h.data(), nbp * sizeof(double), hipMemcpyHostToDevice, stream));
+        OPMGPU_HIP(hipStreamSynchronize(stream));
+    }
 }
 
 void BlackoilDevice::stabilize_update(int relax_type, double omega)

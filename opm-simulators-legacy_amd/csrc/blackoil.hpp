@@ -40,9 +40,13 @@ enum { VP_PW = 0, VP_PG = 1, VP_RHO = 2 /* + phase */, VP_U = 5 /* + phase */, V
 // gives the saturation-function model alone).  A template parameter like the model and for the same reason.
 // KM_KILLOUGH: the default three-phase law whose non-wetting scanning curves are Killough's (opmgpu_set_hysteresis_model) -- a model of its
 // own and not a branch, so that the kernels of every other context are the ones they were: only it loads the m / R planes of the history.
-enum { KM_DEFAULT = 0, KM_STONE = 1, KM_OW = 2, KM_KILLOUGH = 3, KM_PVCDO = 4 };
+// KM_DRDT, or-ed to KM_DEFAULT, KM_STONE or KM_KILLOUGH (never with KM_OW or KM_PVCDO: refused): the cell's saturated rs / rv are capped by the
+// dissolution limits of opmgpu_set_dissolution_limits (DRSDT / DRVDT; km_drdt) -- a template parameter for the same reason: a context
+// without limits runs exactly the instantiations it ran before the limits existed.
+enum { KM_DEFAULT = 0, KM_STONE = 1, KM_OW = 2, KM_KILLOUGH = 3, KM_PVCDO = 4, KM_DRDT = 8 };
 constexpr int km_model(int km) { return km & 3; }
 constexpr bool km_pvcdo(int km) { return (km & KM_PVCDO) != 0; }
+constexpr bool km_drdt(int km) { return (km & KM_DRDT) != 0; }
 
 constexpr int kRedPart = 32;        // d_red: [0, 32) results, per-workgroup partials behind them
 
@@ -89,6 +93,12 @@ public:
     void update_sat_oil_max();
     void set_sat_oil_max(const double* v);
     void get_sat_oil_max(double* v);
+    // DRSDT / DRVDT (the rule: opmgpu_set_dissolution_limits in include/opmgpu.h); the first two throw HipError(OPMGPU_EINVAL) with the reason
+    void set_dissolution_limits(double drsdt, int free_only, double drvdt);
+    void begin_dissolution_step(double dt);
+    void get_dissolution_caps(double* rs_cap, double* rv_cap);
+    void set_dissolution_caps(const double* rs_cap, const double* rv_cap);
+    bool has_dissolution_limits() const { return drdt_on(); }
     int update_hysteresis();
     int set_hysteresis(const double* mdc_ow, const double* mdc_go);
     int get_hysteresis(double* mdc_ow, double* mdc_go, double* d_ow, double* d_go);
@@ -182,6 +192,13 @@ private:
     std::vector<double> h_eps[8], h_unscaled, h_eps_v[5], h_ieps[8];
     std::vector<int32_t> h_imbnum;
     DevArray<double> d_eps, d_eps_u0, d_somax, d_saved, d_ieps, d_ieps_u0, d_hist;     // d_hist: the HP_COUNT planes of the history (fluid_eval.hpp)
+    // DRSDT / DRVDT: the rates [1/s] (negative = off) and DRSDT's option.  With a limit on, d_somax holds three planes of stride nbp,
+    // so_max | rs_cap | rv_cap (the caps ride where so_max rides: no kernel has an argument more); without, so_max alone.  Like so_max
+    // the caps are no part of the state that save / restore copy, and a re-plan carries them over.
+    double drsdt = -1.0, drvdt = -1.0;
+    bool drsdt_free_only = false;
+    bool drdt_on() const { return drsdt >= 0.0 || drvdt >= 0.0; }
+    void resize_somax(bool with_caps);
     int hyst_model = OPMGPU_HYST_CARLSON;    // opmgpu_set_hysteresis_model: no part of the state, of the plan or of the tables
     double killough_a = 0.1;
     void launch_hyst_update(int force);
@@ -204,7 +221,8 @@ private:
     int tab_words = 0;
     static constexpr int kTabLdsMaxBytes = 24 * 1024;     // 6 workgroups x 24 KiB fit the 160 KiB LDS of a CU: no occupancy lost
     // chooses the kernels' KM instantiations (eval_cell)
-    int kmodel() const { return (oil_water() ? KM_OW : (dto_.t.threephase_model != OPMGPU_KRO_DEFAULT ? KM_STONE : (use_hyst && hyst_model == OPMGPU_HYST_KILLOUGH ? KM_KILLOUGH : KM_DEFAULT))) | (dtp_.x.oil_pvcdo ? KM_PVCDO : 0); }
+    int kmodel() const { return kmodel_plain() | (drdt_on() ? KM_DRDT : 0); }
+    int kmodel_plain() const { return (oil_water() ? KM_OW : (dto_.t.threephase_model != OPMGPU_KRO_DEFAULT ? KM_STONE : (use_hyst && hyst_model == OPMGPU_HYST_KILLOUGH ? KM_KILLOUGH : KM_DEFAULT))) | (dtp_.x.oil_pvcdo ? KM_PVCDO : 0); }
     bool oil_water() const { return dto_.t.active_phases == OPMGPU_PHASES_OIL_WATER; }
     int tab_lds_words() const { return tab_words * 8 <= kTabLdsMaxBytes ? tab_words : 0; }
     size_t tab_lds_bytes() const { return size_t(tab_lds_words()) * 8; }

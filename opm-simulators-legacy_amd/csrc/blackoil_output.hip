@@ -415,7 +415,7 @@ void BlackoilDevice::compute_max_dp(const int32_t* eqlnum, int nregions, int n_f
         DevArray<double> d_sres, d_out;
         d_conn.upload(hc, stream); d_eql.upload(he, stream); d_sres.upload(sres, stream);
         d_out.alloc(size_t(nconn));
-        hipLaunchKernelGGL(OPMGPU_BY_MODEL(k_max_dp), dim3(grid_for(nconn)), dim3(kBlock), 0, stream, nconn, n_face_conn, dtp_, d_conn.p, d_eql.p,
+        hipLaunchKernelGGL(OPMGPU_BY_MODEL_PLAIN(k_max_dp), dim3(grid_for(nconn)), dim3(kBlock), 0, stream, nconn, n_face_conn, dtp_, d_conn.p, d_eql.p,
                            cell_planes(), d_sres.p, (const double*)d_zc.p, gravity, d_out.p);
         OPMGPU_HIP(hipGetLastError());
         d_out.download(dp.data(), size_t(nconn), stream);

@@ -154,6 +154,7 @@ void BlackoilDevice::set_pvcdo(const double* pvcdo)
     const int np = dto_.t.n_pvt_regions;
     std::vector<double> blob = h_tab;
     if (pvcdo) {
+        if (drdt_on()) throw HipError(OPMGPU_EINVAL, "setPvcdo: the context has dissolution limits (opmgpu_set_dissolution_limits); the PVCDO oil is not supported with them");
         if (dto_.t.has_disgas) throw HipError(OPMGPU_EINVAL, "setPvcdo: the context has dissolved gas (has_disgas); the PVCDO oil is dead");
         for (int r = 0; r < np; ++r) {
             const double* o = pvcdo + 5 * size_t(r);
@@ -184,6 +185,8 @@ void BlackoilDevice::rebuild_structure()
     if (use_hyst && d_hist.p && has_state) { hist.resize(4 * size_t(nc)); get_hysteresis(hist.data(), hist.data() + nc, hist.data() + 2 * size_t(nc), hist.data() + 3 * size_t(nc)); }
     const bool hyst_carried = !hist.empty();
     if (d_somax.p) { smax.resize(nc); get_sat_oil_max(smax.data()); }
+    std::vector<double> caps;       // (the dissolution caps too)
+    if (d_somax.p && drdt_on()) { caps.resize(2 * size_t(nc)); get_dissolution_caps(caps.data(), caps.data() + nc); }
     if (has_state) { sp.resize(nc); ssat.resize(3 * size_t(nc)); srs.resize(nc); srv.resize(nc); shc.resize(nc); get_state(sp.data(), ssat.data(), srs.data(), srv.data(), shc.data()); }
     const int st2 = ls.set_pattern(nc, rowptr.data(), col.data(), prm.ilu_ordering);
     if (st2 != OPMGPU_OK) throw HipError(st2, "sparsity plan failed");
@@ -260,7 +263,9 @@ void BlackoilDevice::rebuild_structure()
     has_dx = false; has_saved = false;
     d_somax.alloc(nbp); d_somax.zero(stream);
     OPMGPU_HIP(hipStreamSynchronize(stream));
+    resize_somax(drdt_on());
     if (!smax.empty()) set_sat_oil_max(smax.data());
+    if (!caps.empty()) set_dissolution_caps(caps.data(), caps.data() + nc);
     wells_rebind();
     if (has_state) set_state(sp.data(), ssat.data(), srs.data(), srv.data(), shc.data());
     // Killough: the scanning parameters follow from the two history planes in the new numbering (the force path of k_hyst_update)

@@ -689,6 +689,29 @@ int opmgpu_get_sat_oil_max(opmgpu_ctx* c, double* so_max)
     return guarded(c, [&]() { c->model->get_sat_oil_max(so_max); return OPMGPU_OK; });
 }
 
+// DRSDT / DRVDT (the rule is stated in opmgpu.h).  The limits change what the next assembly evaluates: a matrix loaded or factored before
+// the call is that of the old ones.
+int opmgpu_set_dissolution_limits(opmgpu_ctx* c, double drsdt, int drsdt_free_only, double drvdt)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { c->model->set_dissolution_limits(drsdt, drsdt_free_only, drvdt); c->matrix_loaded = false; return int(OPMGPU_OK); });
+}
+int opmgpu_begin_dissolution_step(opmgpu_ctx* c, double dt)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { c->model->begin_dissolution_step(dt); c->matrix_loaded = false; return int(OPMGPU_OK); });
+}
+int opmgpu_get_dissolution_caps(opmgpu_ctx* c, double* rs_cap, double* rv_cap)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { c->model->get_dissolution_caps(rs_cap, rv_cap); return int(OPMGPU_OK); });
+}
+int opmgpu_set_dissolution_caps(opmgpu_ctx* c, const double* rs_cap, const double* rv_cap)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { c->model->set_dissolution_caps(rs_cap, rv_cap); c->matrix_loaded = false; return int(OPMGPU_OK); });
+}
+
 int opmgpu_update_hysteresis(opmgpu_ctx* c)
 {
     if (!c || !c->model) return OPMGPU_EINVAL;
@@ -939,6 +962,9 @@ static int comm_init_common(opmgpu_ctx* c, int rank, int nranks, const uint8_t* 
         // a group's wells may sit on several ranks and the re-share is rank-local: refused here too, so that the context stays single-domain
         if (c->model->well_group_count() > 0)
             return fail(c, OPMGPU_EINVAL, "multi-GPU: controlled well groups are set; group control in a decomposed run (a communicator is attached) is not supported");
+        // ghost cells' step-start rs / rv are not exchanged: the caps of a decomposed run are out of scope, so the context stays single-domain
+        if (c->model->has_dissolution_limits())
+            return fail(c, OPMGPU_EINVAL, "multi-GPU: dissolution limits (DRSDT / DRVDT) are set; a decomposed run (a communicator is attached) does not support them");
         std::unique_ptr<RcclComm> cm(new RcclComm());
         static const int32_t zero2[2] = { 0, 0 };
         const int st = cm->init(rank, nranks, id, transport, n_owned, c->model->nc, n_neigh, neigh_rank, n_neigh ? send_ptr : zero2, send_cells,

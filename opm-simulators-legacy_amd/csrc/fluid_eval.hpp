@@ -12,7 +12,9 @@ namespace opmgpu {
 
 // the instantiation of a cell-evaluating kernel template <int KM> for this deck's model (inside a BlackoilDevice method)
 #define OPMGPU_BY_MODEL_(kernel, oil) (km_model(kmodel()) == KM_OW ? kernel<KM_OW | oil> : (km_model(kmodel()) == KM_STONE ? kernel<KM_STONE | oil> : (km_model(kmodel()) == KM_KILLOUGH ? kernel<KM_KILLOUGH | oil> : kernel<KM_DEFAULT | oil>)))
-#define OPMGPU_BY_MODEL(kernel) (km_pvcdo(kmodel()) ? OPMGPU_BY_MODEL_(kernel, KM_PVCDO) : OPMGPU_BY_MODEL_(kernel, 0))
+#define OPMGPU_BY_MODEL_PLAIN(kernel) (km_pvcdo(kmodel()) ? OPMGPU_BY_MODEL_(kernel, KM_PVCDO) : OPMGPU_BY_MODEL_(kernel, 0))      // for a kernel that evaluates no cell: KM_DRDT ignored
+// with dissolution limits (KM_DRDT: never KM_OW, never KM_PVCDO) the three instantiations that carry the caps, else the ones above
+#define OPMGPU_BY_MODEL(kernel) (km_drdt(kmodel()) ? (km_model(kmodel()) == KM_STONE ? kernel<KM_STONE | KM_DRDT> : (km_model(kmodel()) == KM_KILLOUGH ? kernel<KM_KILLOUGH | KM_DRDT> : kernel<KM_DEFAULT | KM_DRDT>)) : OPMGPU_BY_MODEL_PLAIN(kernel))
 
 struct V4 { double v, p, w, x; };      // value, d/dP, d/dSw, d/dXvar
 
@@ -93,10 +95,22 @@ struct CellPlanes {
     const int32_t *pvtnum, *satnum;
     const double *p, *sw, *so, *sg, *rs, *rv;
     const int8_t* hc;
-    const double *eps, *eps_u0, *somax;
+    const double *eps, *eps_u0, *somax;     // somax: with dissolution limits so_max | rs_cap | rv_cap (rs_cap_of / rv_cap_of)
     long nbp;
     HystArgs hy;
 };
+// DRSDT / DRVDT (KM_DRDT): the caps of a row ride behind so_max, as planes 1 and 2 of the array whose plane 0 is so_max (stride nbp; the
+// array has those planes only in a context with limits, and only a KM_DRDT instantiation reads them).  +inf without.
+template <int KM> __device__ __forceinline__ double rs_cap_of(const double* __restrict__ somax, long nbp, int row)
+{
+    if constexpr (km_drdt(KM)) return somax[nbp + row];
+    else return __builtin_inf();
+}
+template <int KM> __device__ __forceinline__ double rv_cap_of(const double* __restrict__ somax, long nbp, int row)
+{
+    if constexpr (km_drdt(KM)) return somax[2 * nbp + row];
+    else return __builtin_inf();
+}
 template <int KM = KM_DEFAULT>
 __device__ __forceinline__ void hyst_load(const int32_t* __restrict__ imbnum, const double* __restrict__ hist, long nbp, int row, HystD& h)
 {
@@ -430,10 +444,15 @@ struct CellOutput { double mu[3], kr[3], rsSat, rvSat; };
 // branch on the fields, chosen on the host for every kernel that evaluates cells: with the branch k_assemble_rows' default instantiation went from 7 to 20 spilled VGPRs.
 // KM_PVCDO or-ed to it: the oil is the analytic dead oil (oil_pvcdo_pair) instead of the tabulated one -- a template parameter too: as a branch
 // on DT.x.oil_pvcdo it moved the spills and the scratch of ten k_assemble_rows shapes a deck without it runs.
+// KM_DRDT or-ed to a three-phase model: DRSDT / DRVDT (the rule is stated in include/opmgpu.h at opmgpu_set_dissolution_limits).  After the
+// VAPPARS factor a saturated ratio above the cell's cap (strictly: a tie is not capped) is replaced by the cap, a constant; a capped cell
+// with the other phase free then holds UNDERSATURATED oil (gas) at (p, cap), so its PVT takes the 2-D table.  Without the flag rs_cap /
+// rv_cap are not read and every expression below folds to what it was.
 template <bool OUTPUT, bool PVCDO> __device__ void eval_cell_ow(const DevTables& DT, const EpsD& E, int preg, int sreg, double p, double sw_, CellEval& q, CellOutput* out);
 template <bool OUTPUT = false, int KM = KM_DEFAULT>
 __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int preg, int sreg, double p, double sw_, double sg_, double rs_, double rv_, int hc,
-                          int row, CellEval& q, const HystD& H = HystD{ false, 0, 2.0, 2.0, 0.0, 0.0, 1.0, 1.0, 1.0, 1.0 }, const EpsD* EI = nullptr, CellOutput* out = nullptr)
+                          int row, CellEval& q, const HystD& H = HystD{ false, 0, 2.0, 2.0, 0.0, 0.0, 1.0, 1.0, 1.0, 1.0 }, const EpsD* EI = nullptr, CellOutput* out = nullptr,
+                          double rs_cap = __builtin_inf(), double rv_cap = __builtin_inf())
 {
     if constexpr (km_model(KM) == KM_OW) { eval_cell_ow<OUTPUT, km_pvcdo(KM)>(DT, E, preg, sreg, p, sw_, q, out); return; }
     const opmgpu_tables& T = DT.t; const TabX& X = DT.x;
@@ -532,18 +551,21 @@ __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int
     V4 rsSat = mk(0, 0, 0, 0), rvSat = mk(0, 0, 0, 0);
     if (T.has_disgas) { lin_at(T.oil_psat + oa, T.oil_rs + oa, X.oil_drs + oa, ip, p, f, df); rsSat = mk(f, df, 0, 0); }
     if (T.vap2 > 0.0) { vap_factor(T.vap2, so.v, so_max, f, df); rsSat = vmul(vchain(f, df, so), rsSat); }
+    bool capped_s = false, capped_v = false;
+    if constexpr (km_drdt(KM)) { capped_s = rs_cap < rsSat.v; if (capped_s) rsSat = mk(rs_cap, 0, 0, 0); }
     q.rs = (T.has_disgas && isRs) ? Xv : rsSat;
     if (T.has_vapoil) { lin_at(T.gas_pg + gna, T.gas_rvsat + gna, X.gas_drvsat + gna, ipg, q.pg.v, f, df); rvSat = vchain(f, df, q.pg); }
     if (T.vap1 > 0.0) { vap_factor(T.vap1, so.v, so_max, f, df); rvSat = vmul(vchain(f, df, so), rvSat); }
+    if constexpr (km_drdt(KM)) { capped_v = rv_cap < rvSat.v; if (capped_v) rvSat = mk(rv_cap, 0, 0, 0); }
     q.rv = (T.has_vapoil && isRv) ? Xv : rvSat;
     // water PVT (ConstantCompressibilityWaterPvt)
     V4 mu[3];
     water_pvt(T.pvtw + 5 * preg, q.pw, q.b[0], mu[0]);
-    // oil PVT (LiveOilPvt; saturated branch when free gas is present or no DISGAS)
+    // oil PVT (LiveOilPvt; saturated branch when free gas is present -- and the cap does not hold rs below the curve -- or no DISGAS)
     {
         double ib, dibp, dibr = 0.0, ibm, dibmp, dibmr = 0.0;
         if constexpr (km_pvcdo(KM)) oil_pvcdo_pair(X.oil_pvcdo + 5 * preg, p, ib, dibp, ibm, dibmp);
-        else if (freeGas || !T.has_disgas) oil_sat_pair(T, X, oa, ip, p, ib, dibp, ibm, dibmp);
+        else if ((freeGas && !capped_s) || !T.has_disgas) oil_sat_pair(T, X, oa, ip, p, ib, dibp, ibm, dibmp);
         else {
             const int ir = pvt_seg(T.oil_rs + oa, on, q.rs.v);
             pvt2_pair(T.oil_rs + oa, ir, T.oil_col_ptr + oa, T.oil_col_p, T.oil_col_invb, X.oil_col_dinvb, T.oil_col_invbmu, X.oil_col_dinvbmu,
@@ -556,7 +578,7 @@ __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int
     // gas PVT (WetGasPvt; saturated branch when free oil is present or no VAPOIL)
     {
         double ib, dibp, dibr = 0.0, ibm, dibmp, dibmr = 0.0;
-        if (freeOil || !T.has_vapoil) {
+        if ((freeOil && !capped_v) || !T.has_vapoil) {
             lin_at(T.gas_pg + gna, T.gas_invb_sat + gna, X.gas_dinvb_sat + gna, ipg, q.pg.v, ib, dibp);
             lin_at(T.gas_pg + gna, T.gas_invbmu_sat + gna, X.gas_dinvbmu_sat + gna, ipg, q.pg.v, ibm, dibmp);
         } else {
@@ -683,7 +705,8 @@ __device__ __forceinline__ void eval_row(const DevTables& DT, int row, const Cel
     eps_load(C.eps, C.eps_u0, C.nbp, row, C.satnum[row], E);
     hyst_load<KM>(C.hy.imbnum, C.hy.hist, C.nbp, row, H);
     if (H.on) eps_load(C.hy.ieps, C.hy.iureg, C.nbp, row, H.ireg, EI);
-    eval_cell<OUTPUT, KM>(DT, E, C.somax[row], C.pvtnum[row], C.satnum[row], C.p[row], C.sw[row], C.sg[row], C.rs[row], C.rv[row], C.hc[row], row, q, H, &EI, out);
+    eval_cell<OUTPUT, KM>(DT, E, C.somax[row], C.pvtnum[row], C.satnum[row], C.p[row], C.sw[row], C.sg[row], C.rs[row], C.rv[row], C.hc[row], row, q, H, &EI, out,
+                          rs_cap_of<KM>(C.somax, C.nbp, row), rv_cap_of<KM>(C.somax, C.nbp, row));
 }
 
 } // namespace opmgpu

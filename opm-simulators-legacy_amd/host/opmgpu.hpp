@@ -156,6 +156,13 @@ public:
     void updateSatHyst() { throw_on_status(ctx_, opmgpu_update_hysteresis(ctx_)); }
     /// EHYSTR item 2 / item 4: OPMGPU_HYST_CARLSON (the default) or OPMGPU_HYST_KILLOUGH with Killough's curvature parameter (opmgpu.h)
     void setHysteresisModel(int model, double killough_a = 0.1) { throw_on_status(ctx_, opmgpu_set_hysteresis_model(ctx_, model, killough_a)); }
+    /// DRSDT / DRVDT (opmgpu_set_dissolution_limits; the rule is ours and stated in opmgpu.h): rates in 1/s, negative = off.  The caller
+    /// begins every time step -- also the retry of a failed one with a shorter dt, after the state has been restored -- with
+    /// beginDissolutionStep(dt), which takes the caps from the resident state.  The caps themselves for restart: [nc], any pointer may be null.
+    void setDissolutionLimits(double drsdt, bool drsdt_free_only, double drvdt) { throw_on_status(ctx_, opmgpu_set_dissolution_limits(ctx_, drsdt, drsdt_free_only ? 1 : 0, drvdt)); }
+    void beginDissolutionStep(double dt) { throw_on_status(ctx_, opmgpu_begin_dissolution_step(ctx_, dt)); }
+    void getDissolutionCaps(double* rs_cap, double* rv_cap) { throw_on_status(ctx_, opmgpu_get_dissolution_caps(ctx_, rs_cap, rv_cap)); }
+    void setDissolutionCaps(const double* rs_cap, const double* rv_cap) { throw_on_status(ctx_, opmgpu_set_dissolution_caps(ctx_, rs_cap, rv_cap)); }
     /// Sncrt, m, R of the oil-water and of the gas-oil scanning curves ([nc] each, any pointer may be null)
     void getHysteresisScanning(double* sncrt_ow, double* m_ow, double* r_ow, double* sncrt_go, double* m_go, double* r_go)
     {

@@ -233,6 +233,10 @@ SIGNATURES = {
     "opmgpu_set_sat_oil_max": (C.c_int, [C.c_void_p, _dp]),
     "opmgpu_update_sat_oil_max": (C.c_int, [C.c_void_p]),
     "opmgpu_get_sat_oil_max": (C.c_int, [C.c_void_p, _dp]),
+    "opmgpu_set_dissolution_limits": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_double]),
+    "opmgpu_begin_dissolution_step": (C.c_int, [C.c_void_p, C.c_double]),
+    "opmgpu_get_dissolution_caps": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "opmgpu_set_dissolution_caps": (C.c_int, [C.c_void_p, _dp, _dp]),
     "opmgpu_create_solver": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(Params)]),
     "opmgpu_solve_bsr": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, _dp, _dp, C.c_int, _dp, C.POINTER(C.c_int), _dp]),
     "opmgpu_load_bsr": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, _dp, C.c_int]),

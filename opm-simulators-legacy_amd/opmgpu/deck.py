@@ -33,7 +33,8 @@ What `flow_legacy` gets from opm-parser + `DerivedGeology` (opm/autodiff/GeoProp
 Block-centred Cartesian geometry only (corner-point COORD/ZCORN needs opm-grid's processing, out of scope).  TPFA
 transmissibilities as `tpfa_htrans_compute` / `tpfa_trans_compute` do for such cells: half-transmissibility
 K A / (d/2) per side (horizontal ones times NTG, DerivedGeology :135-160), harmonic sum, times the MULT? of the face.
-Everything else (SUMMARY, other report keywords) is skipped; SCHEDULE is kept in deck order for opmgpu/schedule.py.  METRIC units only.
+Everything else (SUMMARY, other report keywords) is skipped; SCHEDULE is kept in deck order for opmgpu/schedule.py (which reads, among the
+rest, DRSDT / DRVDT: the limits on re-dissolution and re-vaporisation).  METRIC units only.
 """
 import re
 

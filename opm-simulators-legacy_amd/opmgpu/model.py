@@ -244,10 +244,14 @@ class GpuBlackoilModel(_CprDiagnostics):
 
     # --- BlackoilModelBase hooks -------------------------------------------------------------
     def prepareStep(self, dt, state=None):
-        """prepareStep (:222-232): pvdt = pv/dt is folded into assemble(); state upload if given."""
+        """prepareStep (:222-232): pvdt = pv/dt is folded into assemble(); state upload if given.  With dissolution limits
+        (setDissolutionLimits) the caps of this time step are then taken from the resident state: call it again when a failed sub-step has
+        restored the saved state and a shorter dt is tried."""
         self.dt = float(dt)
         if state is not None:
             self.setState(state)
+        if self.dissolution_limits is not None:
+            self._chk(self.lib.opmgpu_begin_dissolution_step(self.ctx, self.dt))
 
     def assemble(self, initial_assembly):
         self._chk(self.lib.opmgpu_assemble(self.ctx, self.dt, int(initial_assembly), None, None, None, None, None))
@@ -445,6 +449,30 @@ class GpuBlackoilModel(_CprDiagnostics):
         out = np.zeros(self.nc)
         self._chk(self.lib.opmgpu_get_sat_oil_max(self.ctx, capi.dptr(out)))
         return out
+
+    # DRSDT / DRVDT (opmgpu_set_dissolution_limits; the rule is ours and stated in include/opmgpu.h)
+    dissolution_limits = None       # (drsdt, free_only, drvdt) in force, rates in 1/s with None = off; None = no limits
+
+    def setDissolutionLimits(self, drsdt=None, free_only=False, drvdt=None):
+        """Limits on how fast Rs (drsdt, 1/s; free_only = DRSDT's option FREE) and Rv (drvdt, 1/s) may rise within a time step; None = off,
+        both None removes the limits.  prepareStep(dt) then sets the caps of the step.  ValueError with the library's text when refused;
+        the previous limits stay in force."""
+        self._chk(self.lib.opmgpu_set_dissolution_limits(self.ctx, -1.0 if drsdt is None else float(drsdt), int(bool(free_only)),
+                                                         -1.0 if drvdt is None else float(drvdt)))
+        on_s, on_v = drsdt is not None and drsdt >= 0, drvdt is not None and drvdt >= 0
+        self.dissolution_limits = (float(drsdt) if on_s else None, bool(free_only) and on_s, float(drvdt) if on_v else None) if (on_s or on_v) else None
+
+    def dissolutionCaps(self):
+        """(rs_cap, rv_cap) of the current time step, caller cell order; +inf = no cap"""
+        rs_cap, rv_cap = np.zeros(self.nc), np.zeros(self.nc)
+        self._chk(self.lib.opmgpu_get_dissolution_caps(self.ctx, capi.dptr(rs_cap), capi.dptr(rv_cap)))
+        return rs_cap, rv_cap
+
+    def setDissolutionCaps(self, rs_cap=None, rv_cap=None):
+        """the caps themselves (restart; tests); None leaves a plane as it is"""
+        a = None if rs_cap is None else capi.f64(rs_cap)
+        b = None if rv_cap is None else capi.f64(rv_cap)
+        self._chk(self.lib.opmgpu_set_dissolution_caps(self.ctx, None if a is None else capi.dptr(a), None if b is None else capi.dptr(b)))
 
     # hysteresis history (SaturationPropsFromDeck::updateSatHyst, called once per report step: SimulatorBase_impl.hpp:190-191)
     def updateHysteresis(self):

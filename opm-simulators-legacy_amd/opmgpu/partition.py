@@ -132,6 +132,10 @@ def shm_test_transport_wanted():
 def attach_comm(model, dom, rank, world, unique_id, pressure_hierarchy=None):
     """opmgpu_comm_init (RCCL) -- or opmgpu_comm_init_transport with the shared-memory test transport -- for a model created on dom.grid.
     pressure_hierarchy: 0 / 1 = opmgpu_comm_set_pressure_hierarchy (None: the library's default, OPMGPU_CPR_GLOBAL_AMG)."""
+    if getattr(model, "dissolution_limits", None) is not None:
+        # the ghost cells' step-start Rs / Rv are not exchanged: dropping the limits here would let gas re-dissolve at once without a word
+        # (opmgpu_comm_init refuses a context with limits, and opmgpu_set_dissolution_limits one with a communicator, for the same reason)
+        raise ValueError("the model has dissolution limits (DRSDT / DRVDT): they are not supported in a decomposed run")
     lib = capi.load()
     lists = (dom.n_owned, int(dom.neigh_rank.size), capi.iptr(dom.neigh_rank), capi.iptr(dom.send_ptr), capi.iptr(dom.send_cells),
              capi.iptr(dom.recv_ptr), capi.iptr(dom.recv_cells))

@@ -12,6 +12,12 @@ keywords a standard-well black-oil run needs:
   GCONINJE  group phase mode rate ...             phase WATER | GAS, mode RATE with its target, or NONE | FLD
   WGRUPCON  well YES|NO guide-rate                NO: the well is no member of a controlled group (it runs on its own limits and its rate is
             not counted against the group's target); guide rate defaulted or <= 0: taken from the well potentials (items 4, 5 are not read)
+  DRSDT     value [ALL|FREE]                      the largest rate at which Rs of a cell may rise [sm3/sm3/day]; FREE: only in cells that hold
+            free gas.  DRVDT value: the same for Rv, no option.  In force from their report step on until replaced; per report step in
+            `Schedule.dissolution` (rates per SECOND).  The rule they feed is the device's own (opmgpu_set_dissolution_limits in
+            include/opmgpu.h).  ValueError naming the keyword: either one in a deck without GAS, DRSDT without DISGAS, DRVDT without VAPOIL, a
+            negative or missing value, an option other than ALL / FREE; and DRSDTR, DRVDTR (regional rates), DRSDTCON (convective
+            dissolution), which are not supported
   DATES / TSTEP (report steps), START (RUNSPEC)
   RPTRST    mnemonic list (opmgpu/deck.py:parse_rptrst): REPLACES the list in force (RestartConfig::getRestartKeywords) for the report steps
             that follow it; the SOLUTION section's list holds until then
@@ -75,6 +81,7 @@ class Schedule:
         self.steps = []                 # [(length in s, {name: WellSpec snapshot})]
         self.rptrst = []                # per report step: {RPTRST mnemonic: int} in force for the restart file written at its end
         self.groups = []                # per report step: {"parent": {group: parent}, "prod": {group: (mode, target)}, "inje": {(group, phase): target}}
+        self.dissolution = []           # per report step: (DRSDT rate [1/s] or None, its option FREE, DRVDT rate [1/s] or None)
         self._build()
 
     def _build(self):
@@ -84,6 +91,7 @@ class Schedule:
         now = self.start
         rptrst = self.deck.rptrst()
         groups = {"parent": {}, "prod": {}, "inje": {}}
+        drsdt, free_only, drvdt = None, False, None
         for name, recs in self.deck.schedule:
             if name == "RPTRST":
                 rptrst = parse_rptrst(recs[0] if recs else [])
@@ -162,6 +170,15 @@ class Schedule:
                         raise ValueError("WEFAC %s: unknown well (no WELSPECS before it names or matches it)" % r[0])
                     for wn in matched:
                         specs[wn].efficiency = e
+            elif name in ("DRSDT", "DRVDT"):
+                rate, opt = self._dissolution_rate(name, recs)
+                if name == "DRSDT":
+                    drsdt, free_only = rate, opt == "FREE"
+                else:
+                    drvdt = rate
+            elif name in ("DRSDTR", "DRVDTR", "DRSDTCON"):
+                raise ValueError("%s: %s is not supported (DRSDT / DRVDT set one rate for the whole field)"
+                                 % (name, "convective dissolution" if name == "DRSDTCON" else "a rate per region"))
             elif name == "GEFAC":
                 raise ValueError("GEFAC: group efficiency factors are not supported (WEFAC sets a well's factor)")
             elif name == "GRUPTREE":
@@ -216,6 +233,7 @@ class Schedule:
                     self.steps.append(((d - now).days * DAY, copy.deepcopy({n: specs[n] for n in order})))
                     self.rptrst.append(dict(rptrst))
                     self.groups.append(copy.deepcopy(groups))
+                    self.dissolution.append((drsdt, free_only, drvdt))
                     now = d
             elif name == "TSTEP":
                 for r in recs:
@@ -223,7 +241,31 @@ class Schedule:
                         self.steps.append((float(dt) * DAY, copy.deepcopy({n: specs[n] for n in order})))
                         self.rptrst.append(dict(rptrst))
                         self.groups.append(copy.deepcopy(groups))
+                        self.dissolution.append((drsdt, free_only, drvdt))
                         now = now + datetime.timedelta(days=float(dt))
+
+    def _dissolution_rate(self, name, recs):
+        """DRSDT value [ALL|FREE] / DRVDT value -> (rate per second, option); METRIC: the value is per day"""
+        r = recs[0] if recs else []
+        if self.two_phase:
+            raise ValueError("%s in a deck without GAS (RUNSPEC: OIL WATER)" % name)
+        need = "DISGAS" if name == "DRSDT" else "VAPOIL"
+        if not self.deck.has(need):
+            raise ValueError("%s in a deck without %s" % (name, need))
+        v = _get(r, 0)
+        try:
+            v = float(v)
+        except (TypeError, ValueError):
+            raise ValueError("%s: item 1, the rate, is %r, not a number" % (name, v))
+        if not np.isfinite(v) or v < 0.0:
+            raise ValueError("%s: item 1, the rate %r, is negative or not finite" % (name, v))
+        opt = str(_get(r, 1, "ALL")).upper()
+        if name == "DRVDT":
+            if _get(r, 1) is not None:
+                raise ValueError("DRVDT: item 2 (%r): DRVDT has no option" % r[1])
+        elif opt not in ("ALL", "FREE"):
+            raise ValueError("DRSDT: item 2, the option, is %r, not ALL or FREE" % opt)
+        return v / DAY, opt
 
     PROD_DISTR = {"ORAT": (0.0, 1.0, 0.0), "WRAT": (1.0, 0.0, 0.0), "GRAT": (0.0, 0.0, 1.0), "LRAT": (1.0, 1.0, 0.0)}
     INJE_DISTR = {"WATER": (1.0, 0.0, 0.0), "GAS": (0.0, 0.0, 1.0)}

@@ -3,7 +3,7 @@
 
     deck -> grid / tables / initial state (EQUIL, with SWATINIT) -> [SWATINIT: setSwatInitScaling] -> [THPRES: computeMaxDp of the
     initial state, setThresholdPressures] -> set the state (the order of FlowMain::setupState, FlowMain.hpp:636-692) -> for every report
-    step of the SCHEDULE: wells of the step (WellsManager), well state carried over by name, updateSatOilMax + updateSatHyst (:190-192), AdaptiveTimeStepping.step with the NonlinearSolver (:236-253),
+    step of the SCHEDULE: the step's dissolution limits (DRSDT / DRVDT), wells of the step (WellsManager), well state carried over by name, updateSatOilMax + updateSatHyst (:190-192), AdaptiveTimeStepping.step with the NonlinearSolver (:236-253),
     restart + summary output (:300-306).
 
 The physics runs in libopmgpu.so (state resident on the device across sub-steps); this module is host plumbing.  Output goes to
@@ -162,6 +162,13 @@ class Simulator:
             event = prev_names != list(wl.name)
             if step == self.start_step and self._restart_ws is not None and [str(n)[:8] for n in wl.name] == self._restart_ws[0]:
                 event = False                             # the same wells as at the end of the run the restart file comes from
+            lim = self.schedule.dissolution[step]         # DRSDT / DRVDT in force (the rule is the device's own, include/opmgpu.h)
+            if lim != getattr(self, "_dissolution", (None, False, None)):
+                # a model without the setter (the CPU oracle behind the host well model) would let gas re-dissolve at once, without a word
+                if not hasattr(gm, "setDissolutionLimits"):
+                    raise ValueError("the deck has DRSDT / DRVDT, but the model cannot take dissolution limits (setDissolutionLimits)")
+                gm.setDissolutionLimits(lim[0], lim[1], lim[2])
+                self._dissolution = lim
             if hasattr(gm, "updateSatOilMax"):
                 gm.updateSatOilMax()                      # SimulatorBase_impl.hpp:190-192
                 gm.updateHysteresis()
