@@ -63,7 +63,9 @@ typedef struct opmgpu_grid {
     int32_t        nc;          /* number of (active) cells                                     */
     int32_t        nconn;       /* interior faces + NNCs                                        */
     const int32_t* conn_cells;  /* [nconn*2]                                                    */
-    const double*  trans;       /* [nconn]  transmissibility, SI                                */
+    const double*  trans;       /* [nconn]  transmissibility, SI: finite and >= 0 (0 is legal and
+                                 * closes the connection); a negative, NaN or infinite value is
+                                 * OPMGPU_EINVAL at opmgpu_create, the message names the connection */
     const double*  pv;          /* [nc]     pore volume (geo_.poreVolume())                     */
     const double*  z;           /* [nc]     cell centroid depth (geo_.z())                      */
     double         gravity;     /* geo_.gravity()[2]                                            */

@@ -577,12 +577,22 @@ __global__ __launch_bounds__(kBlock) void k_stabilize(long n, int sor, double om
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
+void BlackoilDevice::check_transmissibilities(const opmgpu_grid* g)
+{
+    if (g->nconn > 0 && !g->trans) throw HipError(OPMGPU_EINVAL, "opmgpu_grid.trans is NULL");
+    for (int f = 0; f < g->nconn; ++f)
+        if (!(g->trans[f] >= 0.0) || !std::isfinite(g->trans[f]))
+            throw HipError(OPMGPU_EINVAL, "the transmissibility of connection " + std::to_string(f) + " (cells " + std::to_string(g->conn_cells[2 * f]) + ", " +
+                                          std::to_string(g->conn_cells[2 * f + 1]) + ") is negative or not finite");
+}
+
 BlackoilDevice::BlackoilDevice(hipStream_t s, LinSolver& ls_, const opmgpu_grid* g, const opmgpu_tables* t, const opmgpu_params* prm_)
     : prm(*prm_), stream(s), ls(ls_)
 {
     nc = g->nc; nconn = g->nconn; gravity = g->gravity;
     n_owned_cells = nc;
     h_conn.assign(g->conn_cells, g->conn_cells + 2 * size_t(nconn));
+    check_transmissibilities(g);
     h_trans.assign(g->trans, g->trans + nconn);
     h_pv.assign(g->pv, g->pv + nc);
     h_z.assign(g->z, g->z + nc);

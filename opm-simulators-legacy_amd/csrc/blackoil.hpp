@@ -54,6 +54,10 @@ class BlackoilDevice {
 public:
     BlackoilDevice(hipStream_t s, LinSolver& ls, const opmgpu_grid* g, const opmgpu_tables* t, const opmgpu_params* prm);
     ~BlackoilDevice();
+    // every transmissibility finite and >= 0 (0 is legal), else HipError(OPMGPU_EINVAL) naming the connection; host only, no device call.
+    // The SELL planes carry the row's side of a connection in the SIGN of T and mark a well-fill entry with NaN: a negative value would
+    // be assembled as |T| and a NaN one as a closed connection
+    static void check_transmissibilities(const opmgpu_grid* g);
 
     int set_wells(int nw, const int32_t* connpos, const int32_t* cells);
     void set_state(const double* p, const double* sat, const double* rs, const double* rv, const int8_t* hc);

@@ -157,6 +157,9 @@ int opmgpu_create(opmgpu_ctx** ctx, int device, const opmgpu_grid* grid, const o
 {
     create_err.clear();
     if (!grid || !tables || grid->nc <= 0 || grid->nconn < 0) return OPMGPU_EINVAL;
+    // refused before any device call (so also where there is no device): a decomposed context takes its local grid through here as well
+    try { BlackoilDevice::check_transmissibilities(grid); }
+    catch (const HipError& e) { if (ctx) *ctx = nullptr; create_err = e.what(); return e.code; }
     const int st = make_ctx(ctx, device, params);
     if (st != OPMGPU_OK) return st;
     opmgpu_ctx* c = *ctx;

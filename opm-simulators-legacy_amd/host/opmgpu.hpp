@@ -97,6 +97,8 @@ struct ConvergenceReport { double B_avg[3], CNV[3], MB[3], linf[3]; bool converg
 /// linear solver outlives BlackoilModel (FlowMain.hpp:237 vs SimulatorBase_impl.hpp:201-203).
 class BlackoilModelGpu {
 public:
+    /// grid.trans must be finite and >= 0 (0 is legal and closes the connection): a negative, NaN or infinite value is
+    /// OPMGPU_EINVAL at opmgpu_create, and the message thrown here names the connection.
     BlackoilModelGpu(const opmgpu_grid& grid, const opmgpu_tables& tables, const opmgpu_params* prm = nullptr, int device = 0)
     {
         nc_ = grid.nc;
