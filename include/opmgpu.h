@@ -742,6 +742,94 @@ int opmgpu_begin_dissolution_step(opmgpu_ctx* ctx, double dt);
 int opmgpu_get_dissolution_caps(opmgpu_ctx* ctx, double* rs_cap /* [nc] or NULL */, double* rv_cap /* [nc] or NULL */);
 int opmgpu_set_dissolution_caps(opmgpu_ctx* ctx, const double* rs_cap /* [nc] or NULL */, const double* rv_cap /* [nc] or NULL */);
 
+/* Analytic aquifers (AQUFETP: Fetkovich, AQUCT: Carter-Tracy, connected by AQUANCON) as source terms of the water equation.  The reference
+ * has no aquifers, so THE RULE IS OURS; it is stated here, restated independently under tests/ (tests/aquifer_reference.py) and pinned to
+ * no other simulator.  All quantities are SI.  Every product and sum below is ONE IEEE float64 operation, evaluated in the order the
+ * parentheses give (left to right where there are none) and never contracted into a fused multiply-add.
+ *
+ * An aquifer a feeds the connections j in [conn_ptr[a], conn_ptr[a+1]), each a pair (cell c_j, fraction alpha_j > 0) with sum_j alpha_j = 1
+ * within 1e-12.  The GLOBAL connection index j (aquifers in order, the connections of one in the order given) is "the listing order".
+ * Both models reduce to one linear law per connection and time step,
+ *     q_j = A_j - B_j * pw_j          [reservoir m3/s of water, positive INTO the cell],
+ * pw_j the water-phase pressure of c_j at the current iterate: the evaluator's VP_PW value p - pcow.
+ *
+ * Begin of a time step of length dt (opmgpu_aquifer_begin_step, after any state upload and again whenever a failed sub-step has restored
+ * the saved state and a shorter dt is tried).  A_j and B_j are fixed here until the next begin.  Every connection evaluates its cell from
+ * the RESIDENT state with the cell evaluator and keeps rho0_j = the water density and p0_j = the water pressure of c_j, and forms
+ *     h_j = (rho0_j * g) * (z[c_j] - d_a)          (d_a the aquifer's datum depth, g the grid's gravity, z the cell depth).
+ * Fetkovich (kind OPMGPU_AQUIFER_FETKOVICH; parameters p_a0, CtV0 = C_t V_0, J; state W_e = the cumulative reservoir volume), per aquifer
+ *     p_a = p_a0 - W_e / CtV0,   tau = CtV0 / J,   x = dt / tau,   E = -expm1(-x) / x,   JE = J * E
+ * and per connection
+ *     B_j = alpha_j * JE,        A_j = B_j * (p_a + h_j).
+ * (E = (1 - exp(-x)) / x makes the step exact for a constant cell pressure; expm1 keeps it accurate for small x.)
+ * Carter-Tracy (OPMGPU_AQUIFER_CARTER_TRACY; parameters p_a0, beta, T_c and the influence table (t_D, P_D)[tab_ptr[a] .. tab_ptr[a+1]) of at
+ * least 2 rows with strictly increasing t_D; state W_e and the aquifer time t = the sum of the committed dt), per aquifer
+ *     tD = t / T_c,   tDp = (t + dt) / T_c,
+ *     i = the segment of tDp by the rule of the PVT tables (Tabulated1DFunction: with n rows i = [t_D[1] < tDp] + sum_{k=2}^{n-2} [t_D[k] <= tDp],
+ *         so the first and the last segment extrapolate linearly beyond the ends),
+ *     Pp = (P_D[i+1] - P_D[i]) / (t_D[i+1] - t_D[i])   (formed once when the aquifers are set),   P = P_D[i] + Pp * (tDp - t_D[i]),
+ *     den = P - tD * Pp,   Tden = T_c * den,   b = beta / Tden,
+ * and per connection
+ *     a_j = (beta * ((p_a0 + h_j) - p0_j) - W_e * Pp) / Tden,   B_j = alpha_j * b,   A_j = alpha_j * (a_j + b * p0_j).
+ * A den that is not positive and finite makes opmgpu_aquifer_begin_step fail with OPMGPU_ENUMERICAL (text names the aquifer) and no step
+ * is begun: it never becomes a NaN in the matrix.  p_a of a Carter-Tracy aquifer, as an output only, is p_a0 - W_e / beta.
+ *
+ * Assembly (every opmgpu_assemble and opmgpu_nonlinear_iteration while aquifers are set and a step has begun; behind the wells' terms).
+ * ONE thread per distinct connected cell evaluates the cell (b_w and pw with their derivatives with respect to v = (p, Sw, X); d pw / d v
+ * = (1, d pw / d Sw, 0)) and, for its connections in the listing order, starting from zeros,
+ *     q_j = A_j - B_j * pw,   s += b_w * q_j,   d_v += (d b_w / d v) * q_j - (b_w * B_j) * (d pw / d v),
+ * then R_water[c] -= s and, for the three entries of the water row of the cell's diagonal block, D[water][v] -= scale_water * d_v (the
+ * sign convention of the well terms; in a float matrix the entry is widened, changed and rounded back once).  A cell may have connections
+ * of several aquifers; no atomics, so the bits are the same from run to run.  No other equation, row or off-diagonal block changes.  The
+ * float copy of a double Jacobian (preconditioner_single) and the CPR weights of the connected rows follow the final diagonal blocks.
+ * Stated limit: outflow (q_j < 0) is not limited by the cell's mobile water.
+ *
+ * Commit (opmgpu_aquifer_commit_step, after a converged step): per aquifer, from the resident (converged) state, q_j as above and qs_j =
+ * b_w,j * q_j per connection; Q = sum_j q_j and Qs = sum_j qs_j by THIS tree: with n connections numbered k = 0 .. n-1 within the aquifer,
+ * slot T (0 <= T < 256) sums its connections k = T, T + 256, T + 512, ... in ascending order starting from 0.0; within each group of 64
+ * consecutive slots (a wave) the slots are folded six times, v[l] = v[l] + v[l + off] for l < off with off = 32, 16, 8, 4, 2, 1 in
+ * turn, leaving the wave's sum in its first slot; the four wave sums are added in order, ((w0 + w1) + w2) + w3.
+ * Then W_e += dt * Q, W_s += dt * Qs (the surface volume, for the material balance), t += dt, and the step is no longer begun.
+ *
+ * Lifecycle.  A begun step that is not committed is discarded by the next begin, and by opmgpu_restore_state (how a failed sub-step is
+ * handled); opmgpu_save_state and opmgpu_restore_state do not touch the committed state (W_e, W_s, t).  Aquifers and their state last
+ * through opmgpu_set_wells / opmgpu_set_device_wells (a re-plan, which discards a begun step like it discards the saved state) and a
+ * change of the solve precision.
+ *
+ * opmgpu_set_aquifers: NULL or naq == 0 removes the aquifers and the context is again the one that never had any; a new set starts with
+ * W_e = W_s = t = 0.  OPMGPU_EINVAL (with text, the previous set stays in force) for: an unknown kind; a non-finite p_a0 or datum; a CtV0, J
+ * (Fetkovich) or beta, T_c (Carter-Tracy) that is not finite and positive; an aquifer without connections; a cell out of range; an alpha
+ * that is not finite and positive, or alphas not summing to 1 within 1e-12; the same cell twice in ONE aquifer; a Carter-Tracy table with
+ * fewer than 2 rows, a non-finite entry or t_D not strictly increasing; a context with a communicator attached (opmgpu_comm_init* in turn
+ * refuses a context with aquifers).  begin_step: OPMGPU_EINVAL for dt <= 0 or not finite, without aquifers, or before a state has been
+ * set.  commit_step: OPMGPU_EINVAL without a begun step.  state_get / state_set: per aquifer W_e, W_s, t (any pointer may be NULL); p_a is
+ * a derived output of get; set refuses non-finite values and discards a begun step.  connections_get: out[6 j + 0..5] = rho0_j, p0_j, A_j,
+ * B_j and, at the RESIDENT state, q_j and qs_j (tests, summary output); OPMGPU_EINVAL without a begun step. */
+enum { OPMGPU_AQUIFER_FETKOVICH = 0, OPMGPU_AQUIFER_CARTER_TRACY = 1 };
+typedef struct opmgpu_aquifers {
+    int32_t        naq;
+    const int32_t* kind;          /* [naq] OPMGPU_AQUIFER_*                                                  */
+    const double*  p_a0;          /* [naq] initial aquifer pressure at the datum                             */
+    const double*  datum;         /* [naq] datum depth d_a                                                   */
+    const double*  CtV0;          /* [naq] Fetkovich: total compressibility x initial water volume (else ignored) */
+    const double*  J;             /* [naq] Fetkovich: productivity index [m3/s/Pa] (else ignored)            */
+    const double*  beta;          /* [naq] Carter-Tracy: influx constant [m3/Pa] (else ignored)              */
+    const double*  Tc;            /* [naq] Carter-Tracy: time constant [s] (else ignored)                    */
+    const int32_t* tab_ptr;       /* [naq+1] rows of the influence tables (a Fetkovich aquifer has none); NULL without Carter-Tracy aquifers */
+    const double*  tab_td;        /* [tab_ptr[naq]]                                                          */
+    const double*  tab_pd;        /* [tab_ptr[naq]]                                                          */
+    const int32_t* conn_ptr;      /* [naq+1]                                                                 */
+    const int32_t* conn_cell;     /* [conn_ptr[naq]] caller cell index                                       */
+    const double*  conn_alpha;    /* [conn_ptr[naq]]                                                         */
+} opmgpu_aquifers;
+enum { OPMGPU_AQUIFER_CONN_K = 6 };
+int opmgpu_set_aquifers(opmgpu_ctx* ctx, const opmgpu_aquifers* aquifers);
+int opmgpu_aquifer_begin_step(opmgpu_ctx* ctx, double dt);
+int opmgpu_aquifer_commit_step(opmgpu_ctx* ctx);
+int opmgpu_aquifer_state_get(opmgpu_ctx* ctx, double* W_e /* [naq] or NULL */, double* W_s, double* t, double* p_a);
+int opmgpu_aquifer_state_set(opmgpu_ctx* ctx, const double* W_e /* [naq] or NULL */, const double* W_s, const double* t);
+int opmgpu_aquifer_connections_get(opmgpu_ctx* ctx, double* out /* [nconn][OPMGPU_AQUIFER_CONN_K] */);
+
 /* Hysteresis history (EclHysteresisTwoPhaseLawParams::update, called once per report step by SimulatorBase_impl.hpp:190-191 ->
  * BlackoilPropsAdFromDeck::updateSatHyst): update = take the resident state's saturations into the history (krnSwMdc of both two-phase
  * systems = running minimum of 1 - So resp. 1 - Sg, the reference's "inconsistent" update) and recompute the Carlson shifts.
@@ -840,6 +928,10 @@ int opmgpu_get_cpr_weights(opmgpu_ctx* ctx, double* w);
 int opmgpu_get_residual(opmgpu_ctx* ctx, double* r);
 int opmgpu_get_jacobian_nnzb(opmgpu_ctx* ctx, int32_t* nnzb);
 int opmgpu_get_jacobian_bsr(opmgpu_ctx* ctx, int32_t* rowptr, int32_t* col, double* val9);
+/* diagnostic (mixed precision, preconditioner_single): the float copy of the DOUBLE Jacobian that came with the last assembly, widened, in
+ * the block order of opmgpu_get_jacobian_bsr.  OPMGPU_EINVAL (with text) when the context holds no such copy at the moment -- a float
+ * assembly, no copy written, or one that is stale: the solve then makes it from the double matrix. */
+int opmgpu_get_jacobian_float_copy(opmgpu_ctx* ctx, double* val9);
 /* timing of device work: runs `reps` launches of one kernel on the context's stream between two
  * hipEvents and returns the average milliseconds per launch (HIP events on the launch stream). */
 enum { OPMGPU_K_SPMV = 0, OPMGPU_K_ILU_APPLY = 1, OPMGPU_K_ILU_FACTOR = 2, OPMGPU_K_ASSEMBLE = 3,

@@ -656,6 +656,7 @@ BlackoilDevice::~BlackoilDevice()
 {
     wells_free();
     vfp_free();
+    aquifer_free();
     if (h_red) (void)hipHostFree(h_red);
     for (auto e : ev_well) if (e) (void)hipEventDestroy(e);
     if (well_stream) (void)hipStreamDestroy(well_stream);
@@ -1004,6 +1005,7 @@ void BlackoilDevice::assemble(double dt, bool initial)
     {
         KtScope kts(ls.kt, KT_WELLS);
         wells_assemble(initial);
+        aquifer_assemble();          // (nothing without aquifers or before a step has begun)
     }
     // the matrix is final (the host well model, if any, adds its blocks later: not then): the solver may start its ILU0 factorisation now
     // (LinSolver::factor_ahead decides).  What only the model can do for it comes first: the float copy that came with the assembly gets the
@@ -1012,6 +1014,10 @@ void BlackoilDevice::assemble(double dt, bool initial)
         if (!dual_written || ls.matrix_is_float) return;
         if (device_wells && nperf > 0)
             hipLaunchKernelGGL(k_refresh_f32_diag, dim3(grid_for(nperf)), dim3(kBlock), 0, stream, nperf, (const int32_t*)d_perf_cells.p, ls.dp.slice_ptr.p, ls.dp.nlower.p,
+                               (const double*)ls.matrix_d(), ls.matrix_f());
+        const int32_t* aq_rows = nullptr;                  // the aquifers' connected rows likewise
+        if (const int naq_rows = aquifer_rows(&aq_rows))
+            hipLaunchKernelGGL(k_refresh_f32_diag, dim3(grid_for(naq_rows)), dim3(kBlock), 0, stream, naq_rows, aq_rows, ls.dp.slice_ptr.p, ls.dp.nlower.p,
                                (const double*)ls.matrix_d(), ls.matrix_f());
         ls.float_copy_valid = true;
     });
@@ -1123,6 +1129,7 @@ void BlackoilDevice::restore_state()
     for (int k = 0; k < 6; ++k) OPMGPU_HIP(hipMemcpyAsync(planes[k]->p, d_saved.p + size_t(k) * nbp, nbp * sizeof(double), hipMemcpyDeviceToDevice, stream));
     OPMGPU_HIP(hipMemcpyAsync(d_hc.p, d_saved_hc.p, nbp, hipMemcpyDeviceToDevice, stream));
     wells_restore();
+    aquifer_discard();          // a begun aquifer step belongs to the sub-step that failed; the committed aquifer state is not touched
 }
 double BlackoilDevice::relative_change()
 {

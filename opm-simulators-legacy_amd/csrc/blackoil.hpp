@@ -103,6 +103,16 @@ public:
     void get_dissolution_caps(double* rs_cap, double* rv_cap);
     void set_dissolution_caps(const double* rs_cap, const double* rv_cap);
     bool has_dissolution_limits() const { return drdt_on(); }
+    // analytic aquifers (aquifer.hip; the rule: opmgpu_set_aquifers in include/opmgpu.h); all throw HipError with the reason
+    struct AquiferDev;
+    void set_aquifers(const opmgpu_aquifers* spec);         // nullptr or naq == 0 removes them
+    void aquifer_begin_step(double dt);
+    void aquifer_commit_step();
+    void aquifer_state_get(double* We, double* Ws, double* t, double* pa);
+    void aquifer_state_set(const double* We, const double* Ws, const double* t);
+    void aquifer_connections_get(double* out);
+    int aquifer_counts(int* nconn) const;                   // the number of aquifers (0 without) and of their connections
+    bool has_aquifers() const;
     int update_hysteresis();
     int set_hysteresis(const double* mdc_ow, const double* mdc_go);
     int get_hysteresis(double* mdc_ow, double* mdc_go, double* d_ow, double* d_go);
@@ -173,6 +183,13 @@ private:
     void wells_rebind();
     void wells_free();
     void vfp_free();
+    AquiferDev* aq = nullptr;
+    void aquifer_free();
+    void aquifer_rebind();                                  // the connections' rows in the current plan; discards a begun step
+    void aquifer_discard();                                 // a begun step that is not committed (restore_state)
+    void aquifer_assemble();                                // the aquifers' terms of a begun step, behind wells_assemble()
+    void aquifer_launch_rates(int apply);
+    int aquifer_rows(const int32_t** rows) const;           // the distinct connected rows while a step has begun, else 0
     WellsDev* wd = nullptr;
     VfpDev* vfp = nullptr;
     std::vector<double> h_surface_density;

@@ -267,6 +267,7 @@ void BlackoilDevice::rebuild_structure()
     if (!smax.empty()) set_sat_oil_max(smax.data());
     if (!caps.empty()) set_dissolution_caps(caps.data(), caps.data() + nc);
     wells_rebind();
+    aquifer_rebind();
     if (has_state) set_state(sp.data(), ssat.data(), srs.data(), srv.data(), shc.data());
     // Killough: the scanning parameters follow from the two history planes in the new numbering (the force path of k_hyst_update)
     if (hyst_carried && hyst_model == OPMGPU_HYST_KILLOUGH) { launch_hyst_update(1); OPMGPU_HIP(hipStreamSynchronize(stream)); }

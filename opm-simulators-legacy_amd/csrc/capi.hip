@@ -715,6 +715,39 @@ int opmgpu_set_dissolution_caps(opmgpu_ctx* c, const double* rs_cap, const doubl
     return guarded(c, [&]() { c->model->set_dissolution_caps(rs_cap, rv_cap); c->matrix_loaded = false; return int(OPMGPU_OK); });
 }
 
+// Analytic aquifers (the rule is stated in opmgpu.h).  A new set, a begun step and a changed state change what the next assembly adds: a
+// matrix loaded or factored before the call is that of the old terms.
+int opmgpu_set_aquifers(opmgpu_ctx* c, const opmgpu_aquifers* aquifers)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { c->model->set_aquifers(aquifers); c->matrix_loaded = false; return int(OPMGPU_OK); });
+}
+int opmgpu_aquifer_begin_step(opmgpu_ctx* c, double dt)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { c->model->aquifer_begin_step(dt); c->matrix_loaded = false; return int(OPMGPU_OK); });
+}
+int opmgpu_aquifer_commit_step(opmgpu_ctx* c)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { c->model->aquifer_commit_step(); c->matrix_loaded = false; return int(OPMGPU_OK); });
+}
+int opmgpu_aquifer_state_get(opmgpu_ctx* c, double* W_e, double* W_s, double* t, double* p_a)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { c->model->aquifer_state_get(W_e, W_s, t, p_a); return int(OPMGPU_OK); });
+}
+int opmgpu_aquifer_state_set(opmgpu_ctx* c, const double* W_e, const double* W_s, const double* t)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { c->model->aquifer_state_set(W_e, W_s, t); c->matrix_loaded = false; return int(OPMGPU_OK); });
+}
+int opmgpu_aquifer_connections_get(opmgpu_ctx* c, double* out)
+{
+    if (!c || !c->model || !out) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { c->model->aquifer_connections_get(out); return int(OPMGPU_OK); });
+}
+
 int opmgpu_update_hysteresis(opmgpu_ctx* c)
 {
     if (!c || !c->model) return OPMGPU_EINVAL;
@@ -898,6 +931,17 @@ int opmgpu_get_jacobian_bsr(opmgpu_ctx* c, int32_t* rowptr, int32_t* col, double
     });
 }
 
+int opmgpu_get_jacobian_float_copy(opmgpu_ctx* c, double* val9)
+{
+    if (!c || !val9 || !c->ls->has_pattern()) return OPMGPU_EINVAL;
+    return guarded(c, [&]() {
+        if (c->ls->matrix_is_float || !c->ls->float_copy_valid)
+            return fail(c, OPMGPU_EINVAL, "opmgpu_get_jacobian_float_copy: the context holds no float copy of a double Jacobian (the solve makes it then)");
+        c->ls->get_float_copy_bsr(val9);
+        return int(OPMGPU_OK);
+    });
+}
+
 int opmgpu_time_kernel(opmgpu_ctx* c, int kernel, int reps, double* ms_per_launch)
 {
     if (!c || reps < 1 || !ms_per_launch) return OPMGPU_EINVAL;
@@ -968,6 +1012,9 @@ static int comm_init_common(opmgpu_ctx* c, int rank, int nranks, const uint8_t* 
         // ghost cells' step-start rs / rv are not exchanged: the caps of a decomposed run are out of scope, so the context stays single-domain
         if (c->model->has_dissolution_limits())
             return fail(c, OPMGPU_EINVAL, "multi-GPU: dissolution limits (DRSDT / DRVDT) are set; a decomposed run (a communicator is attached) does not support them");
+        // an aquifer's connections may sit on several ranks and its sums are rank-local: refused, so the context stays single-domain
+        if (c->model->has_aquifers())
+            return fail(c, OPMGPU_EINVAL, "multi-GPU: aquifers are set; a decomposed run (a communicator is attached) does not support them");
         std::unique_ptr<RcclComm> cm(new RcclComm());
         static const int32_t zero2[2] = { 0, 0 };
         const int st = cm->init(rank, nranks, id, transport, n_owned, c->model->nc, n_neigh, neigh_rank, n_neigh ? send_ptr : zero2, send_cells,

@@ -1036,6 +1036,14 @@ void LinSolver::get_matrix_bsr(const double* sell, double* val9)
     OPMGPU_HIP(hipMemcpyAsync(val9, stage.p, size_t(plan.nnzb) * 9 * sizeof(double), hipMemcpyDeviceToHost, stream));
     OPMGPU_HIP(hipStreamSynchronize(stream));
 }
+// mixed precision: the float copy of the double matrix as it stands (valid or not: the caller checks float_copy_valid), widened
+void LinSolver::get_float_copy_bsr(double* val9)
+{
+    stage.ensure(std::max(size_t(plan.nnzb) * 9, size_t(3) * plan.nbp));
+    hipLaunchKernelGGL((k_sell_to_bsr<float>), dim3(grid_for(plan.nnzb)), dim3(kBlock), 0, stream, plan.nnzb, dp.entry_of_block.p, (const float*)matrix_f(), stage.p);
+    OPMGPU_HIP(hipMemcpyAsync(val9, stage.p, size_t(plan.nnzb) * 9 * sizeof(double), hipMemcpyDeviceToHost, stream));
+    OPMGPU_HIP(hipStreamSynchronize(stream));
+}
 template <class S> void LinSolver::get_lu_bsr(double* val9)
 {
     // the solver's factorisation leaves out the U entries that equal A's (k_ilu_upper reads those from A): factorise once more in full

@@ -287,6 +287,7 @@ public:
     template <class S> void vec_out(const S* d, int layout, double* ddst);
 
     void get_matrix_bsr(const double* sell, double* val9);          // Ad-like (double) SELL -> host BSR
+    void get_float_copy_bsr(double* val9);                          // the float copy of a double matrix (mixed precision) -> host BSR, widened
     template <class S> void get_lu_bsr(double* val9);
 
     template <class S> SolverWork<S>& work();

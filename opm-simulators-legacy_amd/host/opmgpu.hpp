@@ -165,6 +165,16 @@ public:
     void beginDissolutionStep(double dt) { throw_on_status(ctx_, opmgpu_begin_dissolution_step(ctx_, dt)); }
     void getDissolutionCaps(double* rs_cap, double* rv_cap) { throw_on_status(ctx_, opmgpu_get_dissolution_caps(ctx_, rs_cap, rv_cap)); }
     void setDissolutionCaps(const double* rs_cap, const double* rv_cap) { throw_on_status(ctx_, opmgpu_set_dissolution_caps(ctx_, rs_cap, rv_cap)); }
+    /// Analytic aquifers (opmgpu_set_aquifers; the rule is ours and stated in opmgpu.h): nullptr removes them.  The caller begins every
+    /// time step -- also the retry of a failed one, after the state has been restored -- with beginAquiferStep(dt) and commits a
+    /// converged one with commitAquiferStep() before it saves the state.  State per aquifer ([naq], any pointer may be null); the
+    /// connections' record is [nconn][OPMGPU_AQUIFER_CONN_K].
+    void setAquifers(const opmgpu_aquifers* aquifers) { throw_on_status(ctx_, opmgpu_set_aquifers(ctx_, aquifers)); }
+    void beginAquiferStep(double dt) { throw_on_status(ctx_, opmgpu_aquifer_begin_step(ctx_, dt)); }
+    void commitAquiferStep() { throw_on_status(ctx_, opmgpu_aquifer_commit_step(ctx_)); }
+    void getAquiferState(double* W_e, double* W_s, double* t, double* p_a) { throw_on_status(ctx_, opmgpu_aquifer_state_get(ctx_, W_e, W_s, t, p_a)); }
+    void setAquiferState(const double* W_e, const double* W_s, const double* t) { throw_on_status(ctx_, opmgpu_aquifer_state_set(ctx_, W_e, W_s, t)); }
+    void getAquiferConnections(double* out) { throw_on_status(ctx_, opmgpu_aquifer_connections_get(ctx_, out)); }
     /// Sncrt, m, R of the oil-water and of the gas-oil scanning curves ([nc] each, any pointer may be null)
     void getHysteresisScanning(double* sncrt_ow, double* m_ow, double* r_ow, double* sncrt_go, double* m_go, double* r_go)
     {

@@ -80,6 +80,16 @@ class WellsSpec(C.Structure):
                 ("ctrl_ptr", _ip), ("ctrl_vfp", _ip), ("ctrl_alq", _dp)]
 
 
+class AquifersSpec(C.Structure):
+    """opmgpu_aquifers: analytic aquifers (include/opmgpu.h)"""
+    _fields_ = [("naq", C.c_int32), ("kind", _ip), ("p_a0", _dp), ("datum", _dp), ("CtV0", _dp), ("J", _dp), ("beta", _dp), ("Tc", _dp),
+                ("tab_ptr", _ip), ("tab_td", _dp), ("tab_pd", _dp), ("conn_ptr", _ip), ("conn_cell", _ip), ("conn_alpha", _dp)]
+
+
+AQUIFER_FETKOVICH, AQUIFER_CARTER_TRACY = 0, 1
+AQUIFER_CONN_K = 6
+
+
 class VfpTable(C.Structure):
     _fields_ = [("id", C.c_int32), ("is_injector", C.c_int32), ("flo_type", C.c_int32), ("wfr_type", C.c_int32), ("gfr_type", C.c_int32),
                 ("datum_depth", C.c_double), ("nflo", C.c_int32), ("nthp", C.c_int32), ("nwfr", C.c_int32), ("ngfr", C.c_int32),
@@ -237,6 +247,13 @@ SIGNATURES = {
     "opmgpu_begin_dissolution_step": (C.c_int, [C.c_void_p, C.c_double]),
     "opmgpu_get_dissolution_caps": (C.c_int, [C.c_void_p, _dp, _dp]),
     "opmgpu_set_dissolution_caps": (C.c_int, [C.c_void_p, _dp, _dp]),
+    "opmgpu_get_jacobian_float_copy": (C.c_int, [C.c_void_p, _dp]),
+    "opmgpu_set_aquifers": (C.c_int, [C.c_void_p, C.POINTER(AquifersSpec)]),
+    "opmgpu_aquifer_begin_step": (C.c_int, [C.c_void_p, C.c_double]),
+    "opmgpu_aquifer_commit_step": (C.c_int, [C.c_void_p]),
+    "opmgpu_aquifer_state_get": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp]),
+    "opmgpu_aquifer_state_set": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
+    "opmgpu_aquifer_connections_get": (C.c_int, [C.c_void_p, _dp]),
     "opmgpu_create_solver": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(Params)]),
     "opmgpu_solve_bsr": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, _dp, _dp, C.c_int, _dp, C.POINTER(C.c_int), _dp]),
     "opmgpu_load_bsr": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, _dp, C.c_int]),

@@ -29,6 +29,8 @@ What `flow_legacy` gets from opm-parser + `DerivedGeology` (opm/autodiff/GeoProp
             THPRES (threshold pressures between EQLNUM regions, with EQLOPTS THPRES in RUNSPEC: `thpres()` / `threshold_pressures()`
             restate opm/simulators/thresholdPressures.hpp:320-417; a defaulted item 3 takes the model's computeMaxDp of the initial state)
             RPTRST (the mnemonics that select derived per-cell arrays for the restart file, RPTRST_MNEMONICS; also read in SCHEDULE)
+            AQUFETP AQUCT AQUANCON, with AQUTAB in PROPS and AQUDIMS in RUNSPEC read past (analytic aquifers: `aquifers()`, which states
+            the items read and the refusals; AQUFLUX, AQUNUM and AQUCON are refused)
 
 Block-centred Cartesian geometry only (corner-point COORD/ZCORN needs opm-grid's processing, out of scope).  TPFA
 transmissibilities as `tpfa_htrans_compute` / `tpfa_trans_compute` do for such cells: half-transmissibility
@@ -767,6 +769,141 @@ class Deck:
             raise ValueError("SWATINIT outside [0, 1]")
         return v
 
+    # ---------------------------------------------------------------- analytic aquifers
+    def aquifers(self, tables=None):
+        """The deck's analytic aquifers as a list of Aquifer (SI; cells in the numbering of grid()), in ascending aquifer id; [] without
+        AQUFETP / AQUCT.  The device rule they feed is stated in include/opmgpu.h at opmgpu_set_aquifers.
+          AQUFETP  id, datum depth, initial pressure, V_0, C_t, J, PVTW table, [salt], [temperature]      -> CtV0 = C_t V_0, J
+          AQUCT    id, datum depth, initial pressure, k_a, phi, C_t, r_o, h, theta (default 360), PVTW table (default 1), influence
+                   table, [salt], [temperature]    -> beta = 2 pi (theta / 360) h phi C_t r_o^2,  T_c = mu_w phi C_t r_o^2 / k_a, with mu_w the
+                   water viscosity of the named PVTW record at the initial pressure (the rule csrc/fluid_eval.hpp states for water:
+                   mu_w = mu_ref B_ref b_w / (1 + Y (1 + Y / 2)), Y = (C_w - C_v)(p - p_ref), b_w = (1 + X (1 + X / 2)) / B_ref, X = C_w (p - p_ref))
+          AQUTAB   one record per influence table, pairs (t_D, P_D); the first record is table 2 (table 1 is the built-in one of an
+                   infinite aquifer, which is not carried here)
+          AQUANCON id, I1 I2 J1 J2 K1 K2, face (I- I+ J- J+ K- K+), influx coefficient (default: the face area from DX / DY / DZ),
+                   multiplier (default 1), connect interior faces (default NO: only faces whose outward neighbour lies outside the grid
+                   or is inactive)
+        Several faces of one cell towards the same aquifer merge into one connection; alpha_j = coefficient_j multiplier_j / their sum.
+        Refused with a ValueError naming keyword and item: a defaulted initial pressure (items 3), AQUCT with influence table 1 or a
+        table AQUTAB does not hold (item 11), a defaulted influx coefficient on a corner-point grid (AQUANCON item 9), an AQUANCON for an
+        unknown aquifer (item 1), an aquifer without connections, salt items (AQUFETP 8, AQUCT 12), and AQUFLUX / AQUNUM / AQUCON."""
+        for k in ("AQUFLUX", "AQUNUM", "AQUCON"):
+            if self.has(k):
+                raise ValueError("%s is not supported (analytic aquifers: AQUFETP, AQUCT with AQUANCON)" % k)
+        if not (self.has("AQUFETP") or self.has("AQUCT")):
+            if self.has("AQUANCON"):
+                raise ValueError("AQUANCON item 1: no aquifer is defined (AQUFETP / AQUCT)")
+            return []
+        if tables is None:
+            tables = self.tables()
+        item = lambda r, i, d=None: r[i] if len(r) > i and r[i] is not None else d         # noqa: E731
+        nx, ny, nz = self.dims
+        if getattr(self, "active", None) is None:
+            self.grid()
+        n = nx * ny * nz
+        act = np.zeros(n, bool); act[self.active] = True
+        newid = -np.ones(n, np.int64); newid[self.active] = np.arange(self.active.size)
+        aq = {}
+
+        def pvt_record(kw, r, i):
+            reg = int(item(r, i, 1))
+            if reg < 1 or reg > tables.n_pvt:
+                raise ValueError("%s item %d: PVTW table %d outside 1 .. %d" % (kw, i + 1, reg, tables.n_pvt))
+            return reg - 1
+        for r in (self.records("AQUFETP") if self.has("AQUFETP") else []):
+            if not r:
+                continue
+            aid = int(r[0])
+            if item(r, 2) is None:
+                raise ValueError("AQUFETP item 3: a defaulted initial pressure (equilibrium with the reservoir) is not supported")
+            if item(r, 7) is not None:
+                raise ValueError("AQUFETP item 8: a salt concentration is not supported")
+            for i, what in ((1, "datum depth"), (3, "initial water volume"), (4, "total compressibility"), (5, "productivity index")):
+                if item(r, i) is None:
+                    raise ValueError("AQUFETP item %d: the %s must be given" % (i + 1, what))
+            pvt_record("AQUFETP", r, 6)
+            aq[aid] = Aquifer(aid, capi.AQUIFER_FETKOVICH, p_a0=float(r[2]) * BAR, datum=float(r[1]), CtV0=float(r[3]) * float(r[4]) / BAR,
+                              J=float(r[5]) / (DAY * BAR))
+        tabs = [[]]                     # table 1: the built-in one, not carried
+        for r in (self.records("AQUTAB") if self.has("AQUTAB") else []):
+            if r:
+                tabs.append((np.asarray(r[0::2], float), np.asarray(r[1::2], float)))
+        for r in (self.records("AQUCT") if self.has("AQUCT") else []):
+            if not r:
+                continue
+            aid = int(r[0])
+            if aid in aq:
+                raise ValueError("AQUCT item 1: aquifer %d is defined twice" % aid)
+            if item(r, 2) is None:
+                raise ValueError("AQUCT item 3: a defaulted initial pressure (equilibrium with the reservoir) is not supported")
+            if item(r, 11) is not None:
+                raise ValueError("AQUCT item 12: a salt concentration is not supported")
+            for i, what in ((1, "datum depth"), (3, "permeability"), (4, "porosity"), (5, "total compressibility"), (6, "external radius"), (7, "thickness")):
+                if item(r, i) is None:
+                    raise ValueError("AQUCT item %d: the %s must be given" % (i + 1, what))
+            tno = int(item(r, 10, 1))
+            if tno == 1:
+                raise ValueError("AQUCT item 11: the built-in influence table 1 is not carried; give the table in AQUTAB and name it (2 = the first AQUTAB record)")
+            if tno < 1 or tno > len(tabs):
+                raise ValueError("AQUCT item 11: influence table %d is not in AQUTAB (it holds the tables 2 .. %d)" % (tno, len(tabs)))
+            td, pd = tabs[tno - 1]
+            if td.size != pd.size or td.size < 2 or not np.all(np.diff(td) > 0):
+                raise ValueError("AQUTAB table %d: at least 2 rows (t_D, P_D) with strictly increasing t_D are needed" % tno)
+            w = tables.pvtw[pvt_record("AQUCT", r, 9)]
+            p0 = float(r[2]) * BAR
+            mu = water_viscosity(w, p0)
+            k_a, phi, ct, ro, h = float(r[3]) * MD, float(r[4]), float(r[5]) / BAR, float(r[6]), float(r[7])
+            theta = float(item(r, 8, 360.0))
+            aq[aid] = Aquifer(aid, capi.AQUIFER_CARTER_TRACY, p_a0=p0, datum=float(r[1]),
+                              beta=2.0 * np.pi * (theta / 360.0) * h * phi * ct * ro * ro, Tc=mu * phi * ct * ro * ro / k_a, td=td, pd=pd)
+        # AQUANCON: per aquifer {cell: coefficient x multiplier}, cells in order of first appearance
+        dx, dy, dz = (a.ravel() for a in self._cell_sizes())
+        idx = np.arange(n).reshape(nz, ny, nx)
+        area = {"I": dy * dz, "J": dx * dz, "K": dx * dy}
+        conn = {aid: {} for aid in aq}
+        for r in (self.records("AQUANCON") if self.has("AQUANCON") else []):
+            if not r:
+                continue
+            aid = int(r[0])
+            if aid not in aq:
+                raise ValueError("AQUANCON item 1: aquifer %d is not defined (AQUFETP / AQUCT)" % aid)
+            if any(item(r, i) is None for i in range(1, 8)):
+                raise ValueError("AQUANCON items 2-8: the box and the face must be given")
+            i1, i2, j1, j2, k1, k2 = (int(r[i]) for i in range(1, 7))
+            if not (1 <= i1 <= i2 <= nx and 1 <= j1 <= j2 <= ny and 1 <= k1 <= k2 <= nz):
+                raise ValueError("AQUANCON items 2-7: the box %s lies outside the grid" % ((i1, i2, j1, j2, k1, k2),))
+            face = str(r[7]).upper().replace("X", "I").replace("Y", "J").replace("Z", "K")
+            if len(face) != 2 or face[0] not in "IJK" or face[1] not in "+-":
+                raise ValueError("AQUANCON item 8: face %r is none of I- I+ J- J+ K- K+" % r[7])
+            coeff, mult = item(r, 8), float(item(r, 9, 1.0))
+            if coeff is None and self.has("ZCORN"):
+                raise ValueError("AQUANCON item 9: a defaulted influx coefficient on a corner-point grid is not supported")
+            interior = str(item(r, 10, "NO")).upper().startswith("Y")
+            axis, step = "KJI".index(face[0]), (1 if face[1] == "+" else -1)
+            for c in idx[k1 - 1:k2, j1 - 1:j2, i1 - 1:i2].ravel():
+                if not act[c]:
+                    continue
+                kji = [c // (nx * ny), (c // nx) % ny, c % nx]
+                kji[axis] += step
+                inside = 0 <= kji[0] < nz and 0 <= kji[1] < ny and 0 <= kji[2] < nx
+                if inside and act[idx[kji[0], kji[1], kji[2]]] and not interior:
+                    continue                    # the outward neighbour is an active cell
+                v = (float(coeff) if coeff is not None else float(area[face[0]][c])) * mult
+                if not v > 0.0:
+                    raise ValueError("AQUANCON items 9-10: coefficient x multiplier must be positive")
+                cell = int(newid[c])
+                conn[aid][cell] = conn[aid].get(cell, 0.0) + v
+        out = []
+        for aid in sorted(aq):
+            if not conn[aid]:
+                raise ValueError("%s item 1: aquifer %d has no connections (AQUANCON)" % ("AQUFETP" if aq[aid].kind == capi.AQUIFER_FETKOVICH else "AQUCT", aid))
+            a = aq[aid]
+            a.cells = np.fromiter(conn[aid].keys(), np.int64, len(conn[aid]))
+            w = np.fromiter(conn[aid].values(), float, len(conn[aid]))
+            a.alpha = w / w.sum()
+            out.append(a)
+        return out
+
     # ---------------------------------------------------------------- SOLUTION
     def initial_state(self, tables):
         """EQUIL (opmgpu/equil.py), else explicit PRESSURE / SWAT / SGAS / RS / RV arrays (active cells) with the hydrocarbon state from the
@@ -793,6 +930,26 @@ class Deck:
         if not tables.has_disgas:
             hc[hc == capi.HC_OIL_ONLY] = capi.HC_GAS_AND_OIL
         return State(p, sat, rs, rv, hc)
+
+
+class Aquifer:
+    """One analytic aquifer in SI as GpuBlackoilModel.setAquifers takes it: kind (capi.AQUIFER_FETKOVICH / AQUIFER_CARTER_TRACY), p_a0,
+    datum, CtV0 and J (Fetkovich) or beta, Tc and the influence table td / pd (Carter-Tracy), and the connections: cells (indices of the
+    grid's active cells) with their fractions alpha (summing to 1)."""
+
+    def __init__(self, id, kind, p_a0, datum, CtV0=0.0, J=0.0, beta=0.0, Tc=0.0, td=(), pd=(), cells=(), alpha=()):
+        self.id, self.kind, self.p_a0, self.datum = int(id), int(kind), float(p_a0), float(datum)
+        self.CtV0, self.J, self.beta, self.Tc = float(CtV0), float(J), float(beta), float(Tc)
+        self.td, self.pd = np.asarray(td, float), np.asarray(pd, float)
+        self.cells, self.alpha = np.asarray(cells, np.int64), np.asarray(alpha, float)
+
+
+def water_viscosity(w, p):
+    """mu_w(p) of one PVTW row in SI (p_ref, B_ref, C_w, mu_ref, C_v), by the rule csrc/fluid_eval.hpp states for water (water_pvt)"""
+    X = w[2] * (p - w[0])
+    bw = (1.0 + X * (1.0 + X / 2.0)) / w[1]
+    Y = (w[2] - w[4]) * (p - w[0])
+    return w[3] * w[1] * bw / (1.0 + Y * (1.0 + Y / 2.0))
 
 
 def last_zero(x, y):

@@ -252,6 +252,9 @@ class GpuBlackoilModel(_CprDiagnostics):
             self.setState(state)
         if self.dissolution_limits is not None:
             self._chk(self.lib.opmgpu_begin_dissolution_step(self.ctx, self.dt))
+        if self.aquifers is not None:       # the aquifers' A_j, B_j of this time step, likewise from the resident state
+            self._chk(self.lib.opmgpu_aquifer_begin_step(self.ctx, self.dt))
+            self._aquifer_step_begun = True
 
     def assemble(self, initial_assembly):
         self._chk(self.lib.opmgpu_assemble(self.ctx, self.dt, int(initial_assembly), None, None, None, None, None))
@@ -287,10 +290,17 @@ class GpuBlackoilModel(_CprDiagnostics):
 
     # last_state of AdaptiveTimeStepping, kept on the device
     def saveState(self):
+        """Keeps the resident state as the last good one.  A begun aquifer step is committed first: the time-step control saves the state
+        after every converged sub-step, so this is where the aquifers take their influx of that sub-step, once."""
+        if self._aquifer_step_begun:
+            self._chk(self.lib.opmgpu_aquifer_commit_step(self.ctx))
+            self._aquifer_step_begun = False
         self._chk(self.lib.opmgpu_save_state(self.ctx))
 
     def restoreState(self):
+        """Back to the saved state; a begun aquifer step (the failed sub-step's) is discarded, the committed aquifer state stays."""
         self._chk(self.lib.opmgpu_restore_state(self.ctx))
+        self._aquifer_step_begun = False
 
     def computeFluidInPlace(self, fipnum=None, cells=False, nregions=None):
         """BlackoilModelBase::computeFluidInPlace (BlackoilModelBase_impl.hpp:2263-2445) for the resident state: values[region][7]
@@ -474,6 +484,69 @@ class GpuBlackoilModel(_CprDiagnostics):
         b = None if rv_cap is None else capi.f64(rv_cap)
         self._chk(self.lib.opmgpu_set_dissolution_caps(self.ctx, None if a is None else capi.dptr(a), None if b is None else capi.dptr(b)))
 
+    # Analytic aquifers (opmgpu_set_aquifers; the rule is ours and stated in include/opmgpu.h)
+    aquifers = None                 # the list in force (objects with kind, p_a0, datum, ... cells, alpha: opmgpu.deck.Aquifer); None = none
+    _aquifer_step_begun = False
+
+    def setAquifers(self, aquifers):
+        """Fetkovich / Carter-Tracy aquifers as source terms of the water equation.  `aquifers`: a sequence of objects with kind
+        (capi.AQUIFER_FETKOVICH / AQUIFER_CARTER_TRACY), p_a0, datum, CtV0, J (Fetkovich) or beta, Tc, td, pd (Carter-Tracy), cells and
+        alpha (fractions summing to 1) -- opmgpu.deck.Aquifer -- or None / empty to remove them.  A new set starts with W_e = W_s = t =
+        0.  prepareStep(dt) then begins every time step, saveState() commits a converged one, restoreState() discards a failed one.
+        ValueError with the library's text when refused; the previous set stays in force."""
+        aq = list(aquifers or ())
+        if not aq:
+            self._chk(self.lib.opmgpu_set_aquifers(self.ctx, None))
+            self.aquifers, self._aquifer_step_begun = None, False
+            return
+        s = capi.AquifersSpec()
+        ct = [a.kind == capi.AQUIFER_CARTER_TRACY for a in aq]
+        tabs = [np.asarray(a.td, float) if c else np.zeros(0) for a, c in zip(aq, ct)]
+        for a, c, t in zip(aq, ct, tabs):
+            if c and np.asarray(a.pd, float).shape != t.shape:
+                raise ValueError("setAquifers: t_D and P_D of an influence table differ in length")
+        keep = dict(kind=capi.i32([a.kind for a in aq]), p_a0=capi.f64([a.p_a0 for a in aq]), datum=capi.f64([a.datum for a in aq]),
+                    CtV0=capi.f64([0.0 if c else a.CtV0 for a, c in zip(aq, ct)]), J=capi.f64([0.0 if c else a.J for a, c in zip(aq, ct)]),
+                    beta=capi.f64([a.beta if c else 0.0 for a, c in zip(aq, ct)]), Tc=capi.f64([a.Tc if c else 0.0 for a, c in zip(aq, ct)]),
+                    tab_ptr=capi.i32(np.concatenate([[0], np.cumsum([t.size for t in tabs])])),
+                    tab_td=capi.f64(np.concatenate(tabs + [np.zeros(1)])),
+                    tab_pd=capi.f64(np.concatenate([np.asarray(a.pd, float) if c else np.zeros(0) for a, c in zip(aq, ct)] + [np.zeros(1)])),
+                    conn_ptr=capi.i32(np.concatenate([[0], np.cumsum([len(a.cells) for a in aq])])),
+                    conn_cell=capi.i32(np.concatenate([np.asarray(a.cells, np.int64) for a in aq] + [np.zeros(1, np.int64)])),
+                    conn_alpha=capi.f64(np.concatenate([np.asarray(a.alpha, float) for a in aq] + [np.zeros(1)])))
+        for a in aq:
+            if len(a.cells) != len(a.alpha):
+                raise ValueError("setAquifers: %d fractions for %d connected cells" % (len(a.alpha), len(a.cells)))
+        s.naq = len(aq)
+        for k, v in keep.items():
+            setattr(s, k, capi.iptr(v) if v.dtype == np.int32 else capi.dptr(v))
+        self._chk(self.lib.opmgpu_set_aquifers(self.ctx, C.byref(s)))
+        self.aquifers, self._aquifer_step_begun = aq, False
+
+    def aquiferState(self):
+        """(W_e, W_s, t, p_a) per aquifer: cumulative reservoir and surface volume of influx, aquifer time, and the aquifer pressure they imply"""
+        n = len(self.aquifers or ())
+        out = [np.zeros(max(n, 1)) for _ in range(4)]
+        self._chk(self.lib.opmgpu_aquifer_state_get(self.ctx, *[capi.dptr(a) for a in out]))
+        return tuple(a[:n] for a in out)
+
+    def setAquiferState(self, W_e=None, W_s=None, t=None):
+        """the committed aquifer state (restart; tests); None leaves a column as it is.  A begun step is discarded."""
+        arr = [None if v is None else capi.f64(v) for v in (W_e, W_s, t)]
+        n = len(self.aquifers or ())
+        for a in arr:
+            if a is not None and a.shape != (n,):
+                raise ValueError("setAquiferState: one value per aquifer (%d aquifers)" % n)
+        self._chk(self.lib.opmgpu_aquifer_state_set(self.ctx, *[capi.dptr(a) for a in arr]))
+        self._aquifer_step_begun = False
+
+    def aquiferConnections(self):
+        """[nconn][6] of the begun step, connections in the listing order: rho0, p0, A, B and, at the resident state, q and qs = b_w q"""
+        n = sum(len(a.cells) for a in (self.aquifers or ()))
+        out = np.zeros((max(n, 1), capi.AQUIFER_CONN_K))
+        self._chk(self.lib.opmgpu_aquifer_connections_get(self.ctx, capi.dptr(out)))
+        return out[:n]
+
     # hysteresis history (SaturationPropsFromDeck::updateSatHyst, called once per report step: SimulatorBase_impl.hpp:190-191)
     def updateHysteresis(self):
         self._chk(self.lib.opmgpu_update_hysteresis(self.ctx))
@@ -561,6 +634,15 @@ class GpuBlackoilModel(_CprDiagnostics):
         rowptr, col, val = np.zeros(self.nc + 1, np.int32), np.zeros(n.value, np.int32), np.zeros((n.value, 9))
         self._chk(self.lib.opmgpu_get_jacobian_bsr(self.ctx, capi.iptr(rowptr), capi.iptr(col), capi.dptr(val)))
         return rowptr, col, val
+
+    def jacobianFloatCopy(self):
+        """mixed precision: the float copy of the double Jacobian written with the last assembly, widened, in jacobian()'s block order
+        (opmgpu_get_jacobian_float_copy; ValueError when the context holds none at the moment)"""
+        n = C.c_int32(0)
+        self._chk(self.lib.opmgpu_get_jacobian_nnzb(self.ctx, C.byref(n)))
+        val = np.zeros((n.value, 9))
+        self._chk(self.lib.opmgpu_get_jacobian_float_copy(self.ctx, capi.dptr(val)))
+        return val
 
     def spmv(self, x3):
         """y = J x with the assembled system (block-interleaved [nc][3]); with device wells J includes their factored

@@ -136,6 +136,11 @@ def attach_comm(model, dom, rank, world, unique_id, pressure_hierarchy=None):
         # the ghost cells' step-start Rs / Rv are not exchanged: dropping the limits here would let gas re-dissolve at once without a word
         # (opmgpu_comm_init refuses a context with limits, and opmgpu_set_dissolution_limits one with a communicator, for the same reason)
         raise ValueError("the model has dissolution limits (DRSDT / DRVDT): they are not supported in a decomposed run")
+    if getattr(model, "aquifers", None) is not None:
+        # an aquifer's connections may sit on several ranks and its influx sums are rank-local: dropping the aquifers here would run the
+        # deck as a closed box without a word (opmgpu_comm_init refuses a context with aquifers, and opmgpu_set_aquifers one with a
+        # communicator, for the same reason)
+        raise ValueError("the model has analytic aquifers (AQUFETP / AQUCT): they are not supported in a decomposed run")
     lib = capi.load()
     lists = (dom.n_owned, int(dom.neigh_rank.size), capi.iptr(dom.neigh_rank), capi.iptr(dom.send_ptr), capi.iptr(dom.send_cells),
              capi.iptr(dom.recv_ptr), capi.iptr(dom.recv_cells))

@@ -2,7 +2,8 @@
 (opm/autodiff/SimulatorBase_impl.hpp:90-324), reduced to what an external diff needs:
 
     deck -> grid / tables / initial state (EQUIL, with SWATINIT) -> [SWATINIT: setSwatInitScaling] -> [THPRES: computeMaxDp of the
-    initial state, setThresholdPressures] -> set the state (the order of FlowMain::setupState, FlowMain.hpp:636-692) -> for every report
+    initial state, setThresholdPressures] -> set the state (the order of FlowMain::setupState, FlowMain.hpp:636-692) -> [AQUFETP / AQUCT:
+    setAquifers, once] -> for every report
     step of the SCHEDULE: the step's dissolution limits (DRSDT / DRVDT), wells of the step (WellsManager), well state carried over by name, updateSatOilMax + updateSatHyst (:190-192), AdaptiveTimeStepping.step with the NonlinearSolver (:236-253),
     restart + summary output (:300-306).
 
@@ -88,6 +89,16 @@ class Simulator:
             self.threshold_pressures = self.deck.threshold_pressures(self.grid, max_dp)
             self.model.setThresholdPressures(self.threshold_pressures)
             set_state(self.state0)
+        # AQUFETP / AQUCT + AQUANCON: installed once, behind the initial state; the context carries them and their state through the
+        # report steps' well re-plans (the rule is the device's own, include/opmgpu.h)
+        self.aquifers = self.deck.aquifers(self.tables)
+        if self.aquifers:
+            # a model without the setter (the CPU oracle behind the host well model) would run the deck as a closed box, without a word
+            if not hasattr(self.model, "setAquifers"):
+                raise ValueError("the deck has analytic aquifers (AQUFETP / AQUCT), but the model cannot take them (setAquifers)")
+            if self.start_step > 0:
+                raise ValueError("the deck has analytic aquifers: a restarted run is not supported (the restart file does not carry the aquifers' state)")
+            self.model.setAquifers(self.aquifers)
         self.ats = ats or ts.AdaptiveTimeStepping(initial_timestep_days=1.0)
         if getattr(self, "_restart_dtnx", None) is not None:
             self.ats.suggested_next_timestep = self._restart_dtnx
@@ -194,6 +205,9 @@ class Simulator:
                                  "linear": rep["linear_iterations"], "failed": len(rep["failed"])})
             if hasattr(gm, "computeFluidInPlace"):      # COIP of SimulatorBase_impl.hpp:278: values[region][7] at the end of every report step
                 self.reports[-1]["fip"] = gm.computeFluidInPlace(self.fipnum)
+            if self.aquifers:                             # per aquifer (W_e, W_s, p_a): cumulative influx, reservoir and surface volume, and its pressure
+                we, wsurf, _, pa = gm.aquiferState()
+                self.reports[-1]["aquifers"] = [(float(a), float(b), float(c)) for a, b, c in zip(we, wsurf, pa)]
             if self.out:
                 extra = {}
                 rpt = self.schedule.rptrst[step]
