@@ -742,6 +742,57 @@ int opmgpu_begin_dissolution_step(opmgpu_ctx* ctx, double dt);
 int opmgpu_get_dissolution_caps(opmgpu_ctx* ctx, double* rs_cap /* [nc] or NULL */, double* rv_cap /* [nc] or NULL */);
 int opmgpu_set_dissolution_caps(opmgpu_ctx* ctx, const double* rs_cap /* [nc] or NULL */, const double* rv_cap /* [nc] or NULL */);
 
+/* Rock regions and irreversible compaction (ROCKCOMP, ROCKNUM): a rock per cell instead of the one rock of opmgpu_tables, and pore volume
+ * and transmissibility that do not come back when the pressure recovers.  The reference holds one table and has neither keyword, so THE
+ * RULE IS OURS; it is stated here, restated independently under tests/ and pinned to no other simulator.
+ *
+ * Per context: nregions >= 1, a region r = rocknum[c] (0-based) per cell, and a mode, OPMGPU_ROCK_REVERSIBLE or OPMGPU_ROCK_IRREVERSIBLE.
+ * A region has either a TABLE -- rows tab_ptr[r] .. tab_ptr[r+1] of (p, pv_mult, trans_mult), at least 2 rows, p strictly increasing --
+ * or, with 0 rows, the ROCK FORM: the pair (rock_pref[r], rock_comp[r]) in the quadratic form of opmgpu_tables: pv_mult = 1 + X + X^2 / 2,
+ * X = rock_comp (p - rock_pref), and transmissibility multiplier 1.  The context carries one history plane p_min[nc], which starts at +inf.
+ *
+ * Evaluator (every kernel that evaluates a cell, three-phase and OPMGPU_PHASES_OIL_WATER).  For a cell c in a table region:
+ *   on_curve = (mode == OPMGPU_ROCK_REVERSIBLE) || (p <= p_min[c])        a tie is on the curve: a cell that goes on declining needs the slope
+ *   x        = on_curve ? p : p_min[c]
+ *   pv_mult  = L(pv table of r, x),  trans_mult = L(trans table of r, x)
+ * where L is ROCKTAB's rule (opmgpu_tables): piecewise linear, at a breakpoint the LEFT segment, beyond both ends the end segment
+ * extrapolated; y_i + slope_i (x - x_i) with slope_i = (y_(i+1) - y_i) / (x_(i+1) - x_i) formed once, in float64.  d/dp of both is
+ * slope_i when on_curve, else exactly 0.0.  A ROCK-form region is always evaluated at p (elastic), whatever the mode.  Nothing else in
+ * the evaluator changes: pv_mult enters every accumulation term, trans_mult multiplies the three mobilities of the cell, as the one
+ * ROCKTAB of opmgpu_tables does.  While regions are set the rock fields of opmgpu_tables are not read.
+ *
+ * History.  opmgpu_update_rock_history: one kernel, one thread per cell, p_min[c] = fmin(p_min[c], p[c]) from the RESIDENT state (exact:
+ * a float64 restatement matches bit for bit).  The caller runs it once on the initial (or restarted) state and after every converged
+ * sub-step.  opmgpu_save_state / opmgpu_restore_state do not touch p_min: a failed sub-step never updated it.  Regions and p_min last
+ * through opmgpu_set_wells / opmgpu_set_device_wells (a re-plan), a change of the solve precision and save / restore.  In REVERSIBLE mode
+ * p_min is kept and updated all the same; no evaluator reads it.
+ *
+ * set_rock_regions(NULL) removes the regions (and p_min): the context is again the one that never had any, and runs the kernels that one
+ * runs.  A new set of regions keeps p_min.  OPMGPU_EINVAL (with text, the previous set stays in force) for: a NULL array; nregions < 1; a rocknum outside [0, nregions); an
+ * unknown mode; tab_ptr not starting at 0 or decreasing; a table of exactly 1 row; a p that is not strictly increasing; a non-finite
+ * entry; pv_mult <= 0; trans_mult < 0; a non-finite rock_pref / rock_comp; a PVCDO context or a context with dissolution limits
+ * (opmgpu_set_pvcdo and opmgpu_set_dissolution_limits in turn refuse a context with rock regions).  set_rock_history (restart): a NaN, or
+ * no regions are set.  get_rock_history without regions gives +inf.  get_rock_multipliers: pv_mult and trans_mult of every cell at the
+ * resident state (one kernel; either pointer may be NULL; without regions the multipliers of the rock of opmgpu_tables); OPMGPU_EINVAL
+ * before a state has been set.
+ *
+ * Decomposed runs are rank-local: a rank passes the regions of its local cells, ghosts included (a ghost's trans_mult enters the owner's
+ * flux), and updates its own plane; nothing is communicated. */
+#define OPMGPU_ROCK_REVERSIBLE 0
+#define OPMGPU_ROCK_IRREVERSIBLE 1
+typedef struct opmgpu_rock_regions {
+    int32_t nregions, mode;
+    const int32_t* rocknum;                            /* [nc] caller order, 0-based */
+    const double  *rock_pref, *rock_comp;              /* [nregions] */
+    const int32_t* tab_ptr;                            /* [nregions+1] */
+    const double  *tab_p, *tab_pvmult, *tab_transmult; /* [tab_ptr[nregions]] */
+} opmgpu_rock_regions;
+int opmgpu_set_rock_regions(opmgpu_ctx* ctx, const opmgpu_rock_regions* regions /* NULL: back to the rock of opmgpu_tables */);
+int opmgpu_update_rock_history(opmgpu_ctx* ctx);
+int opmgpu_get_rock_history(opmgpu_ctx* ctx, double* p_min /* [nc] */);
+int opmgpu_set_rock_history(opmgpu_ctx* ctx, const double* p_min /* [nc] */);
+int opmgpu_get_rock_multipliers(opmgpu_ctx* ctx, double* pv_mult /* [nc] or NULL */, double* trans_mult /* [nc] or NULL */);
+
 /* Analytic aquifers (AQUFETP: Fetkovich, AQUCT: Carter-Tracy, connected by AQUANCON) as source terms of the water equation.  The reference
  * has no aquifers, so THE RULE IS OURS; it is stated here, restated independently under tests/ (tests/aquifer_reference.py) and pinned to
  * no other simulator.  All quantities are SI.  Every product and sum below is ONE IEEE float64 operation, evaluated in the order the

@@ -50,7 +50,7 @@ __global__ __launch_bounds__(kBlock) void k_cell_values(int nb, int nbp, DevTabl
         hyst_load<KM>(hy.imbnum, hy.hist, nbp, row, H);
         if (H.on) eps_load(hy.ieps, hy.iureg, nbp, row, H.ireg, EI);
         eval_cell<false, KM>(D, E, (D.t.vap1 > 0.0 || D.t.vap2 > 0.0) ? somax[row] : 0.0, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], row, q, H, &EI, nullptr,
-                             rs_cap_of<KM>(somax, nbp, row), rv_cap_of<KM>(somax, nbp, row));
+                             rs_cap_of<KM>(somax, nbp, row), rv_cap_of<KM>(somax, nbp, row), rocknum_of<KM>(satnum, nbp, row), rock_pmin_of<KM>(somax, nbp, row));
         // (no gas phase: the five water / oil planes only -- nobody reads the other five --, and 1 / b_g = 1 per cell)
         constexpr int NP = km_model(KM) == KM_OW ? 2 : 3;
         vals[long(VP_PW) * nbp + row] = q.pw.v; if constexpr (NP == 3) vals[long(VP_PG) * nbp + row] = q.pg.v;
@@ -82,7 +82,7 @@ __global__ __launch_bounds__(kBlock) void k_cell_values(int nb, int nbp, DevTabl
 // Shapes: MS the Jacobian's precision, LDS the tables staged in LDS (the blob fits), DUAL a float copy of a double Jacobian written in the
 // same pass, KM the model.  Compiled for 3 waves per SIMD in the default model's plain LDS shape and for 2 everywhere else
 // (asm_rows_waves; the two concluded experiments behind that are quoted at assemble_kernels).
-constexpr int asm_rows_waves(bool lds, bool dual, int km) { return km == KM_DEFAULT && lds && !dual ? 3 : 2; }      // (the KM_DRDT shapes were never tuned: 2)
+constexpr int asm_rows_waves(bool lds, bool dual, int km) { return km == KM_DEFAULT && lds && !dual ? 3 : 2; }      // (the KM_DRDT and KM_ROCK shapes were never tuned: 2)
 template <class MS, bool LDS, bool DUAL, int KM>
 __global__ __launch_bounds__(kBlock, asm_rows_waves(LDS, DUAL, KM)) void k_assemble_rows(int xm, int nb, int nbp, DevTables DT, const int32_t* __restrict__ pvtnum, const int32_t* __restrict__ satnum,
                                                           const double* __restrict__ pv, const double* __restrict__ p, const double* __restrict__ sw,
@@ -119,7 +119,7 @@ __global__ __launch_bounds__(kBlock, asm_rows_waves(LDS, DUAL, KM)) void k_assem
         hyst_load<KM>(hy.imbnum, hy.hist, nbp, row, H);
         if (H.on) eps_load(hy.ieps, hy.iureg, nbp, row, H.ireg, EI);
         eval_cell<false, KM>(DT, E, (DT.t.vap1 > 0.0 || DT.t.vap2 > 0.0) ? somax[row] : 0.0, pvtnum[row], satnum[row], p[row], sw[row], sg[row], rs[row], rv[row], hc[row], row, q, H, &EI, nullptr,
-                             rs_cap_of<KM>(somax, nbp, row), rv_cap_of<KM>(somax, nbp, row));
+                             rs_cap_of<KM>(somax, nbp, row), rv_cap_of<KM>(somax, nbp, row), rocknum_of<KM>(satnum, nbp, row), rock_pmin_of<KM>(somax, nbp, row));
     }
     // NP == 2, a deck without a gas phase (KM_OW): only water and oil flow.  Neither the own nor the neighbour's p_g, gas density, gas
     // b * mobility, rs and rv planes are loaded (5 of the 10 dependent loads per connection), the gas equation is the identity row and
@@ -913,6 +913,12 @@ template <class F> static auto kernel_by_shape(bool lds, int km, F&& pick)
 {
     auto by_model = [&](auto L) {
         // dissolution limits (KM_DRDT): the three three-phase models with the tabulated oil, nothing else (set_dissolution_limits refuses the rest)
+        if (km_rock(km)) {      // rock regions (KM_ROCK): the four models with the tabulated oil and without limits (set_rock_regions refuses the rest)
+            auto by_rock = [&](auto K) { return pick(L, std::integral_constant<int, decltype(K)::value | KM_ROCK>{}); };
+            return km_model(km) == KM_OW ? by_rock(std::integral_constant<int, KM_OW>{})
+                 : km_model(km) == KM_STONE ? by_rock(std::integral_constant<int, KM_STONE>{})
+                 : km_model(km) == KM_KILLOUGH ? by_rock(std::integral_constant<int, KM_KILLOUGH>{}) : by_rock(std::integral_constant<int, KM_DEFAULT>{});
+        }
         if (km_drdt(km))
             return km_model(km) == KM_STONE ? pick(L, std::integral_constant<int, KM_STONE | KM_DRDT>{})
                  : km_model(km) == KM_KILLOUGH ? pick(L, std::integral_constant<int, KM_KILLOUGH | KM_DRDT>{}) : pick(L, std::integral_constant<int, KM_DEFAULT | KM_DRDT>{});
@@ -1336,16 +1342,17 @@ __global__ __launch_bounds__(kBlock) void k_dissolution_caps(int nb, const doubl
     rs_cap[c] = (on_s && !(free_only && sg[c] == 0.0)) ? rs[c] + d_s : inf;
     rv_cap[c] = on_v ? rv[c] + d_v : inf;
 }
-// d_somax with (so_max | rs_cap | rv_cap) or without the planes of the caps, so_max kept; new caps are +inf (padding rows included)
+// d_somax with (so_max | rs_cap | rv_cap) or without the planes of the caps, so_max kept; new caps are +inf (padding rows included).
+// A context with rock regions (never one with caps) has two planes, so_max | p_min, a new p_min +inf likewise.
 void BlackoilDevice::resize_somax(bool with_caps)
 {
-    const size_t nbp = size_t(ls.plan.nbp);
-    if (d_somax.n == (with_caps ? 3 : 1) * nbp) return;
+    const size_t nbp = size_t(ls.plan.nbp), planes = with_caps ? 3 : (rock_on() ? 2 : 1);
+    if (d_somax.n == planes * nbp) return;
     OPMGPU_HIP(hipStreamSynchronize(stream));        // no kernel in flight reads the array that is replaced
     std::vector<double> h(3 * nbp, std::numeric_limits<double>::infinity());
     d_somax.download(h.data(), nbp, stream);
     OPMGPU_HIP(hipStreamSynchronize(stream));
-    d_somax.alloc((with_caps ? 3 : 1) * nbp);
+    d_somax.alloc(planes * nbp);
     d_somax.upload(h.data(), d_somax.n, stream);
     OPMGPU_HIP(hipStreamSynchronize(stream));
 }
@@ -1361,6 +1368,7 @@ void BlackoilDevice::set_dissolution_limits(double a_s, int free_only, double a_
         if (on_s && !dto_.t.has_disgas) throw HipError(OPMGPU_EINVAL, std::string(who) + "drsdt needs dissolved gas (has_disgas)");
         if (on_v && !dto_.t.has_vapoil) throw HipError(OPMGPU_EINVAL, std::string(who) + "drvdt needs vaporised oil (has_vapoil)");
         if (ls.comm) throw HipError(OPMGPU_EINVAL, std::string(who) + "a communicator is attached; a decomposed run does not support dissolution limits");
+        if (rock_on()) throw HipError(OPMGPU_EINVAL, std::string(who) + "the context has rock regions (opmgpu_set_rock_regions); dissolution limits are not supported with them");
     }
     drsdt = on_s ? a_s : -1.0; drsdt_free_only = on_s && free_only != 0; drvdt = on_v ? a_v : -1.0;
     resize_somax(drdt_on());
@@ -1402,6 +1410,126 @@ void BlackoilDevice::set_dissolution_caps(const double* rs_cap, const double* rv
         OPMGPU_HIP(hipMemcpyAsync(d_somax.p + (1 + k) * nbp, h.data(), nbp * sizeof(double), hipMemcpyHostToDevice, stream));
         OPMGPU_HIP(hipStreamSynchronize(stream));
     }
+}
+
+// ---- rock regions and irreversible compaction (the rule is stated in include/opmgpu.h at opmgpu_set_rock_regions) ---------------------------
+// The regions' tables ride in the blob behind everything else (upload_rock_tables), rocknum behind satnum and p_min behind so_max
+// (rocknum_of / rock_pmin_of): no kernel has an argument more, and only the KM_ROCK instantiations read any of it.  The two kernels of
+// the history and of the multipliers are in blackoil_output.hip.
+void BlackoilDevice::set_rock_regions(const opmgpu_rock_regions* s)
+{
+    const std::string who = "opmgpu_set_rock_regions: ";
+    auto bad = [&](const std::string& what) { return HipError(OPMGPU_EINVAL, who + what); };
+    if (!s) {
+        if (!rock_on()) return;
+        OPMGPU_HIP(hipStreamSynchronize(stream));
+        h_rocknum.clear(); h_rock_ptr.clear(); h_rock_ref.clear(); h_rock_tab.clear(); rock_mode = OPMGPU_ROCK_REVERSIBLE;
+        upload_rock_tables();
+        upload_region_numbers();
+        resize_somax(drdt_on());
+        return;
+    }
+    // everything is checked before anything changes: a refused set leaves the previous one in force
+    if (s->nregions < 1) throw bad("nregions is smaller than 1");
+    if (s->mode != OPMGPU_ROCK_REVERSIBLE && s->mode != OPMGPU_ROCK_IRREVERSIBLE) throw bad("unknown mode " + std::to_string(s->mode));
+    if (!s->rocknum || !s->rock_pref || !s->rock_comp || !s->tab_ptr) throw bad("rocknum, rock_pref, rock_comp or tab_ptr is NULL");
+    const int nr = s->nregions;
+    if (s->tab_ptr[0] != 0) throw bad("tab_ptr does not start at 0");
+    for (int r = 0; r < nr; ++r) {
+        const int n = s->tab_ptr[r + 1] - s->tab_ptr[r];
+        if (n < 0) throw bad("tab_ptr decreases at region " + std::to_string(r));
+        if (n == 1) throw bad("the table of region " + std::to_string(r) + " has exactly 1 row (0 = the ROCK form, else at least 2)");
+    }
+    const int rows = s->tab_ptr[nr];
+    if (rows > 0 && (!s->tab_p || !s->tab_pvmult || !s->tab_transmult)) throw bad("tab_p, tab_pvmult or tab_transmult is NULL");
+    for (int c = 0; c < nc; ++c)
+        if (s->rocknum[c] < 0 || s->rocknum[c] >= nr) throw bad("rocknum of cell " + std::to_string(c) + " is outside [0, nregions)");
+    for (int r = 0; r < nr; ++r) {
+        if (!std::isfinite(s->rock_pref[r]) || !std::isfinite(s->rock_comp[r])) throw bad("rock_pref or rock_comp of region " + std::to_string(r) + " is not finite");
+        for (int i = s->tab_ptr[r]; i < s->tab_ptr[r + 1]; ++i) {
+            const std::string at = "row " + std::to_string(i - s->tab_ptr[r]) + " of the table of region " + std::to_string(r);
+            if (!std::isfinite(s->tab_p[i]) || !std::isfinite(s->tab_pvmult[i]) || !std::isfinite(s->tab_transmult[i])) throw bad(at + " has an entry that is not finite");
+            if (!(s->tab_pvmult[i] > 0.0)) throw bad("pv_mult in " + at + " is not positive");
+            if (s->tab_transmult[i] < 0.0) throw bad("trans_mult in " + at + " is negative");
+            if (i > s->tab_ptr[r] && !(s->tab_p[i] > s->tab_p[i - 1])) throw bad("p in " + at + " is not above the row before it (strictly increasing)");
+        }
+    }
+    if (dtp_.x.oil_pvcdo) throw bad("the context has the analytic dead oil (opmgpu_set_pvcdo); rock regions are not supported with it");
+    if (drdt_on()) throw bad("the context has dissolution limits (opmgpu_set_dissolution_limits); rock regions are not supported with them");
+    // the history lasts through a new set of regions (a schedule may change them); the first set starts it at +inf
+    OPMGPU_HIP(hipStreamSynchronize(stream));
+    h_rocknum.assign(s->rocknum, s->rocknum + nc);
+    h_rock_ptr.assign(s->tab_ptr, s->tab_ptr + nr + 1);
+    h_rock_ref.resize(2 * size_t(nr));
+    for (int r = 0; r < nr; ++r) { h_rock_ref[2 * size_t(r)] = s->rock_pref[r]; h_rock_ref[2 * size_t(r) + 1] = s->rock_comp[r]; }
+    // five planes p | pv_mult | slopes | trans_mult | slopes; a slope is the segment's, formed once here by the IEEE division
+    const size_t m = size_t(std::max(rows, 1));
+    h_rock_tab.assign(5 * m, 0.0);
+    for (int i = 0; i < rows; ++i) { h_rock_tab[i] = s->tab_p[i]; h_rock_tab[m + i] = s->tab_pvmult[i]; h_rock_tab[3 * m + i] = s->tab_transmult[i]; }
+    for (int r = 0; r < nr; ++r)
+        for (int i = s->tab_ptr[r]; i + 1 < s->tab_ptr[r + 1]; ++i) {
+            const double h = s->tab_p[i + 1] - s->tab_p[i];
+            h_rock_tab[2 * m + i] = (s->tab_pvmult[i + 1] - s->tab_pvmult[i]) / h;
+            h_rock_tab[4 * m + i] = (s->tab_transmult[i + 1] - s->tab_transmult[i]) / h;
+        }
+    rock_mode = s->mode;
+    upload_rock_tables();
+    upload_region_numbers();
+    resize_somax(false);
+}
+// the blob as upload_tables formed it, with the regions' arrays behind it when there are regions (never together with PVCDO rows)
+void BlackoilDevice::upload_rock_tables()
+{
+    std::vector<double> blob = h_tab;
+    opmgpu_tables& t = dto_.t;
+    t.rock_pref = plain_rock_.rock_pref; t.rock_comp = plain_rock_.rock_comp; t.rocktab_n = plain_rock_.rocktab_n;
+    t.rocktab_p = plain_rock_.rocktab_p; t.rocktab_pvmult = plain_rock_.rocktab_pvmult; t.rocktab_transmult = plain_rock_.rocktab_transmult;
+    if (rock_on()) {        // the rock fields carry the regions (RockView, fluid_eval.hpp); word offsets like every pointer of dto_
+        const size_t np = h_rock_ptr.size();
+        t.rocktab_transmult = reinterpret_cast<const double*>(blob.size());
+        blob.resize(blob.size() + (np + 1) / 2, 0.0);
+        std::memcpy(&blob[blob.size() - (np + 1) / 2], h_rock_ptr.data(), np * sizeof(int32_t));
+        t.rocktab_pvmult = reinterpret_cast<const double*>(blob.size());
+        blob.insert(blob.end(), h_rock_ref.begin(), h_rock_ref.end());
+        t.rocktab_p = reinterpret_cast<const double*>(blob.size());
+        blob.insert(blob.end(), h_rock_tab.begin(), h_rock_tab.end());
+        t.rocktab_n = int32_t(h_rock_tab.size() / 5); t.rock_pref = 0.0; t.rock_comp = double(rock_mode);
+    }
+    OPMGPU_HIP(hipStreamSynchronize(stream));        // no kernel in flight reads the blob that upload may replace
+    upload_blob(blob);
+}
+// d_satnum for the current plan: the saturation regions and, with rock regions, the rock regions behind them (internal numbering)
+void BlackoilDevice::upload_region_numbers()
+{
+    const Plan& P = ls.plan;
+    const size_t nbp = size_t(P.nbp);
+    std::vector<int32_t> sn((rock_on() ? 2 : 1) * nbp, 0);
+    for (int r = 0; r < nc; ++r) { sn[r] = h_satnum[P.nat[r]]; if (rock_on()) sn[nbp + r] = h_rocknum[P.nat[r]]; }
+    OPMGPU_HIP(hipStreamSynchronize(stream));
+    d_satnum.alloc(sn.size());
+    d_satnum.upload(sn, stream);
+    OPMGPU_HIP(hipStreamSynchronize(stream));
+}
+// p_min in the caller's cell order (restart, tests); +inf without regions
+void BlackoilDevice::get_rock_history(double* p_min)
+{
+    const Plan& P = ls.plan;
+    const size_t nbp = size_t(P.nbp);
+    std::vector<double> h(nbp, std::numeric_limits<double>::infinity());
+    if (rock_on()) { OPMGPU_HIP(hipMemcpyAsync(h.data(), d_somax.p + nbp, nbp * sizeof(double), hipMemcpyDeviceToHost, stream)); OPMGPU_HIP(hipStreamSynchronize(stream)); }
+    for (int r = 0; r < nc; ++r) p_min[P.nat[r]] = h[r];
+}
+void BlackoilDevice::set_rock_history(const double* p_min)
+{
+    if (!rock_on()) throw HipError(OPMGPU_EINVAL, "opmgpu_set_rock_history: no rock regions are set (opmgpu_set_rock_regions)");
+    if (!p_min) throw HipError(OPMGPU_EINVAL, "opmgpu_set_rock_history: p_min is NULL");
+    for (int c = 0; c < nc; ++c) if (std::isnan(p_min[c])) throw HipError(OPMGPU_EINVAL, "opmgpu_set_rock_history: p_min of cell " + std::to_string(c) + " is NaN");
+    const Plan& P = ls.plan;
+    const size_t nbp = size_t(P.nbp);
+    std::vector<double> h(nbp, std::numeric_limits<double>::infinity());
+    for (int r = 0; r < nc; ++r) h[r] = p_min[P.nat[r]];
+    OPMGPU_HIP(hipMemcpyAsync(d_somax.p + nbp, h.data(), nbp * sizeof(double), hipMemcpyHostToDevice, stream));
+    OPMGPU_HIP(hipStreamSynchronize(stream));
 }
 
 void BlackoilDevice::stabilize_update(int relax_type, double omega)

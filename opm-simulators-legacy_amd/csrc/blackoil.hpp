@@ -25,6 +25,9 @@ struct TabX {
     // the offset form, where nobody reads it: the kernels that take that form are instantiated for the oil (KM_PVCDO).
     const double* oil_pvcdo;
 };
+// Rock regions (opmgpu_set_rock_regions) add NO field to the device form: while they are set nobody reads the one rock of opmgpu_tables,
+// so its fields carry the regions instead (RockView in fluid_eval.hpp says how) -- every kernel's argument block, and with it the code of
+// every instantiation a context without regions runs, is what it was.
 // stone_som: Stone I's residual oil saturation Som = min(SOWCR, SOGCR) of every cell (internal numbering), a device pointer in EVERY form of
 // the tables (it is no table: a per-cell plane that rides here so that each launch site of eval_cell sees it); null unless the model is
 // OPMGPU_KRO_STONE1.  The model itself and the per-region exponent are t.threephase_model and t.stone1_exponent (in the blob).
@@ -43,10 +46,14 @@ enum { VP_PW = 0, VP_PG = 1, VP_RHO = 2 /* + phase */, VP_U = 5 /* + phase */, V
 // KM_DRDT, or-ed to KM_DEFAULT, KM_STONE or KM_KILLOUGH (never with KM_OW or KM_PVCDO: refused): the cell's saturated rs / rv are capped by the
 // dissolution limits of opmgpu_set_dissolution_limits (DRSDT / DRVDT; km_drdt) -- a template parameter for the same reason: a context
 // without limits runs exactly the instantiations it ran before the limits existed.
-enum { KM_DEFAULT = 0, KM_STONE = 1, KM_OW = 2, KM_KILLOUGH = 3, KM_PVCDO = 4, KM_DRDT = 8 };
+// KM_ROCK, or-ed to any of the four models (never with KM_PVCDO or KM_DRDT: refused): the cell's pore-volume and transmissibility multipliers
+// come from its rock region's table, evaluated at min(p, p_min) under irreversible compaction (opmgpu_set_rock_regions; km_rock) -- a
+// template parameter once more, so that a context without rock regions runs exactly the instantiations it ran before they existed.
+enum { KM_DEFAULT = 0, KM_STONE = 1, KM_OW = 2, KM_KILLOUGH = 3, KM_PVCDO = 4, KM_DRDT = 8, KM_ROCK = 16 };
 constexpr int km_model(int km) { return km & 3; }
 constexpr bool km_pvcdo(int km) { return (km & KM_PVCDO) != 0; }
 constexpr bool km_drdt(int km) { return (km & KM_DRDT) != 0; }
+constexpr bool km_rock(int km) { return (km & KM_ROCK) != 0; }
 
 constexpr int kRedPart = 32;        // d_red: [0, 32) results, per-workgroup partials behind them
 
@@ -103,6 +110,13 @@ public:
     void get_dissolution_caps(double* rs_cap, double* rv_cap);
     void set_dissolution_caps(const double* rs_cap, const double* rv_cap);
     bool has_dissolution_limits() const { return drdt_on(); }
+    // rock regions and irreversible compaction (the rule: opmgpu_set_rock_regions in include/opmgpu.h); all throw HipError(OPMGPU_EINVAL) with the reason
+    void set_rock_regions(const opmgpu_rock_regions* spec);     // nullptr removes them
+    void update_rock_history();
+    void get_rock_history(double* p_min);
+    void set_rock_history(const double* p_min);
+    void get_rock_multipliers(double* pv_mult, double* trans_mult);
+    bool has_rock_regions() const { return rock_on(); }
     // analytic aquifers (aquifer.hip; the rule: opmgpu_set_aquifers in include/opmgpu.h); all throw HipError with the reason
     struct AquiferDev;
     void set_aquifers(const opmgpu_aquifers* spec);         // nullptr or naq == 0 removes them
@@ -220,6 +234,17 @@ private:
     bool drsdt_free_only = false;
     bool drdt_on() const { return drsdt >= 0.0 || drvdt >= 0.0; }
     void resize_somax(bool with_caps);
+    // Rock regions: the host copy of what opmgpu_set_rock_regions took (rocknum in the caller's order; empty = none).  With regions
+    // d_somax holds two planes so_max | p_min and d_satnum two planes satnum | rocknum (stride nbp; rock_pmin_of / rocknum_of): like the
+    // dissolution caps they ride where an argument of every evaluating kernel rides already.  p_min is no part of the state that
+    // save / restore copy, and a re-plan carries it over.
+    std::vector<int32_t> h_rocknum, h_rock_ptr;
+    std::vector<double> h_rock_ref, h_rock_tab;
+    int rock_mode = 0;
+    bool rock_on() const { return !h_rocknum.empty(); }
+    void upload_rock_tables();              // the blob with or without the regions' tables behind it
+    opmgpu_tables plain_rock_;              // the rock fields of dto_.t as upload_tables formed them (offset form): what removing the regions puts back
+    void upload_region_numbers();           // d_satnum (satnum | rocknum) for the current plan
     int hyst_model = OPMGPU_HYST_CARLSON;    // opmgpu_set_hysteresis_model: no part of the state, of the plan or of the tables
     double killough_a = 0.1;
     void launch_hyst_update(int force);
@@ -242,7 +267,7 @@ private:
     int tab_words = 0;
     static constexpr int kTabLdsMaxBytes = 24 * 1024;     // 6 workgroups x 24 KiB fit the 160 KiB LDS of a CU: no occupancy lost
     // chooses the kernels' KM instantiations (eval_cell)
-    int kmodel() const { return kmodel_plain() | (drdt_on() ? KM_DRDT : 0); }
+    int kmodel() const { return kmodel_plain() | (drdt_on() ? KM_DRDT : 0) | (rock_on() ? KM_ROCK : 0); }
     int kmodel_plain() const { return (oil_water() ? KM_OW : (dto_.t.threephase_model != OPMGPU_KRO_DEFAULT ? KM_STONE : (use_hyst && hyst_model == OPMGPU_HYST_KILLOUGH ? KM_KILLOUGH : KM_DEFAULT))) | (dtp_.x.oil_pvcdo ? KM_PVCDO : 0); }
     bool oil_water() const { return dto_.t.active_phases == OPMGPU_PHASES_OIL_WATER; }
     int tab_lds_words() const { return tab_words * 8 <= kTabLdsMaxBytes ? tab_words : 0; }

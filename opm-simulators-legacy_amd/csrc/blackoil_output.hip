@@ -330,6 +330,59 @@ void BlackoilDevice::check_global_region_count(int n, const char* who)
     if (int(nmax + 0.5) != n) throw HipError(OPMGPU_EINVAL, std::string(who) + ": pass the GLOBAL number of regions on every rank of a decomposed run");
 }
 
+// Rock regions (the rule: include/opmgpu.h at opmgpu_set_rock_regions).  The history, one thread per cell: the smallest pressure the cell
+// has seen.  fmin of two finite doubles (or +inf) is exact, so a float64 restatement matches bit for bit.
+__global__ __launch_bounds__(kBlock) void k_rock_history(int nb, const double* __restrict__ p, double* __restrict__ p_min)
+{
+    const int c = blockIdx.x * kBlock + threadIdx.x;
+    if (c < nb) p_min[c] = fmin(p_min[c], p[c]);
+}
+// The two multipliers of every cell at the resident state, in the CALLER's cell order (either output may be null): what the evaluators
+// form (rock_region_eval) with rock regions, else the one rock of the tables as eval_cell reads it.
+template <bool ROCK>
+__global__ __launch_bounds__(kBlock) void k_rock_multipliers(int nc, DevTables D, const int32_t* __restrict__ nat, CellPlanes C, double* __restrict__ pv_mult,
+                                                             double* __restrict__ trans_mult)
+{
+    const int c = blockIdx.x * kBlock + threadIdx.x;
+    if (c >= nc) return;
+    const double p = C.p[c];
+    double pvm = 1.0, trm = 1.0, d0, d1;
+    if constexpr (ROCK) {
+        bool table;
+        rock_region_eval(D.t, rocknum_of<KM_ROCK>(C.satnum, C.nbp, c), p, rock_pmin_of<KM_ROCK>(C.somax, C.nbp, c), table, pvm, d0, trm, d1);
+    } else {
+        const opmgpu_tables& T = D.t;
+        if (T.rocktab_n > 0) {
+            rocktab_eval(T.rocktab_p, T.rocktab_pvmult, T.rocktab_n, p, pvm, d0);
+            rocktab_eval(T.rocktab_p, T.rocktab_transmult, T.rocktab_n, p, trm, d1);
+        } else if (T.rock_comp != 0.0) {
+            const double cp = T.rock_comp * (p - T.rock_pref);
+            pvm = 1.0 + cp + 0.5 * cp * cp;
+        }
+    }
+    if (pv_mult) pv_mult[nat[c]] = pvm;
+    if (trans_mult) trans_mult[nat[c]] = trm;
+}
+void BlackoilDevice::update_rock_history()
+{
+    if (!rock_on()) throw HipError(OPMGPU_EINVAL, "opmgpu_update_rock_history: no rock regions are set (opmgpu_set_rock_regions)");
+    if (!has_state) throw HipError(OPMGPU_EINVAL, "opmgpu_update_rock_history: no state is resident (opmgpu_set_state)");
+    hipLaunchKernelGGL(k_rock_history, dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, (const double*)d_p.p, d_somax.p + size_t(ls.plan.nbp));
+    OPMGPU_HIP(hipGetLastError());
+}
+void BlackoilDevice::get_rock_multipliers(double* pv_mult, double* trans_mult)
+{
+    if (!has_state) throw HipError(OPMGPU_EINVAL, "opmgpu_get_rock_multipliers: no state is resident (opmgpu_set_state)");
+    DevArray<double> dout; dout.alloc(2 * size_t(nc));
+    auto kern = rock_on() ? k_rock_multipliers<true> : k_rock_multipliers<false>;
+    hipLaunchKernelGGL(kern, dim3(grid_for(nc)), dim3(kBlock), 0, stream, nc, dtp_, ls.dp.nat.p, cell_planes(), pv_mult ? dout.p : (double*)nullptr,
+                       trans_mult ? dout.p + nc : (double*)nullptr);
+    OPMGPU_HIP(hipGetLastError());
+    if (pv_mult) dout.download(pv_mult, size_t(nc), stream);
+    if (trans_mult) OPMGPU_HIP(hipMemcpyAsync(trans_mult, dout.p + nc, size_t(nc) * sizeof(double), hipMemcpyDeviceToHost, stream));
+    OPMGPU_HIP(hipStreamSynchronize(stream));
+}
+
 // the output record of the resident state: one launch, one copy; reads the state and writes a buffer of its own, nothing else
 void BlackoilDevice::simulator_data(double* out)
 {

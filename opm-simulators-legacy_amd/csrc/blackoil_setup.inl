@@ -107,6 +107,7 @@ void BlackoilDevice::upload_tables(const opmgpu_tables* t)
     o.x.gas_dinvbmu_sat = slopes(t->gas_pg, t->gas_invbmu_sat, t->gas_node_ptr, np);
     o.x.gas_col_dinvb = slopes(t->gas_col_rv, t->gas_col_invb, t->gas_col_ptr, ngn); o.x.gas_col_dinvbmu = slopes(t->gas_col_rv, t->gas_col_invbmu, t->gas_col_ptr, ngn);
     o.x.oil_pvcdo = nullptr;
+    plain_rock_ = o.t;      // (its rock fields: what set_rock_regions(nullptr) puts back)
     h_tab = blob;
     upload_blob(blob);
     // unscaled end points of every saturation region (what opm-material's EclEpsScalingPointsInfo::extractUnscaled reads off the
@@ -152,6 +153,10 @@ void BlackoilDevice::upload_blob(const std::vector<double>& blob)
 void BlackoilDevice::set_pvcdo(const double* pvcdo)
 {
     const int np = dto_.t.n_pvt_regions;
+    if (rock_on()) {        // the regions' tables lie where the PVCDO rows would: the two are never set together, so there are no rows to take off either
+        if (pvcdo) throw HipError(OPMGPU_EINVAL, "setPvcdo: the context has rock regions (opmgpu_set_rock_regions); the PVCDO oil is not supported with them");
+        return;
+    }
     std::vector<double> blob = h_tab;
     if (pvcdo) {
         if (drdt_on()) throw HipError(OPMGPU_EINVAL, "setPvcdo: the context has dissolution limits (opmgpu_set_dissolution_limits); the PVCDO oil is not supported with them");
@@ -187,6 +192,8 @@ void BlackoilDevice::rebuild_structure()
     if (d_somax.p) { smax.resize(nc); get_sat_oil_max(smax.data()); }
     std::vector<double> caps;       // (the dissolution caps too)
     if (d_somax.p && drdt_on()) { caps.resize(2 * size_t(nc)); get_dissolution_caps(caps.data(), caps.data() + nc); }
+    std::vector<double> pmin;       // (and the compaction history of the rock regions)
+    if (d_somax.p && rock_on()) { pmin.resize(nc); get_rock_history(pmin.data()); }
     if (has_state) { sp.resize(nc); ssat.resize(3 * size_t(nc)); srs.resize(nc); srv.resize(nc); shc.resize(nc); get_state(sp.data(), ssat.data(), srs.data(), srv.data(), shc.data()); }
     const int st2 = ls.set_pattern(nc, rowptr.data(), col.data(), prm.ilu_ordering);
     if (st2 != OPMGPU_OK) throw HipError(st2, "sparsity plan failed");
@@ -214,9 +221,10 @@ void BlackoilDevice::rebuild_structure()
         for (int r = 0; r < nc; ++r) zi[r] = h_z[P.nat[r]];
         d_zc.upload(zi, stream);
     }
-    std::vector<double> pvi(nbp, 1.0); std::vector<int32_t> pn(nbp, 0), sn(nbp, 0);
-    for (int r = 0; r < nc; ++r) { pvi[r] = h_pv[P.nat[r]]; pn[r] = h_pvtnum[P.nat[r]]; sn[r] = h_satnum[P.nat[r]]; }
-    d_pv.upload(pvi, stream); d_pvtnum.upload(pn, stream); d_satnum.upload(sn, stream);
+    std::vector<double> pvi(nbp, 1.0); std::vector<int32_t> pn(nbp, 0);
+    for (int r = 0; r < nc; ++r) { pvi[r] = h_pv[P.nat[r]]; pn[r] = h_pvtnum[P.nat[r]]; }
+    d_pv.upload(pvi, stream); d_pvtnum.upload(pn, stream);
+    upload_region_numbers();
     if (use_eps) {
         std::vector<double> planes;
         upload_drainage_eps();
@@ -266,6 +274,7 @@ void BlackoilDevice::rebuild_structure()
     resize_somax(drdt_on());
     if (!smax.empty()) set_sat_oil_max(smax.data());
     if (!caps.empty()) set_dissolution_caps(caps.data(), caps.data() + nc);
+    if (!pmin.empty()) set_rock_history(pmin.data());
     wells_rebind();
     aquifer_rebind();
     if (has_state) set_state(sp.data(), ssat.data(), srs.data(), srv.data(), shc.data());

@@ -748,6 +748,35 @@ int opmgpu_aquifer_connections_get(opmgpu_ctx* c, double* out)
     return guarded(c, [&]() { c->model->aquifer_connections_get(out); return int(OPMGPU_OK); });
 }
 
+// Rock regions and irreversible compaction (the rule is stated in opmgpu.h).  Regions and history change what the next assembly evaluates:
+// a matrix loaded or factored before the call is that of the old ones.
+int opmgpu_set_rock_regions(opmgpu_ctx* c, const opmgpu_rock_regions* regions)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { c->model->set_rock_regions(regions); c->matrix_loaded = false; return int(OPMGPU_OK); });
+}
+int opmgpu_update_rock_history(opmgpu_ctx* c)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { c->model->update_rock_history(); c->matrix_loaded = false; return int(OPMGPU_OK); });
+}
+int opmgpu_get_rock_history(opmgpu_ctx* c, double* p_min)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    if (!p_min) return fail(c, OPMGPU_EINVAL, "opmgpu_get_rock_history: p_min is NULL");
+    return guarded(c, [&]() { c->model->get_rock_history(p_min); return int(OPMGPU_OK); });
+}
+int opmgpu_set_rock_history(opmgpu_ctx* c, const double* p_min)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { c->model->set_rock_history(p_min); c->matrix_loaded = false; return int(OPMGPU_OK); });
+}
+int opmgpu_get_rock_multipliers(opmgpu_ctx* c, double* pv_mult, double* trans_mult)
+{
+    if (!c || !c->model) return OPMGPU_EINVAL;
+    return guarded(c, [&]() { c->model->get_rock_multipliers(pv_mult, trans_mult); return int(OPMGPU_OK); });
+}
+
 int opmgpu_update_hysteresis(opmgpu_ctx* c)
 {
     if (!c || !c->model) return OPMGPU_EINVAL;

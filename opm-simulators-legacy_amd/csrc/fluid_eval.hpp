@@ -12,9 +12,10 @@ namespace opmgpu {
 
 // the instantiation of a cell-evaluating kernel template <int KM> for this deck's model (inside a BlackoilDevice method)
 #define OPMGPU_BY_MODEL_(kernel, oil) (km_model(kmodel()) == KM_OW ? kernel<KM_OW | oil> : (km_model(kmodel()) == KM_STONE ? kernel<KM_STONE | oil> : (km_model(kmodel()) == KM_KILLOUGH ? kernel<KM_KILLOUGH | oil> : kernel<KM_DEFAULT | oil>)))
-#define OPMGPU_BY_MODEL_PLAIN(kernel) (km_pvcdo(kmodel()) ? OPMGPU_BY_MODEL_(kernel, KM_PVCDO) : OPMGPU_BY_MODEL_(kernel, 0))      // for a kernel that evaluates no cell: KM_DRDT ignored
+#define OPMGPU_BY_MODEL_PLAIN(kernel) (km_pvcdo(kmodel()) ? OPMGPU_BY_MODEL_(kernel, KM_PVCDO) : OPMGPU_BY_MODEL_(kernel, 0))      // for a kernel that evaluates no cell: KM_DRDT and KM_ROCK ignored
 // with dissolution limits (KM_DRDT: never KM_OW, never KM_PVCDO) the three instantiations that carry the caps, else the ones above
-#define OPMGPU_BY_MODEL(kernel) (km_drdt(kmodel()) ? (km_model(kmodel()) == KM_STONE ? kernel<KM_STONE | KM_DRDT> : (km_model(kmodel()) == KM_KILLOUGH ? kernel<KM_KILLOUGH | KM_DRDT> : kernel<KM_DEFAULT | KM_DRDT>)) : OPMGPU_BY_MODEL_PLAIN(kernel))
+// with rock regions (KM_ROCK: any of the four models, never KM_PVCDO, never KM_DRDT) the four instantiations that read the regions
+#define OPMGPU_BY_MODEL(kernel) (km_rock(kmodel()) ? OPMGPU_BY_MODEL_(kernel, KM_ROCK) : (km_drdt(kmodel()) ? (km_model(kmodel()) == KM_STONE ? kernel<KM_STONE | KM_DRDT> : (km_model(kmodel()) == KM_KILLOUGH ? kernel<KM_KILLOUGH | KM_DRDT> : kernel<KM_DEFAULT | KM_DRDT>)) : OPMGPU_BY_MODEL_PLAIN(kernel)))
 
 struct V4 { double v, p, w, x; };      // value, d/dP, d/dSw, d/dXvar
 
@@ -92,10 +93,10 @@ struct HystArgs { const int32_t* imbnum; const double* hist; const double* ieps;
 // VAPPARS history and the hysteresis arguments, all in internal numbering with stride nbp.  Passed to kernels by value;
 // BlackoilDevice::cell_planes() is the one function that fills it.
 struct CellPlanes {
-    const int32_t *pvtnum, *satnum;
+    const int32_t *pvtnum, *satnum;         // satnum: with rock regions satnum | rocknum (rocknum_of)
     const double *p, *sw, *so, *sg, *rs, *rv;
     const int8_t* hc;
-    const double *eps, *eps_u0, *somax;     // somax: with dissolution limits so_max | rs_cap | rv_cap (rs_cap_of / rv_cap_of)
+    const double *eps, *eps_u0, *somax;     // somax: with dissolution limits so_max | rs_cap | rv_cap (rs_cap_of / rv_cap_of), with rock regions so_max | p_min (rock_pmin_of)
     long nbp;
     HystArgs hy;
 };
@@ -110,6 +111,19 @@ template <int KM> __device__ __forceinline__ double rv_cap_of(const double* __re
 {
     if constexpr (km_drdt(KM)) return somax[2 * nbp + row];
     else return __builtin_inf();
+}
+// Rock regions (KM_ROCK; never together with KM_DRDT): the smallest pressure a row has seen rides behind so_max as plane 1 of that array,
+// the row's rock region behind satnum as plane 1 of that one (stride nbp; the arrays have those planes only in a context with rock
+// regions, and only a KM_ROCK instantiation reads them).
+template <int KM> __device__ __forceinline__ double rock_pmin_of(const double* __restrict__ somax, long nbp, int row)
+{
+    if constexpr (km_rock(KM)) return somax[nbp + row];
+    else return __builtin_inf();
+}
+template <int KM> __device__ __forceinline__ int rocknum_of(const int32_t* __restrict__ satnum, long nbp, int row)
+{
+    if constexpr (km_rock(KM)) return satnum[nbp + row];
+    else return 0;
 }
 template <int KM = KM_DEFAULT>
 __device__ __forceinline__ void hyst_load(const int32_t* __restrict__ imbnum, const double* __restrict__ hist, long nbp, int row, HystD& h)
@@ -140,6 +154,49 @@ __device__ __forceinline__ void rocktab_eval(const double* __restrict__ x, const
     for (int k = 1; k <= n - 2; ++k) i += (x[k] < xv) ? 1 : 0;
     df = (y[i + 1] - y[i]) / (x[i + 1] - x[i]);
     f = y[i] + df * (xv - x[i]);
+}
+
+// The pore-volume and the transmissibility multiplier of a cell in rock region r (the rule: include/opmgpu.h at opmgpu_set_rock_regions).
+// A table region is evaluated at x = p on the curve -- REVERSIBLE, or p <= p_min: a tie is on the curve -- and at x = p_min with slope
+// exactly 0 off it; the two tables share the segment (rocktab_eval's rule: the left segment at a breakpoint, the end segments
+// extrapolated) and take their slopes from the blob.  A ROCK-form region (0 rows) is elastic whatever the mode: the quadratic form of
+// its pair, transmissibility multiplier 1.  `table` tells the caller whether the mobilities carry a multiplier at all.
+// In a context with regions the rock fields of the device form of opmgpu_tables, which nobody reads then, carry them (upload_rock_tables):
+//   rocktab_p         five planes of rocktab_n words: p | pv_mult | its slopes | trans_mult | its slopes, all regions' tables end to end
+//   rocktab_pvmult    [nregions][2] the pairs (p_ref, compressibility) of the ROCK form
+//   rocktab_transmult [nregions + 1] int32 words: the rows of every region's table (0 rows: the ROCK form)
+//   rock_comp         the mode, OPMGPU_ROCK_REVERSIBLE / _IRREVERSIBLE as a double
+struct RockView { const int32_t* rock_ptr; const double *rock_ref, *rock_tab; long rock_rows; int rock_mode; };
+__device__ __forceinline__ RockView rock_view(const opmgpu_tables& T)
+{
+    RockView X;
+    X.rock_ptr = reinterpret_cast<const int32_t*>(T.rocktab_transmult); X.rock_ref = T.rocktab_pvmult; X.rock_tab = T.rocktab_p;
+    X.rock_rows = T.rocktab_n; X.rock_mode = T.rock_comp != 0.0 ? OPMGPU_ROCK_IRREVERSIBLE : OPMGPU_ROCK_REVERSIBLE;
+    return X;
+}
+__device__ __forceinline__ void rock_region_eval(const opmgpu_tables& T, int r, double p, double p_min, bool& table, double& pvm, double& dpvm, double& trm, double& dtrm)
+{
+    const RockView X = rock_view(T);
+    const int a = X.rock_ptr[r], n = X.rock_ptr[r + 1] - a;
+    table = n > 0;
+    trm = 1.0; dtrm = 0.0;
+    if (table) {
+        const bool on_curve = X.rock_mode == OPMGPU_ROCK_REVERSIBLE || p <= p_min;
+        const double xv = on_curve ? p : p_min;
+        const double* __restrict__ x = X.rock_tab + a;
+        const long m = X.rock_rows;
+        int i = 0;
+        for (int k = 1; k <= n - 2; ++k) i += (x[k] < xv) ? 1 : 0;
+        const double h = xv - x[i];
+        dpvm = x[2 * m + i]; pvm = x[m + i] + dpvm * h;
+        dtrm = x[4 * m + i]; trm = x[3 * m + i] + dtrm * h;
+        if (!on_curve) { dpvm = 0.0; dtrm = 0.0; }
+    } else {
+        const double pref = X.rock_ref[2 * r], comp = X.rock_ref[2 * r + 1];
+        const double cp = comp * (p - pref);
+        pvm = 1.0; dpvm = 0.0;
+        if (comp != 0.0) { pvm = 1.0 + cp + 0.5 * cp * cp; dpvm = comp + cp * comp; }
+    }
 }
 
 // Device form of the tables (struct DevTables, blackoil.hpp): the caller's arrays and, as their device-internal companions, the slope
@@ -448,13 +505,15 @@ struct CellOutput { double mu[3], kr[3], rsSat, rvSat; };
 // VAPPARS factor a saturated ratio above the cell's cap (strictly: a tie is not capped) is replaced by the cap, a constant; a capped cell
 // with the other phase free then holds UNDERSATURATED oil (gas) at (p, cap), so its PVT takes the 2-D table.  Without the flag rs_cap /
 // rv_cap are not read and every expression below folds to what it was.
-template <bool OUTPUT, bool PVCDO> __device__ void eval_cell_ow(const DevTables& DT, const EpsD& E, int preg, int sreg, double p, double sw_, CellEval& q, CellOutput* out);
+// KM_ROCK or-ed to any model: rock regions (the rule is stated in include/opmgpu.h at opmgpu_set_rock_regions).  The multipliers of the
+// cell come from rock_region_eval instead of the one rock of opmgpu_tables, whose fields are then not read.  Nothing else changes.
+template <bool OUTPUT, bool PVCDO, bool ROCK> __device__ void eval_cell_ow(const DevTables& DT, const EpsD& E, int preg, int sreg, double p, double sw_, CellEval& q, CellOutput* out, int rreg, double p_min);
 template <bool OUTPUT = false, int KM = KM_DEFAULT>
 __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int preg, int sreg, double p, double sw_, double sg_, double rs_, double rv_, int hc,
                           int row, CellEval& q, const HystD& H = HystD{ false, 0, 2.0, 2.0, 0.0, 0.0, 1.0, 1.0, 1.0, 1.0 }, const EpsD* EI = nullptr, CellOutput* out = nullptr,
-                          double rs_cap = __builtin_inf(), double rv_cap = __builtin_inf())
+                          double rs_cap = __builtin_inf(), double rv_cap = __builtin_inf(), int rreg = 0, double p_min = __builtin_inf())
 {
-    if constexpr (km_model(KM) == KM_OW) { eval_cell_ow<OUTPUT, km_pvcdo(KM)>(DT, E, preg, sreg, p, sw_, q, out); return; }
+    if constexpr (km_model(KM) == KM_OW) { eval_cell_ow<OUTPUT, km_pvcdo(KM), km_rock(KM)>(DT, E, preg, sreg, p, sw_, q, out, rreg, p_min); return; }
     const opmgpu_tables& T = DT.t; const TabX& X = DT.x;
     const bool isSg = hc == OPMGPU_HC_GAS_AND_OIL, isRs = hc == OPMGPU_HC_OIL_ONLY, isRv = hc == OPMGPU_HC_GAS_ONLY;
     const bool freeOil = isSg || isRs, freeGas = isSg || isRv;
@@ -597,6 +656,16 @@ __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int
     // accumulation with rock compressibility, transmissibility multiplier (RockCompressibility.cpp:86-125).  (This block and its two-phase
     // twin in eval_cell_ow stay inline: as a shared helper it changed k_assemble_rows' register allocation in ten shapes.)
     V4 pvm = mk(1, 0, 0, 0);
+    if constexpr (km_rock(KM)) {
+        bool table; double dpv, tr, dtr;
+        rock_region_eval(T, rreg, p, p_min, table, f, dpv, tr, dtr); pvm = mk(f, dpv, 0, 0);
+        if (table) {
+            const V4 trm = mk(tr, dtr, 0, 0);
+            q.mob[0] = vdiv1(vmul(trm, krw), mu[0]); q.mob[1] = vdiv1(vmul(trm, kro), mu[1]); q.mob[2] = vdiv1(vmul(trm, krg), mu[2]);
+        } else {
+            q.mob[0] = vdiv1(krw, mu[0]); q.mob[1] = vdiv1(kro, mu[1]); q.mob[2] = vdiv1(krg, mu[2]);
+        }
+    } else {
     if (T.rocktab_n > 0) {
         rocktab_eval(T.rocktab_p, T.rocktab_pvmult, T.rocktab_n, p, f, df); pvm = mk(f, df, 0, 0);
         rocktab_eval(T.rocktab_p, T.rocktab_transmult, T.rocktab_n, p, f, df);
@@ -608,6 +677,7 @@ __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int
     if (T.rocktab_n == 0 && T.rock_comp != 0.0) {
         const double cp = T.rock_comp * (p - T.rock_pref);
         pvm = mk(1.0 + cp + 0.5 * cp * cp, T.rock_comp + cp * T.rock_comp, 0, 0);
+    }
     }
     q.pvm = pvm;
     const V4 aw = vmul(vmul(pvm, q.b[0]), W);
@@ -626,8 +696,8 @@ __device__ void eval_cell(const DevTables& DT, const EpsD& E, double so_max, int
 // krw(Sw) and pcow(Sw) as with three phases, kro = krow(Sw) with the EC_KROW scaling -- no connate-water clamp, no blend --, the dead-oil
 // PVT, So = 1 - Sw.  No gas table is touched.  The inactive gas phase presents b_g = 1, mu_g = 1, mob_g = 0, rho_g = 0, p_g = p_o,
 // Sg = rs = rv = 0 with all derivatives 0, so that what still indexes three phases needs no guard; d/dXvar of everything is 0.
-template <bool OUTPUT, bool PVCDO>
-__device__ void eval_cell_ow(const DevTables& DT, const EpsD& E, int preg, int sreg, double p, double sw_, CellEval& q, CellOutput* out)
+template <bool OUTPUT, bool PVCDO, bool ROCK>
+__device__ void eval_cell_ow(const DevTables& DT, const EpsD& E, int preg, int sreg, double p, double sw_, CellEval& q, CellOutput* out, int rreg, double p_min)
 {
     const opmgpu_tables& T = DT.t; const TabX& X = DT.x;
     const V4 P = mk(p, 1, 0, 0), W = mk(sw_, 0, 1, 0), zero = mk(0, 0, 0, 0), one = mk(1, 0, 0, 0);
@@ -672,6 +742,17 @@ __device__ void eval_cell_ow(const DevTables& DT, const EpsD& E, int preg, int s
     q.rho[1] = vscale(rhos[1], q.b[1]);
     q.rho[2] = zero;
     V4 pvm = one;
+    if constexpr (ROCK) {
+        bool table; double dpv, tr, dtr;
+        rock_region_eval(T, rreg, p, p_min, table, f, dpv, tr, dtr); pvm = mk(f, dpv, 0, 0);
+        if (table) {
+            const V4 trm = mk(tr, dtr, 0, 0);
+            q.mob[0] = vdiv1(vmul(trm, krw), mu[0]); q.mob[1] = vdiv1(vmul(trm, kro), mu[1]);
+        } else {
+            q.mob[0] = vdiv1(krw, mu[0]); q.mob[1] = vdiv1(kro, mu[1]);
+        }
+        q.mob[2] = zero;
+    } else {
     if (T.rocktab_n > 0) {
         rocktab_eval(T.rocktab_p, T.rocktab_pvmult, T.rocktab_n, p, f, df); pvm = mk(f, df, 0, 0);
         rocktab_eval(T.rocktab_p, T.rocktab_transmult, T.rocktab_n, p, f, df);
@@ -684,6 +765,7 @@ __device__ void eval_cell_ow(const DevTables& DT, const EpsD& E, int preg, int s
     if (T.rocktab_n == 0 && T.rock_comp != 0.0) {
         const double cp = T.rock_comp * (p - T.rock_pref);
         pvm = mk(1.0 + cp + 0.5 * cp * cp, T.rock_comp + cp * T.rock_comp, 0, 0);
+    }
     }
     q.pvm = pvm;
     q.accum[0] = vmul(vmul(pvm, q.b[0]), W);
@@ -706,7 +788,7 @@ __device__ __forceinline__ void eval_row(const DevTables& DT, int row, const Cel
     hyst_load<KM>(C.hy.imbnum, C.hy.hist, C.nbp, row, H);
     if (H.on) eps_load(C.hy.ieps, C.hy.iureg, C.nbp, row, H.ireg, EI);
     eval_cell<OUTPUT, KM>(DT, E, C.somax[row], C.pvtnum[row], C.satnum[row], C.p[row], C.sw[row], C.sg[row], C.rs[row], C.rv[row], C.hc[row], row, q, H, &EI, out,
-                          rs_cap_of<KM>(C.somax, C.nbp, row), rv_cap_of<KM>(C.somax, C.nbp, row));
+                          rs_cap_of<KM>(C.somax, C.nbp, row), rv_cap_of<KM>(C.somax, C.nbp, row), rocknum_of<KM>(C.satnum, C.nbp, row), rock_pmin_of<KM>(C.somax, C.nbp, row));
 }
 
 } // namespace opmgpu

@@ -165,6 +165,14 @@ public:
     void beginDissolutionStep(double dt) { throw_on_status(ctx_, opmgpu_begin_dissolution_step(ctx_, dt)); }
     void getDissolutionCaps(double* rs_cap, double* rv_cap) { throw_on_status(ctx_, opmgpu_get_dissolution_caps(ctx_, rs_cap, rv_cap)); }
     void setDissolutionCaps(const double* rs_cap, const double* rv_cap) { throw_on_status(ctx_, opmgpu_set_dissolution_caps(ctx_, rs_cap, rv_cap)); }
+    /// Rock regions and irreversible compaction (opmgpu_set_rock_regions; the rule is ours and stated in opmgpu.h): nullptr goes back to the
+    /// one rock of the tables.  The caller runs updateRockHistory() once on the initial (or restarted) state and after every converged
+    /// sub-step; save / restore do not touch the history.  History and multipliers: [nc], caller cell order; a multiplier pointer may be null.
+    void setRockRegions(const opmgpu_rock_regions* regions) { throw_on_status(ctx_, opmgpu_set_rock_regions(ctx_, regions)); }
+    void updateRockHistory() { throw_on_status(ctx_, opmgpu_update_rock_history(ctx_)); }
+    void getRockHistory(double* p_min) { throw_on_status(ctx_, opmgpu_get_rock_history(ctx_, p_min)); }
+    void setRockHistory(const double* p_min) { throw_on_status(ctx_, opmgpu_set_rock_history(ctx_, p_min)); }
+    void getRockMultipliers(double* pv_mult, double* trans_mult) { throw_on_status(ctx_, opmgpu_get_rock_multipliers(ctx_, pv_mult, trans_mult)); }
     /// Analytic aquifers (opmgpu_set_aquifers; the rule is ours and stated in opmgpu.h): nullptr removes them.  The caller begins every
     /// time step -- also the retry of a failed one, after the state has been restored -- with beginAquiferStep(dt) and commits a
     /// converged one with commitAquiferStep() before it saves the state.  State per aquifer ([naq], any pointer may be null); the

@@ -87,6 +87,15 @@ class AquifersSpec(C.Structure):
 
 
 AQUIFER_FETKOVICH, AQUIFER_CARTER_TRACY = 0, 1
+
+
+class RockRegionsSpec(C.Structure):
+    """opmgpu_rock_regions: rock regions and the compaction mode (include/opmgpu.h)"""
+    _fields_ = [("nregions", C.c_int32), ("mode", C.c_int32), ("rocknum", _ip), ("rock_pref", _dp), ("rock_comp", _dp),
+                ("tab_ptr", _ip), ("tab_p", _dp), ("tab_pvmult", _dp), ("tab_transmult", _dp)]
+
+
+ROCK_REVERSIBLE, ROCK_IRREVERSIBLE = 0, 1
 AQUIFER_CONN_K = 6
 
 
@@ -254,6 +263,11 @@ SIGNATURES = {
     "opmgpu_aquifer_state_get": (C.c_int, [C.c_void_p, _dp, _dp, _dp, _dp]),
     "opmgpu_aquifer_state_set": (C.c_int, [C.c_void_p, _dp, _dp, _dp]),
     "opmgpu_aquifer_connections_get": (C.c_int, [C.c_void_p, _dp]),
+    "opmgpu_set_rock_regions": (C.c_int, [C.c_void_p, C.POINTER(RockRegionsSpec)]),
+    "opmgpu_update_rock_history": (C.c_int, [C.c_void_p]),
+    "opmgpu_get_rock_history": (C.c_int, [C.c_void_p, _dp]),
+    "opmgpu_set_rock_history": (C.c_int, [C.c_void_p, _dp]),
+    "opmgpu_get_rock_multipliers": (C.c_int, [C.c_void_p, _dp, _dp]),
     "opmgpu_create_solver": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.POINTER(Params)]),
     "opmgpu_solve_bsr": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, _dp, _dp, C.c_int, _dp, C.POINTER(C.c_int), _dp]),
     "opmgpu_load_bsr": (C.c_int, [C.c_void_p, C.c_int, _ip, _ip, _dp, C.c_int]),

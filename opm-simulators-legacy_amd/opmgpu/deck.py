@@ -12,6 +12,9 @@ What `flow_legacy` gets from opm-parser + `DerivedGeology` (opm/autodiff/GeoProp
   GRID      DX DY DZ / DXV DYV DZV, TOPS (+BOX for the top layer) or DEPTHZ (flat) -- or COORD / ZCORN (corner-point, no faults) --, PORO PERMX PERMY PERMZ NTG ACTNUM MINPV, FAULTS + MULTFLT
             MULTX MULTY MULTZ MULTX- MULTY- MULTZ- MULTPV NNC
   PROPS     SWOF SGOF PVTO PVDO PVCDO PVTG PVDG PVTW DENSITY ROCK ROCKTAB VAPPARS SCALECRS (NO and YES) EHYSTR
+            ROCK / ROCKTAB: the first record, for every cell -- unless RUNSPEC holds ROCKCOMP (REVERS or IRREVERS; item 2 the number of
+            rock tables): then every record is read, ROCKOPTS item 3 (PVTNUM, SATNUM or ROCKNUM) names the region array that picks a
+            cell's record, and `rock_regions()` returns them for GpuBlackoilModel.setRockRegions (the rule is stated in include/opmgpu.h)
             PVCDO: one record per PVT region (TABDIMS; too few is a ValueError).  With Co = Cv = 0 in every record it is a constant
             two-node dead-oil table; otherwise the tables carry the rows as `FluidTables.pvcdo` (SI) next to that table as a stand-in,
             and the device evaluates the oil in closed form (opmgpu_set_pvcdo; the rule is stated in include/opmgpu.h).  Not with DISGAS.
@@ -23,7 +26,8 @@ What `flow_legacy` gets from opm-parser + `DerivedGeology` (opm/autodiff/GeoProp
             (SATOPTS HYSTER in RUNSPEC switches the hysteresis on; EHYSTR item 2 = 0 -- Carlson -- or 2 -- Killough, with item 4 its
             curvature parameter -- and item 5 = KR, relative permeabilities only, are the models the device implements:
             `hysteresis_model()`; items 1 and 3 are read past, the wetting-phase models 1, 3, 4 are refused)
-  REGIONS   PVTNUM SATNUM IMBNUM FIPNUM (fluid-in-place regions of computeFluidInPlace; 1-based in the deck and in `fipnum()`)
+  REGIONS   ROCKNUM (with ROCKCOMP and ROCKOPTS item 3 = ROCKNUM)
+            PVTNUM SATNUM IMBNUM FIPNUM (fluid-in-place regions of computeFluidInPlace; 1-based in the deck and in `fipnum()`)
             EQLNUM (equilibration regions: EQUIL's, and the regions THPRES puts barriers between; 1-based in `eqlnum()`)
   SOLUTION  PRESSURE SWAT SGAS RS RV (explicit initial state; EQUIL is outside the hot path)
             THPRES (threshold pressures between EQLNUM regions, with EQLOPTS THPRES in RUNSPEC: `thpres()` / `threshold_pressures()`
@@ -903,6 +907,73 @@ class Deck:
             a.alpha = w / w.sum()
             out.append(a)
         return out
+
+    # ---------------------------------------------------------------- rock regions and compaction
+    def rock_regions(self):
+        """The deck's rock regions as a decks.RockRegions (cells in the numbering of grid()), or None without ROCKCOMP in RUNSPEC -- then
+        tables() carries the first ROCK / ROCKTAB record for every cell, as ever.  The device rule they feed is stated in include/opmgpu.h
+        at opmgpu_set_rock_regions.
+          ROCKCOMP  item 1 REVERS (the default) or IRREVERS; item 2 the number of rock tables (default 1); item 3 water-induced
+                    compaction, NO or defaulted
+          ROCKOPTS  item 1 PRESSURE (the default); item 2 NOSTORE (the default); item 3 the region array that picks a cell's ROCK /
+                    ROCKTAB record: PVTNUM (the default), SATNUM or ROCKNUM
+          ROCKNUM   (REGIONS) 1-based region per cell, when ROCKOPTS item 3 names it
+          ROCKTAB   one record per region, rows (p, pv_mult, trans_mult); a region whose record is missing or empty takes the ROCK form
+          ROCK      one record (p_ref, compressibility) per region
+        Refused with a ValueError naming keyword and item: ROCKCOMP item 1 HYSTER, BOBERG, REVLIMIT, PALM-MAN (or anything else), item 3
+        other than NO; ROCKOPTS item 1 other than PRESSURE, item 2 STORE, an unknown item 3; a region number outside 1 .. the number of
+        tables; a region with neither a ROCKTAB nor a ROCK record."""
+        if not self.has("ROCKCOMP"):
+            return None
+        item = lambda r, i, d=None: r[i] if len(r) > i and r[i] is not None else d         # noqa: E731
+        rc = self.records("ROCKCOMP")[0] if self.records("ROCKCOMP") else []
+        model = str(item(rc, 0, "REVERS")).upper()
+        if model in ("HYSTER", "BOBERG", "REVLIMIT", "PALM-MAN"):
+            raise ValueError("ROCKCOMP item 1: the %s compaction model is not supported (REVERS, IRREVERS)" % model)
+        if model not in ("REVERS", "IRREVERS"):
+            raise ValueError("ROCKCOMP item 1: %r is neither REVERS nor IRREVERS" % item(rc, 0))
+        ntab = int(item(rc, 1, 1))
+        if ntab < 1:
+            raise ValueError("ROCKCOMP item 2: the number of rock tables must be at least 1")
+        if str(item(rc, 2, "NO")).upper() != "NO":
+            raise ValueError("ROCKCOMP item 3: water-induced compaction (%s) is not supported" % item(rc, 2))
+        ro = self.records("ROCKOPTS")[0] if self.has("ROCKOPTS") and self.records("ROCKOPTS") else []
+        if str(item(ro, 0, "PRESSURE")).upper() != "PRESSURE":
+            raise ValueError("ROCKOPTS item 1: %s is not supported (PRESSURE)" % item(ro, 0))
+        if str(item(ro, 1, "NOSTORE")).upper() != "NOSTORE":
+            raise ValueError("ROCKOPTS item 2: %s is not supported (NOSTORE)" % item(ro, 1))
+        regkw = str(item(ro, 2, "PVTNUM")).upper()
+        if regkw not in ("PVTNUM", "SATNUM", "ROCKNUM"):
+            raise ValueError("ROCKOPTS item 3: %r is none of PVTNUM, SATNUM, ROCKNUM" % item(ro, 2))
+        nx, ny, nz = self.dims
+        if getattr(self, "active", None) is None:
+            self.grid()
+        if self.has(regkw):
+            num = self.array(regkw, nx * ny * nz)[self.active]
+            if np.isnan(num).any():
+                raise ValueError("%s must be given for every active cell (ROCKOPTS item 3 names it)" % regkw)
+            num = num.astype(np.int64) - 1
+        else:
+            num = np.zeros(self.active.size, np.int64)
+        if num.size and (num.min() < 0 or num.max() >= ntab):
+            raise ValueError("%s: region %d is outside 1 .. %d (ROCKCOMP item 2)" % (regkw, int(num.max() + 1 if num.max() >= ntab else num.min() + 1), ntab))
+        rocks = self.records("ROCK") if self.has("ROCK") else []
+        tabs = self.records("ROCKTAB") if self.has("ROCKTAB") else []
+        rock, tables = [], []
+        for r in range(ntab):
+            rec = tabs[r] if r < len(tabs) else []
+            if rec:
+                ncol = 5 if len(rec) % 5 == 0 and len(rec) % 3 != 0 else 3
+                tables.append([(rec[i], rec[i + 1], rec[i + 2]) for i in range(0, len(rec), ncol)])
+            else:
+                tables.append(None)
+            if r < len(rocks) and len(rocks[r]) >= 2:
+                rock.append((rocks[r][0], rocks[r][1]))
+            elif tables[-1] is None:
+                raise ValueError("ROCK: no record for region %d, which has no ROCKTAB record either (ROCKCOMP item 2 = %d)" % (r + 1, ntab))
+            else:
+                rock.append((1.0, 0.0))
+        return decks.RockRegions(num, rock, tables, irreversible=(model == "IRREVERS"))
 
     # ---------------------------------------------------------------- SOLUTION
     def initial_state(self, tables):

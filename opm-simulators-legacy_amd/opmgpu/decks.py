@@ -273,6 +273,33 @@ class GridData:
         return self._struct
 
 
+class RockRegions:
+    """Rock regions and the compaction mode as GpuBlackoilModel.setRockRegions takes them (`opmgpu_rock_regions`, SI): `rocknum` the
+    0-based region of every cell, `rock` one pair (p_ref [bar], compressibility [1/bar]) per region, `tables` per region the rows
+    (p [bar], pv_mult, trans_mult) of its table or None for the ROCK form, `irreversible` the mode (ROCKCOMP IRREVERS)."""
+
+    def __init__(self, rocknum, rock, tables=None, irreversible=False):
+        self.rocknum = capi.i32(rocknum)
+        rock = capi.f64(rock).reshape(-1, 2)
+        self.nregions = rock.shape[0]
+        self.rock_pref, self.rock_comp = capi.f64(rock[:, 0] * BAR), capi.f64(rock[:, 1] / BAR)
+        tables = [None] * self.nregions if tables is None else list(tables)
+        if len(tables) != self.nregions:
+            raise ValueError("RockRegions: %d tables for %d regions" % (len(tables), self.nregions))
+        rows = [np.zeros((0, 3)) if t is None else capi.f64(t).reshape(-1, 3) for t in tables]
+        self.tab_ptr = capi.i32(np.concatenate([[0], np.cumsum([r.shape[0] for r in rows])]))
+        allrows = np.concatenate(rows) if rows else np.zeros((0, 3))
+        self.tab_p, self.tab_pvmult, self.tab_transmult = capi.f64(allrows[:, 0] * BAR), capi.f64(allrows[:, 1]), capi.f64(allrows[:, 2])
+        self.mode = capi.ROCK_IRREVERSIBLE if irreversible else capi.ROCK_REVERSIBLE
+
+    def local(self, cells):
+        """the same regions for a subset of the cells (a rank's local cells, ghosts included)"""
+        r = RockRegions.__new__(RockRegions)
+        r.__dict__.update(self.__dict__)
+        r.rocknum = capi.i32(self.rocknum[np.asarray(cells)])
+        return r
+
+
 def with_endpoints(grid, eps, **more):
     """Copy of `grid` carrying ENDSCALE end points (dict name -> scalar / per-cell array, all eight names); more = scalecrs=True,
     eps_v={KRW..}, imbnum=..., ieps={...} (see GridData)."""

@@ -291,10 +291,13 @@ class GpuBlackoilModel(_CprDiagnostics):
     # last_state of AdaptiveTimeStepping, kept on the device
     def saveState(self):
         """Keeps the resident state as the last good one.  A begun aquifer step is committed first: the time-step control saves the state
-        after every converged sub-step, so this is where the aquifers take their influx of that sub-step, once."""
+        after every converged sub-step, so this is where the aquifers take their influx of that sub-step, once.  Under irreversible
+        compaction (setRockRegions) the state that is saved is a converged one too: the rock takes its pressures into its history."""
         if self._aquifer_step_begun:
             self._chk(self.lib.opmgpu_aquifer_commit_step(self.ctx))
             self._aquifer_step_begun = False
+        if self.rock_regions is not None and self.rock_regions.mode == capi.ROCK_IRREVERSIBLE:
+            self.updateRockHistory()
         self._chk(self.lib.opmgpu_save_state(self.ctx))
 
     def restoreState(self):
@@ -483,6 +486,61 @@ class GpuBlackoilModel(_CprDiagnostics):
         a = None if rs_cap is None else capi.f64(rs_cap)
         b = None if rv_cap is None else capi.f64(rv_cap)
         self._chk(self.lib.opmgpu_set_dissolution_caps(self.ctx, None if a is None else capi.dptr(a), None if b is None else capi.dptr(b)))
+
+    # Rock regions and irreversible compaction (opmgpu_set_rock_regions; the rule is ours and stated in include/opmgpu.h)
+    rock_regions = None             # the regions in force (an object with mode, rocknum, rock_pref, rock_comp, tab_ptr, tab_p, tab_pvmult, tab_transmult); None = none
+
+    def setRockRegions(self, regions):
+        """A rock per cell and the compaction mode.  `regions`: an object with mode (capi.ROCK_REVERSIBLE / ROCK_IRREVERSIBLE), rocknum
+        ([nc], 0-based), rock_pref and rock_comp ([nregions]), tab_ptr ([nregions + 1]; 0 rows = the ROCK form) and tab_p, tab_pvmult,
+        tab_transmult -- opmgpu.decks.RockRegions -- or None to go back to the one rock of the tables.  With ROCK_IRREVERSIBLE saveState()
+        takes every saved state into the history; the caller seeds it once with updateRockHistory() on the initial state.  ValueError
+        with the library's text when refused; the previous set stays in force."""
+        if regions is None:
+            self._chk(self.lib.opmgpu_set_rock_regions(self.ctx, None))
+            self.rock_regions = None
+            return
+        rocknum = np.asarray(regions.rocknum)
+        if rocknum.shape != (self.nc,):
+            raise ValueError("setRockRegions: rocknum has %s entries for %d cells" % (rocknum.shape, self.nc))
+        pref, comp = capi.f64(regions.rock_pref), capi.f64(regions.rock_comp)
+        ptr = capi.i32(regions.tab_ptr)
+        if pref.shape != comp.shape or ptr.size != pref.size + 1:
+            raise ValueError("setRockRegions: rock_pref, rock_comp [nregions] and tab_ptr [nregions + 1] differ in length")
+        tabs = [capi.f64(np.concatenate([np.asarray(a, float).ravel(), np.zeros(1)])) for a in (regions.tab_p, regions.tab_pvmult, regions.tab_transmult)]
+        rows = int(ptr[-1]) if ptr.size else 0
+        if any(t.size - 1 != tabs[0].size - 1 for t in tabs) or (ptr.size and rows > tabs[0].size - 1):
+            raise ValueError("setRockRegions: tab_p, tab_pvmult, tab_transmult differ in length or are shorter than tab_ptr says")
+        s = capi.RockRegionsSpec()
+        s.nregions, s.mode = int(pref.size), int(regions.mode)
+        rn = capi.i32(rocknum)
+        s.rocknum, s.rock_pref, s.rock_comp, s.tab_ptr = capi.iptr(rn), capi.dptr(pref), capi.dptr(comp), capi.iptr(ptr)
+        s.tab_p, s.tab_pvmult, s.tab_transmult = (capi.dptr(t) for t in tabs)
+        self._chk(self.lib.opmgpu_set_rock_regions(self.ctx, C.byref(s)))
+        self.rock_regions = regions
+
+    def updateRockHistory(self):
+        """p_min = min(p_min, p) of the resident state, on the device"""
+        self._chk(self.lib.opmgpu_update_rock_history(self.ctx))
+
+    def rockHistory(self):
+        """p_min per cell, caller cell order; +inf = no pressure taken yet (or no regions)"""
+        out = np.zeros(self.nc)
+        self._chk(self.lib.opmgpu_get_rock_history(self.ctx, capi.dptr(out)))
+        return out
+
+    def setRockHistory(self, p_min):
+        """the history itself (restart; tests)"""
+        a = capi.f64(p_min)
+        if a.shape != (self.nc,):
+            raise ValueError("setRockHistory: %s values for %d cells" % (a.shape, self.nc))
+        self._chk(self.lib.opmgpu_set_rock_history(self.ctx, capi.dptr(a)))
+
+    def rockMultipliers(self):
+        """(pv_mult, trans_mult) of every cell at the resident state, caller cell order"""
+        pv, tr = np.zeros(self.nc), np.zeros(self.nc)
+        self._chk(self.lib.opmgpu_get_rock_multipliers(self.ctx, capi.dptr(pv), capi.dptr(tr)))
+        return pv, tr
 
     # Analytic aquifers (opmgpu_set_aquifers; the rule is ours and stated in include/opmgpu.h)
     aquifers = None                 # the list in force (objects with kind, p_a0, datum, ... cells, alpha: opmgpu.deck.Aquifer); None = none

@@ -118,6 +118,12 @@ class LocalDomain:
         g = self.global_of_local
         return State(st.p[g], st.sat[g], st.rs[g], st.rv[g], st.hc[g])
 
+    def local_rock_regions(self, regions, p_min=None):
+        """The rock regions (decks.RockRegions) of this rank's local cells, ghosts included -- a ghost's trans_mult enters the owner's
+        flux --, and with a global history plane p_min its local part: (regions, p_min or None).  Rank-local: nothing is communicated."""
+        g = self.global_of_local
+        return regions.local(g), (None if p_min is None else np.asarray(p_min, float)[g])
+
 
 SHM_TEST_LIB = os.path.join(os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))), "tests", "support", "_build", "libshmtransport.so")
 

@@ -99,6 +99,15 @@ class Simulator:
             if self.start_step > 0:
                 raise ValueError("the deck has analytic aquifers: a restarted run is not supported (the restart file does not carry the aquifers' state)")
             self.model.setAquifers(self.aquifers)
+        # ROCKCOMP: rock regions and the compaction mode, installed once; the context carries them and the history p_min through the
+        # report steps' well re-plans (the rule is the device's own, include/opmgpu.h).  The history starts from the state the run
+        # starts from -- on a restarted run from the file's PRESROCK first (run()) --; saveState() then takes every converged sub-step.
+        self.rock_regions = self.deck.rock_regions()
+        if self.rock_regions is not None:
+            # a model without the setter (the CPU oracle behind the host well model) would run table 1 in every cell, without a word
+            if not hasattr(self.model, "setRockRegions"):
+                raise ValueError("the deck has ROCKCOMP, but the model cannot take rock regions (setRockRegions)")
+            self.model.setRockRegions(self.rock_regions)
         self.ats = ats or ts.AdaptiveTimeStepping(initial_timestep_days=1.0)
         if getattr(self, "_restart_dtnx", None) is not None:
             self.ats.suggested_next_timestep = self._restart_dtnx
@@ -131,7 +140,7 @@ class Simulator:
             hc[hc == capi.HC_OIL_ONLY] = capi.HC_GAS_AND_OIL
         self.state0 = State(np.asarray(r["PRESSURE"], float) * BAR, sat, np.asarray(r["RS"], float), np.asarray(r["RV"], float), hc)
         self.start_step, self.t0 = report - 1, r["DAYS"] * DAY        # report 1 is the initial state, report k + 1 follows schedule step k - 1
-        self._restart_extra = {k: np.asarray(r[k], float) for k in ("SOMAX", "HMDC_OW", "HMDC_GO") if k in r}
+        self._restart_extra = {k: np.asarray(r[k], float) for k in ("SOMAX", "HMDC_OW", "HMDC_GO", "PRESROCK") if k in r}
         self._restart_dtnx = float(r["OPMGDTNX"][0]) * DAY if "OPMGDTNX" in r else None
         if "OPMGXWEL" in r:
             x = np.asarray(r["OPMGXWEL"], float).reshape(-1, 5)
@@ -146,9 +155,18 @@ class Simulator:
                 gm.setSatOilMax(ex["SOMAX"])
             if "HMDC_OW" in ex and hasattr(gm, "setHysteresis"):
                 gm.setHysteresis(ex["HMDC_OW"], ex["HMDC_GO"])
+            if "PRESROCK" in ex and self.rock_regions is not None:
+                from .decks import BAR
+                gm.setRockHistory(ex["PRESROCK"] * BAR)
+        if self.rock_regions is not None:
+            gm.updateRockHistory()                        # the initial (or restarted) state is the first the rock has seen
         if self.out:
             self.out.report = self.start_step             # the restarted run numbers its report steps like the full one
-            self.out.write_restart(t / DAY, gm.getState())
+            extra0 = {}
+            if self.rock_regions is not None:             # (the history of the state the run starts from)
+                from .decks import BAR
+                extra0["PRESROCK"] = gm.rockHistory() / BAR
+            self.out.write_restart(t / DAY, gm.getState(), extra=extra0)
         nsteps = len(self.schedule.steps) if max_steps is None else min(max_steps, len(self.schedule.steps))
         for step in range(self.start_step, nsteps):
             dt = self.schedule.steps[step][0]
@@ -218,6 +236,9 @@ class Simulator:
                 if hasattr(gm, "getHysteresis") and self.grid.imbnum is not None:
                     h = gm.getHysteresis()
                     extra["HMDC_OW"], extra["HMDC_GO"] = h[0], h[1]
+                if self.rock_regions is not None:         # the compaction history [bar], like PRESSURE
+                    from .decks import BAR
+                    extra["PRESROCK"] = gm.rockHistory() / BAR
                 self.out.write_restart(t / DAY, gm.getState(), extra=extra, wells=wl if wl.nw > 0 else None, well_state=ws if wl.nw > 0 else None,
                                        next_step_days=self.ats.suggested_next_timestep / DAY)
                 if wl.nw > 0:
